@@ -11,7 +11,14 @@ starts.  N > 1: one process per GPU; the ranks split the columns of the matrix v
 (every GEMM of the assembly shards) and one RCCL all-reduce adds their partial Schur matrices before
 the replicated factorisation; total work is fixed (`"scaling": "strong"`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--msz 2000] [--nvar 4000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--msz 2000] [--nvar 4000] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the configuration).  `--full` adds what takes runs or probes of its own:
+per-kernel HIP-event timing in the timed steps (phases, roofline, per-rank figures), the cross-rank check of the solution,
+the `alongside` solve and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float64): both solutions (`dely_predictor`, `dely_corrector`) and a fixed, seeded sample of the
+assembled Schur matrix (`schur_H_sample`, all of it when it has at most 2^20 entries).
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts its own N ranks
 (`python -m torch.distributed.run --nproc-per-node N`) BEFORE anything touches a GPU and forwards their
@@ -39,7 +46,11 @@ def parse():
     ap.add_argument("--msz", type=int, default=2000)
     ap.add_argument("--nvar", type=int, default=4000)
     ap.add_argument("--seed", type=int, default=20250614)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel timing, roofline, cross-rank check, alongside solve and CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true")      # (with --full)
     ap.add_argument("--cpu-msz", type=int, default=300)
     ap.add_argument("--cpu-nvar", type=int, default=400)
     ap.add_argument("--cpu-msz2", type=int, default=500)        # SURVEY.md 8d's scaled instance (bounded sample)
@@ -231,6 +242,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -272,8 +285,8 @@ def main():
     rng = np.random.default_rng(args.seed + 2)
     h_pred = torch.from_numpy(rng.standard_normal(nvar)).cuda()
     h_corr = torch.from_numpy(rng.standard_normal(nvar)).cuda()
+    dely_pred = torch.zeros(nvar, dtype=torch.float64, device="cuda")
     dely = torch.zeros(nvar, dtype=torch.float64, device="cuda")
-    from loraine_jl_amd import sharding
     if sharded:
         # the exchange lives in the library (csrc/comm.hip): RCCL communicator created from a unique id that travels
         # through the launcher's process group; every lrn_schur_assemble then agrees on the path (first call), reduces a
@@ -287,7 +300,7 @@ def main():
         dev.schur_assemble(0)                                   # makeBBBBs on the owned share + the exchange
         info = dev.schur_factor()                               # cholesky(BBBB)
         assert info == 0, f"Schur matrix not PD (info={info})"
-        dev._chk(lib.lrn_schur_solve(dev.h, ptr(h_pred), ptr(dely)), "solve")   # predictor
+        dev._chk(lib.lrn_schur_solve(dev.h, ptr(h_pred), ptr(dely_pred)), "solve")   # predictor
         dev._chk(lib.lrn_schur_solve(dev.h, ptr(h_corr), ptr(dely)), "solve")   # corrector
 
     def barrier():
@@ -304,7 +317,8 @@ def main():
     dev.set_option("profile", 0)
     for _ in range(args.warmup):
         step()
-    dev.set_option("profile", 1)          # per-kernel HIP-event timing on the library's stream
+    if args.full:
+        dev.set_option("profile", 1)      # per-kernel HIP-event timing on the library's stream
     dev.reset_timing()
     barrier()
     t0 = time.perf_counter()
@@ -318,6 +332,57 @@ def main():
     elapsed = float(tmax.item())
     ms_per_step = elapsed / args.steps * 1e3
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dev, dely_pred, dely, args.seed)
+    chol_path, via_l = dev.count("schur_chol") > 0, dev.count("schur_via_l") > 0
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "ms/IP-iteration (Schur assembly + solve), dense SDP n=2000 m=4000",
+            "value": ms_per_step, "unit": "ms", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ranks_seen": dist.get_world_size() if sharded else 1,
+            "ms_per_step": ms_per_step, "higher_is_better": False, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"C4 synthetic dense SDP, matrix side {msz}, {nvar} constraints, kit=0 "
+                                   f"(assembly + Cholesky + predictor/corrector solves)",
+                       "msz": msz, "nvar": nvar, "seed": args.seed,
+                       "parallelism": "1 GPU" if world == 1 else (
+                           f"columns of the matrix variable over {world} GPUs + RCCL all-reduce of the partial Schur matrices"
+                           if chol_path else f"Schur column blocks over {world} GPUs + RCCL all-gather")},
+            "algorithmic_tflops": flops_model(msz, nvar) / (ms_per_step * 1e-3) / 1e12,
+            "assembly_path": ("cholesky (H_ij = <L'A_iL, L'A_jL>, W = LL')" if chol_path
+                              else ("T_k = L (L'A_kL) L', W = LL'" if via_l else "T_k = W A_k W")),
+            "data_gen_s": t_gen,
+        }
+    if args.full:
+        full_report(args, out, dev, sharded, world, rank, msz, nvar, dely, transport if sharded else None)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if sharded:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, dev, dely_pred, dely, seed):
+    """What the last timed step computed, as a caller of the path receives it: the predictor and corrector solutions and
+    the assembled Schur matrix H (a fixed, seeded sample of its entries in column-major order when it has more than
+    2^20 of them)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "dely_predictor.npy"), dely_pred.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "dely_corrector.npy"), dely.cpu().numpy().astype(np.float64))
+    H = dev.schur_get().reshape(-1, order="F")
+    if H.size > 1 << 20:
+        idx = np.sort(np.random.default_rng(seed + 3).choice(H.size, size=1 << 20, replace=False))
+        H = H[idx]
+    np.save(os.path.join(path, "schur_H_sample.npy"), H)
+
+
+def full_report(args, out, dev, sharded, world, rank, msz, nvar, dely, transport):
+    """--full: the figures that need per-kernel timing, probes or runs of their own, added to rank 0's `out`."""
+    import numpy as np
+    import torch.distributed as dist
+    from loraine_jl_amd import sharding
     # the sharded path must leave the same solution on every rank (replicated factor + solves on the
     # all-gathered matrix): compare a checksum of the corrector solve across ranks
     chk = float(dely.double().sum().item())
@@ -394,31 +459,11 @@ def main():
         dist.all_gather_object(reports, mine)
     if rank == 0:
         slow = max(reports, key=lambda r_: r_["phases"]["assemble"])          # the rank the step waits for
-        chol_path, via_l = slow["chol_path"], slow["via_l"]
         roof = slow["roofline"]
         if (msz, nvar, world) == (2000, 4000, 1):
             roof["traffic"] = pmc_traffic_bytes(slow["kpat"])
         roof["peak_probe"] = dev.mfma_f64_peak()
-        out = {
-            "metric": "ms/IP-iteration (Schur assembly + solve), dense SDP n=2000 m=4000",
-            "value": ms_per_step, "unit": "ms", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ranks_seen": dist.get_world_size() if sharded else 1,
-            "ms_per_step": ms_per_step, "higher_is_better": False, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"C4 synthetic dense SDP, matrix side {msz}, {nvar} constraints, kit=0 "
-                                   f"(assembly + Cholesky + predictor/corrector solves)",
-                       "msz": msz, "nvar": nvar, "seed": args.seed,
-                       "parallelism": "1 GPU" if world == 1 else (
-                           f"columns of the matrix variable over {world} GPUs + RCCL all-reduce of the partial Schur matrices"
-                           if chol_path else f"Schur column blocks over {world} GPUs + RCCL all-gather")},
-            "algorithmic_tflops": flops_model(msz, nvar) / (ms_per_step * 1e-3) / 1e12,
-            "assembly_path": ("cholesky (H_ij = <L'A_iL, L'A_jL>, W = LL')" if chol_path
-                              else ("T_k = L (L'A_kL) L', W = LL'" if via_l else "T_k = W A_k W")),
-            "roofline": roof,
-            "phase_ms_per_step": slow["phases"],
-            "dely_checksum": chk,
-            "data_gen_s": t_gen,
-        }
+        out.update({"roofline": roof, "phase_ms_per_step": slow["phases"], "dely_checksum": chk})
         if world > 1:
             out["per_rank"] = [{"rank": r_["rank"], "columns": r_["columns"], "assemble_ms": r_["phases"]["assemble"],
                                 "gemm1_ms": r_["phases"]["gemm1"], "gemm2_ms": r_["phases"]["gemm2"],
@@ -447,11 +492,6 @@ def main():
             dev.close()
             out["cpu_baseline"] = cpu_baseline(args.cpu_msz, args.cpu_nvar, args.seed + 7, args.cpu_msz2,
                                                args.cpu_nvar2, args.cpu_sample2)
-        print(json.dumps(out), flush=True)
-    if sharded:
-        dist.barrier()
-        dist.destroy_process_group()
-
 
 if __name__ == "__main__":
     main()

@@ -145,3 +145,34 @@ def test_bench_dense_instance_is_the_oracles_model():
     Hs = lo.makeBBBBsi(0, bench._DenseRows(rows, msz), AA, W, nvar, qA, sigmaA, ii_stop=7)
     assert np.array_equal(Hs[:, :7], H[:, :7])
     assert np.count_nonzero(Hs[7:, 7:]) == 0                       # nothing beyond the sampled constraints
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs`: float64 files, all of H when it is small, otherwise the same seeded 2^20 entries
+    (column-major positions) on every run -- well inside 64 MB."""
+    import torch
+    import bench
+
+    class FakeDev:
+        def __init__(self, n):
+            self.n = n
+
+        def schur_get(self):
+            return np.arange(self.n * self.n, dtype=np.float64).reshape(self.n, self.n, order="F")
+
+    for n in (300, 1100):
+        x = torch.arange(n, dtype=torch.float64)
+        got = []
+        for run in ("a", "b"):
+            d = tmp_path / f"{n}{run}"
+            bench.dump_outputs(str(d), FakeDev(n), x, -x, 7)
+            got.append({f: np.load(d / f) for f in ("dely_predictor.npy", "dely_corrector.npy", "schur_H_sample.npy")})
+            assert sum(os.path.getsize(d / f) for f in os.listdir(d)) < 64 << 20
+        for f, a in got[0].items():
+            assert a.dtype == np.float64 and np.array_equal(a, got[1][f])
+        assert np.array_equal(got[0]["dely_corrector.npy"], -np.arange(n))
+        H = got[0]["schur_H_sample.npy"]
+        if n * n <= 1 << 20:
+            assert np.array_equal(H, np.arange(n * n))
+        else:
+            assert H.size == 1 << 20 and np.all(np.diff(H) > 0) and 0 <= H[0] and H[-1] < n * n

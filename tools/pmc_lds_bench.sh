@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/pmc_lds; rm -rf $O; mkdir -p $O
-timeout -k 10 400 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES --kernel-trace --output-format csv -d $O/p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $O/p.log 2>&1
+timeout -k 10 400 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES --kernel-trace --output-format csv -d $O/p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $O/p.log 2>&1
 python3 - <<'PY'
 import csv, glob, collections
 fs=glob.glob("gpurun_out/pmc_lds/p/*/*counter_collection.csv")
