@@ -51,6 +51,13 @@ int lrn_upload_model(lrn_ctx* ctx, int nlmi, int nvar, const int64_t* msizes,
                      const int64_t* sigmaA, const int64_t* qA,
                      int nlin, const int64_t* Clin_colptr, const int64_t* Clin_rowval,
                      const double* Clin_nzval);
+/* Rank-k constraint data of block ilmi (datarank >= 1; reference docs/src/low-rank_data.md): A_k = V_k diag(d_k) V_k'
+ * with d in {+1, -1}, every constraint padded to khat columns (khat = 1, 2, 4, 8 or 16; padding columns empty, weight 0).
+ * V: (nvar * khat) x msz CSC, 1-based, row k * khat + p = column p of V_k (the orientation of B above); d: nvar * khat
+ * weights in the same order.  Call after lrn_upload_model / lrn_synthetic_dense_model; lrn_schur_assemble(mode 1) uses
+ * them.  AA stays what every other entry point reads. */
+int lrn_upload_lowrank(lrn_ctx* ctx, int ilmi, int khat, const int64_t* V_colptr, const int64_t* V_rowval,
+                       const double* V_nzval, const double* d);
 /* Builder-defined synthetic dense SDP data generated on the device:
  * A_k = (R_k + R_k')/2, R_k iid N(0,1) from a counter-based Philox stream; nlmi = 1. */
 int lrn_synthetic_dense_model(lrn_ctx* ctx, int msz, int nvar, uint64_t seed);
@@ -106,7 +113,8 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * sparse: from this matrix side on through the pattern entries of W M W), "lyap_form" (second-order term of the corrector:
  * 1 = the better conditioned equivalent Lyapunov equation (Yh/s + s Zh) R + R (.) = C/s + s Zh C Zh, 0 = Yh R + R Yh = C),
  * "ns_lanczos" / "ns_lanczos_min" (1: scale and schedule of the Newton-Schulz iteration from a 24-step Lanczos run on K for
- * blocks of side >= ns_lanczos_min = 1500), "comm_fail_ensure" (test hook: the next exchange of this rank fails its buffer
+ * blocks of side >= ns_lanczos_min = 1500), "lowrank_form" (rank-k assembly, mode 1: U = G'V by a gather over the factor
+ * entries (0), one dense MFMA product (1), or by the factors' density (-1, default)), "comm_fail_ensure" (test hook: the next exchange of this rank fails its buffer
  * allocation), "reset_timing". */
 int lrn_set_option(lrn_ctx* ctx, const char* key, double value);
 /* multi-GPU: this context assembles the Schur columns it owns (block-cyclic) */
@@ -123,8 +131,9 @@ int lrn_set_scaling(lrn_ctx* ctx, int ilmi, const double* W, const double* G_or_
 int lrn_set_lin(lrn_ctx* ctx, const double* X_lin, const double* S_lin_inv);
 
 /* ---- Schur complement: makeBBBBs / makeBBBB_rank1 (src/makeBBBB.jl:1-218) ------------- */
-/* mode 0 = general (makeBBBBs), -1 = rank-one data (makeBBBB_rank1); adds the C_lin term
- * (predictor_corrector.jl:36-38).  H_out (nvar x nvar) may be NULL; when given it receives
+/* mode 0 = general (makeBBBBs), -1 = rank-one data (makeBBBB_rank1), 1 = rank-k factors of lrn_upload_lowrank
+ * (H_ij = sum d_p d_q (u_p'u_q)^2 over the factor columns p of A_i, q of A_j, U = G'V; LRN_ERR_STATE without factors
+ * or without G / W); adds the C_lin term (predictor_corrector.jl:36-38).  H_out (nvar x nvar) may be NULL; when given it receives
  * Matrix(Hermitian(BBBB, :L)) (predictor_corrector.jl:39). */
 int lrn_schur_assemble(lrn_ctx* ctx, int mode, double* H_out);
 int lrn_schur_get(lrn_ctx* ctx, double* H_out);

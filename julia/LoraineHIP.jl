@@ -17,6 +17,7 @@ const LIB = get(ENV, "LORAINE_HIP_LIB", joinpath(@__DIR__, "..", "loraine.jl_amd
 mutable struct Ctx
     h::Ptr{Cvoid}
     chol_is_object::Bool      # this IP iteration's factor came out of the +1e-4*I loop (predictor_corrector.jl:85)
+    lowrank::Bool             # rank-k factors uploaded (upload_lowrank!): datarank >= 1 assembles from them (mode 1)
 end
 
 function check(ctx::Ctx, rc::Cint, what)
@@ -29,7 +30,7 @@ function Ctx(device::Integer = 0)
     r = Ref{Ptr{Cvoid}}(C_NULL)
     rc = ccall((:lrn_create, LIB), Cint, (Ref{Ptr{Cvoid}}, Cint), r, device)
     rc == 0 || error("lrn_create failed ($rc): no MI355X visible? (there is no CPU fallback)")
-    ctx = Ctx(r[], false)
+    ctx = Ctx(r[], false, false)
     finalizer(c -> ccall((:lrn_destroy, LIB), Cint, (Ptr{Cvoid},), c.h), ctx)
     return ctx
 end
@@ -62,6 +63,15 @@ function upload_model!(ctx::Ctx, model)
             model.nlin, lcp, lrv, lnz)
     end
     check(ctx, rc, "lrn_upload_model")
+end
+
+# ---- rank-k factors of block i (datarank = k >= 1, docs/src/low-rank_data.md): A_j = V_j diag(d_j) V_j', every
+# constraint padded to khat in (1, 2, 4, 8, 16) columns; V is (n * khat) x msz, row (j - 1) * khat + p = column p of V_j
+function upload_lowrank!(ctx::Ctx, i::Integer, khat::Integer, V::SparseMatrixCSC{Float64, Int64}, d::Vector{Float64})
+    check(ctx, ccall((:lrn_upload_lowrank, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+        ctx.h, i - 1, khat, V.colptr, V.rowval, V.nzval, d), "lrn_upload_lowrank")
+    ctx.lowrank = true
 end
 
 # ---- prepare_W (src/prepare_W.jl:28-94) -------------------------------------------------------
@@ -98,7 +108,7 @@ function makeBBBB!(ctx::Ctx, solver; want_matrix::Bool = false)
         check(ctx, ccall((:lrn_set_lin, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
             ctx.h, vec(solver.X_lin), vec(solver.S_lin_inv)), "lrn_set_lin")
     end
-    mode = solver.datarank == -1 ? -1 : 0
+    mode = solver.datarank >= 1 && ctx.lowrank ? 1 : (solver.datarank == -1 ? -1 : 0)
     H = want_matrix ? Matrix{Float64}(undef, solver.model.n, solver.model.n) : nothing
     check(ctx, ccall((:lrn_schur_assemble, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}),
         ctx.h, mode, want_matrix ? H : C_NULL), "lrn_schur_assemble")

@@ -46,6 +46,12 @@ struct LmiBlock {
   bool has_B = false;
   long bnnz = 0;
   lrn::DBuf b_ptr, b_col, b_val;
+  // rank-k factors (datarank >= 1, lrn_upload_lowrank): A_k = V_k diag(d_k) V_k', every constraint padded to lr_khat
+  // columns; CSR by factor column h * lr_khat + p in H index order (h = position when nlmi == 1), weights in that order
+  int lr_khat = 0;
+  bool has_V = false;
+  long vnnz = 0;
+  lrn::DBuf v_ptr, v_col, v_val, v_w;
   // --- NT scaling state (device, msz x msz col-major)
   lrn::DBuf X, S, W, G, Gi, Si, D, DDsi;
   lrn::DBuf Vprev;          // right singular vectors of the previous prepare_W (Jacobi warm start)
@@ -63,6 +69,8 @@ struct LmiBlock {
   bool chol_valid = false;  // LXf, LSf hold the Cholesky factors of the CURRENT X, S (nt_factor; lrn_ip_stats computes them as its
                             // positive-definiteness certificate, the next prepare_w_ns re-uses them)
   bool have_Bd = false;     // dense copy of the rank-one factors (rank-one assembly from W)
+  lrn::DBuf Vd;             // dense copy of the rank-k factors, msz x (nvar * lr_khat) (dense U product, assembly from W)
+  bool have_Vd = false;
 };
 
 struct lrn_ctx;
@@ -125,6 +133,8 @@ struct LrnOptions {
   int matvec_h = 0;               // CG operator through the assembled Schur matrix (hop.hip): 0 auto (cost model), 1 never
                                   // (the matrix-free MyA always), 2 always
   int pcg_lookahead = 2;          // lrn_pcg: iterations the host queues beyond the one whose convergence test it has read
+  int lowrank_form = -1;          // rank-k assembly: U = G' V (or W V) by a sparse gather (0), one dense MFMA product (1), by the
+                                  // factors' density (-1)
 };
 
 struct lrn_ctx {
@@ -158,7 +168,7 @@ struct lrn_ctx {
   bool H_partial = false;     // world > 1, Cholesky path: H is this rank's partial SUM (exchange = all-reduce)
   bool H_owned_only = false;  // world > 1: H holds only the column blocks this rank assembled (CG operator, hop.hip)
   // which NT scaling (W of every block, X_lin ./ S_lin) the assembled H belongs to: scal_version counts the changes of the
-  // scaling, H_version is its value at the last assembly, H_mode the mode of that assembly (0 general, -1 rank-one)
+  // scaling, H_version is its value at the last assembly, H_mode the mode of that assembly (0 general, -1 rank-one, 1 rank-k)
   long scal_version = 0, H_version = -1;
   int H_mode = 0;
   // CG operator through the assembled matrix (hop.hip): the decision taken for scaling `hop_version`, the operator

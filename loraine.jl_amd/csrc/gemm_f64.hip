@@ -212,6 +212,50 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
   }
 
   // ---- epilogue
+  if (EPI && (d.flags & GEMM_SQUARE_BLOCKSUM)) {
+    // rank-k Schur assembly: every kb x kb block of the weighted squares lies inside one 16 x 16 accumulator block
+    // (kb | 16).  Columns of a block are lanes fr .. fr + kb - 1 (xor 1 .. kb/2), rows are (lane >> 4) + 4 r: kb = 2, 4
+    // pair / join the lane quarters (xor 16, 32), kb = 8, 16 also the registers.  A butterfly leaves the same sum in every
+    // lane of the group (x + y == y + x): one lane stores it.  Rows and columns beyond M / N hold zeros (zero operands,
+    // zero weight) and take part in the shuffles, which the whole wave executes.
+    const int kb = d.blk_k;
+    const int kq = kb < 4 ? kb : 4;                  // rows of a block among the lane quarters
+    const int rstep = kb > 4 ? kb / 4 : 1;           // registers per block
+    const bool lo = d.flags & GEMM_TRI_LOWER, up = d.flags & GEMM_TRI_UPPER;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int mb0 = m0 + wm * (BM / 2) + i * 16;
+        const int n = n0 + wn * (BN / 2) + j * 16 + fr;
+        const double wcol = n < d.N ? d.blk_w[n] : 0.0;
+        double s[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = mb0 + MFMA_F64_ROW(lane, r);
+          const double v = d.alpha * acc[i][j][r];
+          s[r] = v * v * (m < d.M ? d.blk_w[m] : 0.0) * wcol;
+        }
+        if (kb >= 8) { s[0] += s[1]; s[2] += s[3]; }
+        if (kb >= 16) s[0] += s[2];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (r % rstep) continue;
+          double v = s[r];
+          for (int o = 1; o < kb && o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+          if (kb >= 2) v += __shfl_xor(v, 16, 64);
+          if (kb >= 4) v += __shfl_xor(v, 32, 64);
+          const int m = mb0 + MFMA_F64_ROW(lane, r);
+          if ((fr % kb) || ((lane >> 4) % kq) || m >= d.M || n >= d.N) continue;
+          const int bm = m / kb, bn = n / kb;
+          if ((lo && bm < bn) || (up && bm > bn)) continue;
+          double* c = Cg + (long)bm * d.sCm + (long)bn * d.sCn;
+          if (d.beta != 0.0) v += d.beta * (*c);
+          *c = v;
+        }
+      }
+    return;
+  }
   const bool x2 = EPI && (d.flags & GEMM_OFFDIAG_X2) && (tm != tn);
   const double alpha = x2 ? 2.0 * d.alpha : d.alpha;
   const bool sq = EPI && (d.flags & GEMM_SQUARE);
@@ -979,12 +1023,13 @@ static bool kseg_lds_path_ok(const GemmDesc& d) {
   if ((d.flags & GEMM_KFLAT) ? ((d.kflat_total & 15) || (d.kflat_diag & 15)) : (d.kseg_ld & 15)) return false;
   if ((d.sAm & 1) || (d.sBn & 1) || (d.bA & 1) || (d.bB & 1)) return false;
   if (((uintptr_t)d.A & 15) || ((uintptr_t)d.B & 15)) return false;
-  if (d.flags & (GEMM_OFFDIAG_X2 | GEMM_SQUARE)) return false;
+  if (d.flags & (GEMM_OFFDIAG_X2 | GEMM_SQUARE | GEMM_SQUARE_BLOCKSUM)) return false;
   return true;
 }
 
 static bool lds_path_ok(const GemmDesc& d) {
   if (d.sAm != 1 || d.sBn != 1 || d.ksplit != 1) return false;
+  if (d.flags & GEMM_SQUARE_BLOCKSUM) return false;        // (its epilogue is the generic kernel's)
   // (round 4: rows that are only 8-byte aligned -- odd leading dimensions -- are fine: the 16-byte DMA was measured correct
   // from them on gfx950, tools/probe_unaligned_dma.py and test_gpu_blocks.py; LRN_LDS_ALIGNED=1 restores the old rule)
   static const bool aligned_only = getenv("LRN_LDS_ALIGNED") != nullptr;
@@ -1217,6 +1262,12 @@ static int gemm_impl(hipStream_t st, const GemmDesc& din) {
   if (kfrom && (d.ksplit != 1 || kseg)) return gemm_fail(LRN_ERR_ARG, "gemm: kfrom && (d.ksplit != 1 || kseg)");
   if ((d.flags & (GEMM_KFROM_N | GEMM_KTO_N)) && d.N > d.K) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & (GEMM_KFROM_N | GEMM_KTO_N)) && d.N > d.K");
   if ((d.flags & (GEMM_KFROM_M | GEMM_KTO_M)) && d.M > d.K) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & (GEMM_KFROM_M | GEMM_KTO_M)) && d.M > d.K");
+  if ((d.flags & GEMM_SQUARE_BLOCKSUM) &&
+      (!d.blk_w || d.blk_k < 1 || d.blk_k > 16 || (d.blk_k & (d.blk_k - 1)) || d.M % d.blk_k || d.N % d.blk_k ||
+       d.ksplit != 1 || d.batch != 1 || kseg || kfrom || d.C2 ||
+       (d.flags & (GEMM_SQUARE | GEMM_OFFDIAG_X2 | GEMM_C_PACKED | GEMM_C_MIRROR))))
+    return gemm_fail(LRN_ERR_ARG, "gemm: GEMM_SQUARE_BLOCKSUM needs blk_w, blk_k in {1, 2, 4, 8, 16} dividing M and N, one "
+                                  "unsplit, unbatched product and no other epilogue");
   if ((d.flags & GEMM_C_PACKED) && (d.pk_off & 15)) return gemm_fail(LRN_ERR_ARG, "gemm: GEMM_C_PACKED needs pk_off % 16 == 0 (block width of the packed layout)");
   if ((d.flags & GEMM_C_PACKED) && (!swapped || d.pk_m <= 0 || d.beta != 0.0)) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & GEMM_C_PACKED) && (!swapped || d.pk_m <= 0 || d.beta != 0.0)");
   // tile choice: 128x128 unless the problem is too small to fill the chip with it
@@ -1375,7 +1426,7 @@ static int gemm_impl(hipStream_t st, const GemmDesc& din) {
   const bool bkc = (d.sBk == 1 && d.sBn != 1);
   dim3 grid(ntile, 1, d.batch * d.ksplit);
   if (grid.z > 65535) return gemm_fail(LRN_ERR_ARG, "gemm: grid.z > 65535");
-  const bool epi = (d.flags & (GEMM_OFFDIAG_X2 | GEMM_SQUARE | GEMM_C_PACKED | GEMM_C_MIRROR)) || d.C2;
+  const bool epi = (d.flags & (GEMM_OFFDIAG_X2 | GEMM_SQUARE | GEMM_SQUARE_BLOCKSUM | GEMM_C_PACKED | GEMM_C_MIRROR)) || d.C2;
   if (d.C2 && (d.M != d.N || d.batch != 1 || d.ksplit != 1 || kseg)) return gemm_fail(LRN_ERR_ARG, "gemm: C2 needs a square, unbatched, unsplit product");
   if (kflat) {
     if (big) {

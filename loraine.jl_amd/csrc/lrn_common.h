@@ -74,6 +74,10 @@ enum : int {
   GEMM_LAB_NO_KLOOP = 1 << 21,  // ... without its K loop (the first K-step is still loaded and waited for)
   GEMM_LAB_NO_LOAD = 1 << 22,   // ... without the first load either (with the two above: an empty workgroup)
   GEMM_LAB_ONE_WG = 1 << 23,    // ... launched with 24 KB of unused dynamic LDS: one workgroup per CU instead of two
+  GEMM_SQUARE_BLOCKSUM = 1 << 26, // epilogue of the rank-k Schur assembly (generic kernel): t = (alpha*acc)^2 * w[m] * w[n],
+                           // summed over each blk_k x blk_k block (blk_k | 16: a block lies in one MFMA accumulator block, the
+                           // sum is a fixed butterfly over registers and lanes of one wave); C[m / blk_k][n / blk_k] = sum
+                           // (+ beta*c), with TRI_LOWER / TRI_UPPER only the blocks on and below / above the diagonal
   GEMM_KFLAT = 512,        // both operands K-contiguous, K = flat index of the packed lower layout;
                            // the first kflat_nsd splits cover the diagonal blocks [0, kflat_diag), the
                            // others the strictly-lower blocks [kflat_diag, K)
@@ -143,6 +147,10 @@ struct GemmDesc {
   unsigned long long* lab_trace = nullptr;   // measurement only (LRN_MID_TRACE): 8 words per workgroup, clocks of its phases
   int kstagger = 0;        // GEMM_KFLAT: workgroup (tm, tn) starts its K walk ((tm + tn) & 7) * kstagger chunks into
                            // its split and wraps around (see gemm_f64_kseg_lds_kernel)
+  // GEMM_SQUARE_BLOCKSUM: weight of row m and of column n (one vector: op(A) and op(B) index the same factor list from
+  // the same origin), block side 1, 2, 4, 8 or 16; M and N multiples of it
+  const double* blk_w = nullptr;
+  int blk_k = 0;
 };
 
 int gemm(hipStream_t st, const GemmDesc& d);

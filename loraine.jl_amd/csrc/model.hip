@@ -162,7 +162,7 @@ static void free_block(LmiBlock& b) {
   release(b.tri_tab);
   for (DBuf* d : {&b.ent_ptr, &b.ent_r, &b.ent_c, &b.ent_v, &b.Adense, &b.hidx, &b.sigma_d, &b.ipos_d, &b.cq_q, &b.cq_ptr, &b.cq_j, &b.cq_v, &b.pc_ptr, &b.pc_r, &b.pc_t, &b.ent_t, &b.Mv, &b.Zs, &b.b_ptr, &b.b_col,
                   &b.b_val, &b.X, &b.S, &b.W, &b.G, &b.Gi, &b.Si, &b.D, &b.DDsi, &b.Vprev, &b.Cd, &b.Rd, &b.delX, &b.delS, &b.Xn, &b.Sn, &b.RNT,
-                  &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd})
+                  &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd, &b.v_ptr, &b.v_col, &b.v_val, &b.v_w, &b.Vd})
     release(*d);
 }
 
@@ -548,4 +548,70 @@ extern "C" int lrn_get_constraint(lrn_ctx* c, int ilmi, int k, double* A_out) {
                      b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), pos,
                      c->scratch.as<double>(), b.msz);
   return copy_out(c, A_out, c->scratch.p, mm);
+}
+
+// Rank-k factors of the constraints of block ilmi (datarank >= 1): A_k = V_k diag(d_k) V_k', V as an (nvar * khat) x msz
+// CSC (1-based; row k * khat + p = column p of V_k, the orientation of B in lrn_upload_model), d[nvar * khat].  Stored as
+// CSR by factor column in H index order (schur.hip::assemble_lowrank).  Host or device arrays.
+extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t* V_colptr, const int64_t* V_rowval,
+                                  const double* V_nzval, const double* d) {
+  if (!c) return LRN_ERR_ARG;
+  if (ilmi < 0 || ilmi >= c->nlmi) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: block %d of %d", ilmi, c->nlmi);
+  if (khat != 1 && khat != 2 && khat != 4 && khat != 8 && khat != 16)
+    return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: khat = %d (1, 2, 4, 8 or 16)", khat);
+  if (!V_colptr || !d) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: null factor array");
+  LRN_HIP(c, hipSetDevice(c->device));
+  LmiBlock& b = c->lmi[ilmi];
+  const int m = b.msz, nvar = c->nvar;
+  const long R = (long)nvar * khat;
+  if ((double)R * m >= 9.0e18 / 8.0 || R > 0x7fffffffL) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: too many factor columns");
+  std::vector<int64_t> cp(m + 1);
+  LRN_HIP(c, hipMemcpy(cp.data(), V_colptr, (size_t)(m + 1) * 8, hipMemcpyDefault));
+  const long nnz = cp[m] - 1;
+  if (cp[0] != 1 || nnz < 0) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: colptr must start at 1 and not decrease");
+  for (int q = 0; q < m; ++q)
+    if (cp[q + 1] < cp[q]) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: colptr decreases at column %d", q);
+  if (nnz > 0 && (!V_rowval || !V_nzval)) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: null factor array");
+  std::vector<int64_t> rv(nnz);
+  std::vector<double> nz(nnz), w(R), wh(R);
+  if (nnz > 0) {
+    LRN_HIP(c, hipMemcpy(rv.data(), V_rowval, (size_t)nnz * 8, hipMemcpyDefault));
+    LRN_HIP(c, hipMemcpy(nz.data(), V_nzval, (size_t)nnz * 8, hipMemcpyDefault));
+  }
+  LRN_HIP(c, hipMemcpy(w.data(), d, (size_t)R * 8, hipMemcpyDefault));
+  // factor row k * khat + p -> U column hrow(k) * khat + p
+  auto hcol = [&](long r) { const long k = r / khat; return (long)(c->pos_space ? b.ipos[k] : (int)k) * khat + r % khat; };
+  std::vector<long> ptr(R + 1, 0);
+  for (long e = 0; e < nnz; ++e) {
+    if (rv[e] < 1 || rv[e] > R) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: rowval %lld out of range", (long long)rv[e]);
+    ptr[hcol(rv[e] - 1) + 1]++;
+  }
+  for (long h = 0; h < R; ++h) ptr[h + 1] += ptr[h];
+  std::vector<int> col(nnz);
+  std::vector<double> val(nnz);
+  std::vector<long> fill(ptr.begin(), ptr.end() - 1);
+  for (int q = 0; q < m; ++q)
+    for (long e = cp[q] - 1; e < cp[q + 1] - 1; ++e) {
+      const long f = fill[hcol(rv[e] - 1)]++;
+      col[f] = q;
+      val[f] = nz[e];
+    }
+  for (long r = 0; r < R; ++r) wh[hcol(r)] = w[r];
+  LRN_TRY(ensure(c, b.v_ptr, (size_t)(R + 1) * 8));
+  LRN_TRY(ensure(c, b.v_col, (size_t)std::max<long>(nnz, 1) * 4));
+  LRN_TRY(ensure(c, b.v_val, (size_t)std::max<long>(nnz, 1) * 8));
+  LRN_TRY(ensure(c, b.v_w, (size_t)R * 8));
+  LRN_TRY(copy_in(c, b.v_ptr.p, ptr.data(), (size_t)(R + 1) * 8));
+  if (nnz > 0) {
+    LRN_TRY(copy_in(c, b.v_col.p, col.data(), (size_t)nnz * 4));
+    LRN_TRY(copy_in(c, b.v_val.p, val.data(), (size_t)nnz * 8));
+  }
+  LRN_TRY(copy_in(c, b.v_w.p, wh.data(), (size_t)R * 8));
+  release(b.Vd);                 // (the dense copy is rebuilt from these factors on first use)
+  b.have_Vd = false;
+  b.lr_khat = khat;
+  b.vnnz = nnz;
+  b.has_V = true;
+  LRN_HIP(c, hipStreamSynchronize(c->stream));
+  return LRN_OK;
 }

@@ -20,6 +20,8 @@
 //        makeBBBB.jl:188-209, is its 1x1 case).
 //   rank-one data (mode -1): BG = B G (sparse x dense), H += (BG BG').^2 with the square
 //        fused in the MFMA GEMM epilogue (makeBBBB.jl:7-14).
+//   rank-k data (mode 1): U = G' V, H += blocksum(d d' .* (U'U).^2) over khat x khat blocks, again in the
+//        epilogue of one MFMA product (assemble_lowrank).
 #include <algorithm>
 
 #include "ctx.h"
@@ -195,6 +197,20 @@ __global__ void b_dense_kernel(const long* __restrict__ bptr, const int* __restr
                                int msz, double* __restrict__ Bdt) {
   const int h = blockIdx.x;
   for (long f = bptr[h] + threadIdx.x; f < bptr[h + 1]; f += blockDim.x) Bdt[(long)bcol[f] + (long)h * msz] = bval[f];
+}
+
+// U[k + h*msz] = sum_e val_e M[col_e, k]  (one workgroup per factor column h): U = G' V, or U = W V from the symmetric W read
+// down its columns (sym, coalesced)
+__global__ __launch_bounds__(256) void lowrank_gather_kernel(const long* __restrict__ ptr, const int* __restrict__ col,
+                                                             const double* __restrict__ val, const double* __restrict__ M,
+                                                             int msz, int sym, double* __restrict__ U) {
+  const long h = blockIdx.x;
+  const long b = ptr[h], e = ptr[h + 1];
+  for (int k = threadIdx.x; k < msz; k += 256) {
+    double s = 0.0;
+    for (long f = b; f < e; ++f) s += val[f] * (sym ? M[(long)k + (long)col[f] * msz] : M[(long)col[f] + (long)k * msz]);
+    U[(long)k + h * msz] = s;
+  }
 }
 
 // H += C_lin diag(xs) C_lin'  (lower triangle): one thread per target entry sums its contributions in
@@ -423,7 +439,7 @@ static bool chol_path_applicable(lrn_ctx* c, LmiBlock& b, long* pcap_out) {
 // lrn_schur_plan: 1 = the next assembly of this rank would take the Cholesky path (partial sums, all-reduce),
 // 0 = Schur column blocks (all-gather) -- from this rank's own view
 int schur_plan(lrn_ctx* c, int mode) {
-  if (mode == -1 || c->nlmi != 1) return 0;
+  if (mode == -1 || mode == 1 || c->nlmi != 1) return 0;
   LmiBlock& b = c->lmi[0];
   long pcap = 0;
   const int pin = c->opt.schur_plan;
@@ -969,6 +985,73 @@ static int assemble_rank1(lrn_ctx* c, LmiBlock& b) {
   return LRN_OK;
 }
 
+// Rank-k data (mode 1): A_k = V_k diag(d_k) V_k' with every constraint padded to khat columns (zero columns of weight 0).
+// With U = G' V (or W V against the dense copy of V when only W exists, as assemble_rank1 does) and T = U' U (U' V):
+//     H_ij = tr(A_i W A_j W) = sum_{p in i, q in j} d_p d_q (u_p' v_q)^2,
+// the entrywise square of T weighted by d d' and summed over khat x khat blocks -- one MFMA product whose epilogue does
+// all of that (GEMM_SQUARE_BLOCKSUM), T never stored.  A sign flip of a whole constraint leaves H unchanged, so the sign
+// convention of AA (row j = -vec(A_j)) does not matter here.  Blocks accumulate (beta = 1) into the zeroed H.
+static int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
+  const int n = c->nvar, m = b.msz;
+  if (!b.has_V) return set_error(c, LRN_ERR_STATE, "rank-k mode requested but no factors were uploaded (lrn_upload_lowrank)");
+  const bool fromW = !b.have_G;
+  if (fromW && !b.have_W) return set_error(c, LRN_ERR_STATE, "rank-k mode needs G or W (lrn_prepare_w / lrn_set_scaling)");
+  const int kh = b.lr_khat;
+  const long R = (long)n * kh;
+  const double* M = fromW ? b.W.as<double>() : b.G.as<double>();
+  // U by one dense product or by a gather over the stored factor entries: the gather reads nnz * msz words of G / W, the
+  // product does 2 R msz^2 flop -- the gather wins below a density of about 2 %
+  const bool dense = c->opt.lowrank_form == 1 || (c->opt.lowrank_form < 0 && (double)b.vnnz > 0.02 * (double)R * m);
+  if ((dense || fromW) && !b.have_Vd) {
+    LRN_TRY(ensure(c, b.Vd, (size_t)m * R * 8));
+    LRN_HIP(c, hipMemsetAsync(b.Vd.p, 0, (size_t)m * R * 8, c->stream));
+    hipLaunchKernelGGL(b_dense_kernel, dim3((unsigned)R), dim3(64), 0, c->stream, b.v_ptr.as<long>(), b.v_col.as<int>(),
+                       b.v_val.as<double>(), m, b.Vd.as<double>());
+    b.have_Vd = true;
+  }
+  LRN_TRY(ensure(c, c->BG, (size_t)m * R * 8));
+  double* U = c->BG.as<double>();
+  tic(c);
+  if (dense) {
+    GemmDesc g;     // U = G' Vd (or W Vd), msz x R
+    g.A = M;
+    if (fromW) { g.sAm = 1; g.sAk = m; } else { g.sAm = m; g.sAk = 1; }
+    g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
+    g.C = U; g.sCm = 1; g.sCn = m;
+    g.M = m; g.N = (int)R; g.K = m;
+    LRN_TRY(gemm(c->stream, g));
+  } else {
+    hipLaunchKernelGGL(lowrank_gather_kernel, dim3((unsigned)R), dim3(256), 0, c->stream, b.v_ptr.as<long>(),
+                       b.v_col.as<int>(), b.v_val.as<double>(), M, m, fromW ? 1 : 0, U);
+  }
+  toc(c, "lowrank_u");     // (U alone; "lowrank" below: U and the blocked product, from the same start)
+  // owned column blocks of the lower triangle (all of it on one GPU): H column j <-> U columns j kh .. j kh + kh - 1
+  std::vector<std::pair<int, int>> cols;
+  if (c->world > 1) {
+    for (int c0 = 0; c0 < n; c0 += c->shard_bs)
+      if (shard_owner(c0 / c->shard_bs, c->world) == c->rank) cols.push_back({c0, std::min(n, c0 + c->shard_bs)});
+  } else {
+    cols.push_back({0, n});
+  }
+  for (auto& cb : cols) {
+    const int c0 = cb.first, c1 = cb.second;
+    const long u0 = (long)c0 * kh * m;
+    GemmDesc g;     // H[c0:, c0:c1] += blocksum(d d' .* (U' U)[c0 kh:, c0 kh:c1 kh].^2), lower blocks
+    g.A = U + u0; g.sAm = m; g.sAk = 1;
+    g.B = (fromW ? b.Vd.as<double>() : U) + u0; g.sBk = 1; g.sBn = m;
+    g.C = c->H.as<double>() + (long)c0 + (long)c0 * n; g.sCm = 1; g.sCn = n;
+    g.M = (n - c0) * kh; g.N = (c1 - c0) * kh; g.K = m;
+    g.beta = 1.0;
+    g.flags = GEMM_TRI_LOWER | GEMM_SQUARE_BLOCKSUM;
+    g.blk_w = b.v_w.as<double>() + (long)c0 * kh;
+    g.blk_k = kh;
+    LRN_TRY(gemm(c->stream, g));
+  }
+  toc(c, "lowrank");
+  if (!c->profile) c->counts["lowrank"] += 1;     // (the route is counted whether or not the phases are timed)
+  return LRN_OK;
+}
+
 int schur_assemble(lrn_ctx* c, int mode) {
   const int n = c->nvar;
   if (n <= 0) return set_error(c, LRN_ERR_STATE, "no model uploaded");
@@ -986,6 +1069,10 @@ int schur_assemble(lrn_ctx* c, int mode) {
   for (auto& b : c->lmi) {
     if (mode == -1) {
       LRN_TRY(assemble_rank1(c, b));
+      continue;
+    }
+    if (mode == 1) {
+      LRN_TRY(assemble_lowrank(c, b));
       continue;
     }
     if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");

@@ -180,6 +180,16 @@ class Device:
         self._chk(rc, "lrn_upload_model")
         self.nvar, self.msizes, self.nlin = nvar, [int(x) for x in ms], nlin
 
+    def upload_lowrank(self, ilmi, khat, V, d):
+        """Rank-k factors of block ilmi: V (nvar * khat x msz, sparse or dense), row k * khat + p = column p of V_k;
+        d (nvar * khat) weights +-1 (0 in the padding).  Used by schur_assemble(1)."""
+        cp, rv, nz = self._csc64(sp.csc_matrix(V))
+        w = np.ascontiguousarray(np.asarray(d, dtype=np.float64).ravel())
+        if w.size != V.shape[0]:
+            raise ValueError(f"{w.size} weights for {V.shape[0]} factor columns")
+        self._chk(self.lib.lrn_upload_lowrank(self.h, int(ilmi), int(khat), ptr(cp), ptr(rv), ptr(nz), ptr(w)),
+                  "lrn_upload_lowrank")
+
     def synthetic_dense_model(self, msz, nvar, seed):
         self._chk(self.lib.lrn_synthetic_dense_model(self.h, int(msz), int(nvar), C.c_uint64(seed)),
                   "lrn_synthetic_dense_model")

@@ -5,7 +5,7 @@ its construction: SDPA sparse files -> MOI-equivalent sign mapping (src/MOI_wrap
 
     max  b'y - b_const   s.t.  sum_j y_j A_ij <= C_i  (i = 1..nlmi),   C_lin' y <= d_lin
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List
 
 import numpy as np
@@ -29,6 +29,10 @@ class MyModel:
     msizes: np.ndarray
     nlin: int
     nlmi: int
+    # rank-k factors (datarank = k >= 1): per block (V, d, khat), V (n * khat x m_i) sparse with row k * khat + p = column p
+    # of V_k, d the weights +-1 (0 in the padding), A_k = V_k diag(d_k) V_k'; [] when the data has no such form
+    lowrank: list = field(default_factory=list)
+    lowrank_note: str = ""     # why datarank >= 1 found no factors (the solver prints it and falls back to datarank = 0)
 
 
 def _rank_one_rows(blockA, n):
@@ -50,6 +54,111 @@ def _rank_one_rows(blockA, n):
                              "use `datarank = 0` to disable the rank-1 conversion.")
         out[k, support] = bk
     return out.tocsr()
+
+
+LOWRANK_TOL = 5.0e-6          # ||A_k - V_k D_k V_k'||_F, the limit prep_B applies to the rank-one form (src/model.jl:189)
+LOWRANK_MAX = 16              # largest padded rank of the rank-k assembly
+
+
+def padded_rank(r):
+    """khat: the power of two >= r (at least 1)."""
+    k = 1
+    while k < r:
+        k *= 2
+    return k
+
+
+def _factor_residual(Ak, V, d):
+    """||A_k - V diag(d) V'||_F on the union of the supports of A_k and of the rows of V (dense m x r V)."""
+    Ak = sp.csc_matrix(Ak)
+    rows = np.union1d(np.unique(Ak.indices), np.nonzero(np.any(V != 0.0, axis=1))[0]).astype(np.int64)
+    if rows.size == 0:
+        return 0.0
+    sub = Ak[rows, :][:, rows].toarray()
+    Vs = V[rows, :]
+    return float(np.linalg.norm(sub - (Vs * d) @ Vs.T))
+
+
+def lowrank_factor(Ak, m, kmax):
+    """A_k = V diag(d) V' from eigh on the support of A_k: eigenpairs with |lam| > 1e-12 max|lam|, v = u sqrt|lam|,
+    d = sign(lam).  -> (V (m x r dense), d) or None when the rank exceeds kmax or the residual LOWRANK_TOL."""
+    Ak = sp.csc_matrix(Ak)
+    if Ak.nnz == 0:
+        return np.zeros((m, 0)), np.zeros(0)
+    support = np.unique(np.concatenate([Ak.indices, np.repeat(np.arange(m), np.diff(Ak.indptr))]))
+    sub = Ak[support, :][:, support].toarray()
+    lam, vecs = np.linalg.eigh(0.5 * (sub + sub.T))
+    big = np.abs(lam) > 1e-12 * np.max(np.abs(lam)) if lam.size else np.zeros(0, bool)
+    if int(big.sum()) > kmax:
+        return None
+    V = np.zeros((m, int(big.sum())))
+    V[support, :] = vecs[:, big] * np.sqrt(np.abs(lam[big]))
+    d = np.sign(lam[big])
+    if not _factor_residual(Ak, V, d) <= LOWRANK_TOL:
+        return None
+    return V, d
+
+
+def pad_factors(facs, n, m):
+    """[(V_k (m x r_k), d_k)] * n -> (V (n * khat x m) csr, d (n * khat), khat): zero columns of weight 0 in the padding."""
+    khat = padded_rank(max([f[0].shape[1] for f in facs] + [1]))
+    rr, cc, vv = [], [], []
+    d = np.zeros(n * khat)
+    for k, (Vk, dk) in enumerate(facs):
+        r = Vk.shape[1]
+        if r == 0:
+            continue
+        q, p = np.nonzero(Vk)
+        rr.append(k * khat + p)
+        cc.append(q)
+        vv.append(Vk[q, p])
+        d[k * khat:k * khat + r] = dk
+    cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
+    V = sp.csr_matrix((cat(vv, float), (cat(rr, np.int64), cat(cc, np.int64))), shape=(n * khat, m))
+    return V, d, khat
+
+
+def lowrank_factors(A, n, k):
+    """Rank-k factors of every constraint of every block (datarank = k) -> (list of (V, d, khat) per block, "") or
+    ([], reason) when a constraint has no such form: then the whole model takes the general path."""
+    if k > LOWRANK_MAX:
+        return [], f"datarank = {k} > {LOWRANK_MAX}"
+    out = []
+    for i, blk in enumerate(A):
+        m = blk[0].shape[0]
+        facs = []
+        for j in range(n):
+            f = lowrank_factor(blk[j + 1], m, k)
+            if f is None:
+                return [], f"constraint {j + 1} of LMI block {i + 1} is not of rank <= {k}"
+            facs.append(f)
+        out.append(pad_factors(facs, n, m))
+    return out, ""
+
+
+def user_factors(A, n, factors):
+    """factors[i][k] = (V, d) for constraint k + 1 (A[i][k + 1]) -> per block (V, d, khat); a factor that does not
+    reproduce its A_k within LOWRANK_TOL raises ValueError."""
+    if len(factors) != len(A):
+        raise ValueError(f"factors for {len(factors)} LMI blocks, the model has {len(A)}")
+    out = []
+    for i, blk in enumerate(A):
+        m = blk[0].shape[0]
+        if len(factors[i]) != n:
+            raise ValueError(f"block {i + 1}: factors of {len(factors[i])} constraints, the model has {n}")
+        facs = []
+        for j, (V, d) in enumerate(factors[i]):
+            V = np.asarray(V.toarray() if sp.issparse(V) else V, dtype=np.float64).reshape(m, -1)
+            d = np.asarray(d, dtype=np.float64).ravel()
+            if d.size != V.shape[1] or V.shape[1] > LOWRANK_MAX:
+                raise ValueError(f"block {i + 1}, constraint {j + 1}: {V.shape[1]} factor columns, {d.size} weights "
+                                 f"(at most {LOWRANK_MAX})")
+            miss = _factor_residual(blk[j + 1], V, d)
+            if not miss <= LOWRANK_TOL:
+                raise ValueError(f"block {i + 1}, constraint {j + 1}: ||A - V D V'||_F = {miss:.3e} > {LOWRANK_TOL}")
+            facs.append((V, d))
+        out.append(pad_factors(facs, n, m))
+    return out
 
 
 def _prepare_A(A, datarank, kappa, n):
@@ -80,7 +189,7 @@ def _prepare_A(A, datarank, kappa, n):
     return AA, B, C, nzA, sigmaA, qA
 
 
-def build_model(A, b, b_const=0.0, d_lin=None, C_lin=None, datarank=0, kappa=8) -> MyModel:
+def build_model(A, b, b_const=0.0, d_lin=None, C_lin=None, datarank=0, kappa=8, factors=None) -> MyModel:
     n = len(b)
     for blk in A:
         for k in range(len(blk)):
@@ -91,8 +200,13 @@ def build_model(A, b, b_const=0.0, d_lin=None, C_lin=None, datarank=0, kappa=8) 
         C_lin = sp.csr_matrix((n, 0))
         d_lin = np.zeros(0)
     msizes = np.array([blk[0].shape[0] for blk in A], dtype=np.int64)
+    lowrank, note = [], ""
+    if factors is not None:
+        lowrank = user_factors(A, n, factors)
+    elif datarank >= 1 and len(A) > 0:
+        lowrank, note = lowrank_factors(A, n, datarank)
     return MyModel(A, AA, B, C, nzA, sigmaA, qA, np.asarray(b, float), float(b_const), np.asarray(d_lin, float),
-                   sp.csr_matrix(C_lin), n, msizes, int(C_lin.shape[1]), len(A))
+                   sp.csr_matrix(C_lin), n, msizes, int(C_lin.shape[1]), len(A), lowrank, note)
 
 
 def _tokens(line):

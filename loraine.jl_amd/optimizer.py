@@ -70,10 +70,12 @@ class Optimizer:
         self._pending = ("sdpa", path)
         return self
 
-    def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False):
+    def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factors=None):
         """Problem in the reference's own form: max/min over y with LMIs sum_j y_j A_ij - A_i0 >= 0
-        given as A[i] = [F_0, F_1, ..., F_n] and rows  C_lin' y <= d_lin."""
-        self._pending = ("arrays", (A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense)))
+        given as A[i] = [F_0, F_1, ..., F_n] and rows  C_lin' y <= d_lin.
+        factors (optional): factors[i][k] = (V, d) with A[i][k + 1] = V diag(d) V' (V msz x r, r <= 16, d = +-1), used
+        instead of the factors datarank >= 1 would compute; checked against A (||A - V D V'||_F <= 5e-6, else ValueError)."""
+        self._pending = ("arrays", (A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense), factors))
         return self
 
     def _copy_to(self):
@@ -84,9 +86,9 @@ class Optimizer:
             model = model_from_sdpa(payload, datarank=drank, kappa=kappa)
             self.max_sense = False
         else:
-            A, b, b_const, d_lin, C_lin, max_sense = payload
+            A, b, b_const, d_lin, C_lin, max_sense, factors = payload
             self.max_sense = max_sense
-            model = build_model(A, b, b_const, d_lin, C_lin, datarank=drank, kappa=kappa)
+            model = build_model(A, b, b_const, d_lin, C_lin, datarank=drank, kappa=kappa, factors=factors)
         opts = dict(self.options)
         if self.silent:
             opts["verb"] = 0

@@ -80,8 +80,7 @@ class ResidentSolver(MySolver):
             self.Rd_lin = m.d_lin - self.S_lin - m.C_lin.T @ self.y
             dev.set_lin(self.X_lin, self.S_lin_inv)
         if self.kit == 0:
-            mode = -1 if (self.datarank == -1 and m.nlmi > 0) else 0
-            dev.schur_assemble(mode)                                         # [GPU] (+ the exchange when sharded)
+            dev.schur_assemble(self._schur_mode())                           # [GPU] (+ the exchange when sharded)
         rhs = 0.0
         if m.nlmi > 0:
             # Rp = b - AA*vec(X) (:12) is not used before makeRHS (:44): both products in ONE pass over the constraint

@@ -104,6 +104,23 @@ class MySolver:
             self.dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes,
                                   B=model.B if len(model.B) else None,
                                   C_lin=model.C_lin if model.nlin else None)    # [GPU] one-time
+        # datarank = k >= 1 (kit = 0): the Schur matrix from the rank-k factors of the data (mode 1); a model whose data has
+        # no such form (or k > 16) takes the general path, as the reference's docs promise (docs/src/Loraine_options.md)
+        self.lowrank = False
+        if self.datarank >= 1 and self.kit == 0 and model.nlmi > 0:
+            if model.lowrank:
+                for i, (V, d, khat) in enumerate(model.lowrank):
+                    self.dev.upload_lowrank(i, khat, V, d)                      # [GPU] one-time
+                self.lowrank = True
+            else:
+                self._say(f" ---No rank-{self.datarank} factors ({model.lowrank_note}), setting datarank = 0")
+                self.datarank = 0
+
+    def _schur_mode(self):
+        """lrn_schur_assemble mode: -1 rank-one data (datarank = -1), 1 rank-k factors (datarank >= 1), 0 general."""
+        if self.datarank == -1 and self.model.nlmi > 0:
+            return -1
+        return 1 if self.lowrank and self.datarank >= 1 else 0
 
     def _say(self, msg):
         if self.verb > 0:
@@ -277,8 +294,7 @@ class MySolver:
         self.Rp = Rp
         dev = self.dev
         if self.kit == 0:
-            mode = -1 if (self.datarank == -1 and m.nlmi > 0) else 0
-            dev.schur_assemble(mode)                                           # [GPU] makeBBBB*
+            dev.schur_assemble(self._schur_mode())                             # [GPU] makeBBBB*
             if self.dist is not None:
                 self.dist.allgather(dev)                                       # multi-GPU: column blocks -> all ranks
         if m.nlmi > 0:
