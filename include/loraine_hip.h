@@ -55,9 +55,19 @@ int lrn_upload_model(lrn_ctx* ctx, int nlmi, int nvar, const int64_t* msizes,
  * with d in {+1, -1}, every constraint padded to khat columns (khat = 1, 2, 4, 8 or 16; padding columns empty, weight 0).
  * V: (nvar * khat) x msz CSC, 1-based, row k * khat + p = column p of V_k (the orientation of B above); d: nvar * khat
  * weights in the same order.  Call after lrn_upload_model / lrn_synthetic_dense_model; lrn_schur_assemble(mode 1) uses
- * them.  AA stays what every other entry point reads. */
+ * them.  AA stays what every other entry point reads (unless the block is declared factored, below). */
 int lrn_upload_lowrank(lrn_ctx* ctx, int ilmi, int khat, const int64_t* V_colptr, const int64_t* V_rowval,
                        const double* V_nzval, const double* d);
+/* Factored block (after lrn_upload_model and lrn_upload_lowrank): on = 1 declares that the factors ARE the constraint data
+ * of block ilmi -- its AA was uploaded without entries, no A_k exists as a matrix on host or device.  AA vec(.) and
+ * mat(AA' .) of the resident path (lrn_ip_*) then run in factor form: Q = Z Vd by one FP64 MFMA product and a column dot
+ * per constraint; M = -Vd diag(w o x) Vd' by one lower-triangle product, mirrored (exactly symmetric).  The Schur matrix
+ * comes from lrn_schur_assemble(mode 1).  LRN_ERR_STATE when no factors were uploaded or when the block's AA has any entry
+ * (no constraint may be counted twice).  On a factored block lrn_get_constraint, lrn_matvec / lrn_matvec_partial,
+ * lrn_prec_setup, lrn_pcg and modes 0 / -1 of lrn_schur_assemble return LRN_ERR_STATE.  on = 0 takes the declaration back.
+ * lrn_get_count: "op_factored" / "op_dense" / "op_sparse" count the operator calls by route; "device_bytes",
+ * "device_bytes_peak" (device memory of this context now / at most) and "adense_bytes" (dense constraint slabs) are state. */
+int lrn_set_factored(lrn_ctx* ctx, int ilmi, int on);
 /* Builder-defined synthetic dense SDP data generated on the device:
  * A_k = (R_k + R_k')/2, R_k iid N(0,1) from a counter-based Philox stream; nlmi = 1. */
 int lrn_synthetic_dense_model(lrn_ctx* ctx, int msz, int nvar, uint64_t seed);
@@ -114,7 +124,8 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * 1 = the better conditioned equivalent Lyapunov equation (Yh/s + s Zh) R + R (.) = C/s + s Zh C Zh, 0 = Yh R + R Yh = C),
  * "ns_lanczos" / "ns_lanczos_min" (1: scale and schedule of the Newton-Schulz iteration from a 24-step Lanczos run on K for
  * blocks of side >= ns_lanczos_min = 1500), "lowrank_form" (rank-k assembly, mode 1: U = G'V by a gather over the factor
- * entries (0), one dense MFMA product (1), or by the factors' density (-1, default)), "comm_fail_ensure" (test hook: the next exchange of this rank fails its buffer
+ * entries (0), one dense MFMA product (1), or by the factors' density (-1, default)), "profile_ops" (measurement: every
+ * AA vec(.) / mat(AA' .) timed by itself under "aa_times" / "aa_times2" / "aat_to_mat"; synchronises, not for solves), "comm_fail_ensure" (test hook: the next exchange of this rank fails its buffer
  * allocation), "reset_timing". */
 int lrn_set_option(lrn_ctx* ctx, const char* key, double value);
 /* multi-GPU: this context assembles the Schur columns it owns (block-cyclic) */

@@ -74,6 +74,12 @@ function upload_lowrank!(ctx::Ctx, i::Integer, khat::Integer, V::SparseMatrixCSC
     ctx.lowrank = true
 end
 
+# ---- factored block i: the factors of upload_lowrank! are its constraint data (AA uploaded without entries); the resident
+# entry points lrn_ip_* then work from the factors, the Schur matrix comes from mode 1 (kit = 0 only)
+function set_factored!(ctx::Ctx, i::Integer, on::Bool = true)
+    check(ctx, ccall((:lrn_set_factored, LIB), Cint, (Ptr{Cvoid}, Cint, Cint), ctx.h, i - 1, on ? 1 : 0), "lrn_set_factored")
+end
+
 # ---- prepare_W (src/prepare_W.jl:28-94) -------------------------------------------------------
 function prepare_W(ctx::Ctx, solver)
     for i in 1:solver.model.nlmi

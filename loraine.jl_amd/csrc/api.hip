@@ -13,7 +13,7 @@ void prec_free(lrn_ctx* c);
 
 extern "C" {
 
-int lrn_version(void) { return 101; }
+int lrn_version(void) { return 102; }
 
 int lrn_device_count(void) {
   int n = 0;
@@ -111,6 +111,7 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "prec_dense")) c->opt.prec_dense = (int)value;
   else if (!strcmp(key, "wmw_pattern_min")) c->opt.wmw_pattern_min = std::max(2, (int)value);
   else if (!strcmp(key, "profile_symv")) c->opt.profile_symv = (int)value;
+  else if (!strcmp(key, "profile_ops")) c->opt.profile_ops = (int)value;
   else if (!strcmp(key, "matvec_h")) { c->opt.matvec_h = (int)value; c->hop_version = -1; }
   else if (!strcmp(key, "comm_fail_ensure")) lrn::comm_inject_ensure_failure(c);      // test hook (tests/test_gpu_comm.py)
   else if (!strcmp(key, "pcg_lookahead")) c->opt.pcg_lookahead = std::max(0, std::min(8, (int)value));
@@ -361,6 +362,15 @@ int lrn_get_timing(lrn_ctx* c, const char* key, double* ms) {
 int64_t lrn_get_count(lrn_ctx* c, const char* key) {
   if (!c || !key) return 0;
   if (!strcmp(key, "shard_bs")) return c->shard_bs;      // state, not a per-call counter (survives reset_timing)
+  // device memory this context holds now / held at most (every buffer of the library goes through lrn::ensure), and the
+  // dense constraint slabs of all blocks: state as well
+  if (!strcmp(key, "device_bytes")) return (int64_t)c->dev_bytes;
+  if (!strcmp(key, "device_bytes_peak")) return (int64_t)c->dev_bytes_peak;
+  if (!strcmp(key, "adense_bytes")) {
+    int64_t s = 0;
+    for (const auto& b : c->lmi) if (b.Adense.p) s += (int64_t)b.Adense.bytes;
+    return s;
+  }
   auto it = c->counts.find(key);
   return it == c->counts.end() ? 0 : it->second;
 }

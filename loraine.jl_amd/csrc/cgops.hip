@@ -867,6 +867,7 @@ static bool dense_stream_ok(const LmiBlock& b, const double* Z) {
 }
 
 bool use_sparse_matvec(const lrn_ctx* c, const LmiBlock& b) {
+  if (b.factored) return false;        // (no stored column of AA to walk: the data are the factors)
   if (!b.sp_ok || c->opt.matvec_sparse == 1) return false;
   if (c->opt.matvec_sparse == 2) return true;
   // ~4e-12 ncq msz s against 4 msz^3 / 6e13 s.  Below msz ~ 1500 both routes are bound by their launches and L2: the
@@ -960,7 +961,7 @@ int wmw(lrn_ctx* c, LmiBlock& b, double* M, double* P, double* Z) {
 // of Z = W M W are needed on the pattern of the constraints only -- N = M W is one product, Z[p,q] = W(:,p) . N(:,q) one
 // wave per stored entry (the kernels of the pattern-restricted CG operator above) -- instead of the second n^3 product.
 bool wmw_pattern_ok(const lrn_ctx* c, const LmiBlock& b) {
-  return b.sp_ok && b.nd == 0 && b.msz >= c->opt.wmw_pattern_min && b.have_W;
+  return !b.factored && b.sp_ok && b.nd == 0 && b.msz >= c->opt.wmw_pattern_min && b.have_W;
 }
 
 int aa_times_wmw_pattern(lrn_ctx* c, LmiBlock& b, const double* M, double* N, double* y) {
@@ -982,8 +983,177 @@ int ensure_m(lrn_ctx* c, int m) {
   return LRN_OK;
 }
 
-// y += AA vec(Z)
+// ---- factor form of the two data operators (factored blocks, lrn_set_factored): A_k = V_k diag(d_k) V_k' exists only as the
+// dense factor matrix Vd (msz x R, R = nvar khat, column h khat + p = column p of the constraint with H index h) and the
+// weights w (d, 0 in the padding).  With AA = -A:
+//     (AA vec(Z))_k = -sum_p w_kp v_kp' Z v_kp          Q = Z Vd by one FP64 MFMA product, then per column <Q_c, Vd_c>
+//     mat(AA' x)    = -Vd diag(w o (x (x) 1_khat)) Vd'   columns scaled into a workspace, one lower-triangle product, mirrored
+// Q and the scaled copy live in the BG workspace (msz x R, what the mode-1 assembly uses for U).  Every sum has a fixed
+// order: one wave per constraint walks its khat columns in order, lanes stride the rows, one shuffle tree -- no atomics.
+
+// out[nat(h)] -= sum_p w[h kh + p] <Q(:, h kh + p), Vd(:, h kh + p)>   (sigma: H index -> constraint, null = identity)
+__global__ __launch_bounds__(256) void fac_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Vd,
+                                                         const double* __restrict__ w, int m, int kh, int nvar,
+                                                         const int* __restrict__ sigma, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (h >= nvar) return;
+  double s = 0.0;
+  for (int p = 0; p < kh; ++p) {
+    const long col = (long)h * kh + p;
+    const double wp = w[col];
+    if (wp == 0.0) continue;                       // padding column (wave-uniform)
+    const double* __restrict__ q = Q + col * m;
+    const double* __restrict__ v = Vd + col * m;
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+    int r = lane;
+    for (; r + 192 < m; r += 256) {
+      t0 += q[r] * v[r];
+      t1 += q[r + 64] * v[r + 64];
+      t2 += q[r + 128] * v[r + 128];
+      t3 += q[r + 192] * v[r + 192];
+    }
+    for (; r < m; r += 64) t0 += q[r] * v[r];
+    s += wp * ((t0 + t1) + (t2 + t3));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if (lane == 0) out[sigma ? sigma[h] : h] -= s;
+}
+
+// Vs(:, c) = -w[c] x[nat(c / kh)] Vd(:, c)   (one workgroup per factor column)
+__global__ __launch_bounds__(256) void fac_scale_kernel(const double* __restrict__ Vd, const double* __restrict__ w,
+                                                        const double* __restrict__ x, const int* __restrict__ sigma, int m,
+                                                        int kh, double* __restrict__ Vs) {
+  const long col = blockIdx.x;
+  const int h = (int)(col / kh);
+  const double sc = -(w[col] * x[sigma ? sigma[h] : h]);
+  const double* __restrict__ v = Vd + col * m;
+  double* __restrict__ o = Vs + col * m;
+  for (int r = threadIdx.x; r < m; r += 256) o[r] = sc * v[r];
+}
+
+static int fac_workspace(lrn_ctx* c, LmiBlock& b, double** ws) {
+  if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
+  LRN_TRY(ensure(c, c->BG, (size_t)b.msz * (size_t)c->nvar * b.lr_khat * 8));
+  *ws = c->BG.as<double>();
+  return LRN_OK;
+}
+
+// y += AA vec(Z), Z symmetric
+static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
+  const int m = b.msz, kh = b.lr_khat;
+  const long R = (long)c->nvar * kh;
+  double* Q = nullptr;
+  LRN_TRY(fac_workspace(c, b, &Q));
+  GemmDesc g;     // Q = Z Vd, msz x R
+  g.A = Z; g.sAm = 1; g.sAk = m;
+  g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
+  g.C = Q; g.sCm = 1; g.sCn = m;
+  g.M = m; g.N = (int)R; g.K = m;
+  LRN_TRY(gemm(c->stream, g));
+  hipLaunchKernelGGL(fac_coldot_kernel, dim3((c->nvar + 3) / 4), dim3(256), 0, c->stream, Q, b.Vd.as<double>(),
+                     b.v_w.as<double>(), m, kh, c->nvar, c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, y);
+  c->counts["op_factored"] += 1;
+  return LRN_OK;
+}
+
+// M = mat(AA' x), exactly symmetric
+static int aat_to_mat_factored(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
+  const int m = b.msz, kh = b.lr_khat;
+  const long R = (long)c->nvar * kh;
+  double* Vs = nullptr;
+  LRN_TRY(fac_workspace(c, b, &Vs));
+  hipLaunchKernelGGL(fac_scale_kernel, dim3((unsigned)R), dim3(256), 0, c->stream, b.Vd.as<double>(), b.v_w.as<double>(), x,
+                     c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, m, kh, Vs);
+  GemmDesc g;     // M = Vs Vd', the tiles on and below the diagonal
+  g.A = Vs; g.sAm = 1; g.sAk = m;
+  g.B = b.Vd.as<double>(); g.sBk = m; g.sBn = 1;
+  g.C = M; g.sCm = 1; g.sCn = m;
+  g.M = m; g.N = m; g.K = (int)R;
+  g.flags = GEMM_TRI_LOWER;
+  // From 16 x 16 128-tiles on gemm() no longer splits K by itself, but the lower triangle alone (msz 2000: 136 tiles on 512
+  // workgroup slots) leaves most of the chip idle over a long K = R.  K is cut into ks equal parts run as a BATCH of the
+  // same kernel into ks slabs, added in a fixed order.  ks by the round model of gemm_f64.hip (1.85 us per K-step of a
+  // round of 512 workgroups, 1.25 / 2 for a round of up to 256 / 512) plus the pass over the slabs.
+  const long tm = (m + 127) / 128, tiles = tm * (tm + 1) / 2;
+  int ks = 1;
+  static const int forced = getenv("LRN_FAC_SPLIT") ? atoi(getenv("LRN_FAC_SPLIT")) : 0;      // (measurement: ks, 1 = none)
+  if (forced >= 1 && forced <= 16 && R % forced == 0) ks = forced;
+  else if (tm * tm >= 256 && tiles < 512) {
+    double best = 1e300;
+    for (int k : {1, 2, 3, 4, 5, 6, 8}) {
+      if (R % k || (k > 1 && R / k < 512)) continue;
+      const long wg = tiles * k, rem = wg % 512;
+      const double rounds = 2.0 * (double)(wg / 512) + (rem == 0 ? 0.0 : (rem <= 256 ? 1.25 : 2.0));
+      const double us = (double)(R / k) / 16.0 * 1.85 * rounds + (k > 1 ? 5.0 + (double)(k + 1) * m * (double)m * 8.0 / 4.0e6 : 0.0);
+      if (us < best) { best = us; ks = k; }
+    }
+  }
+  if (ks > 1) {
+    const long mm = (long)m * m;
+    LRN_TRY(ensure(c, c->slabs, (size_t)ks * mm * 8));
+    g.C = c->slabs.as<double>();
+    g.K = (int)(R / ks);
+    g.batch = ks;
+    g.bA = (long)(R / ks) * m; g.bB = (long)(R / ks) * m; g.bC = mm;
+    LRN_TRY(gemm(c->stream, g));
+    LRN_TRY(reduce_slabs(c->stream, c->slabs.as<double>(), mm, ks, M, mm, 0.0));
+  } else {
+    LRN_TRY(gemm(c->stream, g));
+  }
+  hipLaunchKernelGGL(mirror_lower_tiled_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(32, 8), 0, c->stream, M, m);
+  c->counts["op_factored"] += 1;
+  return LRN_OK;
+}
+
+// option "profile_ops": one data operator between two events of its own (the phases of the resident loop -- "rhs",
+// "residual_d", "find_step" -- contain other products as well)
+struct OpTimer {
+  lrn_ctx* c;
+  const char* key;
+  hipEvent_t a = nullptr, b = nullptr;
+  OpTimer(lrn_ctx* c_, const char* key_) : c(c_), key(key_) {
+    if (!c->opt.profile_ops) return;
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = nullptr; return; }
+    (void)hipEventRecord(a, c->stream);
+  }
+  int done(int rc) {
+    if (a) {
+      (void)hipEventRecord(b, c->stream);
+      (void)hipEventSynchronize(b);
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, a, b);
+      c->timing[key] += ms;
+      c->counts[key] += 1;
+      (void)hipEventDestroy(a);
+      (void)hipEventDestroy(b);
+    }
+    return rc;
+  }
+};
+
+static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);
+static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);
+static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M);
 int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
+  OpTimer t(c, "aa_times");
+  return t.done(aa_times_impl(c, b, Z, y));
+}
+int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
+  OpTimer t(c, "aa_times2");
+  return t.done(aa_times2_impl(c, b, Z1, y1, Z2, y2));
+}
+int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
+  OpTimer t(c, "aat_to_mat");
+  return t.done(aat_to_mat_impl(c, b, x, M));
+}
+
+// y += AA vec(Z)
+static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
+  if (b.factored) return aa_times_factored(c, b, Z, y);
+  if (b.npos_nz > b.nd) c->counts["op_sparse"] += 1;
+  if (b.nd > 0) c->counts["op_dense"] += 1;
   if (b.npos_nz > b.nd)
     hipLaunchKernelGGL(aa_times_kernel, dim3((b.npos_nz - b.nd + 3) / 4), dim3(256), 0, c->stream, b.ent_ptr.as<long>(),
                        b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), Z, b.msz, b.nd, b.npos_nz,
@@ -1055,12 +1225,14 @@ __global__ __launch_bounds__(256) void aa_dense_dot2_kernel(const double* __rest
 }
 
 // y1 += AA vec(Z1), y2 += AA vec(Z2) with the dense constraint data read once
-int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
-  if (b.nd <= 0 || dense_passes_sharded(c, b)) {      // (the sharded pass is 1/world of the data already)
-    LRN_TRY(aa_times(c, b, Z1, y1));
-    return aa_times(c, b, Z2, y2);
+static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
+  if (b.factored || b.nd <= 0 || dense_passes_sharded(c, b)) {      // (the sharded pass is 1/world of the data already; factor form: two products)
+    LRN_TRY(aa_times_impl(c, b, Z1, y1));
+    return aa_times_impl(c, b, Z2, y2);
   }
+  c->counts["op_dense"] += 1;
   if (b.npos_nz > b.nd) {
+    c->counts["op_sparse"] += 1;
     for (int h = 0; h < 2; ++h)
       hipLaunchKernelGGL(aa_times_kernel, dim3((b.npos_nz - b.nd + 3) / 4), dim3(256), 0, c->stream, b.ent_ptr.as<long>(),
                          b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), h ? Z2 : Z1, b.msz, b.nd, b.npos_nz,
@@ -1082,9 +1254,12 @@ int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const doubl
 }
 
 // M = mat(AA' x)  (symmetrised msz x msz, kron_etc.jl:13-18)
-int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
+static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
+  if (b.factored) return aat_to_mat_factored(c, b, x, M);
   const int m = b.msz;
   const long mm = (long)m * m;
+  if (b.ncq > 0) c->counts["op_sparse"] += 1;
+  if (b.nd > 0) c->counts["op_dense"] += 1;
   LRN_HIP(c, hipMemsetAsync(M, 0, (size_t)mm * 8, c->stream));
   if (b.ncq > 0)
     hipLaunchKernelGGL(aat_gather_kernel, dim3((unsigned)((b.ncq + 3) / 4)), dim3(256), 0, c->stream, b.cq_q.as<long>(),
@@ -1928,8 +2103,18 @@ int pcg_dev(lrn_ctx* c, const double* b, double tol, int maxit, double* x, int* 
 
 using namespace lrn;
 
+// the CG side (mat-vec, H_alpha, PCG) reads the entries of AA: not for factored blocks
+static int no_factored(lrn_ctx* c, const char* what) {
+  for (size_t il = 0; il < c->lmi.size(); ++il)
+    if (c->lmi[il].factored)
+      return set_error(c, LRN_ERR_STATE, "%s: block %d is factored (lrn_set_factored): the CG path needs the constraint "
+                                         "matrices, factored data is solved with kit = 0", what, (int)il);
+  return LRN_OK;
+}
+
 extern "C" int lrn_matvec(lrn_ctx* c, const double* x, double* Ax) {
   if (!c || !x || !Ax) return LRN_ERR_ARG;
+  LRN_TRY(no_factored(c, "lrn_matvec"));
   LRN_HIP(c, hipSetDevice(c->device));
   const int n = c->nvar;
   LRN_TRY(copy_in(c, c->v0.p, x, (size_t)n * 8));
@@ -1944,6 +2129,7 @@ extern "C" int lrn_matvec(lrn_ctx* c, const double* x, double* Ax) {
 
 extern "C" int lrn_matvec_partial(lrn_ctx* c, const double* x, double* Ax_partial) {
   if (!c || !x || !Ax_partial) return LRN_ERR_ARG;
+  LRN_TRY(no_factored(c, "lrn_matvec_partial"));
   LRN_HIP(c, hipSetDevice(c->device));
   const int n = c->nvar;
   LRN_TRY(copy_in(c, c->v0.p, x, (size_t)n * 8));
@@ -1969,6 +2155,7 @@ extern "C" int lrn_make_rhs(lrn_ctx* c, const double* Rp, const double* const* R
 
 extern "C" int lrn_prec_setup(lrn_ctx* c, int prec, int erank, int aamat, int* info) {
   if (!c) return LRN_ERR_ARG;
+  LRN_TRY(no_factored(c, "lrn_prec_setup"));
   LRN_HIP(c, hipSetDevice(c->device));
   return prec_setup(c, prec, erank, aamat, info);
 }
@@ -1986,6 +2173,7 @@ extern "C" int lrn_prec_apply(lrn_ctx* c, const double* x, double* Mx) {
 
 extern "C" int lrn_pcg(lrn_ctx* c, const double* h, double tol, int maxit, double* x, int* exit_code, int* iters) {
   if (!c || !h || !x || !exit_code || !iters) return LRN_ERR_ARG;
+  LRN_TRY(no_factored(c, "lrn_pcg"));
   LRN_HIP(c, hipSetDevice(c->device));
   const int n = c->nvar;
   LRN_TRY(copy_in(c, c->v0.p, h, (size_t)n * 8));

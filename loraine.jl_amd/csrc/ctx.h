@@ -71,6 +71,9 @@ struct LmiBlock {
   bool have_Bd = false;     // dense copy of the rank-one factors (rank-one assembly from W)
   lrn::DBuf Vd;             // dense copy of the rank-k factors, msz x (nvar * lr_khat) (dense U product, assembly from W)
   bool have_Vd = false;
+  // factored block (lrn_set_factored): the factors ARE the constraint data -- AA has no entry, AA vec(.) and mat(AA' .) go
+  // through Vd (cgops.hip, "factor form"), the Schur matrix through mode 1 only
+  bool factored = false;
 };
 
 struct lrn_ctx;
@@ -129,6 +132,8 @@ struct LrnOptions {
                                   // (also in lrn_prec_apply)
   int wmw_pattern_min = 1500;     // right-hand sides AA vec(W M W) with all constraints sparse: from this side on through the
                                   // pattern entries of W M W (one n^3 product instead of two)
+  int profile_ops = 0;            // measurement: time every AA vec(.) / mat(AA' .) by itself ("aa_times", "aa_times2", "aat_to_mat";
+                                  // synchronises: not for solves; tools/factored_pass_times.py)
   int profile_symv = 0;           // measurement: time every application of H x by itself (synchronises: not for solves)
   int matvec_h = 0;               // CG operator through the assembled Schur matrix (hop.hip): 0 auto (cost model), 1 never
                                   // (the matrix-free MyA always), 2 always
@@ -195,6 +200,7 @@ struct lrn_ctx {
   // timing of the last assembly / factor / solve (ms, HIP events on ctx stream)
   std::map<std::string, double> timing;
   std::map<std::string, long> counts;
+  size_t dev_bytes = 0, dev_bytes_peak = 0;   // device memory held through lrn::ensure (lrn_get_count "device_bytes" / "device_bytes_peak")
   bool profile = true;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t evA = nullptr, evB = nullptr;      // stream <-> stream2 dependencies (prepare_w_block)
@@ -236,6 +242,7 @@ int schur_factor(lrn_ctx* c, int* info);
 int schur_solve(lrn_ctx* c, const double* h, double* dely);
 int schur_add_diag(lrn_ctx* c, double eps);
 int schur_get(lrn_ctx* c, double* Hout);
+int lowrank_dense_factors(lrn_ctx* c, LmiBlock& b);     // b.Vd from the uploaded rank-k factors (once per upload)
 // hop.hip: the CG operator through the assembled matrix
 // y = H x; qpart (may be null): receives *nq partial sums of x'y (*nq = 0: not formed, e.g. sharded)
 int hop_apply(lrn_ctx* c, const double* x_dev, double* y_dev, double* qpart = nullptr, int* nq = nullptr);

@@ -34,6 +34,7 @@ __host__ __device__ inline int shard_global_block(int rank, int lb, int world) {
 struct DBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  size_t* acct = nullptr;   // the owning context's byte count (lrn::ensure / lrn::release keep it)
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 

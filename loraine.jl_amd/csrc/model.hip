@@ -22,12 +22,19 @@ int ensure(lrn_ctx* c, DBuf& b, size_t bytes, bool zero) {
   if (bytes == 0) bytes = 8;
   if (b.bytes < bytes) {
     if (b.p) (void)hipFree(b.p);
+    if (b.acct) *b.acct -= b.bytes;
     b.p = nullptr;
     b.bytes = 0;
+    b.acct = nullptr;
     hipError_t e = hipMalloc(&b.p, bytes);
     if (e != hipSuccess)
       return set_error(c, LRN_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
     b.bytes = bytes;
+    if (c) {
+      b.acct = &c->dev_bytes;
+      c->dev_bytes += bytes;
+      c->dev_bytes_peak = std::max(c->dev_bytes_peak, c->dev_bytes);
+    }
     zero = true;
   }
   if (zero) LRN_HIP(c, hipMemsetAsync(b.p, 0, b.bytes, c->stream));
@@ -36,8 +43,10 @@ int ensure(lrn_ctx* c, DBuf& b, size_t bytes, bool zero) {
 
 void release(DBuf& b) {
   if (b.p) (void)hipFree(b.p);
+  if (b.p && b.acct) *b.acct -= b.bytes;
   b.p = nullptr;
   b.bytes = 0;
+  b.acct = nullptr;
 }
 
 bool is_device_ptr(const void* p) {
@@ -539,6 +548,8 @@ extern "C" int lrn_synthetic_dense_model(lrn_ctx* c, int msz, int nvar, uint64_t
 extern "C" int lrn_get_constraint(lrn_ctx* c, int ilmi, int k, double* A_out) {
   if (!c || ilmi < 0 || ilmi >= c->nlmi || k < 0 || k >= c->nvar || !A_out) return LRN_ERR_ARG;
   LmiBlock& b = c->lmi[ilmi];
+  if (b.factored)
+    return set_error(c, LRN_ERR_STATE, "lrn_get_constraint: block %d is factored (lrn_set_factored): no constraint matrix is stored", ilmi);
   size_t mm = (size_t)b.msz * b.msz * 8;
   int pos = b.ipos[k];
   if (pos < b.nd) return copy_out(c, A_out, b.Adense.as<double>() + (size_t)pos * b.msz * b.msz, mm);
@@ -612,6 +623,30 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
   b.lr_khat = khat;
   b.vnnz = nnz;
   b.has_V = true;
+  if (b.factored) LRN_TRY(lowrank_dense_factors(c, b));      // (new factors of a factored block: its operators read Vd)
+  LRN_HIP(c, hipStreamSynchronize(c->stream));
+  return LRN_OK;
+}
+
+// on = 1: the factors of lrn_upload_lowrank ARE the constraint data of block ilmi (A_k = V_k diag(d_k) V_k', AA = -A as
+// everywhere): AA vec(.) and mat(AA' .) of the resident path run in factor form (cgops.hip), the Schur matrix comes from
+// mode 1.  The block's AA must be without entries -- no constraint may be counted twice.  on = 0 takes the declaration back.
+extern "C" int lrn_set_factored(lrn_ctx* c, int ilmi, int on) {
+  if (!c) return LRN_ERR_ARG;
+  if (ilmi < 0 || ilmi >= c->nlmi) return set_error(c, LRN_ERR_ARG, "lrn_set_factored: block %d of %d", ilmi, c->nlmi);
+  LRN_HIP(c, hipSetDevice(c->device));
+  LmiBlock& b = c->lmi[ilmi];
+  if (!on) {
+    b.factored = false;
+    return LRN_OK;
+  }
+  if (!b.has_V)
+    return set_error(c, LRN_ERR_STATE, "lrn_set_factored: no factors were uploaded for block %d (lrn_upload_lowrank)", ilmi);
+  if (b.nent > 0 || b.nd > 0 || b.npos_nz > 0 || b.ncq > 0)
+    return set_error(c, LRN_ERR_STATE, "lrn_set_factored: the AA of block %d has entries (%ld): a factored block takes its "
+                                       "constraints from the factors alone", ilmi, b.nent);
+  LRN_TRY(lowrank_dense_factors(c, b));
+  b.factored = true;
   LRN_HIP(c, hipStreamSynchronize(c->stream));
   return LRN_OK;
 }

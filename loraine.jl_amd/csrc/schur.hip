@@ -991,6 +991,20 @@ static int assemble_rank1(lrn_ctx* c, LmiBlock& b) {
 // the entrywise square of T weighted by d d' and summed over khat x khat blocks -- one MFMA product whose epilogue does
 // all of that (GEMM_SQUARE_BLOCKSUM), T never stored.  A sign flip of a whole constraint leaves H unchanged, so the sign
 // convention of AA (row j = -vec(A_j)) does not matter here.  Blocks accumulate (beta = 1) into the zeroed H.
+// the dense copy Vd (msz x nvar khat) of the uploaded factors: built on first use, at lrn_set_factored for a factored block
+int lowrank_dense_factors(lrn_ctx* c, LmiBlock& b) {
+  if (b.have_Vd) return LRN_OK;
+  if (!b.has_V) return set_error(c, LRN_ERR_STATE, "no rank-k factors were uploaded (lrn_upload_lowrank)");
+  const int m = b.msz;
+  const long R = (long)c->nvar * b.lr_khat;
+  LRN_TRY(ensure(c, b.Vd, (size_t)m * R * 8));
+  LRN_HIP(c, hipMemsetAsync(b.Vd.p, 0, (size_t)m * R * 8, c->stream));
+  hipLaunchKernelGGL(b_dense_kernel, dim3((unsigned)R), dim3(64), 0, c->stream, b.v_ptr.as<long>(), b.v_col.as<int>(),
+                     b.v_val.as<double>(), m, b.Vd.as<double>());
+  b.have_Vd = true;
+  return LRN_OK;
+}
+
 static int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
   const int n = c->nvar, m = b.msz;
   if (!b.has_V) return set_error(c, LRN_ERR_STATE, "rank-k mode requested but no factors were uploaded (lrn_upload_lowrank)");
@@ -1002,13 +1016,7 @@ static int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
   // U by one dense product or by a gather over the stored factor entries: the gather reads nnz * msz words of G / W, the
   // product does 2 R msz^2 flop -- the gather wins below a density of about 2 %
   const bool dense = c->opt.lowrank_form == 1 || (c->opt.lowrank_form < 0 && (double)b.vnnz > 0.02 * (double)R * m);
-  if ((dense || fromW) && !b.have_Vd) {
-    LRN_TRY(ensure(c, b.Vd, (size_t)m * R * 8));
-    LRN_HIP(c, hipMemsetAsync(b.Vd.p, 0, (size_t)m * R * 8, c->stream));
-    hipLaunchKernelGGL(b_dense_kernel, dim3((unsigned)R), dim3(64), 0, c->stream, b.v_ptr.as<long>(), b.v_col.as<int>(),
-                       b.v_val.as<double>(), m, b.Vd.as<double>());
-    b.have_Vd = true;
-  }
+  if (dense || fromW) LRN_TRY(lowrank_dense_factors(c, b));
   LRN_TRY(ensure(c, c->BG, (size_t)m * R * 8));
   double* U = c->BG.as<double>();
   tic(c);
@@ -1063,6 +1071,10 @@ int schur_assemble(lrn_ctx* c, int mode) {
     (void)hipEventCreate(&a1);
     (void)hipEventRecord(a0, c->stream);
   }
+  for (const auto& b : c->lmi)
+    if (b.factored && mode != 1)
+      return set_error(c, LRN_ERR_STATE, "lrn_schur_assemble: mode %d on a factored block (lrn_set_factored): its constraints "
+                                         "exist as factors only, mode 1 assembles from them", mode);
   LRN_HIP(c, hipMemsetAsync(c->H.p, 0, (size_t)n * n * 8, c->stream));
   c->H_partial = false;
   c->H_owned_only = false;

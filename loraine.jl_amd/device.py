@@ -190,6 +190,11 @@ class Device:
         self._chk(self.lib.lrn_upload_lowrank(self.h, int(ilmi), int(khat), ptr(cp), ptr(rv), ptr(nz), ptr(w)),
                   "lrn_upload_lowrank")
 
+    def set_factored(self, ilmi, on=True):
+        """Declare the uploaded factors of block ilmi to be its constraint data (its AA has no entry): the resident
+        operators AA vec(.) / mat(AA' .) run in factor form, the Schur matrix comes from schur_assemble(1)."""
+        self._chk(self.lib.lrn_set_factored(self.h, int(ilmi), 1 if on else 0), "lrn_set_factored")
+
     def synthetic_dense_model(self, msz, nvar, seed):
         self._chk(self.lib.lrn_synthetic_dense_model(self.h, int(msz), int(nvar), C.c_uint64(seed)),
                   "lrn_synthetic_dense_model")

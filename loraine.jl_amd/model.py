@@ -33,6 +33,13 @@ class MyModel:
     # of V_k, d the weights +-1 (0 in the padding), A_k = V_k diag(d_k) V_k'; [] when the data has no such form
     lowrank: list = field(default_factory=list)
     lowrank_note: str = ""     # why datarank >= 1 found no factors (the solver prints it and falls back to datarank = 0)
+    # factored model (build_factored_model): the constraints of a factored block exist as `lowrank` only -- its AA has no
+    # entry, its A holds F_0 alone.  factored = any block is; factored_blocks[i] per block; aa_fro[i] = ||AA_i||_F from the
+    # factors (what the initpoint = 1 heuristic reads from AA otherwise)
+    factored: bool = False
+    from_factors: bool = False     # built by build_factored_model (some or all blocks may have been materialised)
+    factored_blocks: list = field(default_factory=list)
+    aa_fro: list = field(default_factory=list)
 
 
 def _rank_one_rows(blockA, n):
@@ -207,6 +214,104 @@ def build_model(A, b, b_const=0.0, d_lin=None, C_lin=None, datarank=0, kappa=8, 
         lowrank, note = lowrank_factors(A, n, datarank)
     return MyModel(A, AA, B, C, nzA, sigmaA, qA, np.asarray(b, float), float(b_const), np.asarray(d_lin, float),
                    sp.csr_matrix(C_lin), n, msizes, int(C_lin.shape[1]), len(A), lowrank, note)
+
+
+def factors_fro(V, d, khat, n, chunk=256):
+    """||AA_i||_F from the padded factors of one block: ||V_k D_k V_k'||_F^2 = sum_pq d_p d_q (v_p' v_q)^2, a khat x khat
+    Gram matrix per constraint -- no msz x msz matrix is formed."""
+    V = sp.csr_matrix(V)
+    d = np.asarray(d, float).reshape(n, khat)
+    tot = 0.0
+    for k0 in range(0, n, chunk):
+        k1 = min(n, k0 + chunk)
+        Vk = V[k0 * khat:k1 * khat].toarray().reshape(k1 - k0, khat, -1)
+        G = np.einsum("kpm,kqm->kpq", Vk, Vk)
+        tot += float(np.einsum("kp,kq,kpq->", d[k0:k1], d[k0:k1], G * G))
+    return float(np.sqrt(max(tot, 0.0)))
+
+
+def _check_factors(F0, factors, n):
+    """factors[i][k] = (V, d) -> dense (m x r) V and d per constraint, or ValueError."""
+    if len(factors) != len(F0):
+        raise ValueError(f"factors for {len(factors)} LMI blocks, F0 has {len(F0)}")
+    out = []
+    for i, blk in enumerate(factors):
+        m = F0[i].shape[0]
+        if F0[i].shape != (m, m):
+            raise ValueError(f"block {i + 1}: F0 is {F0[i].shape}, not square")
+        if len(blk) != n:
+            raise ValueError(f"block {i + 1}: factors of {len(blk)} constraints, b has {n} entries")
+        facs = []
+        for j, (V, d) in enumerate(blk):
+            V = np.asarray(V.toarray() if sp.issparse(V) else V, dtype=np.float64)
+            if V.ndim == 1:
+                V = V.reshape(-1, 1)
+            d = np.asarray(d, dtype=np.float64).ravel()
+            if V.ndim != 2 or V.shape[0] != m:
+                raise ValueError(f"block {i + 1}, constraint {j + 1}: V is {V.shape}, the block has side {m}")
+            if d.size != V.shape[1] or V.shape[1] > LOWRANK_MAX:
+                raise ValueError(f"block {i + 1}, constraint {j + 1}: {V.shape[1]} factor columns, {d.size} weights "
+                                 f"(at most {LOWRANK_MAX})")
+            facs.append((V, d))
+        out.append(facs)
+    return out
+
+
+def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, kappa=8, factored_form=-1) -> MyModel:
+    """A model given by F_0 (per block), b, optional linear rows and the factors alone: A_ik = V diag(d) V' with
+    factors[i][k] = (V (m_i x r, r <= 16, dense or sparse), d (+-1)).  No A_ik is formed for a factored block: its AA is
+    an n x m^2 matrix without entries (nzA = 0, identity sigmaA) and `lowrank` carries the data.
+    factored_form: 1 = every block factored; -1 = a block whose factors are so small that the sparse path serves it --
+    sum_k nnz(V_k V_k') <= kappa * n, i.e. on average at most `datasparsity` entries per constraint, the count below which
+    the reference treats a constraint as sparse -- is materialised (sparse AA built from the factors, the existing
+    path) and stays un-factored."""
+    n = len(b)
+    if factored_form not in (-1, 1):
+        raise ValueError(f"factored_form = {factored_form} (-1 auto, 1 always factored)")
+    facs_all = _check_factors(F0, factors, n)
+    nlmi = len(F0)
+    A, AA, C, lowrank, fblocks, aa_fro = [], [], [], [], [], []
+    nzA = np.zeros((n, nlmi), dtype=np.int64)
+    sigmaA = np.zeros((n, nlmi), dtype=np.int64)
+    qA = np.zeros((2, nlmi), dtype=np.int64)
+    for i, facs in enumerate(facs_all):
+        if sp.issparse(F0[i]):
+            F = sp.csc_matrix(F0[i])
+            F.eliminate_zeros()
+        else:
+            F = np.asarray(F0[i], dtype=np.float64)            # (a dense F_0 stays dense: C is then a dense array too)
+        m = F.shape[0]
+        lr = pad_factors(facs, n, m)
+        lowrank.append(lr)
+        supp = [int(np.count_nonzero(np.any(V != 0.0, axis=1))) for V, _ in facs]
+        small = sum(s * s for s in supp) <= kappa * n
+        if factored_form == -1 and small:
+            blk = [sp.csc_matrix(F)]
+            for (V, d), s in zip(facs, supp):
+                rows = np.nonzero(np.any(V != 0.0, axis=1))[0]
+                sub = (V[rows] * d) @ V[rows].T
+                Ak = sp.coo_matrix((sub.ravel(), (np.repeat(rows, s), np.tile(rows, s))), shape=(m, m)).tocsc()
+                Ak.eliminate_zeros()
+                blk.append(Ak)
+            AAi, _, Ci, nz, sg, q = _prepare_A([blk], 0, kappa, n)
+            A.append(blk); AA.append(AAi[0]); C.append(Ci[0])
+            nzA[:, i], sigmaA[:, i], qA[:, i] = nz[:, 0], sg[:, 0], q[:, 0]
+            fblocks.append(False)
+            aa_fro.append(float(sp.linalg.norm(AAi[0])))
+        else:
+            A.append([F])
+            AA.append(sp.csr_matrix((n, m * m)))
+            C.append(sp.csc_matrix(-F) if sp.issparse(F) else -F)
+            sigmaA[:, i] = np.arange(n)
+            fblocks.append(True)
+            aa_fro.append(factors_fro(*lr, n))
+    if C_lin is None or C_lin.shape[1] == 0:
+        C_lin = sp.csr_matrix((n, 0))
+        d_lin = np.zeros(0)
+    msizes = np.array([blk[0].shape[0] for blk in A], dtype=np.int64)
+    return MyModel(A, AA, [], C, nzA, sigmaA, qA, np.asarray(b, float), float(b_const), np.asarray(d_lin, float),
+                   sp.csr_matrix(C_lin), n, msizes, int(C_lin.shape[1]), nlmi, lowrank, "",
+                   any(fblocks), True, fblocks, aa_fro)
 
 
 def _tokens(line):

@@ -12,7 +12,7 @@ calls a JuMP user makes:
 import numpy as np
 
 from . import solvers
-from .model import MyModel, build_model, model_from_sdpa
+from .model import MyModel, build_factored_model, build_model, model_from_sdpa
 
 # MOI.TerminationStatus values used by the reference (MOI_wrapper.jl:252-265)
 OPTIMIZE_NOT_CALLED = "OPTIMIZE_NOT_CALLED"
@@ -78,6 +78,20 @@ class Optimizer:
         self._pending = ("arrays", (A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense), factors))
         return self
 
+    def load_factored_model(self, F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factored_form=-1):
+        """The same problem given by its factors alone: F0[i] the constant matrix of block i (the A[i][0] of load_model),
+        factors[i][k] = (V, d) with A_i,k+1 = V diag(d) V' (V msz x r, r <= 16, d = +-1, dense or sparse).  No A_ik, no
+        row of AA and no dense constraint slab is ever formed, on the host or on the device; implies datarank = the
+        largest rank (at least 1) and needs kit = 0 and the resident solver (ValueError otherwise).
+        factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
+        times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
+        if not self.resident:
+            raise ValueError("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
+                             "multiplies by AA")
+        self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
+                                      int(factored_form)))
+        return self
+
     def _copy_to(self):
         kind, payload = self._pending
         drank = int(self.options.get("datarank", 0))
@@ -85,6 +99,13 @@ class Optimizer:
         if kind == "sdpa":
             model = model_from_sdpa(payload, datarank=drank, kappa=kappa)
             self.max_sense = False
+        elif kind == "factored":
+            F0, factors, b, b_const, d_lin, C_lin, max_sense, form = payload
+            self.max_sense = max_sense
+            model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
+            if model.factored and int(self.options.get("kit", 0)) != 0:
+                raise ValueError("a factored model (load_factored_model) needs kit = 0: the CG path reads the constraint "
+                                 "matrices, which do not exist")
         else:
             A, b, b_const, d_lin, C_lin, max_sense, factors = payload
             self.max_sense = max_sense

@@ -16,6 +16,8 @@ from .solvers import MySolver, _dense, _fro
 
 
 class ResidentSolver(MySolver):
+    _resident = True
+
     # ------------------------------------------------------------------ setup
     def setup_solver(self):
         super().setup_solver()

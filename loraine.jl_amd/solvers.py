@@ -80,6 +80,8 @@ class Halpha:
 class MySolver:
     """src/Solvers.jl:18-147 + load() :187-302."""
 
+    _resident = False          # resident.ResidentSolver: X, S and the data operators stay on the device
+
     def __init__(self, model: MyModel, options=None, device: Device = None, device_index=0):
         opt = dict(DEFAULT_OPTIONS)
         for key, val in (options or {}).items():
@@ -94,6 +96,19 @@ class MySolver:
             setattr(self, key, float(opt[key]))
         self.model = model
         self._check_ranges()
+        if getattr(model, "from_factors", False) and model.lowrank:
+            # a model given by its factors: mode 1 with the rank the factors have
+            self.datarank = max(1, max(int(np.max(np.count_nonzero(np.asarray(d).reshape(-1, kh), axis=1), initial=0))
+                                       for _, d, kh in model.lowrank))
+        if getattr(model, "factored", False):
+            # the constraints exist as factors only: direct solver on the resident path (the CG path reads the entries
+            # of AA in H_alpha, the NumPy host loop multiplies by AA)
+            if self.kit != 0:
+                raise ValueError("a factored model (load_factored_model) needs kit = 0: the CG path reads the constraint "
+                                 "matrices, which do not exist")
+            if not self._resident:
+                raise ValueError("a factored model (load_factored_model) needs the resident solver "
+                                 "(Optimizer(resident=True)): the NumPy host loop multiplies by AA")
         self.cg_iter_tot = 0
         self.dist = None                 # sharding.DistributedHotPath when run with one process per GPU
         self.exact_regularised_solve = False   # True: (H + d I)^-1 h instead of the reference's double solve (:85,90)
@@ -111,6 +126,8 @@ class MySolver:
             if model.lowrank:
                 for i, (V, d, khat) in enumerate(model.lowrank):
                     self.dev.upload_lowrank(i, khat, V, d)                      # [GPU] one-time
+                    if getattr(model, "factored", False) and model.factored_blocks[i]:
+                        self.dev.set_factored(i)                                # [GPU] the factors are the data
                 self.lowrank = True
             else:
                 self._say(f" ---No rank-{self.datarank} factors ({model.lowrank_note}), setting datarank = 0")
@@ -179,7 +196,9 @@ class MySolver:
             if self.initpoint == 0:
                 eps_, eta_ = 1.0, float(m.n)
             else:
-                f = np.linalg.norm(b2) / (1.0 + _fro(m.AA[i]))
+                # (||AA_i||_F: of a factored block from its factors, model.factors_fro)
+                naa = m.aa_fro[i] if getattr(m, "factored", False) and m.factored_blocks[i] else _fro(m.AA[i])
+                f = np.linalg.norm(b2) / (1.0 + naa)
                 eps_ = math.sqrt(s) * max(1.0, math.sqrt(s) * f)
                 mf = (1.0 + max(f, _fro(m.C[i]))) / math.sqrt(s)
                 eta_ = math.sqrt(s) * max(1.0, mf)

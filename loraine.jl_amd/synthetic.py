@@ -115,3 +115,42 @@ class LowRankProblem:
         qA = np.full((2, 1), n if 9 > kappa else 0, dtype=np.int64)
         return MyModel(None, [self.AA()], [], [self.C_dense()], nzA, sigmaA, qA, self.b.copy(), 0.0, np.zeros(0),
                        sp.csr_matrix((n, 0)), n, np.array([self.msz], dtype=np.int64), 0, 1)
+
+
+# ------------------------------------------------------------------------------------------------
+# Factor-only data with a planted optimum: the constraints exist as V_k, d_k alone (Optimizer.load_factored_model)
+class FactoredLowRankProblem:
+    """max b'y  s.t.  S = C - sum_k y_k M_k >= 0 with M_k = -A_k, A_k = V_k diag(d_k) V_k' (the library's AA = -A), V_k
+    dense msz x krank with N(0, 1/msz) entries, d = +-1.  The optimum is planted the way LowRankProblem plants its own:
+    X* = Q diag(lam) Q' (rank xrank, trace sqrt(msz) -- see the warning there), S* = I - Q Q', y* ~ 0.1 N(0,1),
+    b_k = <M_k, X*> = -sum_p d_kp |lam^1/2 Q' v_kp|^2,  C = S* + sum_k y*_k M_k = S* - Vall diag(y* (x) d) Vall'.
+    Everything is formed from products of V: no msz x msz matrix per constraint exists at any point."""
+
+    def __init__(self, msz, nvar, krank=2, xrank=4, seed=20250616, xtrace=None):
+        rng = np.random.default_rng(seed)
+        self.msz, self.nvar, self.krank, self.xrank = int(msz), int(nvar), int(krank), int(xrank)
+        self.V = rng.standard_normal((nvar, msz, krank)) / np.sqrt(msz)
+        self.d = rng.choice([-1.0, 1.0], size=(nvar, krank))
+        Q, _ = np.linalg.qr(rng.standard_normal((msz, xrank)))
+        lam = 1.0 + np.arange(xrank) / xrank
+        self.Q, self.lam = Q, lam * ((np.sqrt(msz) if xtrace is None else xtrace) / lam.sum())
+        QV = np.einsum("ma,kmp->kap", Q, self.V)                                  # Q' V_k
+        self.b = -np.einsum("kp,a,kap,kap->k", self.d, self.lam, QV, QV)
+        self.ystar = 0.1 * rng.standard_normal(nvar)
+        self.optimum = float(self.b @ self.ystar)
+
+    def factors(self):
+        return [[(self.V[k], self.d[k]) for k in range(self.nvar)]]
+
+    def C_dense(self):
+        m = self.msz
+        Vall = self.V.transpose(1, 0, 2).reshape(m, -1)                           # column k * krank + p = column p of V_k
+        Cd = np.eye(m) - self.Q @ self.Q.T - (Vall * (self.ystar[:, None] * self.d).ravel()) @ Vall.T
+        return np.asfortranarray(0.5 * (Cd + Cd.T))
+
+    def F0(self):
+        return [-self.C_dense()]
+
+    def constraint(self, k):
+        """A_k as a dense matrix (tests at small size / the CPU oracle)."""
+        return (self.V[k] * self.d[k]) @ self.V[k].T
