@@ -7,9 +7,7 @@
 // src/kron_etc.jl.  nvar-/nlin-vectors and scalars stay with the host driver.
 //
 // eigmin (predictor_corrector.jl:272,285; Solvers.jl:503,505) is a Lanczos iteration on the
-// device: y = M q on all CUs (bandwidth-bound symmetric mat-vec), one fused single-workgroup
-// kernel per step for alpha, the three-term update and beta, no host sync inside a batch of
-// steps; the host only bisects the tiny tridiagonal matrix.
+// device (lz.hip); this file holds its callers.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -18,7 +16,6 @@
 
 #include "../../include/loraine_hip.h"
 #include "ops.h"
-#include "tridiag.h"
 
 namespace lrn {
 
@@ -94,6 +91,9 @@ __global__ void add_diag_mat_kernel(double* __restrict__ M, int n, double eps) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) M[(long)i * n + i] += eps;
 }
+void add_diag_mat(hipStream_t st, double* M, int n, double eps) {
+  hipLaunchKernelGGL(add_diag_mat_kernel, dim3((n + 255) / 256), dim3(256), 0, st, M, n, eps);
+}
 
 // two-stage reductions: partial[b] = sum A.*B (B may be null -> A.*A)
 __global__ __launch_bounds__(256) void dot_part_kernel(const double* __restrict__ A, const double* __restrict__ B, long n,
@@ -133,985 +133,6 @@ static int dot_dev(lrn_ctx* c, const double* A, const double* B, long n, double*
   LRN_TRY(ensure(c, c->redbuf, (size_t)(np + 64) * 8));
   hipLaunchKernelGGL(dot_part_kernel, dim3(np), dim3(256), 0, c->stream, A, B, n, c->redbuf.as<double>());
   hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(256), 0, c->stream, c->redbuf.as<double>(), np, out_dev);
-  return LRN_OK;
-}
-
-// ------------------------------------------------------------------ Lanczos eigmin
-__global__ void lz_init_kernel(double* __restrict__ q, int n) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  unsigned h = (unsigned)i * 2654435761u + 12345u;     // fixed pseudo-random start vector
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  q[i] = ((double)h / 4294967296.0) - 0.5;
-}
-
-// ypart[chunk][i] = sum_{j in chunk} M[i + j*n] q[j]
-__global__ __launch_bounds__(256) void symv_part_kernel(const double* __restrict__ M, int n, int cper,
-                                                        const double* __restrict__ q, double* __restrict__ ypart) {
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  int c0 = blockIdx.y * cper, c1 = min(n, c0 + cper);
-  double s = 0.0;
-  for (int j = c0; j < c1; ++j) s += M[(long)i + (long)j * n] * q[j];
-  ypart[(long)blockIdx.y * n + i] = s;
-}
-
-__device__ __forceinline__ double wg_sum1024b(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < 16; ++i) s += sh[i];
-  return s;
-}
-
-// one Lanczos step (no re-orthogonalisation): w = sum ypart; a = q.w; w -= a q + b_prev q_prev;
-// b = ||w||; q_next = w / b.   j == -1: just normalise q in place (start vector).
-__global__ __launch_bounds__(1024) void lz_step_kernel(const double* __restrict__ ypart, int nchunk, int n, int j,
-                                                       double* __restrict__ q, double* __restrict__ qprev,
-                                                       double* __restrict__ w, double* __restrict__ ab) {
-  __shared__ double sh[16];
-  const int t = threadIdx.x;
-  if (j < 0) {
-    double s = 0.0;
-    for (int i = t; i < n; i += 1024) s += q[i] * q[i];
-    s = wg_sum1024b(s, sh);
-    double r = 1.0 / sqrt(s);
-    for (int i = t; i < n; i += 1024) { q[i] *= r; qprev[i] = 0.0; }
-    return;
-  }
-  const double bprev = j > 0 ? ab[2 * (j - 1) + 1] : 0.0;
-  double a = 0.0;
-  for (int i = t; i < n; i += 1024) {
-    double s = 0.0;
-    for (int k = 0; k < nchunk; ++k) s += ypart[(long)k * n + i];
-    w[i] = s;
-    a += q[i] * s;
-  }
-  a = wg_sum1024b(a, sh);
-  double b2 = 0.0;
-  for (int i = t; i < n; i += 1024) {
-    double v = w[i] - a * q[i] - bprev * qprev[i];
-    w[i] = v;
-    b2 += v * v;
-  }
-  b2 = wg_sum1024b(b2, sh);
-  double b = sqrt(b2);
-  double r = b > 0.0 ? 1.0 / b : 0.0;
-  for (int i = t; i < n; i += 1024) {
-    double qi = q[i];
-    qprev[i] = qi;
-    q[i] = w[i] * r;
-  }
-  if (t == 0) { ab[2 * j] = a; ab[2 * j + 1] = b; }
-}
-
-// One Lanczos step in ONE launch (n <= LZ_FUSED_MAX; round 3).  The two-kernel step above costs two dependent launches
-// (10 + 7 us at msz 800, rocprofv3) for a few microseconds of work.  Here every workgroup first finishes step j-1 by
-// itself -- alpha_{j-1} from the partial dots of the previous launch, w = y_{j-1} - alpha q_{j-1} - beta_{j-2} q_{j-2},
-// beta_{j-1} = ||w|| and q_j = w / beta_{j-1} for ALL n entries, redundantly (n <= 4096 flops per thread block, in LDS) --
-// and then computes its 16 rows of y_j = M q_j and their share of q_j . y_j.  Vectors rotate through three (q) and two (y)
-// buffers so that nothing a workgroup still reads is overwritten inside a launch.  `do_symv` = 0: only finish step j-1
-// (last launch of a batch: the host needs alpha, beta of every step it reads).
-static constexpr int LZ_FUSED_MAX = 16384;      // (round 4: 4096 -> 16384, q_j in up to 128 KB of LDS: at msz 10^4 the two-kernel
-                                                // step costs 0.21 + 0.24 ms -- its single-workgroup half sums 64 partial vectors)
-__device__ __forceinline__ void lz_fused_body(const double* __restrict__ M, int n, int nwg, int j, int do_symv, int qmod,
-                                              double* Q3, double* Y2, double* PA2, double* ab, double* qs, double* sh) {
-  const int t = threadIdx.x;
-  double* qj = Q3 + (size_t)(j % qmod) * n;       // qmod = 3: rotating buffers; > number of steps: every q_j is kept
-  if (j == 0) {
-    for (int i = t; i < n; i += 256) qs[i] = qj[i];
-  } else {
-    const double* qm1 = Q3 + (size_t)((j - 1) % qmod) * n;  // q_{j-1}
-    const double* qm2 = Q3 + (size_t)((j > 1 ? j - 2 : 0) % qmod) * n;   // q_{j-2}
-    const double* ym1 = Y2 + (size_t)((j + 1) & 1) * n;     // y_{j-1}
-    const double* pa = PA2 + (size_t)((j + 1) & 1) * nwg;
-    double a = 0.0;
-    for (int e = t; e < nwg; e += 256) a += pa[e];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-    if ((t & 63) == 0) sh[t >> 6] = a;
-    __syncthreads();
-    const double alpha = sh[0] + sh[1] + sh[2] + sh[3];
-    const double bprev = j > 1 ? ab[2 * (j - 2) + 1] : 0.0;
-    __syncthreads();
-    double b2 = 0.0;
-    for (int i = t; i < n; i += 256) {
-      const double v = ym1[i] - alpha * qm1[i] - (j > 1 ? bprev * qm2[i] : 0.0);
-      qs[i] = v;
-      b2 += v * v;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) b2 += __shfl_down(b2, off, 64);
-    if ((t & 63) == 0) sh[t >> 6] = b2;
-    __syncthreads();
-    const double beta = sqrt(sh[0] + sh[1] + sh[2] + sh[3]);
-    const double r = beta > 0.0 ? 1.0 / beta : 0.0;
-    for (int i = t; i < n; i += 256) {
-      const double v = qs[i] * r;
-      qs[i] = v;
-      if (blockIdx.x == 0) qj[i] = v;
-    }
-    if (blockIdx.x == 0 && t == 0) { ab[2 * (j - 1)] = alpha; ab[2 * (j - 1) + 1] = beta; }
-  }
-  __syncthreads();
-  if (!do_symv) return;
-  // rows [16 blockIdx.x, +16) of M q = the same COLUMNS of the symmetric M (contiguous): wave w takes four of them, its
-  // lanes run down the columns with the four loads of a step in flight together (round 4; round 3 walked the rows with a
-  // stride of n and four loads in flight per thread: 50 dependent rounds of L2 latency at msz 800)
-  {
-    const int lane = t & 63, w = t >> 6;
-    const int c0 = blockIdx.x * 16 + 4 * w;
-    const double* m0 = M + (size_t)min(c0 + 0, n - 1) * n;
-    const double* m1 = M + (size_t)min(c0 + 1, n - 1) * n;
-    const double* m2 = M + (size_t)min(c0 + 2, n - 1) * n;
-    const double* m3 = M + (size_t)min(c0 + 3, n - 1) * n;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll 4
-    for (int k = lane; k < n; k += 64) {
-      const double q = qs[k];
-      a0 += m0[k] * q; a1 += m1[k] * q; a2 += m2[k] * q; a3 += m3[k] * q;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      a0 += __shfl_down(a0, off, 64); a1 += __shfl_down(a1, off, 64);
-      a2 += __shfl_down(a2, off, 64); a3 += __shfl_down(a3, off, 64);
-    }
-    if (lane == 0) { sh[4 * w + 0] = a0; sh[4 * w + 1] = a1; sh[4 * w + 2] = a2; sh[4 * w + 3] = a3; }
-  }
-  __syncthreads();
-  if (t < 16) {
-    const double y = sh[t];
-    const int ii = blockIdx.x * 16 + t;
-    double d = 0.0;
-    if (ii < n) {
-      Y2[(size_t)(j & 1) * n + ii] = y;
-      d = qs[ii] * y;
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) d += __shfl_down(d, off, 16);
-    if (t == 0) PA2[(size_t)(j & 1) * nwg + blockIdx.x] = d;
-  }
-}
-
-__global__ __launch_bounds__(256) void lz_fused_kernel(const double* __restrict__ M, int n, int nwg, int j, int do_symv, int qmod,
-                                                       double* Q3, double* Y2, double* PA2, double* ab) {
-  extern __shared__ double qs[];            // q_j (n doubles)
-  __shared__ double sh[16 * 16 + 8];
-  lz_fused_body(M, n, nwg, j, do_symv, qmod, Q3, Y2, PA2, ab, qs, sh);
-}
-
-// The same step of TWO independent runs on matrices of one size in one launch: blockIdx.y picks the run (round 4, second
-// session).  The two eigmin searches of a step-length computation used to live on two streams so that their launch chains
-// overlap.  Under rocprofv3's kernel trace they do not (tools/lz_overlap.py on a maxG11 solve: 4 % of the kernel time of the
-// two queues overlaps); without the profiler both forms take the same time (same box, profiles/r04_lanczos_pair_ab.txt:
-// find_step 4.99 vs 4.96 ms at 480 steps, 0.84 vs 0.90 at 64) -- the chains did overlap, and what a step-length search costs
-// is its LONGER chain at 8-10 us per step.  The paired form is the default all the same: half the launches for the host to
-// issue, one stream, no events between streams.
-struct LzPair {
-  const double* M[2];
-  double* Q3[2];
-  double* Y2[2];
-  double* PA2[2];
-  double* ab[2];
-};
-__global__ __launch_bounds__(256) void lz_fused_pair_kernel(LzPair a, int n, int nwg, int j, int do_symv, int qmod) {
-  extern __shared__ double qs[];            // q_j (n doubles)
-  __shared__ double sh[16 * 16 + 8];
-  const int r = blockIdx.y;                 // (uniform: the arrays of the argument block are read with scalar loads)
-  lz_fused_body(a.M[r], n, nwg, j, do_symv, qmod, a.Q3[r], a.Y2[r], a.PA2[r], a.ab[r], qs, sh);
-}
-
-// more than 64 KB of dynamic LDS need the attribute (once per device); false: the two-kernel step is taken
-static bool lz_big_lds_ok() {
-  static bool done[64] = {}, ok[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  if (!done[dev]) {
-    ok[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LZ_FUSED_MAX * 8) == hipSuccess &&
-              hipFuncSetAttribute(reinterpret_cast<const void*>(lz_fused_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LZ_FUSED_MAX * 8) == hipSuccess;
-    if (!ok[dev]) (void)hipGetLastError();
-    done[dev] = true;
-  }
-  return ok[dev];
-}
-
-// ---- the same steps [j0, j1) in ONE launch (round 4; MEASURED SLOWER, kept behind LRN_LZ_PERSIST=1 for the record): a batch
-// of Lanczos steps is a chain of launches of 7-8 us each for 2-3 us of work.  Here the nwg <= 256 workgroups stay
-// resident and meet at a barrier after every step: a monotonic counter in global memory (release fence, one atomic add per
-// workgroup, acquire fence; every workgroup executes the same number of barriers).  The kernel can NOT hang: a workgroup
-// that waits longer than `limit` ticks of the 100 MHz wall clock (its peers were not scheduled -- a GPU shared with another
-// process, an over-subscribed chip) raises flag[1], every workgroup leaves at its next barrier, and the host redoes the run
-// with one launch per step (lz_fetch).  flag[0]: the counter, flag[1]: abort.
-__device__ __forceinline__ bool lz_grid_barrier(unsigned* flag, unsigned target, long long limit, int* ok_s) {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    atomicAdd(flag, 1u);
-    int ok = 1;
-    const long long t0 = wall_clock64();
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      if (__hip_atomic_load(flag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = 0; break; }
-      if (wall_clock64() - t0 > limit) {
-        __hip_atomic_store(flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = 0;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    __threadfence();
-    *ok_s = ok;
-  }
-  __syncthreads();
-  return *ok_s != 0;
-}
-
-__global__ __launch_bounds__(256) void lz_fused_multi_kernel(const double* __restrict__ M, int n, int nwg, int j0, int j1,
-                                                             int qmod, double* Q3, double* Y2, double* PA2, double* ab,
-                                                             unsigned* flag, unsigned base, long long limit) {
-  extern __shared__ double qs[];
-  __shared__ double sh[16 * 16 + 8];
-  __shared__ int ok_s;
-  unsigned target = base;
-  for (int j = j0; j < j1; ++j) {
-    lz_fused_body(M, n, nwg, j, 1, qmod, Q3, Y2, PA2, ab, qs, sh);
-    target += (unsigned)nwg;
-    if (!lz_grid_barrier(flag, target, limit, &ok_s)) return;
-  }
-  if (blockIdx.x == 0) lz_fused_body(M, n, nwg, j1, 0, qmod, Q3, Y2, PA2, ab, qs, sh);      // finish step j1 - 1
-}
-
-// ---- RESIDENT steps, second form (round 4, second session; option lz_resident).  What made the kernel above slower than
-// one launch per step is not the barrier but its two device-scope fences (tools/lab/xcd_barrier.hip,
-// profiles/r04_xcd_barrier.txt: a barrier of 51 workgroups with an 801-vector exchanged costs 4.7 us per step with
-// __threadfence() on both sides and 2.3 us when counter AND payload travel as relaxed agent-scope atomics -- they bypass the
-// L1s and meet at the coherent level, nothing has to be written back or invalidated), and that every step still re-read its
-// 16 columns of M and three vectors from L2.  Here, for n <= 1024:
-//  * a workgroup keeps its 16 columns of M in REGISTERS for the whole launch (wave w: columns 4 w .. 4 w + 3, lane l: rows
-//    l, l + 64, ...: the order in which lz_fused_body sums them) and q_j, q_{j-1}, q_{j-2} in LDS;
-//  * the only data other workgroups produce -- the 16 entries of y_j and the partial sum of q_j . y_j per workgroup -- are
-//    written and read with relaxed agent-scope atomic stores / loads; beta_{j-1} stays in a register;
-//  * there is no barrier at all: a word that has not been written yet holds a mark, and a reader polls the 17 words of every
-//    workgroup until no mark is left (LZ_MARK_BITS below); every poll loop is bounded by the wall clock and an abort word.
-// The arithmetic, operation by operation, is lz_fused_body's: same coefficients bit for bit
-// (test_resident_lanczos_steps_are_the_launched_ones).  blockIdx.y: the run (two runs of a step-length search in lock-step).
-struct LzRes {
-  const double* M;
-  double* Q3;
-  double* Y3;            // three n-vectors: y_j in buffer j % 3
-  double* PA3;           // three nwg-vectors: the workgroups' shares of q_j . y_j
-  double* ab;
-  unsigned* flag;        // flag[1]: abort word
-};
-struct LzResPair { LzRes r[2]; };
-
-__device__ __forceinline__ double lz_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void lz_st(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// "Not written yet": a quiet NaN with a payload no computation produces.  The exchange needs NO counter: a workgroup's
-// 17 words of step j go to buffer j % 3, which it has filled with this value at step j - 1 -- at a time when every
-// workgroup was done reading the buffer's previous content (that of step j - 3: read in the first phase of step j - 2, and a
-// workgroup publishes its words of step j - 2 only after that phase; seeing all of those is what lets step j - 1 begin) --
-// and whose reset it has seen acknowledged before it published step j - 1 (s_waitcnt vmcnt(0) between the two).  A reader
-// therefore finds either the mark or the word of step j, never an older word, and polls until no mark is left.
-static constexpr unsigned long long LZ_MARK_BITS = 0x7ff8a5a5deadbeefULL;
-__device__ __forceinline__ bool lz_is_mark(double v) { return (unsigned long long)__double_as_longlong(v) == LZ_MARK_BITS; }
-
-__global__ void lz_mark_kernel(double* __restrict__ p, int cnt) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < cnt) p[i] = __longlong_as_double((long long)LZ_MARK_BITS);
-}
-
-static constexpr int LZ_RES_MAX = 1024;       // 16 rows per lane and column
-__global__ __launch_bounds__(256) void lz_resident_kernel(LzResPair args, int n, int nwg, int j0, int j1, int qmod, long long limit) {
-  extern __shared__ double ql[];            // three n-vectors: q_j, q_{j-1}, q_{j-2} rotate through them
-  __shared__ double sh[16 * 16 + 8];
-  __shared__ int ok_s;
-  const LzRes& R = args.r[blockIdx.y];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int c0 = blockIdx.x * 16 + 4 * w;
-  const double mark = __longlong_as_double((long long)LZ_MARK_BITS);
-  constexpr int U = LZ_RES_MAX / 64;
-  double mreg[4][U];
-#pragma unroll
-  for (int cc = 0; cc < 4; ++cc) {
-    const double* col = R.M + (size_t)min(c0 + cc, n - 1) * n;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = lane + 64 * u;
-      mreg[cc][u] = k < n ? col[k] : 0.0;
-    }
-  }
-  // state of the recurrence at entry: q_{j0-1}, q_{j0-2} (the ring of the previous launches), beta_{j0-2}
-  double bprev = 0.0;
-  if (j0 > 0) {
-    const double* g1 = R.Q3 + (size_t)((j0 - 1) % qmod) * n;
-    double* l1 = ql + (size_t)((j0 - 1) % 3) * n;
-    for (int i = t; i < n; i += 256) l1[i] = g1[i];
-    if (j0 > 1) {
-      const double* g2 = R.Q3 + (size_t)((j0 - 2) % qmod) * n;
-      double* l2 = ql + (size_t)((j0 - 2) % 3) * n;
-      for (int i = t; i < n; i += 256) l2[i] = g2[i];
-      bprev = R.ab[2 * (j0 - 2) + 1];
-    }
-  }
-  if (t == 0) ok_s = 1;
-  __syncthreads();
-  double alpha_out = 0.0;
-  for (int j = j0; j <= j1; ++j) {
-    const bool finish = j == j1;            // (workgroup 0 only: alpha, beta of step j1 - 1 and q_{j1} for the host and the next launch)
-    if (finish && blockIdx.x != 0) break;
-    double* qs = ql + (size_t)(j % 3) * n;
-    double* qj = R.Q3 + (size_t)(j % qmod) * n;
-    bool polled = true;
-    if (j == 0) {
-      for (int i = t; i < n; i += 256) qs[i] = qj[i];
-    } else {
-      const double* qm1 = ql + (size_t)((j - 1) % 3) * n;
-      const double* qm2 = ql + (size_t)((j > 1 ? j - 2 : 0) % 3) * n;
-      const double* ym1 = R.Y3 + (size_t)((j - 1) % 3) * n;
-      const double* pa = R.PA3 + (size_t)((j - 1) % 3) * nwg;
-      // the words of step j - 1 of every workgroup: polled until none is the mark (all requests of a poll in flight together)
-      double yv[LZ_RES_MAX / 256];
-      double a = 0.0;
-      long long t0 = 0;
-      for (int tries = 0;; ++tries) {
-        int bad = 0;
-#pragma unroll
-        for (int u = 0; u < LZ_RES_MAX / 256; ++u) {
-          const int i = t + 256 * u;
-          yv[u] = i < n ? lz_ld(ym1 + i) : 0.0;
-        }
-        a = t < nwg ? lz_ld(pa + t) : 0.0;            // (nwg <= 64)
-#pragma unroll
-        for (int u = 0; u < LZ_RES_MAX / 256; ++u) bad |= lz_is_mark(yv[u]) ? 1 : 0;
-        bad |= lz_is_mark(a) ? 1 : 0;
-        if (tries > 0 && t == 0) {                    // bounded: the wall clock, and the other workgroups' verdict
-          if (tries == 1) t0 = wall_clock64();
-          if (__hip_atomic_load(R.flag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ok_s = 0;
-          else if (wall_clock64() - t0 > limit) {
-            __hip_atomic_store(R.flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok_s = 0;
-          }
-        }
-        if (!__syncthreads_or(bad)) break;
-        if (!ok_s) { polled = false; break; }
-      }
-      if (!polled) return;
-      // this workgroup's words of buffer (j + 1) % 3 back to the mark (see LZ_MARK_BITS): issued first thing -- everybody has
-      // published step j - 1, so nobody reads that buffer's old content any more --, acknowledged by the time step j is published
-      if (!finish && t < 16) {
-        const int ii = blockIdx.x * 16 + t;
-        if (ii < n) lz_st(R.Y3 + (size_t)((j + 1) % 3) * n + ii, mark);
-        if (t == 0) lz_st(R.PA3 + (size_t)((j + 1) % 3) * nwg + blockIdx.x, mark);
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
-      if ((t & 63) == 0) sh[t >> 6] = a;
-      __syncthreads();
-      const double alpha = sh[0] + sh[1] + sh[2] + sh[3];
-      __syncthreads();
-      double b2 = 0.0;
-#pragma unroll
-      for (int u = 0; u < LZ_RES_MAX / 256; ++u) {
-        const int i = t + 256 * u;
-        if (i < n) {
-          const double v = yv[u] - alpha * qm1[i] - (j > 1 ? bprev * qm2[i] : 0.0);
-          qs[i] = v;
-          b2 += v * v;
-        }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) b2 += __shfl_down(b2, off, 64);
-      if ((t & 63) == 0) sh[t >> 6] = b2;
-      __syncthreads();
-      const double beta = sqrt(sh[0] + sh[1] + sh[2] + sh[3]);
-      const double r = beta > 0.0 ? 1.0 / beta : 0.0;
-      for (int i = t; i < n; i += 256) qs[i] *= r;
-      alpha_out = alpha;
-      bprev = beta;
-    }
-    if (j == 0 && !finish && t < 16) {      // (step 0: the marks of buffer 1; lz_resident_prepare has set them already, kept for symmetry)
-      const int ii = blockIdx.x * 16 + t;
-      if (ii < n) lz_st(R.Y3 + (size_t)n + ii, mark);
-      if (t == 0) lz_st(R.PA3 + (size_t)nwg + blockIdx.x, mark);
-    }
-    __syncthreads();
-    if (finish) {      // (workgroup 0)
-      if (j > 0) {
-        for (int i = t; i < n; i += 256) qj[i] = qs[i];
-        if (t == 0) { R.ab[2 * (j - 1)] = alpha_out; R.ab[2 * (j - 1) + 1] = bprev; }
-      }
-      break;
-    }
-    {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int k = lane + 64 * u;
-        if (k < n) {
-          const double q = qs[k];
-          a0 += mreg[0][u] * q; a1 += mreg[1][u] * q; a2 += mreg[2][u] * q; a3 += mreg[3][u] * q;
-        }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        a0 += __shfl_down(a0, off, 64); a1 += __shfl_down(a1, off, 64);
-        a2 += __shfl_down(a2, off, 64); a3 += __shfl_down(a3, off, 64);
-      }
-      if (lane == 0) { sh[4 * w + 0] = a0; sh[4 * w + 1] = a1; sh[4 * w + 2] = a2; sh[4 * w + 3] = a3; }
-    }
-    __syncthreads();
-    if (t < 16) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the marks above have been acknowledged
-      const double y = sh[t];
-      const int ii = blockIdx.x * 16 + t;
-      double d = 0.0;
-      if (ii < n) {
-        lz_st(R.Y3 + (size_t)(j % 3) * n + ii, y);
-        d = qs[ii] * y;
-      }
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) d += __shfl_down(d, off, 16);
-      if (t == 0) lz_st(R.PA3 + (size_t)(j % 3) * nwg + blockIdx.x, d);
-    }
-    // q_j, alpha_{j-1}, beta_{j-1} for the host and the next launch: plain stores of workgroup 0, BEHIND the publication
-    // (the wait for the marks' acknowledgement would otherwise wait for them as well, every step, with everybody waiting)
-    if (blockIdx.x == 0 && j > 0) {
-      for (int i = t; i < n; i += 256) qj[i] = qs[i];
-      if (t == 0) { R.ab[2 * (j - 1)] = alpha_out; R.ab[2 * (j - 1) + 1] = bprev; }
-    }
-    __syncthreads();      // (sh and the q ring are rewritten by the next step)
-  }
-}
-
-// steps [j0, j1) of the single-launch Lanczos recurrence with every q_j kept (Q: (j1 + 1) x n doubles, q_0 = unit start
-// vector in Q[0..n)), then the finishing launch: alpha_j, beta_j of all steps < j1 are in ab, q_{j1} in Q.  For
-// lanczos.hip (preconditioner setup); n <= LZ_FUSED_MAX.
-int lz_fused_steps(hipStream_t st, const double* M, int n, int j0, int j1, int qcap, double* Q, double* Y2, double* PA2,
-                   double* ab) {
-  if (n > LZ_FUSED_LIMIT || j1 + 1 > qcap) return LRN_ERR_ARG;
-  const int nwg = (n + 15) / 16;
-  const size_t lds = (size_t)n * 8;
-  for (int j = j0; j < j1; ++j)
-    hipLaunchKernelGGL(lz_fused_kernel, dim3(nwg), dim3(256), lds, st, M, n, nwg, j, 1, qcap, Q, Y2, PA2, ab);
-  hipLaunchKernelGGL(lz_fused_kernel, dim3(1), dim3(256), lds, st, M, n, nwg, j1, 0, qcap, Q, Y2, PA2, ab);
-  return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-}
-
-// the same steps as ONE resident launch (lz_resident_kernel; n <= LZ_RES_MAX): Y3 / PA3 = three n- / nwg-vectors and flag =
-// two words of the caller's workspace (flag[1]: abort word), all prepared by lz_resident_prepare before the run's first step
-bool lz_resident_ok(const lrn_ctx* c, int n) {
-  return c->opt.lz_resident != 0 && !c->lz_no_persist && n <= LZ_RES_MAX && n >= 32;
-}
-// before the first step of a run: the three exchange buffers hold the mark, the abort word is clear
-void lz_resident_prepare(hipStream_t st, int n, double* Y3, double* PA3, unsigned* flag) {
-  const int nwg = (n + 15) / 16;
-  hipLaunchKernelGGL(lz_mark_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, st, Y3, 3 * n);
-  hipLaunchKernelGGL(lz_mark_kernel, dim3((3 * nwg + 255) / 256), dim3(256), 0, st, PA3, 3 * nwg);
-  (void)hipMemsetAsync(flag, 0, 16, st);
-}
-int lz_resident_steps(hipStream_t st, const double* M, int n, int j0, int j1, int qcap, double* Q, double* Y3, double* PA3,
-                      double* ab, unsigned* flag) {
-  if (n > LZ_RES_MAX || j1 + 1 > qcap || qcap < 3) return LRN_ERR_ARG;
-  const int nwg = (n + 15) / 16;
-  LzResPair a;
-  a.r[0] = LzRes{M, Q, Y3, PA3, ab, flag};
-  a.r[1] = a.r[0];
-  hipLaunchKernelGGL(lz_resident_kernel, dim3(nwg, 1), dim3(256), (size_t)3 * n * 8, st, a, n, nwg, j0, j1, qcap, 2000000LL);
-  return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-}
-
-// (the eigenvalues of the tridiagonal matrices: tridiag.h -- bisection on a division-free Sturm count, bracket from the
-// previous batch's value)
-
-// |beta_m * s_m| for the Ritz pair (theta, s) of T_m: the residual norm ||M v - theta v|| of the
-// Ritz vector, a rigorous bound on the distance from theta to the spectrum.  s by two steps of
-// inverse iteration on the tridiagonal matrix (Thomas algorithm with a tiny shift).
-static double ritz_residual(const std::vector<double>& a, const std::vector<double>& b, int m, double theta) {
-  if (m <= 1) return 0.0;
-  std::vector<double> s(m, 1.0 / std::sqrt((double)m)), d(m), u(m), y(m);
-  double scale = 0.0;
-  for (int i = 0; i < m; ++i) scale = std::max(scale, std::fabs(a[i]) + (i < m - 1 ? std::fabs(b[i]) : 0.0));
-  const double shift = theta - 1e-13 * std::max(scale, 1e-300) - 1e-300;
-  for (int it = 0; it < 3; ++it) {
-    // solve (T - shift I) y = s  (T - shift I is positive definite up to rounding)
-    d[0] = a[0] - shift;
-    if (d[0] == 0.0) d[0] = 1e-300;
-    u[0] = s[0];
-    for (int i = 1; i < m; ++i) {
-      double l = b[i - 1] / d[i - 1];
-      d[i] = a[i] - shift - l * b[i - 1];
-      if (d[i] == 0.0) d[i] = 1e-300;
-      u[i] = s[i] - l * u[i - 1];
-    }
-    y[m - 1] = u[m - 1] / d[m - 1];
-    for (int i = m - 2; i >= 0; --i) y[i] = (u[i] - b[i] * y[i + 1]) / d[i];
-    double nrm = 0.0;
-    for (int i = 0; i < m; ++i) nrm += y[i] * y[i];
-    nrm = std::sqrt(nrm);
-    if (!(nrm > 0.0) || !std::isfinite(nrm)) return std::fabs(b[m - 1]);
-    for (int i = 0; i < m; ++i) s[i] = y[i] / nrm;
-  }
-  return std::fabs(b[m - 1] * s[m - 1]);
-}
-
-// One Lanczos iteration as a resumable run: batches of 16 steps are queued on the run's stream, the (alpha, beta)
-// pairs come back in one copy per batch and the host decides on the tridiagonal matrix.  The two eigmin calls of a
-// step-length search run side by side: in one launch per pair of steps (eigmin_dev_pair_merged), or, above LZ_FUSED_MAX,
-// as two launch chains on two streams (eigmin_dev_pair).
-struct LzRun {
-  const double* M = nullptr;
-  int n = 0;
-  hipStream_t st = nullptr;
-  double *q = nullptr, *qprev = nullptr, *w = nullptr, *ypart = nullptr, *ab = nullptr;
-  int nchunk = 1, cper = 1, mmax = 0, m = 0, m1 = 0;
-  std::vector<double> a, b, hab;
-  double theta = 0.0, theta_prev = 0.0, scale = 0.0;
-  double last_move = 0.0;                   // |theta - theta_prev| of the last collect: how far the next one is expected to move
-  int mc = 0;                               // steps whose coefficients the host holds (lz_fetch); a batch [mc, m1) may be queued ahead
-  bool ahead = false;
-  double err_prev = 0.0, err_last = 0.0;    // residual / (1e-3 x its scale) at the last two looks (0: none): lz_queue_ahead
-  bool have_prev = false, conv = false, done = false;
-  bool fused = false;                       // lz_fused_kernel: Q3 = q (3 n), Y2 = w (2 n), PA2 = ypart (2 nwg)
-  int nwg = 0;
-  bool persist = false;                     // lz_fused_multi_kernel: a batch of steps per launch
-  bool resident = false;                    // lz_resident_kernel: the same, M in registers, relaxed-atomic exchange (option lz_resident)
-  double *y3 = nullptr, *pa3 = nullptr;     // its exchange buffers (3 n, 3 nwg doubles)
-  unsigned* flag = nullptr;                 // its barrier counter and abort word
-  unsigned bar_base = 0;                    // barriers passed so far x nwg
-};
-
-static int lz_begin(lrn_ctx* c, LzRun& r, const double* M, int n, hipStream_t st, DBuf& buf) {
-  r.M = M; r.n = n; r.st = st;
-  // without re-orthogonalisation the extreme Ritz value may need more than n steps
-  r.mmax = std::min(1500, 4 * n + 40);
-  // column chunks of the symmetric mat-vec: ~64 columns per thread keeps the step kernel's reduction short
-  r.nchunk = std::max(1, std::min(64, n / 64));
-  r.cper = (n + r.nchunk - 1) / r.nchunk;
-  r.nchunk = (n + r.cper - 1) / r.cper;
-  static const bool no_fused = getenv("LRN_LZ_UNFUSED") != nullptr;
-  r.fused = !no_fused && n <= LZ_FUSED_MAX && n >= 32 && ((size_t)n * 8 <= 60 * 1024 || lz_big_lds_ok());
-  r.nwg = (n + 15) / 16;
-  LRN_TRY(ensure(c, buf, ((size_t)5 * n + (size_t)std::max(r.nchunk * n, 2 * r.nwg) + 2 * (size_t)r.mmax + 64 + 3 * (size_t)n + 3 * (size_t)r.nwg) * 8));
-  r.q = buf.as<double>();                 // fused: Q3 = q[0..3n)
-  r.qprev = r.q + n;
-  r.w = r.q + 3 * (size_t)n;              // fused: Y2 = w[0..2n)
-  r.ypart = r.w + 2 * (size_t)n;          // fused: PA2
-  r.ab = r.ypart + (size_t)std::max(r.nchunk * n, 2 * r.nwg);
-  // (measurement knob, off: with two runs interleaved on two streams the per-step launches are hidden already and the
-  // barrier -- device-scope release / acquire across eight L2s -- costs more than a launch: maxG11 find_step 1.0 -> 1.25 ms)
-  static const bool persist_on = getenv("LRN_LZ_PERSIST") && atoi(getenv("LRN_LZ_PERSIST")) != 0;
-  r.persist = r.fused && persist_on && !c->lz_no_persist && r.nwg <= 256 && (size_t)n * 8 <= 60 * 1024;
-  r.resident = r.fused && !r.persist && c->opt.lz_resident != 0 && !c->lz_no_persist && n <= LZ_RES_MAX;
-  r.flag = reinterpret_cast<unsigned*>(r.ab + 2 * (size_t)r.mmax + 8);      // (inside the 64 doubles of slack)
-  r.y3 = r.ab + 2 * (size_t)r.mmax + 64;
-  r.pa3 = r.y3 + 3 * (size_t)n;
-  r.bar_base = 0;
-  return LRN_OK;
-}
-
-// start vector (after lz_begin; a fresh workspace is zeroed on c->stream, which r.st must have waited for)
-static void lz_start(LzRun& r) {
-  if (r.persist) (void)hipMemsetAsync(r.flag, 0, 16, r.st);
-  if (r.resident) lz_resident_prepare(r.st, r.n, r.y3, r.pa3, r.flag);
-  r.bar_base = 0;
-  hipLaunchKernelGGL(lz_init_kernel, dim3((r.n + 255) / 256), dim3(256), 0, r.st, r.q, r.n);
-  hipLaunchKernelGGL(lz_step_kernel, dim3(1), dim3(1024), 0, r.st, r.ypart, r.nchunk, r.n, -1, r.q, r.qprev, r.w, r.ab);
-}
-
-static void lz_launch(LzRun& r) {
-  const int batch = r.n <= 16 ? r.n : 16;
-  r.m1 = std::min(r.mmax, r.m + batch);
-  if (r.resident) {
-    LzResPair a;
-    a.r[0] = LzRes{r.M, r.q, r.y3, r.pa3, r.ab, r.flag};
-    a.r[1] = a.r[0];
-    hipLaunchKernelGGL(lz_resident_kernel, dim3(r.nwg, 1), dim3(256), (size_t)3 * r.n * 8, r.st, a, r.n, r.nwg, r.m, r.m1, 3, 2000000LL);
-    return;
-  }
-  if (r.fused && r.persist) {
-    hipLaunchKernelGGL(lz_fused_multi_kernel, dim3(r.nwg), dim3(256), (size_t)r.n * 8, r.st, r.M, r.n, r.nwg, r.m, r.m1, 3, r.q,
-                       r.w, r.ypart, r.ab, r.flag, r.bar_base, 2000000LL);          // limit: 20 ms at 100 MHz
-    r.bar_base += (unsigned)(r.m1 - r.m) * (unsigned)r.nwg;
-    return;
-  }
-  if (r.fused) {
-    const size_t lds = (size_t)r.n * 8;
-    for (int j = r.m; j < r.m1; ++j)
-      hipLaunchKernelGGL(lz_fused_kernel, dim3(r.nwg), dim3(256), lds, r.st, r.M, r.n, r.nwg, j, 1, 3, r.q, r.w, r.ypart, r.ab);
-    hipLaunchKernelGGL(lz_fused_kernel, dim3(1), dim3(256), lds, r.st, r.M, r.n, r.nwg, r.m1, 0, 3, r.q, r.w, r.ypart, r.ab);
-    return;
-  }
-  for (int j = r.m; j < r.m1; ++j) {
-    hipLaunchKernelGGL(symv_part_kernel, dim3((r.n + 255) / 256, r.nchunk), dim3(256), 0, r.st, r.M, r.n, r.cper, r.q, r.ypart);
-    hipLaunchKernelGGL(lz_step_kernel, dim3(1), dim3(1024), 0, r.st, r.ypart, r.nchunk, r.n, j, r.q, r.qprev, r.w, r.ab);
-  }
-}
-
-// waits for the batch in flight and brings its coefficients: r.mc steps are on the host afterwards
-static int lz_fetch(lrn_ctx* c, LzRun& r) {
-  const int m1 = r.m1;
-  r.hab.resize(2 * (size_t)m1);
-  LRN_HIP(c, hipMemcpyAsync(r.hab.data(), r.ab, (size_t)2 * m1 * 8, hipMemcpyDeviceToHost, r.st));
-  unsigned fl[2] = {0u, 0u};
-  if (r.persist || r.resident) LRN_HIP(c, hipMemcpyAsync(fl, r.flag, 8, hipMemcpyDeviceToHost, r.st));
-  LRN_HIP(c, hipStreamSynchronize(r.st));
-  if ((r.persist || r.resident) && fl[1] != 0u) {
-    // the resident workgroups did not all meet in time (see lz_fused_multi_kernel): from now on one launch per step on
-    // this context, and this run again from its start vector
-    c->lz_no_persist = true;
-    c->counts["lz_persist_abort"] += 1;
-    r.persist = false;
-    r.resident = false;
-    r.m = 0; r.have_prev = false; r.scale = 0.0;
-    r.err_prev = r.err_last = 0.0;
-    lz_start(r);
-    lz_launch(r);
-    return lz_fetch(c, r);
-  }
-  r.mc = m1;
-  r.m = m1;
-  r.ahead = false;
-  return LRN_OK;
-}
-
-// A run that is alone on the GPU (its partner of eigmin_dev_pair has ended, or eigmin_dev) leaves the stream empty while
-// the host looks at T: a synchronisation, a bisection, an inverse iteration and the first launch of the next batch, ~50 us
-// per 117 us batch (maxG11: 7.3 us per step in runs of 16-30 steps, 12 in runs of 120).  Between lz_fetch and lz_decide:
-// when the last two looks say that the coming one cannot end the run -- the residual, extrapolated geometrically, stays
-// above 1e-2 of its scale, out of reach of every rule of lz_decide (the Kato-Temple rule needs 1e-3, the plain one 1e-11;
-// the sign-class rule is excluded by theta < 0) -- the next batch is queued before that look.  Timing only: the looks and
-// their verdicts are the same; a batch queued in vain is ignored (eigmin_dev_pair makes c->stream wait for it).
-static bool lz_cannot_end_at_next_look(const LzRun& r) {
-  static const bool off = getenv("LRN_LZ_NOAHEAD") != nullptr;      // (measurement knob)
-  if (off || r.persist || r.ahead || r.mc >= r.mmax || !(r.err_prev > 0.0) || !(r.err_last > 0.0)) return false;
-  if (!(r.theta_prev < 0.0)) return false;
-  const double next = r.err_last * std::min(1.0, r.err_last / r.err_prev);
-  return next > 10.0;
-}
-
-static void lz_queue_ahead(lrn_ctx* c, LzRun& r) {
-  if (!lz_cannot_end_at_next_look(r)) return;
-  lz_launch(r);                       // (r.m == r.mc: the batch [mc, m1))
-  r.ahead = true;
-  c->counts["lanczos_ahead"] += 1;
-}
-
-// the look at T of the fetched steps: r.done when converged, settled or out of steps
-static int lz_decide(lrn_ctx* c, LzRun& r) {
-  const int m1 = r.mc;
-  r.a.resize(m1); r.b.resize(m1);
-  int mm_ = m1;
-  for (int j = 0; j < m1; ++j) {
-    r.a[j] = r.hab[2 * j]; r.b[j] = r.hab[2 * j + 1];
-    r.scale = std::max(r.scale, std::fabs(r.a[j]) + std::fabs(r.b[j]));
-    if (!(r.b[j] > 1e-14 * r.scale) && j + 1 < m1) { mm_ = j + 1; break; }      // invariant subspace
-  }
-  // T of the previous batch is a leading block of this one: its smallest eigenvalue bounds this one from above
-  r.theta = tri_eig_kth(r.a, r.b, mm_, 0, r.have_prev ? &r.theta_prev : nullptr, r.last_move);
-  if (mm_ < m1) { r.conv = true; r.done = true; return LRN_OK; }
-  // stop on the rigorous residual bound; for a clearly non-negative spectrum (theta > 0 is an
-  // upper bound of lambda_min) the callers only need the sign class once theta has settled
-  const double res = ritz_residual(r.a, r.b, mm_, r.theta);
-  r.err_prev = r.err_last;
-  r.err_last = res / (1e-3 * std::max(std::max(std::fabs(r.theta), 1e-4 * r.scale), 1e-300));
-  if (res <= 1e-11 * std::max(std::fabs(r.theta), 1e-4 * r.scale)) { r.conv = true; r.done = true; return LRN_OK; }
-  // Kato-Temple: theta - lambda_min <= res^2 / (lambda_2 - theta).  lambda_2 is bounded below through the second Ritz
-  // pair (an eigenvalue lies within res2 of theta2; if that eigenvalue is lambda_min itself -- a ghost copy -- the gap
-  // below is <= 0 and the rule does not fire).  The step-length rule consumes lambda_min to ~1e-10 relative.
-  static const double kt_tol = getenv("LRN_EIGMIN_KT") ? atof(getenv("LRN_EIGMIN_KT")) : 1e-10;
-  if (kt_tol > 0.0 && mm_ >= 8 && r.theta <= -1e-6 && res <= 1e-3 * std::max(std::fabs(r.theta), 1e-4 * r.scale)) {
-    const double th2 = tri_eig_kth(r.a, r.b, mm_, 1);
-    const double res2 = ritz_residual(r.a, r.b, mm_, th2);
-    const double gap = (th2 - res2) - r.theta;
-    if (gap > 0.0 && res < 0.25 * gap && res * res / gap <= kt_tol * std::fabs(r.theta)) {
-      r.conv = true; r.done = true;
-      return LRN_OK;
-    }
-  }
-  if (r.have_prev && r.theta > 0.0 && std::fabs(r.theta - r.theta_prev) <= 1e-3 * r.theta && r.mc >= 64) { r.done = true; return LRN_OK; }
-  r.last_move = r.have_prev ? std::fabs(r.theta - r.theta_prev) : 0.0;
-  r.theta_prev = r.theta;
-  r.have_prev = true;
-  if (r.mc >= r.mmax) r.done = true;
-  return LRN_OK;
-}
-
-// Both ends of the spectrum of a symmetric matrix from `nsteps` plain Lanczos steps: lo = smallest Ritz value (an UPPER
-// bound of lambda_min), hi = largest Ritz value, res_hi = residual norm of its Ritz pair (an eigenvalue lies within res_hi
-// of hi).  For the scaling of the Newton-Schulz iteration (prepw.hip), where a wrong value costs steps, not correctness.
-int lanczos_ends(lrn_ctx* c, const double* M, int n, int nsteps, double* lo, double* hi, double* res_hi) {
-  LzRun r;
-  LRN_TRY(lz_begin(c, r, M, n, c->stream, c->lzbuf));
-  r.mmax = std::min(r.mmax, std::max(4, nsteps));
-  lz_start(r);
-  std::vector<double> hab;
-  while (r.m < r.mmax) {
-    lz_launch(r);
-    r.m = r.m1;
-  }
-  const int m = r.m;
-  hab.resize(2 * (size_t)m);
-  LRN_TRY(copy_out(c, hab.data(), r.ab, (size_t)2 * m * 8));
-  std::vector<double> a(m), b(m), an(m);
-  int mm_ = m;
-  double scale = 0.0;
-  for (int j = 0; j < m; ++j) {
-    a[j] = hab[2 * j]; b[j] = hab[2 * j + 1]; an[j] = -a[j];
-    scale = std::max(scale, std::fabs(a[j]) + std::fabs(b[j]));
-    if (!(b[j] > 1e-14 * scale) && j + 1 < m) { mm_ = j + 1; break; }      // invariant subspace: the Ritz values are exact
-  }
-  if (!(scale == scale) || mm_ < 1) return set_error(c, LRN_ERR_STATE, "lanczos_ends: not a finite matrix");
-  *lo = tri_eig_kth(a, b, mm_, 0);
-  const double top = -tri_eig_kth(an, b, mm_, 0);    // largest eigenvalue of T = - smallest of -T (same off-diagonal)
-  *hi = top;
-  *res_hi = mm_ < m ? 0.0 : ritz_residual(an, b, mm_, -top);
-  c->counts["lanczos_ends_steps"] += m;
-  return LRN_OK;
-}
-
-int eigmin_dev(lrn_ctx* c, const double* M, int n, double* lam, int* steps_out, bool* converged = nullptr,
-               double* scale_out = nullptr) {
-  if (converged) *converged = true;
-  if (scale_out) *scale_out = 0.0;
-  if (n == 1) {
-    LRN_TRY(copy_out(c, lam, M, 8));
-    if (steps_out) *steps_out = 1;
-    return LRN_OK;
-  }
-  LzRun r;
-  LRN_TRY(lz_begin(c, r, M, n, c->stream, c->lzbuf));
-  lz_start(r);
-  while (!r.done) {
-    if (!r.ahead) lz_launch(r);
-    LRN_TRY(lz_fetch(c, r));
-    lz_queue_ahead(c, r);                    // (alone on the GPU: see there)
-    LRN_TRY(lz_decide(c, r));
-  }
-  *lam = r.theta;
-  c->counts["lanczos_steps"] += r.m;
-  c->counts["lanczos_runs"] += 1;
-  if (steps_out) *steps_out = r.m;
-  if (converged) *converged = r.conv;
-  if (scale_out) *scale_out = r.scale;
-  LRN_HIP(c, hipGetLastError());
-  return LRN_OK;
-}
-
-// ---- two runs in lock-step, one launch per pair of steps (lz_fused_pair_kernel), both on c->stream
-static void lz_launch_pair(LzRun* r) {
-  const int n = r[0].n;
-  const int batch = n <= 16 ? n : 16;
-  const int m0 = r[0].m, m1 = std::min(r[0].mmax, m0 + batch);
-  LzPair a;
-  for (int k = 0; k < 2; ++k) { a.M[k] = r[k].M; a.Q3[k] = r[k].q; a.Y2[k] = r[k].w; a.PA2[k] = r[k].ypart; a.ab[k] = r[k].ab; }
-  if (r[0].resident && r[1].resident) {
-    LzResPair ra;
-    for (int k = 0; k < 2; ++k) ra.r[k] = LzRes{r[k].M, r[k].q, r[k].y3, r[k].pa3, r[k].ab, r[k].flag};
-    hipLaunchKernelGGL(lz_resident_kernel, dim3(r[0].nwg, 2), dim3(256), (size_t)3 * n * 8, r[0].st, ra, n, r[0].nwg, m0, m1, 3, 2000000LL);
-    r[0].m1 = r[1].m1 = m1;
-    return;
-  }
-  const size_t lds = (size_t)n * 8;
-  for (int j = m0; j < m1; ++j)
-    hipLaunchKernelGGL(lz_fused_pair_kernel, dim3(r[0].nwg, 2), dim3(256), lds, r[0].st, a, n, r[0].nwg, j, 1, 3);
-  hipLaunchKernelGGL(lz_fused_pair_kernel, dim3(1, 2), dim3(256), lds, r[0].st, a, n, r[0].nwg, m1, 0, 3);
-  r[0].m1 = r[1].m1 = m1;
-}
-
-static int lz_fetch_pair(lrn_ctx* c, LzRun* r, bool* aborted) {
-  const int m1 = r[0].m1;
-  unsigned fl[2][2] = {{0u, 0u}, {0u, 0u}};
-  for (int k = 0; k < 2; ++k) {
-    r[k].hab.resize(2 * (size_t)m1);
-    LRN_HIP(c, hipMemcpyAsync(r[k].hab.data(), r[k].ab, (size_t)2 * m1 * 8, hipMemcpyDeviceToHost, r[0].st));
-    if (r[k].resident) LRN_HIP(c, hipMemcpyAsync(fl[k], r[k].flag, 8, hipMemcpyDeviceToHost, r[0].st));
-  }
-  LRN_HIP(c, hipStreamSynchronize(r[0].st));
-  *aborted = fl[0][1] != 0u || fl[1][1] != 0u;      // a resident launch gave up at a barrier: the caller starts over, launched
-  if (*aborted) return LRN_OK;
-  for (int k = 0; k < 2; ++k) { r[k].mc = m1; r[k].m = m1; r[k].ahead = false; }
-  return LRN_OK;
-}
-
-static int eigmin_dev_pair_merged(lrn_ctx* c, const double* M1, const double* M2, int n, double lam[2], bool conv[2],
-                                  double scale[2], bool* taken) {
-  LzRun r[2];
-  LRN_TRY(lz_begin(c, r[0], M1, n, c->stream, c->lzbuf));
-  LRN_TRY(lz_begin(c, r[1], M2, n, c->stream, c->lzbuf2));
-  *taken = r[0].fused && r[1].fused && !r[0].persist && !r[1].persist && r[0].mmax == r[1].mmax;
-  if (!*taken) return LRN_OK;                // (n > LZ_FUSED_MAX or < 32: the two-stream form below)
-  lz_start(r[0]);
-  lz_start(r[1]);
-  while (!r[0].done && !r[1].done) {
-    if (!r[0].ahead) lz_launch_pair(r);
-    bool aborted = false;
-    LRN_TRY(lz_fetch_pair(c, r, &aborted));
-    if (aborted) {
-      c->lz_no_persist = true;               // (lz_begin: no resident launches on this context from now on)
-      c->counts["lz_persist_abort"] += 1;
-      return eigmin_dev_pair_merged(c, M1, M2, n, lam, conv, scale, taken);
-    }
-    if (lz_cannot_end_at_next_look(r[0]) && lz_cannot_end_at_next_look(r[1])) {
-      lz_launch_pair(r);                     // (queued before the host looks at the batch it has just fetched: lz_queue_ahead)
-      r[0].ahead = r[1].ahead = true;
-      c->counts["lanczos_ahead"] += 1;
-    }
-    LRN_TRY(lz_decide(c, r[0]));
-    LRN_TRY(lz_decide(c, r[1]));
-    c->counts["lanczos_pair_batches"] += 1;
-    if (r[0].resident && r[1].resident) c->counts["lanczos_resident_batches"] += 1;
-  }
-  // the longer run goes on alone (a pair batch queued ahead carries its steps [mc, m1) already)
-  for (int k = 0; k < 2; ++k) {
-    while (!r[k].done) {
-      if (!r[k].ahead) lz_launch(r[k]);
-      LRN_TRY(lz_fetch(c, r[k]));
-      lz_queue_ahead(c, r[k]);
-      LRN_TRY(lz_decide(c, r[k]));
-    }
-  }
-  for (int k = 0; k < 2; ++k) {
-    lam[k] = r[k].theta; conv[k] = r[k].conv; scale[k] = r[k].scale;
-    c->counts["lanczos_steps"] += r[k].m;
-    c->counts["lanczos_runs"] += 1;
-  }
-  LRN_HIP(c, hipGetLastError());
-  return LRN_OK;
-}
-
-// The Lanczos runs of two matrices of the same size side by side (second one on c->stream2, which first waits for
-// everything queued on c->stream): results as from two eigmin_dev calls.  Option eigmin_pair = 2 (default): both runs in one
-// launch per step instead (eigmin_dev_pair_merged); 1: this two-stream form.
-static int eigmin_dev_pair(lrn_ctx* c, const double* M1, const double* M2, int n, double lam[2], bool conv[2],
-                           double scale[2]) {
-  if (c->opt.eigmin_pair >= 2) {
-    bool taken = false;
-    LRN_TRY(eigmin_dev_pair_merged(c, M1, M2, n, lam, conv, scale, &taken));
-    if (taken) return LRN_OK;
-  }
-  if (!c->stream2) LRN_HIP(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-  LzRun r[2];
-  LRN_TRY(lz_begin(c, r[0], M1, n, c->stream, c->lzbuf));
-  LRN_TRY(lz_begin(c, r[1], M2, n, c->stream2, c->lzbuf2));
-  LRN_HIP(c, hipEventRecord(c->ev1, c->stream));             // the matrices, and the zeroing of a fresh workspace
-  LRN_HIP(c, hipStreamWaitEvent(c->stream2, c->ev1, 0));
-  lz_start(r[0]);
-  lz_start(r[1]);
-  lz_launch(r[0]);
-  lz_launch(r[1]);
-  while (!r[0].done || !r[1].done) {
-    for (int k = 0; k < 2; ++k) {
-      if (r[k].done) continue;
-      LRN_TRY(lz_fetch(c, r[k]));
-      if (r[1 - k].done) lz_queue_ahead(c, r[k]);      // (otherwise the other run's batch keeps the GPU busy meanwhile)
-      LRN_TRY(lz_decide(c, r[k]));
-      if (!r[k].done && !r[k].ahead) lz_launch(r[k]);
-    }
-  }
-  if (r[1].ahead) {                          // a batch queued in vain on stream2 still reads M2 and its workspace
-    LRN_HIP(c, hipEventRecord(c->ev1, c->stream2));
-    LRN_HIP(c, hipStreamWaitEvent(c->stream, c->ev1, 0));
-  }
-  for (int k = 0; k < 2; ++k) {
-    lam[k] = r[k].theta; conv[k] = r[k].conv; scale[k] = r[k].scale;
-    c->counts["lanczos_steps"] += r[k].m;
-    c->counts["lanczos_runs"] += 1;
-  }
-  LRN_HIP(c, hipGetLastError());
-  return LRN_OK;
-}
-
-// ---- certified smallest eigenvalue
-// A Ritz value is only an UPPER bound of lambda_min, and plain Lanczos resolves the spectrum relative to
-// its spread: lambda_min = -1 next to eigenvalues of 1e6..1e10 (a poor direction after a regularised
-// Schur solve) comes back as -0.94 or even +9 -- the step-length rule (predictor_corrector.jl:272-291)
-// would then leave the cone.  Every estimate is therefore certified by one Cholesky test
-//   M - (theta - delta) I  positive definite  <=>  lambda_min > theta - delta,
-// and if the test fails lambda_min is bracketed by bisection over such tests (the reference calls a
-// dense `eigmin`; a positive-definiteness test is its GEMM-rich equivalent on this hardware).
-static int chol_shift_is_pd(lrn_ctx* c, const double* M, int n, double shift, bool* pd) {
-  hipStream_t st = c->stream;
-  LRN_TRY(ensure(c, c->info_dev, 64));
-  const size_t nn = (size_t)n * n;
-  LRN_TRY(ensure(c, c->ezbuf, (nn + (size_t)n * CHOL_NB + chol_linv_doubles(n) + 64) * 8));
-  double* F = c->ezbuf.as<double>();
-  double* work = F + nn;
-  double* linv = work + (size_t)n * CHOL_NB;
-  int* info = c->info_dev.as<int>() + 8;
-  LRN_HIP(c, hipMemcpyAsync(F, M, nn * 8, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(add_diag_mat_kernel, dim3((n + 255) / 256), dim3(256), 0, st, F, n, shift);
-  LRN_HIP(c, hipMemsetAsync(info, 0, 4, st));
-  LRN_TRY(potrf_lower(st, F, n, n, linv, work, info));
-  int h = 0;
-  LRN_TRY(copy_out(c, &h, info, 4));
-  *pd = h == 0;
-  c->counts["eigmin_chol_tests"] += 1;
-  return LRN_OK;
-}
-
-static int eigmin_certify(lrn_ctx* c, const double* M, int n, double theta, bool conv, double scale, double* lam);
-
-int eigmin_certified(lrn_ctx* c, const double* M, int n, double* lam) {
-  double theta = 0.0, scale = 0.0;
-  bool conv = false;
-  LRN_TRY(eigmin_dev(c, M, n, &theta, nullptr, &conv, &scale));
-  return eigmin_certify(c, M, n, theta, conv, scale, lam);
-}
-
-// eigmin_certified of two matrices of the same size: the two Lanczos runs interleaved, then the certificates
-int eigmin_certified_pair(lrn_ctx* c, const double* M1, const double* M2, int n, double* lam1, double* lam2) {
-  if (n == 1 || !c->opt.eigmin_pair) {
-    LRN_TRY(eigmin_certified(c, M1, n, lam1));
-    return eigmin_certified(c, M2, n, lam2);
-  }
-  double th[2], sc[2];
-  bool cv[2];
-  LRN_TRY(eigmin_dev_pair(c, M1, M2, n, th, cv, sc));
-  LRN_TRY(eigmin_certify(c, M1, n, th[0], cv[0], sc[0], lam1));
-  return eigmin_certify(c, M2, n, th[1], cv[1], sc[1], lam2);
-}
-
-static int eigmin_certify(lrn_ctx* c, const double* M, int n, double theta, bool conv, double scale, double* lam) {
-  static const bool trace = getenv("LRN_EIGMIN_TRACE") != nullptr;
-  if (trace) fprintf(stderr, "[eigmin n=%d] theta=%.12g conv=%d scale=%.3g\n", n, theta, (int)conv, scale);
-  if (n == 1) { *lam = theta; return LRN_OK; }
-  // a Ritz value converged to 1e-11 on a spectrum of moderate spread (the usual O(1) scaled directions)
-  // needs no certificate: the failures are unconverged runs on spectra spanning 1e6 and more
-  if (conv && theta <= -1e-6 && scale <= 1e3 * std::fabs(theta)) { *lam = theta; return LRN_OK; }
-  bool pd = false;
-  if (theta > -1e-6) {
-    // callers only use the class "lambda_min > -1e-6" (step 0.99, DIMACS err2/err4 = 0)
-    LRN_TRY(chol_shift_is_pd(c, M, n, 1e-6, &pd));
-    if (pd) { *lam = theta; return LRN_OK; }
-  } else {
-    const double delta = 1e-7 * std::fabs(theta);
-    LRN_TRY(chol_shift_is_pd(c, M, n, delta - theta, &pd));
-    if (pd) { *lam = theta; return LRN_OK; }
-  }
-  // the Ritz value was not converged: bracket lambda_min in (lo, hi], hi = theta is an upper bound
-  c->counts["eigmin_bisections"] += 1;
-  double hi = theta, beta = std::max(2.0 * std::fabs(theta), 1.0);
-  for (int it = 0; it < 200; ++it) {
-    LRN_TRY(chol_shift_is_pd(c, M, n, beta, &pd));
-    if (pd) break;
-    hi = std::min(hi, -beta);
-    beta *= 4.0;
-  }
-  if (!pd) return set_error(c, LRN_ERR_STATE, "eigmin: matrix has no finite lower bound (NaN/Inf entries?)");
-  double lo = -beta;
-  for (int it = 0; it < 100 && hi - lo > 1e-9 * std::max(std::fabs(lo), 1e-6); ++it) {
-    const double mid = 0.5 * (lo + hi);
-    LRN_TRY(chol_shift_is_pd(c, M, n, -mid, &pd));
-    if (trace) fprintf(stderr, "   bisect mid=%.12g pd=%d\n", mid, (int)pd);
-    if (pd) lo = mid; else hi = mid;
-  }
-  *lam = lo;          // the safe side: slightly too negative shortens the step
   return LRN_OK;
 }
 
@@ -1400,8 +421,7 @@ extern "C" int lrn_ip_add_diag(lrn_ctx* c, int il, int which, double eps) {
   BLK(il);
   if (which != 1 && which != 2) return LRN_ERR_ARG;
   b.chol_valid = false;
-  hipLaunchKernelGGL(add_diag_mat_kernel, dim3((b.msz + 255) / 256), dim3(256), 0, c->stream,
-                     (which == 1 ? b.X : b.S).as<double>(), b.msz, eps);
+  add_diag_mat(c->stream, (which == 1 ? b.X : b.S).as<double>(), b.msz, eps);
   return LRN_OK;
 }
 

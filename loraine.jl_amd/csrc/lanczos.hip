@@ -11,6 +11,7 @@
 #include <cmath>
 #include <vector>
 
+#include "lz.h"
 #include "ops.h"
 #include "tridiag.h"
 
@@ -119,10 +120,6 @@ __global__ __launch_bounds__(256) void lx_trace_kernel(const double* __restrict_
 
 // ---- host-side tridiagonal helpers
 // (eigenvalues: tridiag.h)
-static double tri_eig_by_index(const std::vector<double>& a, const std::vector<double>& b, int m, int idx) {
-  return tri_eig_kth(a, b, m, idx);
-}
-
 // eigenvector of T for eigenvalue theta by inverse iteration; (T - shift I) is factored with
 // partial pivoting (the LAPACK dgttrf / dgtts2 recurrences); returns a unit vector s
 static void tri_eigvec(const std::vector<double>& a, const std::vector<double>& b, int m, double theta,
@@ -177,7 +174,7 @@ static void tri_eigvec(const std::vector<double>& a, const std::vector<double>& 
   s = x;
 }
 
-// k <= 1, n <= 4096: the same quantities from the PLAIN recurrence, one launch per step (lz_fused_steps, ipstep.hip).
+// k <= 1, n <= 4096: the same quantities from the PLAIN recurrence, one launch per step or less (lz_queue_steps, lz.hip).
 // The full re-orthogonalisation below costs seven launches per step (4.2 ms of the 6.6 ms H_alpha setup on thetaG11); one
 // extreme Ritz pair does not need it: until its Ritz value has converged no ghost copy exists, and the Ritz vector Q s of a
 // converged value is accurate although the q_j have lost their orthogonality along it (Paige).  *ok = false: not taken
@@ -187,25 +184,24 @@ static int lanczos_extremes_plain(lrn_ctx* c, const double* M, int n, int k, dou
   hipStream_t st = c->stream;
   *ok = false;
   const int mmax = std::min(n - 1, 240);
-  const int nwg = (n + 15) / 16;
-  LRN_TRY(ensure(c, c->lxbuf, ((size_t)(mmax + 2) * n + 3 * (size_t)n + 3 * (size_t)nwg + 2 * (size_t)mmax + (size_t)mmax + 64) * 8));
-  double* Q = c->lxbuf.as<double>();
-  double* Y2 = Q + (size_t)(mmax + 2) * n;           // (resident launches: three buffers each; launched steps use two)
-  double* PA2 = Y2 + 3 * (size_t)n;
-  double* ab = PA2 + 3 * (size_t)nwg;
+  LzWork w;      // every q_j is kept: the Ritz vector is Q s
+  w.M = M; w.n = n; w.st = st;
+  w.nwg = (n + 15) / 16;
+  w.qmod = mmax + 2;
+  LRN_TRY(ensure(c, c->lxbuf, ((size_t)w.qmod * n + 3 * (size_t)n + 3 * (size_t)w.nwg + 2 * (size_t)mmax + (size_t)mmax + 64) * 8));
+  double* Q = w.Q = c->lxbuf.as<double>();
+  w.Y = Q + (size_t)w.qmod * n;                      // (resident launches: three buffers each; launched steps use two)
+  w.PA = w.Y + 3 * (size_t)n;
+  double* ab = w.ab = w.PA + 3 * (size_t)w.nwg;
   double* Sdev = ab + 2 * (size_t)mmax + 8;
   hipLaunchKernelGGL(lx_init_kernel, dim3((n + 255) / 256), dim3(256), 0, st, Q, n, 0u);
   hipLaunchKernelGGL(lx_norm_kernel, dim3(1), dim3(1024), 0, st, Q, n, -1, Q, ab);
-  // resident launches (ipstep.hip, lz_resident_kernel): a batch of steps per launch; two words of the workspace's slack
-  // hold its abort word
-  const bool resident = lz_resident_ok(c, n);
-  unsigned* flag = reinterpret_cast<unsigned*>(Sdev + mmax + 8);
-  if (resident) lz_resident_prepare(st, n, Y2, PA2, flag);
-  auto steps = [&](int j0, int j1) -> int {
-    if (resident) return lz_resident_steps(st, M, n, j0, j1, mmax + 2, Q, Y2, PA2, ab, flag);
-    return lz_fused_steps(st, M, n, j0, j1, mmax + 2, Q, Y2, PA2, ab);
-  };
-  std::vector<double> a, b, hab, s_top, s_min;
+  // resident launches: a batch of steps per launch; two words of the workspace's slack hold the abort word
+  w.form = lz_resident_ok(c, n) ? LZ_RESIDENT : LZ_FUSED;
+  w.flag = reinterpret_cast<unsigned*>(Sdev + mmax + 8);
+  lz_prepare(w);
+  LzWork* const wp[1] = {&w};
+  std::vector<double> a, b, s_top, s_min;
   double th_top = 0.0, th_min = 0.0;
   // T of a batch is a leading block of the next one's: its extreme eigenvalues bound the next ones (from below / above)
   bool have_prev = false;
@@ -223,37 +219,27 @@ static int lanczos_extremes_plain(lrn_ctx* c, const double* M, int n, int k, dou
   while (!done && m < mmax) {
     const int m1 = std::min(mmax, m + 24);
     if (queued < m1) {
-      LRN_TRY(steps(queued, m1));
+      LRN_TRY(lz_queue_steps(wp, 1, queued, m1));
       queued = m1;
     }
     m = m1;
-    hab.resize(2 * (size_t)m);
-    LRN_TRY(copy_out(c, hab.data(), ab, (size_t)2 * m * 8));      // (returns when the batch [.., m) has run)
-    if (resident) {
-      unsigned fl[2] = {0u, 0u};
-      LRN_TRY(copy_out(c, fl, flag, 8));
-      if (fl[1] != 0u) {             // a resident launch gave up at a barrier: launched steps on this context from now on,
-        c->lz_no_persist = true;     // and this setup through the caller's full version
-        c->counts["lz_persist_abort"] += 1;
-        return LRN_OK;
-      }
+    bool gave_up = false;
+    LRN_TRY(lz_fetch(c, wp, 1, m, &gave_up));      // (returns when the batch [.., m) has run)
+    if (gave_up) {                   // launched steps on this context from now on, and this setup through the caller's
+      lz_record_give_up(c);          // full version
+      return LRN_OK;
     }
     if (!no_spec && queued == m && m < mmax && err_prev > 0.0 && err_last > 0.0) {
       const double next = err_last * std::min(1.0, err_last / err_prev);
       if (next > 100.0) {
         const int m2 = std::min(mmax, m + 24);
-        LRN_TRY(steps(m, m2));
+        LRN_TRY(lz_queue_steps(wp, 1, m, m2));
         queued = m2;
         c->counts["lanczos_plain_ahead"] += 1;
       }
     }
-    a.resize(m); b.resize(m);
     double scale = 0.0;
-    for (int j = 0; j < m; ++j) {
-      a[j] = hab[2 * j]; b[j] = hab[2 * j + 1];
-      scale = std::max(scale, std::fabs(a[j]) + std::fabs(b[j]));
-      if (!(b[j] > 1e-13 * scale)) return LRN_OK;                     // invariant subspace: the full version restarts
-    }
+    if (tri_unpack(w.hab, m, 1e-13, a, b, scale) < m) return LRN_OK;      // invariant subspace: the full version restarts
     if (m <= k + 1) continue;
     double worst = 0.0;
     if (k == 1) {
@@ -375,11 +361,11 @@ int lanczos_extremes(lrn_ctx* c, const double* M, int n, int k, double* lam_top,
       // wanted Ritz pairs: k largest (ascending order), then the smallest
       double worst = 0.0;
       for (int i = 0; i < k; ++i) {
-        th[i] = tri_eig_by_index(a, b, m, m - k + i);
+        th[i] = tri_eig_kth(a, b, m, m - k + i);
         tri_eigvec(a, b, m, th[i], svec[i], i);
         worst = std::max(worst, std::fabs(b[m - 1] * svec[i][m - 1]) / std::max(std::fabs(th[i]), 1e-300));
       }
-      th[k] = tri_eig_by_index(a, b, m, 0);
+      th[k] = tri_eig_kth(a, b, m, 0);
       tri_eigvec(a, b, m, th[k], svec[k], k);
       // lambda_min only enters tau = (lambda_min + mean)/2: converge it relative to the mean
       double top = 0.0;

@@ -40,16 +40,14 @@ int pgemm_nt_sym(lrn_ctx* c, hipStream_t st, int n, const double* A, const doubl
 // k largest eigenpairs (ascending), smallest eigenvalue and trace of a dense symmetric matrix
 int lanczos_extremes(lrn_ctx* c, const double* M, int n, int k, double* lam_top, double* U_top, double* lam_min,
                      double* trace, int* steps_out);
-// both ends of the spectrum from nsteps plain Lanczos steps (ipstep.hip): lo >= lambda_min, an eigenvalue within res_hi of hi
+// ---- lz.hip: the plain Lanczos recurrence
+// both ends of the spectrum from nsteps plain Lanczos steps: lo >= lambda_min, an eigenvalue within res_hi of hi
 int lanczos_ends(lrn_ctx* c, const double* M, int n, int nsteps, double* lo, double* hi, double* res_hi);
-// single-launch Lanczos steps [j0, j1) keeping every q_j (ipstep.hip); PA2: 2 * ceil(n / 16) doubles, Y2: 2 n doubles
-int lz_fused_steps(hipStream_t st, const double* M, int n, int j0, int j1, int qcap, double* Q, double* Y2, double* PA2,
-                   double* ab);
-static constexpr int LZ_FUSED_LIMIT = 4096;
-// the same as one resident launch per batch (option lz_resident, n <= 1024): Y3 / PA3 = three n- / ceil(n/16)-vectors, flag =
-// two words (flag[1] != 0 afterwards: the launch gave up, nothing of the batch is valid); lz_resident_prepare before step 0
-bool lz_resident_ok(const lrn_ctx* c, int n);
-void lz_resident_prepare(hipStream_t st, int n, double* Y3, double* PA3, unsigned* flag);
-int lz_resident_steps(hipStream_t st, const double* M, int n, int j0, int j1, int qcap, double* Q, double* Y3, double* PA3,
-                      double* ab, unsigned* flag);
+// smallest Ritz value (an UPPER bound of lambda_min) and the steps it took; scale: the norm estimate max |a_j| + |b_j|
+int eigmin_dev(lrn_ctx* c, const double* M, int n, double* lam, int* steps_out, bool* converged = nullptr,
+               double* scale_out = nullptr);
+// lambda_min certified by Cholesky tests; _pair: of two matrices of the same size, their Lanczos runs side by side
+int eigmin_certified(lrn_ctx* c, const double* M, int n, double* lam);
+int eigmin_certified_pair(lrn_ctx* c, const double* M1, const double* M2, int n, double* lam1, double* lam2);
+void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I (ipstep.hip)
 }  // namespace lrn

@@ -1,4 +1,4 @@
-// Host-side eigenvalues of the Lanczos tridiagonal matrices (lanczos.hip, ipstep.hip).
+// Host-side eigenvalues of the Lanczos tridiagonal matrices (lanczos.hip, lz.hip).
 //
 // Every batch of Lanczos steps ends with the host looking at T_m = tridiag(b, a, b): the smallest (or k-th) eigenvalue by
 // bisection on the Sturm count, then the residual bound of its Ritz pair.  While the host does that the stream is empty,
@@ -96,6 +96,20 @@ struct TriEig {
     return 0.5 * (lo + hi);
   }
 };
+
+// a, b (resized to m) from the (alpha_j, beta_j) pairs of m Lanczos steps; `scale` grows to max_j |a_j| + |b_j| on the way.
+// Stops at the first j with !(beta_j > tau * scale) -- an invariant subspace: T splits behind row j -- and returns it, a
+// and b filled up to and including j; m: there is none.  What a split means is the caller's business.
+inline int tri_unpack(const std::vector<double>& hab, int m, double tau, std::vector<double>& a, std::vector<double>& b,
+                      double& scale) {
+  a.resize(m); b.resize(m);
+  for (int j = 0; j < m; ++j) {
+    a[j] = hab[2 * j]; b[j] = hab[2 * j + 1];
+    scale = std::max(scale, std::fabs(a[j]) + std::fabs(b[j]));
+    if (!(b[j] > tau * scale)) return j;
+  }
+  return m;
+}
 
 inline double tri_eig_kth(const std::vector<double>& a, const std::vector<double>& b, int m, int k,
                           const double* upper = nullptr, double width = 0.0) {
