@@ -126,7 +126,18 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * blocks of side >= ns_lanczos_min = 1500), "lowrank_form" (rank-k assembly, mode 1: U = G'V by a gather over the factor
  * entries (0), one dense MFMA product (1), or by the factors' density (-1, default)), "profile_ops" (measurement: every
  * AA vec(.) / mat(AA' .) timed by itself under "aa_times" / "aa_times2" / "aat_to_mat"; synchronises, not for solves), "comm_fail_ensure" (test hook: the next exchange of this rank fails its buffer
- * allocation), "reset_timing". */
+ * allocation), "lz_res_limit" (ticks of the 100 MHz wall clock a workgroup of a resident Lanczos launch waits for its peers
+ * before the launch gives up; default 2 000 000 = 20 ms, clamped to [1000, 2 000 000]: the option shortens the wait, it
+ * never lengthens it; lrn_get_count("lz_res_limit") returns the value in effect), "lz_test_withhold" (test hook, one shot:
+ * value = k + 100000 (run + 2 (step + 3 wg)) arms the k-th resident Lanczos launch queued on this context from now on,
+ * 1 <= k < 100000 -- in it ONE workgroup (wg 0: workgroup 0, which also writes for the host; 1: the last, ragged one) of ONE
+ * run (run 0 / 1 of a pair in lock-step; a launch of a single run has run 0 only) keeps its publication of ONE step (step 0:
+ * the first of the launch, 1: a middle one, 2: the last) to itself.  Its peers' wait runs into lz_res_limit, all workgroups
+ * return normally, the host repeats the run with one launch per step; lrn_get_count("lz_test_withheld") goes up when the armed
+ * launch is queued and, like "lz_no_persist", survives reset_timing; 0 disarms), "reset_timing".
+ * Counters of this path (lrn_get_count): "lz_resident_launches" (resident launches queued), "lz_persist_abort" (those that
+ * gave up), and the STATE "lz_no_persist" (0 / 1, survives reset_timing: a resident launch of this context has given up, all
+ * Lanczos steps are launched one by one from then on). */
 int lrn_set_option(lrn_ctx* ctx, const char* key, double value);
 /* multi-GPU: this context assembles the Schur columns it owns (block-cyclic) */
 int lrn_set_shard(lrn_ctx* ctx, int rank, int world);

@@ -120,6 +120,17 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "jacobi_early")) c->opt.jacobi_early = value;
   else if (!strcmp(key, "eigmin_pair")) c->opt.eigmin_pair = (int)value;
   else if (!strcmp(key, "lz_resident")) c->opt.lz_resident = (int)value;
+  else if (!strcmp(key, "lz_res_limit")) {      // an option can shorten the wait of a resident launch, never lengthen it
+    if (!(value == value)) return LRN_ERR_ARG;
+    c->lz_res_limit = (long long)std::max(1000.0, std::min(2000000.0, value));
+  }
+  else if (!strcmp(key, "lz_test_withhold")) {      // test hook (tests/test_gpu_lz_giveup.py): k + 100000 (run + 2 (step + 3 wg))
+    if (!(value >= 0.0 && value < 1200000.0)) return LRN_ERR_ARG;
+    const long code = (long)value;
+    const long sel = code / 100000;
+    c->lz_wh_left = code % 100000;
+    c->lz_wh_run = (int)(sel % 2); c->lz_wh_step = (int)(sel / 2 % 3); c->lz_wh_wg = (int)(sel / 6);
+  }
   else if (!strcmp(key, "prepw_streams")) c->opt.prepw_streams = (int)value;
   else if (!strcmp(key, "jacobi_warm")) c->opt.jacobi_warm = value != 0.0;
   else if (!strcmp(key, "nt_mode")) c->opt.nt_mode = (int)value;
@@ -362,6 +373,9 @@ int lrn_get_timing(lrn_ctx* c, const char* key, double* ms) {
 int64_t lrn_get_count(lrn_ctx* c, const char* key) {
   if (!c || !key) return 0;
   if (!strcmp(key, "shard_bs")) return c->shard_bs;      // state, not a per-call counter (survives reset_timing)
+  if (!strcmp(key, "lz_no_persist")) return c->lz_no_persist ? 1 : 0;      // a resident Lanczos launch of this context has given up
+  if (!strcmp(key, "lz_res_limit")) return (int64_t)c->lz_res_limit;
+  if (!strcmp(key, "lz_test_withheld")) return (int64_t)c->lz_wh_fired;     // (test hook lz_test_withhold: it has fired)
   // device memory this context holds now / held at most (every buffer of the library goes through lrn::ensure), and the
   // dense constraint slabs of all blocks: state as well
   if (!strcmp(key, "device_bytes")) return (int64_t)c->dev_bytes;

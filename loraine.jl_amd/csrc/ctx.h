@@ -183,6 +183,12 @@ struct lrn_ctx {
   long cg_cur_iters = 0, cg_prev_iters = 0;
   lrn::DBuf hopbuf;           // partial sums of the triangular mat-vec
   bool lz_no_persist = false; // a resident Lanczos launch gave up waiting for its peers once (lz_record_give_up): launched steps from then on
+  long long lz_res_limit = 2000000;   // option "lz_res_limit": ticks of the 100 MHz wall clock a resident workgroup waits for its peers (20 ms)
+  // test hook "lz_test_withhold" (one shot): the lz_wh_left-th resident launch from now on has one workgroup of one run keep
+  // one step's publication to itself (0: not armed); lz_wh_run 0/1, lz_wh_step 0/1/2 = first/middle/last step of the launch,
+  // lz_wh_wg 0/1 = workgroup 0 / the last one
+  long lz_wh_left = 0, lz_wh_fired = 0;      // fired: launches the hook has silenced (count "lz_test_withheld")
+  int lz_wh_run = 0, lz_wh_step = 0, lz_wh_wg = 0;
   double* pin = nullptr;      // host-mapped words the CG kernels write their exit code to (lrn_pcg), and their device address
   double* pin_dev = nullptr;
   lrn::DBuf cgpart;           // partial sums of the CG recurrence kernels

@@ -185,7 +185,7 @@ static int lanczos_extremes_plain(lrn_ctx* c, const double* M, int n, int k, dou
   *ok = false;
   const int mmax = std::min(n - 1, 240);
   LzWork w;      // every q_j is kept: the Ritz vector is Q s
-  w.M = M; w.n = n; w.st = st;
+  w.c = c; w.M = M; w.n = n; w.st = st;
   w.nwg = (n + 15) / 16;
   w.qmod = mmax + 2;
   LRN_TRY(ensure(c, c->lxbuf, ((size_t)w.qmod * n + 3 * (size_t)n + 3 * (size_t)w.nwg + 2 * (size_t)mmax + (size_t)mmax + 64) * 8));

@@ -15,6 +15,7 @@ enum LzForm {
 
 // One run: q_j lives in buffer j % qmod of Q (qmod = 3: a ring; larger: every q_j is kept), (alpha_j, beta_j) in ab[2 j ..].
 struct LzWork {
+  lrn_ctx* c = nullptr;           // resident launches: their wait limit, launch counter and test hook live on the context
   const double* M = nullptr;
   int n = 0, nwg = 0;             // nwg = ceil(n / 16)
   hipStream_t st = nullptr;

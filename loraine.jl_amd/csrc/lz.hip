@@ -267,8 +267,11 @@ __global__ void lz_mark_kernel(double* __restrict__ p, int cnt) {
 }
 
 static constexpr int LZ_RES_MAX = 1024;       // 16 rows per lane and column
-static constexpr long long LZ_POLL_LIMIT = 2000000LL;      // ticks a resident workgroup waits for its peers: 20 ms at 100 MHz
-__global__ __launch_bounds__(256) void lz_resident_kernel(LzResPair args, int n, int nwg, int j0, int j1, int qmod, long long limit) {
+// limit: ticks a resident workgroup waits for its peers (option lz_res_limit; 20 ms at 100 MHz by default).  wh_step, wh_wg:
+// test hook lz_test_withhold -- workgroup wh_wg (64 blockIdx.y + blockIdx.x) keeps its words of step wh_step to itself, so
+// that its peers' wait expires (-1: none)
+__global__ __launch_bounds__(256) void lz_resident_kernel(LzResPair args, int n, int nwg, int j0, int j1, int qmod, long long limit,
+                                                          int wh_step, int wh_wg) {
   extern __shared__ double ql[];            // three n-vectors: q_j, q_{j-1}, q_{j-2} rotate through them
   __shared__ double sh[16 * 16 + 8];
   __shared__ int ok_s;
@@ -276,6 +279,7 @@ __global__ __launch_bounds__(256) void lz_resident_kernel(LzResPair args, int n,
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int c0 = blockIdx.x * 16 + 4 * w;
   const double mark = __longlong_as_double((long long)LZ_MARK_BITS);
+  const int silent_step = (int)(blockIdx.y * 64 + blockIdx.x) == wh_wg ? wh_step : -1;      // (uniform)
   constexpr int U = LZ_RES_MAX / 64;
   double mreg[4][U];
 #pragma unroll
@@ -407,7 +411,7 @@ __global__ __launch_bounds__(256) void lz_resident_kernel(LzResPair args, int n,
       if (lane == 0) { sh[4 * w + 0] = a0; sh[4 * w + 1] = a1; sh[4 * w + 2] = a2; sh[4 * w + 3] = a3; }
     }
     __syncthreads();
-    if (t < 16) {
+    if (t < 16 && j != silent_step) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the marks above have been acknowledged
       const double y = sh[t];
       const int ii = blockIdx.x * 16 + t;
@@ -463,12 +467,20 @@ int lz_queue_steps(const LzWork* const w[], int nruns, int j0, int j1) {
   if (b.n != n || b.qmod != qmod || b.form != a.form || qmod < 3 || (qmod > 3 && j1 + 1 > qmod)) return LRN_ERR_ARG;
   switch (a.form) {
     case LZ_RESIDENT: {
-      if (n > LZ_RES_MAX) return LRN_ERR_ARG;
+      if (n > LZ_RES_MAX || !a.c) return LRN_ERR_ARG;
+      lrn_ctx* c = a.c;
       LzResPair ra;
       ra.r[0] = LzRes{a.M, a.Q, a.Y, a.PA, a.ab, a.flag};
       ra.r[1] = LzRes{b.M, b.Q, b.Y, b.PA, b.ab, b.flag};
+      int wh_step = -1, wh_wg = -1;
+      if (c->lz_wh_left > 0 && --c->lz_wh_left == 0) {      // test hook lz_test_withhold: this launch is the armed one
+        wh_step = c->lz_wh_step == 0 ? j0 : c->lz_wh_step == 1 ? j0 + (j1 - j0) / 2 : j1 - 1;
+        wh_wg = 64 * std::min(c->lz_wh_run, nruns - 1) + (c->lz_wh_wg ? nwg - 1 : 0);
+        c->lz_wh_fired += 1;
+      }
+      c->counts["lz_resident_launches"] += 1;
       hipLaunchKernelGGL(lz_resident_kernel, dim3(nwg, nruns), dim3(256), (size_t)3 * n * 8, a.st, ra, n, nwg, j0, j1, qmod,
-                         LZ_POLL_LIMIT);
+                         c->lz_res_limit, wh_step, wh_wg);
       break;
     }
     case LZ_FUSED: {
@@ -576,7 +588,7 @@ static void lz_set_form(LzRun& r, LzForm form) {
 
 static int lz_begin(lrn_ctx* c, LzRun& r, const double* M, int n, hipStream_t st, DBuf& buf) {
   LzWork& w = r.w;
-  w.M = M; w.n = n; w.st = st;
+  w.c = c; w.M = M; w.n = n; w.st = st;
   w.nwg = (n + 15) / 16;
   // without re-orthogonalisation the extreme Ritz value may need more than n steps
   r.mmax = std::min(1500, 4 * n + 40);

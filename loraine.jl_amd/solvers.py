@@ -534,6 +534,8 @@ class MySolver:
                 ns_steps=d.count("ns_steps"), lyap_steps=d.count("lyap_steps"), lyap_ms=d.timing("lyap"),
                 ns_fallback=d.count("ns_fallback"), lyap_fallback=d.count("lyap_fallback"),
                 lanczos_steps=d.count("lanczos_steps"), lanczos_runs=d.count("lanczos_runs"),
+                lz_persist_abort=d.count("lz_persist_abort"), lz_resident_launches=d.count("lz_resident_launches"),
+                lanczos_resident_batches=d.count("lanczos_resident_batches"),
                 stats_chol=d.count("stats_chol"), eigmin_chol_tests=d.count("eigmin_chol_tests"),
                 schur_chol=d.count("schur_chol"), schur_via_l=d.count("schur_via_l"), wchol_fail=d.count("wchol_fail"),
                 alpha=[float(a) for a in self.alpha] + [float(self.alpha_lin)],

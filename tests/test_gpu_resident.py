@@ -46,7 +46,9 @@ def test_lanczos_eigmin(dev, n, kind):
         assert (got > -1e-6) == (ref > -1e-6), (got, ref, steps)
 
 
-@pytest.mark.parametrize("n", [64, 333, 801, 1024])
+# (32, 33, 47: the smallest resident sizes -- two or three workgroups, the `t < nwg` load of the partial sums nearly empty;
+# 1009: the last ragged size below the register limit)
+@pytest.mark.parametrize("n", [32, 33, 47, 64, 333, 801, 1009, 1024])
 def test_resident_lanczos_steps_are_the_launched_ones(dev, n):
     """Option "lz_resident": 16 Lanczos steps per launch (the workgroup's columns of M in registers, y and the partial dot
     products exchanged through relaxed agent-scope atomics, unwritten words marked, no barrier) against one launch per step:
@@ -159,6 +161,7 @@ def test_second_stream_changes_nothing(dev, name, opts):
         assert o.termination_status() == "OPTIMAL"
         # (the counters are those of the last IP iteration: the solver's trace takes and resets them)
         assert dev.count("lz_persist_abort") == 0               # no resident launch gave up at a barrier ...
+        assert dev.count("lz_no_persist") == 0                  # ... in any iteration of any solve on this context (state)
         if name == "maxG11":                 # (control1: blocks of side 10 and 5, below the single-launch step kernel)
             assert (dev.count("lanczos_pair_batches") > 0) == (pair == 2)
             assert (dev.count("lanczos_resident_batches") > 0) == (pair == 2 and res == 1)      # ... and none had before

@@ -191,7 +191,7 @@ def test_lanczos_extremes(dev, n, k):
     assert np.allclose(U.T @ U, np.eye(k), atol=1e-10)
 
 
-@pytest.mark.parametrize("n", [600, 801])
+@pytest.mark.parametrize("n", [64, 600, 801, 1024])
 def test_lanczos_extremes_resident_steps_are_the_launched_ones(dev, n):
     """The plain-recurrence route of the H_alpha setup (k = 1) with resident launches of 24 steps (option lz_resident,
     default) and with one launch per step: same Ritz values, same Ritz vector, same step count, bit for bit -- also on a
@@ -209,7 +209,7 @@ def test_lanczos_extremes_resident_steps_are_the_launched_ones(dev, n):
                 out.append(dev.dbg_lanczos(W, 1))
             finally:
                 dev.set_option("lz_resident", 1)
-        assert dev.count("lz_persist_abort") == 0
+        assert dev.count("lz_persist_abort") == 0 and dev.count("lz_no_persist") == 0
         (lt0, U0, lmin0, tr0, st0), (lt1, U1, lmin1, tr1, st1) = out
         assert st0 == st1 and lmin0 == lmin1 and tr0 == tr1
         assert np.array_equal(lt0, lt1) and np.array_equal(U0, U1)
