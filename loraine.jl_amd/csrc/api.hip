@@ -523,16 +523,15 @@ int lrn_dbg_mfma_probe(lrn_ctx* c, const double* A, const double* B, double* D) 
   return rc;
 }
 
-static int dbg_factor(lrn_ctx* c, int n, const double* A, DBuf& dA, DBuf& dI, int* info) {
+static int dbg_factor(lrn_ctx* c, int n, const double* A, DBuf& dA, int* info) {
   DBuf dW;
   LRN_TRY(ensure(c, dA, (size_t)n * n * 8));
-  LRN_TRY(ensure(c, dI, chol_linv_doubles(n) * 8));
-  LRN_TRY(ensure(c, dW, (size_t)n * CHOL_NB * 8));
+  LRN_TRY(ensure(c, dW, chol_work_doubles(n) * 8));
   LRN_TRY(ensure(c, c->info_dev, 64));
   LRN_TRY(copy_in(c, dA.p, A, (size_t)n * n * 8));
   LRN_HIP(c, hipMemsetAsync(c->info_dev.p, 0, 4, c->stream));
   tic(c);
-  LRN_TRY(potrf_lower(c->stream, dA.as<double>(), n, n, dI.as<double>(), dW.as<double>(), c->info_dev.as<int>()));
+  LRN_TRY(potrf_lower(c->stream, dA.as<double>(), n, n, dW.as<double>(), c->info_dev.as<int>()));
   toc(c, "dbg_potrf");
   int h = 0;
   LRN_TRY(copy_out(c, &h, c->info_dev.p, 4));
@@ -544,45 +543,44 @@ static int dbg_factor(lrn_ctx* c, int n, const double* A, DBuf& dA, DBuf& dI, in
 int lrn_dbg_potrf(lrn_ctx* c, int n, double* A, int* info) {
   if (!c || !A || n <= 0) return LRN_ERR_ARG;
   LRN_HIP(c, hipSetDevice(c->device));
-  DBuf dA, dI;
-  LRN_TRY(dbg_factor(c, n, A, dA, dI, info));
+  DBuf dA;
+  LRN_TRY(dbg_factor(c, n, A, dA, info));
   int rc = copy_out(c, A, dA.p, (size_t)n * n * 8);
-  release(dA); release(dI);
+  release(dA);
   return rc;
 }
 
 int lrn_dbg_potrs(lrn_ctx* c, int n, const double* A, const double* b, double* x, int* info) {
   if (!c || !A || !b || !x || n <= 0) return LRN_ERR_ARG;
   LRN_HIP(c, hipSetDevice(c->device));
-  DBuf dA, dI, v;
+  DBuf dA, v;
   int inf = 0;
-  LRN_TRY(dbg_factor(c, n, A, dA, dI, &inf));
+  LRN_TRY(dbg_factor(c, n, A, dA, &inf));
   if (info) *info = inf;
-  if (inf != 0) { release(dA); release(dI); return LRN_OK; }
+  if (inf != 0) { release(dA); return LRN_OK; }
   LRN_TRY(ensure(c, v, (size_t)(4 * n + 64) * 8, true));
   double* vb = v.as<double>();
   LRN_TRY(copy_in(c, vb, b, (size_t)n * 8));
-  LRN_TRY(potrs_vec(c->stream, dA.as<double>(), n, n, dI.as<double>(), vb, vb + n, vb + 2 * n, vb + 3 * n));
+  LRN_TRY(potrs_vec(c->stream, dA.as<double>(), n, n, vb, vb + n, vb + 2 * n, vb + 3 * n));
   int rc = copy_out(c, x, vb + n, (size_t)n * 8);
-  release(dA); release(dI); release(v);
+  release(dA); release(v);
   return rc;
 }
 
 int lrn_dbg_trsm(lrn_ctx* c, int n, int nrhs, int trans, const double* A, double* B, int* info) {
   if (!c || !A || !B || n <= 0 || nrhs <= 0) return LRN_ERR_ARG;
   LRN_HIP(c, hipSetDevice(c->device));
-  DBuf dA, dI, dB, dT;
+  DBuf dA, dB, dT;
   int inf = 0;
-  LRN_TRY(dbg_factor(c, n, A, dA, dI, &inf));
+  LRN_TRY(dbg_factor(c, n, A, dA, &inf));
   if (info) *info = inf;
-  if (inf != 0) { release(dA); release(dI); return LRN_OK; }
+  if (inf != 0) { release(dA); return LRN_OK; }
   LRN_TRY(ensure(c, dB, (size_t)n * nrhs * 8));
   LRN_TRY(ensure(c, dT, (size_t)CHOL_NB * nrhs * 8));
   LRN_TRY(copy_in(c, dB.p, B, (size_t)n * nrhs * 8));
-  LRN_TRY(trsm_left_lower(c->stream, dA.as<double>(), n, n, dI.as<double>(), trans != 0, dB.as<double>(), nrhs, n,
-                          dT.as<double>()));
+  LRN_TRY(trsm_left_lower(c->stream, dA.as<double>(), n, n, trans != 0, dB.as<double>(), nrhs, n, dT.as<double>()));
   int rc = copy_out(c, B, dB.p, (size_t)n * nrhs * 8);
-  release(dA); release(dI); release(dB); release(dT);
+  release(dA); release(dB); release(dT);
   return rc;
 }
 

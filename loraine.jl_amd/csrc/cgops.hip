@@ -27,13 +27,15 @@ struct Prec {
   double dsum = 0.0;
   DBuf d;        // nvar
   DBuf ts;       // nvar x ksz
-  DBuf cholS, linvS, cw;
+  DBuf cholS;
+  DBuf workS;    // chol_work_doubles of the factorisations of Z and S + I, then NB x ksz of the solve with cholS
   DBuf y, y2, y3, y4, zpart;
   DBuf E, Um, AU, sig;
   // H_alpha with linear constraints: AAAATtau = tau^2 I + C_lin diag(X_lin ./ S_lin) C_lin' is not
   // diagonal (Solvers.jl:743-745); its dense Cholesky factor L_D replaces the D^-1/2 scalings
   bool has_LD = false;
-  DBuf LD, linvD, wD, Cd;
+  DBuf LD, Cd;
+  DBuf workD;    // chol_work_doubles(nvar) of the factorisation, then NB x max(ksz, 1) of the solves with L_D
   // SMW core as an explicit inverse (option prec_inv): Sm = S + I, Ainv = (S + I)^-1 = L^-T L^-1
   bool has_inv = false;
   DBuf Sm, Ainv;
@@ -105,8 +107,8 @@ __global__ void mirror_lower_full_kernel(double* __restrict__ A, int n) {
 void prec_free(lrn_ctx* c) {
   if (!c->prec) return;
   Prec* p = c->prec;
-  for (DBuf* d : {&p->d, &p->ts, &p->cholS, &p->linvS, &p->cw, &p->y, &p->y2, &p->y3, &p->y4, &p->zpart, &p->E, &p->Um,
-                  &p->AU, &p->sig, &p->LD, &p->linvD, &p->wD, &p->Cd, &p->Sm, &p->Ainv, &p->Minv, &p->T1})
+  for (DBuf* d : {&p->d, &p->ts, &p->cholS, &p->workS, &p->y, &p->y2, &p->y3, &p->y4, &p->zpart, &p->E, &p->Um,
+                  &p->AU, &p->sig, &p->LD, &p->workD, &p->Cd, &p->Sm, &p->Ainv, &p->Minv, &p->T1})
     release(*d);
   delete p;
   c->prec = nullptr;
@@ -1712,8 +1714,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     const int nl = c->nlin;
     LRN_TRY(ensure(c, P->Cd, (size_t)n * nl * 8));
     LRN_TRY(ensure(c, P->LD, (size_t)n * n * 8));
-    LRN_TRY(ensure(c, P->linvD, chol_linv_doubles(n) * 8));
-    LRN_TRY(ensure(c, P->wD, (size_t)n * CHOL_NB * 8 + (size_t)CHOL_NB * std::max(ksz, 1) * 8));
+    LRN_TRY(ensure(c, P->workD, (chol_work_doubles(n) + (size_t)CHOL_NB * std::max(ksz, 1)) * 8));
     LRN_HIP(c, hipMemsetAsync(P->Cd.p, 0, (size_t)n * nl * 8, st));
     hipLaunchKernelGGL(lin_dense_kernel, dim3(nb(nl)), dim3(256), 0, st, c->cl_ptr.as<long>(), c->cl_rown.as<int>(),
                        c->cl_val.as<double>(), c->lin_xs.as<double>(), nl, n, P->Cd.as<double>());
@@ -1726,7 +1727,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     LRN_TRY(gemm(st, gd));
     hipLaunchKernelGGL(prec_add_diag_kernel, dim3(nb(n)), dim3(256), 0, st, P->LD.as<double>(), n, dsum);
     LRN_HIP(c, hipMemsetAsync(c->info_dev.p, 0, 4, st));
-    LRN_TRY(potrf_lower(st, P->LD.as<double>(), n, n, P->linvD.as<double>(), P->wD.as<double>(), c->info_dev.as<int>()));
+    LRN_TRY(potrf_lower(st, P->LD.as<double>(), n, n, P->workD.as<double>(), c->info_dev.as<int>()));
     int hd = 0;
     LRN_TRY(copy_out(c, &hd, c->info_dev.p, 4));
     if (hd != 0) { if (info) *info = hd; return LRN_OK; }
@@ -1762,8 +1763,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       // Z = chol(2 W0 + Um Um') = chol(2W - Um Um')   (Solvers.jl:725-731)
       LRN_TRY(ensure_m(c, m));
       double* Zf = c->m0.as<double>();
-      LRN_TRY(ensure(c, P->linvS, chol_linv_doubles(std::max(m, ksz)) * 8));
-      LRN_TRY(ensure(c, P->cw, (size_t)std::max(m, ksz) * CHOL_NB * 8));
+      LRN_TRY(ensure(c, P->workS, chol_work_doubles(std::max(m, ksz)) * 8));
       // 2W - UU' is positive definite in exact arithmetic; late in the solve cond(W) passes 1e16 and
       // the rounding of W = GG' can cost the factorisation (the reference's eigen-based W0 is exposed to
       // the same, Solvers.jl:725-731 raise PosDefException).  A preconditioner only has to be SPD:
@@ -1777,7 +1777,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
           c->counts["prec_z_shift"] += 1;
         }
         LRN_HIP(c, hipMemsetAsync(c->info_dev.p, 0, 4, st));
-        LRN_TRY(potrf_lower(st, Zf, m, m, P->linvS.as<double>(), P->cw.as<double>(), c->info_dev.as<int>()));
+        LRN_TRY(potrf_lower(st, Zf, m, m, P->workS.as<double>(), c->info_dev.as<int>()));
         LRN_TRY(copy_out(c, &h, c->info_dev.p, 4));
         if (h == 0) break;
       }
@@ -1805,8 +1805,8 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       col0 += k * m;
     }
     if (P->has_LD)      // ts = L_D^-1 t   (the reference: AAAATtau \ t, Solvers.jl:767)
-      LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, P->linvD.as<double>(), false, P->ts.as<double>(), ksz, n,
-                              P->wD.as<double>() + (size_t)n * CHOL_NB));
+      LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, false, P->ts.as<double>(), ksz, n,
+                              P->workD.as<double>() + chol_work_doubles(n)));
     // S = ts' ts + I ; cholS   (Solvers.jl:804-805)
     LRN_TRY(ensure(c, P->cholS, (size_t)ksz * ksz * 8));
     GemmDesc g;
@@ -1825,11 +1825,9 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       LRN_HIP(c, hipMemcpyAsync(P->Sm.p, P->cholS.p, (size_t)ksz * ksz * 8, hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(mirror_lower_full_kernel, dim3(nb((long)ksz * ksz)), dim3(256), 0, st, P->Sm.as<double>(), ksz);
     }
-    LRN_TRY(ensure(c, P->linvS, chol_linv_doubles(ksz) * 8));
-    LRN_TRY(ensure(c, P->cw, (size_t)ksz * CHOL_NB * 8));
+    LRN_TRY(ensure(c, P->workS, chol_work_doubles(ksz) * 8));
     LRN_HIP(c, hipMemsetAsync(c->info_dev.p, 0, 4, st));
-    LRN_TRY(potrf_lower(st, P->cholS.as<double>(), ksz, ksz, P->linvS.as<double>(), P->cw.as<double>(),
-                        c->info_dev.as<int>()));
+    LRN_TRY(potrf_lower(st, P->cholS.as<double>(), ksz, ksz, P->workS.as<double>(), c->info_dev.as<int>()));
     int h = 0;
     LRN_TRY(copy_out(c, &h, c->info_dev.p, 4));
     if (h != 0) { if (info) *info = h; return LRN_OK; }
@@ -1838,10 +1836,10 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       LRN_TRY(ensure_m(c, ksz));
       double* Li = c->m0.as<double>();
       double* LiT = c->m1.as<double>();
-      LRN_TRY(ensure(c, P->cw, ((size_t)ksz * CHOL_NB + (size_t)CHOL_NB * ksz) * 8));
+      LRN_TRY(ensure(c, P->workS, (chol_work_doubles(ksz) + (size_t)CHOL_NB * ksz) * 8));
       hipLaunchKernelGGL(eye_fill_kernel, dim3(nb((long)ksz * ksz)), dim3(256), 0, st, Li, ksz);
-      LRN_TRY(trsm_left_lower(st, P->cholS.as<double>(), ksz, ksz, P->linvS.as<double>(), false, Li, ksz, ksz,
-                              P->cw.as<double>() + (size_t)ksz * CHOL_NB));
+      LRN_TRY(trsm_left_lower(st, P->cholS.as<double>(), ksz, ksz, false, Li, ksz, ksz,
+                              P->workS.as<double>() + chol_work_doubles(ksz)));
       hipLaunchKernelGGL(transpose_sq_kernel, dim3((ksz + 31) / 32, (ksz + 31) / 32), dim3(32, 8), 0, st, Li, ksz, LiT);
       LRN_TRY(gemm_nt_sym(st, ksz, LiT, LiT, P->Ainv.as<double>(), 1.0));      // L^-T L^-1
     }
@@ -1935,8 +1933,7 @@ int prec_apply_dev(lrn_ctx* c, const double* x, double* Mx, double* tmpv) {
   const int ksz = P->ksz;                                    // MyM (Solvers.jl:866-904), ts form
   if (P->has_LD) {      // v = L_D^-1 x  (d holds ones)
     hipLaunchKernelGGL(div_kernel, dim3(nb(n)), dim3(256), 0, st, x, P->d.as<double>(), tmpv, n, 1);
-    LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, P->linvD.as<double>(), false, tmpv, 1, n,
-                            P->wD.as<double>() + (size_t)n * CHOL_NB));
+    LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, false, tmpv, 1, n, P->workD.as<double>() + chol_work_doubles(n)));
     hipLaunchKernelGGL(gemv_t_kernel, dim3(ksz), dim3(256), 0, st, P->ts.as<double>(), n, tmpv, (const double*)nullptr,
                        P->y.as<double>());
   } else {              // v = x ./ sqrt(d) formed inside the two kernels that read it (same operations, one launch less)
@@ -1954,8 +1951,8 @@ int prec_apply_dev(lrn_ctx* c, const double* x, double* Mx, double* tmpv) {
     hipLaunchKernelGGL(symv_rows_kernel, dim3(g16), dim3(256), lds, st, P->Ainv.as<double>(), ksz, P->y3.as<double>(),
                        P->y4.as<double>(), 1.0, 1.0, P->y2.as<double>());
   } else {
-    LRN_TRY(potrs_vec(st, P->cholS.as<double>(), ksz, ksz, P->linvS.as<double>(), P->y.as<double>(), P->y2.as<double>(),
-                      P->y3.as<double>(), P->y4.as<double>()));
+    LRN_TRY(potrs_vec(st, P->cholS.as<double>(), ksz, ksz, P->y.as<double>(), P->y2.as<double>(), P->y3.as<double>(),
+                      P->y4.as<double>()));
   }
   const int nchunk = std::min(32, std::max(1, ksz / 32));
   const int cper = (ksz + nchunk - 1) / nchunk;
@@ -1964,8 +1961,7 @@ int prec_apply_dev(lrn_ctx* c, const double* x, double* Mx, double* tmpv) {
   hipLaunchKernelGGL(smw_final_kernel, dim3(nb(n)), dim3(256), 0, st, P->has_LD ? tmpv : x, P->zpart.as<double>(), nchunk, n,
                      P->d.as<double>(), Mx, P->has_LD ? 0 : 1);
   if (P->has_LD)
-    LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, P->linvD.as<double>(), true, Mx, 1, n,
-                            P->wD.as<double>() + (size_t)n * CHOL_NB));
+    LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, true, Mx, 1, n, P->workD.as<double>() + chol_work_doubles(n)));
   return LRN_OK;
 }
 

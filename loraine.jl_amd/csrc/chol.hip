@@ -4,19 +4,22 @@
 // 39,57,90,199), cholesky(X), cholesky(S) (src/prepare_W.jl:7,33-34) and cholesky(S+I)
 // (src/Solvers.jl:805).
 //
-//  * right-looking, NB = 64: the diagonal block is factored by ONE workgroup entirely in
-//    LDS; the panel solve X L_kk' = A21 is a forward substitution with one thread per row
-//    (L_kk in LDS, the row in registers) and the trailing update (A22 -= L21 L21', lower
-//    tiles only) runs on the FP64 MFMA GEMM.
+//  * right-looking, NB = 64, ONE launch per block column: potrf_step_kernel applies the trailing update with panel k
+//    (A22 -= L21 L21', lower 64 x 64 tiles on the FP64 MFMA), factors diagonal block k + 1 in LDS (diag_block_factor, four
+//    wavefronts) and solves panel k + 1 by strips of 16 rows (strip_solve).  Only the first diagonal block and the first
+//    panel of the matrix -- and of every super-block -- are launches of their own (potrf_diag_blk_kernel,
+//    potrf_panel_mfma_kernel).
+//  * from n = POTRF_SB_MIN on a second blocking level: inside a super-block of POTRF_SB_COLS columns the steps update the
+//    super-block's own columns only; the rest of the trailing matrix takes the whole super-block at once on the general GEMM.
+//  * workspace (chol_work_doubles(n) in chol.h): TWO panel buffers of n x NB doubles.  Step k reads the solved panel k from
+//    one and writes panel k + 1 into the other; behind the panel, at offset (n - NB) NB, each holds a contiguous copy of
+//    the next diagonal tile as it was before its factorisation, which the replicas of potrf_step_kernel read.
 //  * a non-positive pivot is reported LAPACK-style through a device `info` word
 //    (first failing 1-based column); later blocks then skip their work.
 //  * triangular solves substitute through the 64x64 diagonal blocks (no explicit inverses:
 //    the Schur matrix, S + I of H_alpha and X, S late in the solve have condition numbers
 //    beyond 1e12, where inv(L_kk) costs the digits LAPACK's backward-stable solves keep);
 //    the off-diagonal panels are streamed once per block (bandwidth-bound, coalesced).
-//    The `Linv` arguments of the entry points are kept for the callers' workspaces but unused.
-#include <cstdlib>
-
 #include "lrn_common.h"
 #include "chol.h"
 
@@ -25,11 +28,13 @@ namespace lrn {
 static constexpr int NB = CHOL_NB;
 
 // ------------------------------------------------------------------ diagonal block
-// A (nb x nb, lower, ld) -> L in place (Linv: unused, kept for the signature).
+// A (nb x nb, lower, ld) -> L in place.
 // diag0 != NULL (Schur matrix only): pivots at or below the rounding level of their original diagonal
 // entry, pivot <= boost * diag0[j] (zero and negative ones included), are replaced by a huge value --
 // the row drops out of the factor and the solves return 0 for it (the usual pivot boosting of
-// interior-point Cholesky codes).  info[1] counts them; more than `max_boost` is a failure.
+// interior-point Cholesky codes).  Only where diag0[j] > 0: a structurally empty row (a variable that occurs in no
+// constraint) is not rounding noise; it fails like in the reference, whose +1e-4 I loop and regularisation count then
+// decide.  info[1] counts the boosted pivots; more than `max_boost` is a failure.
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __builtin_amdgcn_readlane(lo, lane);
@@ -37,75 +42,14 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   return __hiloint2double(hi, lo);
 }
 
-// The factorisation of the block by ONE wavefront without LDS or barriers: lane i keeps row i of the block in
-// registers, the pivot and the column entries l_kj travel by v_readlane (wave-uniform SGPRs feeding
-// the FMAs).  64 columns x (63 - j) rank-one updates = 2016 FMA per lane; 44 us per block against 57 us
-// for a 256-thread LDS version with 3 barriers per column.  Entries above the diagonal of a lane's row
-// are scratch.
-__global__ __launch_bounds__(64) void potrf_diag_wave_kernel(double* __restrict__ A, int ld, int nb, int col0,
-                                                             int* __restrict__ info, const double* __restrict__ diag0,
-                                                             double boost, int max_boost) {
-  // column j of the factor, as it is produced: written once by the wave and read back by every lane as LDS
-  // broadcasts (uniform address) -- the rank-one update a[k] -= l_ij l_kj needs l_kj of lane k in every lane, and 2016
-  // such values per block through v_readlane (two per value, one SGPR pair, a wait state each) cost more (41 -> 38 us
-  // per block; 63 blocks per factorisation of the C4 Schur matrix.  The 64 columns as ONE basic block with selects
-  // instead of the per-column branches: 164 us -- the scheduler hoists the reads and spills).  One wave: its LDS
-  // operations execute in order, no barrier.
-  __shared__ double colbuf[2][NB];
-  const int i = threadIdx.x;
-  if (*info != 0) return;
-  double a[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) a[j] = (i < nb && j < nb && i >= j) ? A[(long)i + (long)j * ld] : (i == j ? 1.0 : 0.0);
-  double d0v = 1.0;                              // lane j: original diagonal entry of column col0 + j (pivot boosting)
-  if (diag0 && i < nb) d0v = diag0[col0 + i];
-  int bad = 0;
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    if (bad == 0) {
-      double piv = readlane_f64(a[j], j);
-      if (diag0 && j < nb) {
-        const double d0 = readlane_f64(d0v, j);
-        // d0 > 0: a structurally empty row (a variable that occurs in no constraint) is not rounding noise;
-        // it fails like in the reference, whose +1e-4 I loop and regularisation count then decide
-        if (d0 > 0.0 && piv <= boost * d0 && piv == piv) {
-          piv = 1e40 * fmax(fabs(d0), 1.0);
-          int cnt = 0;
-          if (i == 0) cnt = atomicAdd(info + 1, 1) + 1;
-          cnt = __builtin_amdgcn_readfirstlane(cnt);
-          if (cnt > max_boost) bad = col0 + j + 1;
-        }
-      }
-      if (!(piv > 0.0)) bad = col0 + j + 1;        // also catches NaN; wave-uniform
-      if (bad == 0) {
-        const double sq = sqrt(piv);
-        const double rl = 1.0 / sq;
-        const double lij = a[j] * rl;
-        a[j] = (i == j) ? sq : lij;
-        double* cb = colbuf[j & 1];
-        cb[i] = lij;
-#pragma unroll
-        for (int k = j + 1; k < NB; ++k) a[k] -= lij * cb[k];
-      }
-    }
-  }
-  if (bad) {
-    if (i == 0) atomicCAS(info, 0, bad);
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < NB; ++j)
-    if (i < nb && j < nb && i >= j) A[(long)i + (long)j * ld] = a[j];
-}
-
-// The diagonal block by FOUR wavefronts in eight panels of 8 columns (round 3).  The one-wave kernel above spends 28 of
-// its 37.5 us in the per-column chain -- pivot broadcast, sqrt, divide, an LDS round trip -- in front of 63 - j FMAs that
-// the in-order wave cannot overlap with it.  Here the block lives in LDS; wave 0 factors a 64 x 8 panel with the rows in
+// The diagonal block by FOUR wavefronts in eight panels of 8 columns.  What bounds a 64 x 64 factorisation is the per-column
+// chain -- pivot broadcast, sqrt, divide -- in front of 63 - j FMAs that an in-order wave cannot overlap with it.  Here the
+// block lives in LDS; wave 0 factors a 64 x 8 panel with the rows in
 // 8 registers per lane (the chain: v_readlane of the pivot, v_rsq_f64 + one Goldschmidt and one Newton step -- 8 dependent
 // operations instead of the ~45 of sqrt and divide -- and at most 7 lagging FMAs per column, their multipliers by
 // v_readlane), then all four waves apply the rank-8 update to the 16 x 16 blocks of the trailing part on the MFMA
 // (two v_mfma_f64_16x16x4 per block; block columns that the panel itself crosses are masked in the B operand).
-// Entries above the diagonal are scratch.  Same pivot rules as above (boosting, first failing column in info[0]).
+// Entries above the diagonal are scratch.  Pivot rules as described above (boosting, first failing column in info[0]).
 __device__ __forceinline__ void rsqrt_pair(double p, double& sq, double& rinv) {
   if (p > 1e-280 && p < 1e280) {
     const double y = __builtin_amdgcn_rsq(p);
@@ -254,112 +198,13 @@ __global__ __launch_bounds__(256) void potrf_diag_blk_kernel(double* __restrict_
   }
 }
 
-// Panel of the factorisation: rows of A21 (rem x NB, ld) solve  x L_kk' = a  by forward substitution,
-// one thread per row with the row in registers and L_kk (NB x NB, lower, full block) in LDS.
-// Writes the result back in place and into the contiguous work panel W (rem x NB, ld rem).
-__global__ __launch_bounds__(256) void potrf_panel_kernel(double* __restrict__ A21, int ld, int rem,
-                                                          const double* __restrict__ Lkk, double* __restrict__ W,
-                                                          const int* __restrict__ info) {
-  __shared__ double l[NB][NB + 1];
-  __shared__ double rinv[NB];
-  if (*info != 0) return;
-  const int t = threadIdx.x;
-  for (int e = t; e < NB * NB; e += 256) {
-    int i = e % NB, j = e / NB;
-    l[i][j] = i >= j ? Lkk[(long)i + (long)j * ld] : 0.0;
-  }
-  __syncthreads();
-  if (t < NB) rinv[t] = 1.0 / l[t][t];
-  __syncthreads();
-  const int row = blockIdx.x * 256 + t;
-  if (row >= rem) return;
-  // (measured on tru9, nvar = 3240: this left-looking LDS form 35 us per panel; right-looking 44 us;
-  // L_kk through scalar loads instead of LDS 57 us)
-  double x[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) x[j] = A21[(long)row + (long)j * ld];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    double s = x[j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) s -= x[k] * l[j][k];
-    x[j] = s * rinv[j];
-  }
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    A21[(long)row + (long)j * ld] = x[j];
-    W[(long)row + (long)j * rem] = x[j];
-  }
-}
-
-// The same panel solve with EIGHT lanes per row (round 3).  One thread per row walks 2016 dependent FMA + LDS-read pairs
-// (30 us per panel, n / 64 panels per factorisation: a third of the factorisation of the C2 / C3 / truss matrices).  Here
-// lane (row, b) owns the 8 columns [8 b, 8 b + 8) of its row: in stage s the lanes with b = s solve their 8 x 8
-// triangular block and publish x through LDS, the lanes with b > s subtract its contribution from their columns -- a
-// critical path of 8 x (36 + 64) pairs instead of 2016.  32 rows per workgroup.
-__global__ __launch_bounds__(256) void potrf_panel8_kernel(double* __restrict__ A21, int ld, int rem,
-                                                           const double* __restrict__ Lkk, double* __restrict__ W,
-                                                           const int* __restrict__ info) {
-  __shared__ double l[NB][NB + 1];
-  __shared__ double rinv[NB];
-  __shared__ double xs[32][NB + 1];
-  if (*info != 0) return;
-  const int t = threadIdx.x;
-  for (int e = t; e < NB * NB; e += 256) {
-    int i = e % NB, j = e / NB;
-    l[i][j] = i >= j ? Lkk[(long)i + (long)j * ld] : 0.0;
-  }
-  __syncthreads();
-  if (t < NB) rinv[t] = 1.0 / l[t][t];
-  const int rl = t >> 3, b = t & 7;                 // row of the workgroup, block of 8 columns
-  const int row = blockIdx.x * 32 + rl;
-  const bool live = row < rem;
-  double a[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) a[c] = live ? A21[(long)row + (long)(8 * b + c) * ld] : 0.0;
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    if (b == s) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        double v = a[c];
-#pragma unroll
-        for (int k = 0; k < c; ++k) v -= a[k] * l[8 * s + c][8 * s + k];
-        v *= rinv[8 * s + c];
-        a[c] = v;
-        xs[rl][8 * s + c] = v;
-      }
-    }
-    __syncthreads();
-    if (b > s) {
-      double x[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) x[k] = xs[rl][8 * s + k];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        double v = a[c];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v -= x[k] * l[8 * b + c][8 * s + k];
-        a[c] = v;
-      }
-    }
-  }
-  if (!live) return;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    A21[(long)row + (long)(8 * b + c) * ld] = a[c];
-    W[(long)row + (long)(8 * b + c) * rem] = a[c];
-  }
-}
-
-// The panel solve by strips of 16 rows, one wavefront per strip, no barrier after the prologue (round 3).  The strip
+// The panel solve X L_kk' = A21 by strips of 16 rows, one wavefront per strip, no barrier after the prologue.  The strip
 // X (16 x 64) stays in registers as four 16 x 16 blocks in the MFMA result layout.  For each block column c: the block
 // goes to LDS, lanes 0..15 (one row each) solve it against the 16 x 16 diagonal sub-block of L_kk right-looking -- a
 // dependent chain of 16 multiply / FMA pairs, the multipliers l_kj as LDS broadcasts -- and the blocks c' > c take
-// X_c L[c', c]' off on the MFMA (4 x v_mfma_f64_16x16x4 each).  Critical path per strip: 4 x (16-step chain + 4 MFMAs)
-// instead of the 8 x (36 + 64) dependent FMA / LDS pairs and 8 barriers of the eight-lane kernel above
-// (19 us at n = 800, 32 us at n = 4000).  No inverse of the diagonal sub-blocks: substitution, as everywhere in this file.
+// X_c L[c', c]' off on the MFMA (4 x v_mfma_f64_16x16x4 each).  Critical path per strip: 4 x (16-step chain + 4 MFMAs),
+// against the 2016 dependent FMA / LDS-read pairs of one thread per row.  No inverse of the diagonal sub-blocks:
+// substitution, as everywhere in this file.
 // The solve of one 16 x 64 strip (see the kernel below): C = the strip as four MFMA-layout blocks, X = its LDS image (in / out:
 // the solved strip), Ls = L_kk (lower part read only), rinv = 1 / diag(L_kk).  One wave; LDS operations of one wave execute
 // in order, no barrier.
@@ -448,111 +293,28 @@ __global__ __launch_bounds__(256) void potrf_panel_mfma_kernel(double* __restric
   }
 }
 
-// Trailing update of the factorisation, A22 -= Wk Wk' on the lower 64 x 64 tiles (Wk: rem x 64, contiguous), as a
-// kernel of its own (round 3).  The general GEMM walks K = 64 in four 16-steps with a barrier each and reads C in its
-// epilogue: five dependent global round trips for 2 MFLOP per tile -- 42 us per update at n = 4000 (two thirds of the
-// factorisation), 12 us at n = 800.  Here a workgroup requests its C tile (into the accumulators, MFMA result layout, the
-// lane-contiguous dimension along the columns of A22 in memory) and its two 64 x 64 panels at once -- ONE round trip --
-// then runs 64 MFMAs per wave from LDS and stores the tile.
-// The workgroup of tile (0, 0) -- the next diagonal block -- goes on to factor it (diag_block_factor) from LDS instead
-// of storing it for a kernel of its own: one launch and one global round trip less per block column, and the pivot
-// chain of block k + 1 runs beside the other tiles of update k.  (The sums start from zero and meet C once at the
-// end, like in the general GEMM: starting from C costs a factor 5 in the backward error.)
-__global__ __launch_bounds__(256) void potrf_syrk_kernel(double* __restrict__ C, int ld, int rem,
-                                                         const double* __restrict__ Wp, int* __restrict__ info,
-                                                         int fuse_diag, int col0, const double* __restrict__ diag0,
-                                                         double boost, int max_boost) {
-  constexpr int LS = NB + 8;     // k-rows 16 banks apart: every bank is hit by two of the 64 lanes of a fragment read -- the two
-                                 // passes 512 bytes take anyway; with NB + 16 the two panels fill 80 KB and one workgroup a CU
-  __shared__ double PA[NB][LS];
-  __shared__ double PB[NB][LS];
-  __shared__ int bad_s;
-  const int I = blockIdx.x, J = blockIdx.y;        // tile row / column of A22
-  if (J > I) return;
-  if (*info != 0) return;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int i0 = NB * I, j0 = NB * J;
-  const int cr = lane >> 4, cc = lane & 15;
-  // the C tile: wave w owns columns j0 + 16 w .. + 15 of the tile, all 64 rows (four 16 x 16 blocks)
-  v4f64 cv[4], acc[4];
-#pragma unroll
-  for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = i0 + 16 * bb + cc, j = j0 + 16 * w + cr + 4 * r;
-      cv[bb][r] = (i < rem && j < rem) ? C[(long)i + (long)j * ld] : 0.0;
-      acc[bb][r] = 0.0;
-    }
-  {
-    const int row = t & 63, kq = t >> 6;
-    double va[16], vb[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int k = kq + 4 * q;
-      va[q] = (j0 + row < rem) ? Wp[(long)(j0 + row) + (long)k * rem] : 0.0;
-      vb[q] = (I != J && i0 + row < rem) ? Wp[(long)(i0 + row) + (long)k * rem] : 0.0;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      PA[kq + 4 * q][row] = va[q];
-      if (I != J) PB[kq + 4 * q][row] = vb[q];
-    }
-  }
-  if (t == 0) bad_s = 0;
-  __syncthreads();
-  const double (*Pb)[LS] = (I != J) ? PB : PA;
-#pragma unroll
-  for (int kk = 0; kk < NB / 4; ++kk) {
-    const double a = PA[4 * kk + cr][16 * w + cc];
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb)
-      acc[bb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Pb[4 * kk + cr][16 * bb + cc], acc[bb], 0, 0, 0);
-  }
-  if (fuse_diag && I == 0 && J == 0) {
-    // this tile is the next diagonal block: factor it here
-    const int nb = rem < NB ? rem : NB;
-    __syncthreads();                               // (every wave is done with the panels)
-    double (*M)[NB + 1] = reinterpret_cast<double (*)[NB + 1]>(&PA[0][0]);
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * bb + cc, j = 16 * w + cr + 4 * r;
-        M[i][j] = (i < nb && j < nb && i >= j) ? cv[bb][r] - acc[bb][r] : (i == j ? 1.0 : 0.0);
-      }
-    __syncthreads();
-    diag_block_factor(M, bad_s, nb, col0, info, diag0, boost, max_boost);
-    if (bad_s) {
-      if (t == 0) atomicCAS(info, 0, bad_s);
-      return;
-    }
-    for (int e = t; e < NB * NB; e += 256) {
-      const int i = e % NB, j = e / NB;
-      if (i < nb && j < nb && i >= j) C[(long)i + (long)j * ld] = M[i][j];
-    }
-    return;
-  }
-#pragma unroll
-  for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = i0 + 16 * bb + cc, j = j0 + 16 * w + cr + 4 * r;
-      if (i < rem && j < rem) C[(long)i + (long)j * ld] = cv[bb][r] - acc[bb][r];
-    }
-}
-
-// One launch per block column (round 3): the trailing update with panel k, the factorisation of diagonal block k + 1 AND
-// the panel solve k + 1.  The workgroups of tile column 0 hold the rows of the next panel; each of them also forms tile
-// (0, 0) from the panel rows it has loaded anyway (64 more MFMAs per wave), factors it -- a replica of what the workgroup
-// of tile (0, 0) does, same arithmetic, same bits, no synchronisation between workgroups -- and solves its 64 rows by
+// One launch per block column: the trailing update with panel k, A22 -= Wk Wk' on the lower 64 x 64 tiles (Wk = Wp: rem x 64,
+// contiguous), the factorisation of diagonal block k + 1 AND the panel solve k + 1.
+// The update: a workgroup requests its C tile (into registers, MFMA result layout, the lane-contiguous dimension along the
+// columns of A22 in memory) and its two 64 x 64 panels at once -- ONE global round trip, where the general GEMM walks
+// K = 64 in four 16-steps with a barrier each and reads C in its epilogue: five dependent round trips for 2 MFLOP per
+// tile -- then runs 64 MFMAs per wave from LDS.  The sums start from zero and meet C once at the end, like in the general
+// GEMM: starting from C costs a factor 5 in the backward error.
+// The workgroup of tile (0, 0) -- the leader -- goes on to factor that tile, the next diagonal block, from LDS
+// (diag_block_factor) instead of storing it for a kernel of its own: one launch and one global round trip less per block
+// column, and the pivot chain of block k + 1 runs beside the other tiles of update k.
+// The other workgroups of tile column 0 hold the rows of the next panel; each of them also forms tile
+// (0, 0) from the panel rows it has loaded anyway (64 more MFMAs per wave), factors it -- a replica of what the leader
+// does, same arithmetic, same bits, no synchronisation between workgroups -- and solves its 64 rows by
 // strips (strip_solve) straight from the registers of the update: the panel never makes the round trip through memory as
 // an unsolved block, and the chain per block column is one kernel (update + 13 us of pivots + 4 x 16-step substitutions)
-// instead of two.  Wn: the next panel (rem - 64 rows, contiguous) -- a second work buffer, the update reads Wp.
+// instead of two.  Wn: the next panel (rem - 64 rows, contiguous) in the other panel buffer -- the update reads Wp.
 // The replicas must not read tile (0, 0) from A: the leader overwrites it with the factor, and a replica that is dispatched
 // late (two factorisations on two streams share the workgroup slots) would read L for A.  They read T00 (64 x 64,
 // contiguous), a copy of the tile that the workgroup of tile (1, 1) of the PREVIOUS step stored beside the matrix
-// (T00n: the copy this step's (1, 1) workgroup leaves for the next step; both in the slack of the panel buffers).
+// (T00n: the copy this step's (1, 1) workgroup leaves for the next step; both behind the panels in the two buffers).
+// LS = NB + 8 puts the k-rows of a panel 16 banks apart: every bank is hit by two of the 64 lanes of a fragment read -- the
+// two passes 512 bytes take anyway; with NB + 16 the two panels fill 80 KB and one workgroup a CU.
 __global__ __launch_bounds__(256) void potrf_step_kernel(double* __restrict__ C, int ld, int rem,
                                                          const double* __restrict__ Wp, double* __restrict__ Wn,
                                                          const double* __restrict__ T00, double* __restrict__ T00n,
@@ -742,150 +504,65 @@ __device__ __forceinline__ void block_subst_wave(double (*lb)[NB + 1], double* v
   if (lane < nb) v[lane] = r;
 }
 
-__global__ void copy_panel_kernel(const double* __restrict__ src, int lds_, double* __restrict__ dst,
-                                  int ldd, int rows, int cols, const int* __restrict__ info) {
-  if (info && *info != 0) return;
-  long n = (long)rows * cols;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-    int i = (int)(e % rows), j = (int)(e / rows);
-    dst[(long)i + (long)j * ldd] = src[(long)i + (long)j * lds_];
-  }
+// ------------------------------------------------------------------ the factorisation
+int potrf_lower(hipStream_t st, double* A, int n, int ld, double* work, int* info_dev) {
+  return potrf_lower_boost(st, A, n, ld, work, info_dev, nullptr, 0.0, 0);
 }
 
-int potrf_lower(hipStream_t st, double* A, int n, int ld, double* Linv, double* work, int* info_dev) {
-  return potrf_lower_boost(st, A, n, ld, Linv, work, info_dev, nullptr, 0.0, 0);
-}
+// Second blocking level (round 4): above n ~ 6000 the step kernel is bound by the HBM traffic of the trailing matrix,
+// which it re-streams for every 64 columns (n = 20 000: 333 GB, 100 ms at 26 TFLOP/s).  Inside a super-block a step updates
+// only the super-block's own remaining columns (all rows below); the rest of the trailing matrix gets the sixteen panels at
+// once, C -= L_sb L_sb' with K = 1024 on the 128-tile direct-to-LDS GEMM (a sixteenth of the traffic), and the next
+// super-block starts like the factorisation itself.
+// (width sweep at n = 10^4 / 20 000: 256 -> 14.8 / 73.8 ms, 512 -> 13.1 / 61.9, 1024 -> 12.4 / 58.0; one level: 16.1 / 100)
+static constexpr int POTRF_SB_COLS = 16 * NB;
+static constexpr int POTRF_SB_MIN = 9000;     // (6144: 5.1 -> 5.8 ms, slower; 10^4: 16.1 -> 14.8)
 
-int potrf_lower_boost(hipStream_t st, double* A, int n, int ld, double* Linv, double* work, int* info_dev,
-                      const double* diag0, double boost, int max_boost) {
-  // work: n x NB doubles
-  int nblk = (n + NB - 1) / NB;
-  static const bool diag_wave = getenv("LRN_POTRF_DIAG1") != nullptr;       // (measurement: the one-wave kernel)
-  static const bool one_lane = getenv("LRN_POTRF_PANEL1") != nullptr;
-  static const bool eight_lanes = getenv("LRN_POTRF_PANEL8") != nullptr;    // (measurement: the round-3a kernel)
-  static const bool use_gemm = getenv("LRN_POTRF_GEMM") != nullptr;         // (measurement: the general GEMM, as in round 2)
-  static const bool no_fuse = getenv("LRN_POTRF_NOFUSE") != nullptr;        // (measurement: diagonal blocks as launches of their own)
-  static const bool no_step = getenv("LRN_POTRF_NOSTEP") != nullptr;        // (measurement: diagonal + panel + update kernels)
-  if (!no_step && !diag_wave && !one_lane && !eight_lanes && !use_gemm && !no_fuse && Linv && n > NB) {
-    // one launch per block column (potrf_step_kernel); the panels alternate between `work` and `Linv` (n x NB doubles each)
-    hipLaunchKernelGGL(potrf_diag_blk_kernel, dim3(1), dim3(256), 0, st, A, ld, NB, 0, info_dev, diag0, boost, max_boost);
-    double* cur = work;
-    hipLaunchKernelGGL(potrf_panel_mfma_kernel, dim3((n - NB + 63) / 64), dim3(256), 0, st, A + NB, 1L, (long)ld, n - NB, A, ld,
-                       NB, 0, cur, 1L, (long)(n - NB), info_dev);
-    // the copies of the next diagonal tile live behind the largest panel a buffer can hold: (n - NB) x NB doubles of
-    // n x NB (work) / >= n x NB (Linv)
-    const size_t t00_off = (size_t)(n - NB) * NB;
-    {
-      const int e0 = n - NB < NB ? n - NB : NB;        // tile (0, 0) of the first trailing matrix, as it is in A
-      if (hipMemcpy2DAsync(cur + t00_off, (size_t)NB * 8, A + (long)NB + (long)NB * ld, (size_t)ld * 8, (size_t)e0 * 8, e0,
-                           hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return LRN_ERR_HIP;
-    }
-    // Second blocking level (round 4; n >= 9000): above n ~ 6000 the step kernel is bound by the HBM traffic of the
-    // trailing matrix, which it re-streams for every 64 columns (n = 20 000: 333 GB, 100 ms at 26 TFLOP/s).  Super-blocks of
-    // SB = 1024 columns: inside one, a step updates only the super-block's own remaining columns (all rows below); the rest
-    // of the trailing matrix gets the sixteen panels at once, C -= L_sb L_sb' with K = 1024 on the 128-tile direct-to-LDS GEMM
-    // (a sixteenth of the traffic), and the next super-block starts like the factorisation itself (diagonal block + panel
-    // as launches of their own, the copy of tile (0, 0) for the replicas).
-    static const int sb_min = getenv("LRN_POTRF_SB_MIN") ? atoi(getenv("LRN_POTRF_SB_MIN")) : 9000;   // (6144: 5.1 -> 5.8 ms, slower; 10^4: 16.1 -> 14.8)
-    // (width sweep at n = 10^4 / 20 000: 256 -> 14.8 / 73.8 ms, 512 -> 13.1 / 61.9, 1024 -> 12.4 / 58.0; one level: 16.1 / 100)
-    static const int SB = getenv("LRN_POTRF_SB") ? std::max(2 * NB, (atoi(getenv("LRN_POTRF_SB")) / NB) * NB) : 16 * NB;
-    if (n >= sb_min && (ld & 1) == 0) {
-      for (int ks = 0; ks < n; ks += SB) {
-        if (ks > 0) {
-          // start of a super-block: its first diagonal block and panel (the trailing matrix is up to date: big update below)
-          const int remk = n - ks;
-          if (remk <= 0) break;
-          hipLaunchKernelGGL(potrf_diag_blk_kernel, dim3(1), dim3(256), 0, st, A + (long)ks + (long)ks * ld, ld,
-                             remk < NB ? remk : NB, ks, info_dev, diag0, boost, max_boost);
-          if (remk <= NB) break;
-          hipLaunchKernelGGL(potrf_panel_mfma_kernel, dim3((remk - NB + 63) / 64), dim3(256), 0, st,
-                             A + (long)(ks + NB) + (long)ks * ld, 1L, (long)ld, remk - NB, A + (long)ks + (long)ks * ld, ld, NB, 0,
-                             cur, 1L, (long)(remk - NB), info_dev);
-          const int e0 = remk - NB < NB ? remk - NB : NB;
-          if (hipMemcpy2DAsync(cur + t00_off, (size_t)NB * 8, A + (long)(ks + NB) + (long)(ks + NB) * ld, (size_t)ld * 8,
-                               (size_t)e0 * 8, e0, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return LRN_ERR_HIP;
-        }
-        const int ke = ks + SB < n ? ks + SB : n;                 // end of the super-block
-        for (int k0 = ks; k0 + NB < ke && n - k0 - NB > 0; k0 += NB) {
-          const int rem = n - k0 - NB;
-          const int nt = (rem + NB - 1) / NB;
-          const int ntj = (ke - k0 - NB + NB - 1) / NB;           // tile columns of the trailing matrix inside the super-block
-          double* nxt = (cur == work) ? Linv : work;
-          hipLaunchKernelGGL(potrf_step_kernel, dim3(nt, ntj < nt ? ntj : nt), dim3(256), 0, st,
-                             A + (long)(k0 + NB) + (long)(k0 + NB) * ld, ld, rem, cur, nxt, cur + t00_off, nxt + t00_off,
-                             info_dev, k0 + NB, diag0, boost, max_boost);
-          cur = nxt;
-        }
-        if (ke >= n) break;
-        GemmDesc u;                                               // A[ke:, ke:] -= L[ke:, ks:ke] L[ke:, ks:ke]'  (lower tiles)
-        u.A = A + (long)ke + (long)ks * ld; u.sAm = 1; u.sAk = ld;
-        u.B = A + (long)ke + (long)ks * ld; u.sBk = ld; u.sBn = 1;
-        u.C = A + (long)ke + (long)ke * ld; u.sCm = 1; u.sCn = ld;
-        u.M = n - ke; u.N = n - ke; u.K = ke - ks;
-        u.alpha = -1.0; u.beta = 1.0; u.flags = GEMM_TRI_LOWER;
-        const int rcg = gemm(st, u);
-        if (rcg) return rcg;
-      }
-      return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-    }
-    for (int k0 = 0; n - k0 - NB > 0; k0 += NB) {
-      const int rem = n - k0 - NB;
-      const int nt = (rem + NB - 1) / NB;
-      double* nxt = (cur == work) ? Linv : work;
-      hipLaunchKernelGGL(potrf_step_kernel, dim3(nt, nt), dim3(256), 0, st, A + (long)(k0 + NB) + (long)(k0 + NB) * ld, ld,
-                         rem, cur, nxt, cur + t00_off, nxt + t00_off, info_dev, k0 + NB, diag0, boost, max_boost);
-      cur = nxt;
-    }
+int potrf_lower_boost(hipStream_t st, double* A, int n, int ld, double* work, int* info_dev, const double* diag0,
+                      double boost, int max_boost) {
+  if (n <= NB) {
+    hipLaunchKernelGGL(potrf_diag_blk_kernel, dim3(1), dim3(256), 0, st, A, ld, n, 0, info_dev, diag0, boost, max_boost);
     return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
   }
-  bool diag_done = false;                 // the diagonal block of this step was factored by the previous update kernel
-  for (int b = 0; b < nblk; ++b) {
-    int k0 = b * NB;
-    int nb = n - k0 < NB ? n - k0 : NB;
-    double* Akk = A + (long)k0 + (long)k0 * ld;
-    if (!diag_done) {
-      if (diag_wave)
-        hipLaunchKernelGGL(potrf_diag_wave_kernel, dim3(1), dim3(64), 0, st, Akk, ld, nb, k0, info_dev, diag0, boost,
-                           max_boost);
-      else
-        hipLaunchKernelGGL(potrf_diag_blk_kernel, dim3(1), dim3(256), 0, st, Akk, ld, nb, k0, info_dev, diag0, boost,
-                           max_boost);
-    }
-    diag_done = false;
-    int rem = n - k0 - nb;
-    if (rem <= 0) break;
-    // panel: Wk = A21 * Lkk^-T      (rem x nb), by substitution
-    if (one_lane || nb < NB)
-      hipLaunchKernelGGL(potrf_panel_kernel, dim3((rem + 255) / 256), dim3(256), 0, st,
-                         A + (long)(k0 + nb) + (long)k0 * ld, ld, rem, Akk, work, info_dev);
-    else if (!eight_lanes)
-      hipLaunchKernelGGL(potrf_panel_mfma_kernel, dim3((rem + 63) / 64), dim3(256), 0, st,
-                         A + (long)(k0 + nb) + (long)k0 * ld, 1L, (long)ld, rem, Akk, ld, NB, 0, work, 1L, (long)rem, info_dev);
-    else
-      hipLaunchKernelGGL(potrf_panel8_kernel, dim3((rem + 31) / 32), dim3(256), 0, st,
-                         A + (long)(k0 + nb) + (long)k0 * ld, ld, rem, Akk, work, info_dev);
-    int rc;
-    // trailing: A22 -= Wk Wk^T (lower tiles)
-    if (!use_gemm && nb == NB) {
+  const int sb = (n >= POTRF_SB_MIN && (ld & 1) == 0) ? POTRF_SB_COLS : n;      // (otherwise one super-block is the matrix)
+  // the two panel buffers; the copy of the next diagonal tile lives behind the largest panel, (n - NB) x NB
+  double* cur = work;
+  double* nxt = work + (size_t)n * NB;
+  const size_t t00_off = (size_t)(n - NB) * NB;
+  for (int ks = 0; ks < n; ks += sb) {
+    // start of a super-block (its part of the matrix is up to date): the first diagonal block and panel as launches of
+    // their own, and tile (0, 0) of the first trailing matrix, as it is in A, for the replicas of the first step
+    const int remk = n - ks;
+    double* Akk = A + (long)ks + (long)ks * ld;
+    hipLaunchKernelGGL(potrf_diag_blk_kernel, dim3(1), dim3(256), 0, st, Akk, ld, remk < NB ? remk : NB, ks, info_dev, diag0,
+                       boost, max_boost);
+    if (remk <= NB) break;
+    hipLaunchKernelGGL(potrf_panel_mfma_kernel, dim3((remk - NB + 63) / 64), dim3(256), 0, st, Akk + NB, 1L, (long)ld,
+                       remk - NB, Akk, ld, NB, 0, cur, 1L, (long)(remk - NB), info_dev);
+    const int e0 = remk - NB < NB ? remk - NB : NB;
+    if (hipMemcpy2DAsync(cur + t00_off, (size_t)NB * 8, Akk + (long)NB + (long)NB * ld, (size_t)ld * 8, (size_t)e0 * 8, e0,
+                         hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return LRN_ERR_HIP;
+    const int ke = ks + sb < n ? ks + sb : n;                   // end of the super-block
+    for (int k0 = ks; k0 + NB < ke; k0 += NB) {
+      const int rem = n - k0 - NB;
       const int nt = (rem + NB - 1) / NB;
-      const int fuse = (!no_fuse && !diag_wave) ? 1 : 0;
-      hipLaunchKernelGGL(potrf_syrk_kernel, dim3(nt, nt), dim3(256), 0, st, A + (long)(k0 + nb) + (long)(k0 + nb) * ld, ld,
-                         rem, work, info_dev, fuse, k0 + nb, diag0, boost, max_boost);
-      diag_done = fuse != 0;
-      continue;
+      const int ntj = (ke - k0 - 1) / NB;                       // tile columns of the trailing matrix inside the super-block
+      hipLaunchKernelGGL(potrf_step_kernel, dim3(nt, ntj < nt ? ntj : nt), dim3(256), 0, st,
+                         A + (long)(k0 + NB) + (long)(k0 + NB) * ld, ld, rem, cur, nxt, cur + t00_off, nxt + t00_off,
+                         info_dev, k0 + NB, diag0, boost, max_boost);
+      std::swap(cur, nxt);
     }
-    GemmDesc u;
-    u.A = work; u.sAm = 1; u.sAk = rem;
-    u.B = work; u.sBk = rem; u.sBn = 1;
-    u.C = A + (long)(k0 + nb) + (long)(k0 + nb) * ld; u.sCm = 1; u.sCn = ld;
-    u.M = rem; u.N = rem; u.K = nb;
+    if (ke >= n) break;
+    GemmDesc u;                                                 // A[ke:, ke:] -= L[ke:, ks:ke] L[ke:, ks:ke]'  (lower tiles)
+    u.A = A + (long)ke + (long)ks * ld; u.sAm = 1; u.sAk = ld;
+    u.B = A + (long)ke + (long)ks * ld; u.sBk = ld; u.sBn = 1;
+    u.C = A + (long)ke + (long)ke * ld; u.sCm = 1; u.sCn = ld;
+    u.M = n - ke; u.N = n - ke; u.K = ke - ks;
     u.alpha = -1.0; u.beta = 1.0; u.flags = GEMM_TRI_LOWER;
-    rc = gemm(st, u);
-    if (rc) return rc;
+    const int rcg = gemm(st, u);
+    if (rcg) return rcg;
   }
-  (void)Linv;
   return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
 }
 
@@ -903,7 +580,6 @@ __device__ __forceinline__ void load_diag_block(const double* __restrict__ L, in
 // launch gaps; the right-hand side lives in LDS.
 static constexpr int POTRS_SMALL = 512;       // (above it the super-block kernels below win: n = 801 357 -> ~180 us)
 __global__ __launch_bounds__(1024) void potrs_small_kernel(const double* __restrict__ L, int ld, int n,
-                                                           const double* __restrict__ Linv,
                                                            const double* __restrict__ h, double* __restrict__ x) {
   __shared__ double r[POTRS_SMALL];
   __shared__ double lb[NB][NB + 1];
@@ -1167,11 +843,9 @@ __global__ __launch_bounds__(TRSV_T) void trsv_bwd_sb_kernel(const double* __res
 }
 
 // x = L^{-T} L^{-1} h ; r, y: scratch (n doubles each); h is read-only.
-int potrs_vec(hipStream_t st, const double* L, int n, int ld, const double* Linv, const double* h,
-              double* x, double* r, double* y) {
-  (void)Linv;
+int potrs_vec(hipStream_t st, const double* L, int n, int ld, const double* h, double* x, double* r, double* y) {
   if (n <= POTRS_SMALL) {
-    hipLaunchKernelGGL(potrs_small_kernel, dim3(1), dim3(1024), 0, st, L, ld, n, Linv, h, x);
+    hipLaunchKernelGGL(potrs_small_kernel, dim3(1), dim3(1024), 0, st, L, ld, n, h, x);
     return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
   }
   hipMemcpyAsync(r, h, (size_t)n * 8, hipMemcpyDeviceToDevice, st);
@@ -1194,24 +868,21 @@ int potrs_vec(hipStream_t st, const double* L, int n, int ld, const double* Linv
 // ------------------------------------------------------------------ triangular solves (matrix)
 // X = L^{-1} B  (trans=false)  or  X = L^{-T} B (trans=true); B (n x nrhs, ldb) overwritten.
 // tmp: NB x nrhs doubles.
-int trsm_left_lower(hipStream_t st, const double* L, int n, int ld, const double* Linv, bool trans,
-                    double* B, int nrhs, int ldb, double* tmp) {
-  (void)Linv;
+int trsm_left_lower(hipStream_t st, const double* L, int n, int ld, bool trans, double* B, int nrhs, int ldb,
+                    double* tmp) {
   int nblk = (n + NB - 1) / NB;
   for (int bi = 0; bi < nblk; ++bi) {
     int b = trans ? nblk - 1 - bi : bi;
     int k0 = b * NB, nb = n - k0 < NB ? n - k0 : NB;
-    // X_b = op(L_kk)^-1 B_b by substitution, one thread per right-hand side; tmp = X_b (NB x nrhs)
     // X_b = op(L_kk)^-1 B_b: per right-hand side a row of the strip solve x L_kk' = b (x L_kk = b for the transposed
-    // system); nrhs >= 16: by strips of 16 right-hand sides on the MFMA (round 3: the one-thread-per-column kernel walks
-    // 2016 dependent FMA / LDS pairs, 53 us per block at nrhs = 801), else one thread per right-hand side
-    static const bool trsm_thread = getenv("LRN_TRSM_THREAD") != nullptr;
-    if (nrhs >= 16 && !trsm_thread)
+    // system); nrhs >= 16: by strips of 16 right-hand sides on the MFMA (the one-thread-per-column kernel walks
+    // 2016 dependent FMA / LDS pairs, 53 us per block at nrhs = 801), else one thread per right-hand side; tmp = X_b (NB x nrhs)
+    if (nrhs >= 16)
       hipLaunchKernelGGL(potrf_panel_mfma_kernel, dim3((nrhs + 63) / 64), dim3(256), 0, st, B + k0, (long)ldb, 1L, nrhs,
                          L + (long)k0 + (long)k0 * ld, ld, nb, trans ? 1 : 0, tmp, (long)NB, 1L, (const int*)nullptr);
     else
-    hipLaunchKernelGGL(trsm_diag_kernel, dim3((nrhs + 255) / 256), dim3(256), 0, st,
-                       L + (long)k0 + (long)k0 * ld, ld, nb, trans ? 1 : 0, B + k0, ldb, nrhs, tmp);
+      hipLaunchKernelGGL(trsm_diag_kernel, dim3((nrhs + 255) / 256), dim3(256), 0, st,
+                         L + (long)k0 + (long)k0 * ld, ld, nb, trans ? 1 : 0, B + k0, ldb, nrhs, tmp);
     int rc;
     GemmDesc u;
     u.B = tmp; u.sBk = 1; u.sBn = NB;

@@ -163,8 +163,7 @@ struct lrn_ctx {
   // Schur complement
   lrn::DBuf H;          // assembled (lower triangle authoritative), nvar x nvar
   lrn::DBuf L;          // factor
-  lrn::DBuf Linv;       // inverse diagonal blocks
-  lrn::DBuf cholwork;   // nvar * NB
+  lrn::DBuf cholwork;   // workspace of the factorisation: chol_work_doubles(nvar)
   lrn::DBuf info_dev;   // int
   lrn::DBuf v0, v1, v2, v3;   // nvar-vectors (solve scratch)
   lrn::DBuf hdiag;            // diag(H) before the factorisation (pivot boosting)

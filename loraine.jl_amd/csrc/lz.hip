@@ -843,15 +843,14 @@ static int chol_shift_is_pd(lrn_ctx* c, const double* M, int n, double shift, bo
   hipStream_t st = c->stream;
   LRN_TRY(ensure(c, c->info_dev, 64));
   const size_t nn = (size_t)n * n;
-  LRN_TRY(ensure(c, c->ezbuf, (nn + (size_t)n * CHOL_NB + chol_linv_doubles(n) + 64) * 8));
+  LRN_TRY(ensure(c, c->ezbuf, (nn + chol_work_doubles(n) + 64) * 8));
   double* F = c->ezbuf.as<double>();
   double* work = F + nn;
-  double* linv = work + (size_t)n * CHOL_NB;
   int* info = c->info_dev.as<int>() + 8;
   LRN_HIP(c, hipMemcpyAsync(F, M, nn * 8, hipMemcpyDeviceToDevice, st));
   add_diag_mat(st, F, n, shift);
   LRN_HIP(c, hipMemsetAsync(info, 0, 4, st));
-  LRN_TRY(potrf_lower(st, F, n, n, linv, work, info));
+  LRN_TRY(potrf_lower(st, F, n, n, work, info));
   int h = 0;
   LRN_TRY(copy_out(c, &h, info, 4));
   *pd = h == 0;

@@ -97,9 +97,9 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   const int n = b.msz;
   const size_t mm = (size_t)n * n * 8;
   hipStream_t st = c->stream;
-  // workspace: LX, LS, CC/tmp, V, Y, Y2  (6 n^2) + Linv blocks x2 + chol / trsm work x2
-  size_t linv = chol_linv_doubles(n);
-  size_t need = (6 * (size_t)n * n + 2 * linv + 2 * ((size_t)n * CHOL_NB + (size_t)CHOL_NB * n) + 4 * (size_t)n) * 8;
+  // workspace: LX, LS, CC/tmp, V, Y, Y2  (6 n^2) + chol / trsm work x2 (one per stream)
+  const size_t cwd = chol_work_doubles(n);
+  size_t need = (6 * (size_t)n * n + 2 * (cwd + (size_t)CHOL_NB * n) + 4 * (size_t)n) * 8;
   LRN_TRY(ensure(c, c->scratch, need));
   double* LX = c->scratch.as<double>();
   double* LS = LX + (size_t)n * n;
@@ -107,12 +107,10 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   double* V = CC + (size_t)n * n;
   double* Y = V + (size_t)n * n;
   double* Y2 = Y + (size_t)n * n;
-  double* LinvX = Y2 + (size_t)n * n;
-  double* LinvS = LinvX + linv;
-  double* cw = LinvS + linv;              // n*NB
-  double* tw = cw + (size_t)n * CHOL_NB;  // NB*n
-  double* cw2 = tw + (size_t)CHOL_NB * n;
-  double* tw2 = cw2 + (size_t)n * CHOL_NB;
+  double* cw = Y2 + (size_t)n * n;        // cholesky(X)
+  double* tw = cw + cwd;                  // NB*n
+  double* cw2 = tw + (size_t)CHOL_NB * n; // cholesky(S): beside cholesky(X) with two streams
+  double* tw2 = cw2 + cwd;
   LRN_TRY(ensure(c, c->info_dev, 64));
   int* dinfo = c->info_dev.as<int>();
   int* dinfoS = dinfo + 12;
@@ -135,11 +133,11 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   // Cholesky of X (stream) and S (second stream)
   LRN_HIP(c, hipMemcpyAsync(LX, b.X.p, mm, hipMemcpyDeviceToDevice, st));
   LRN_HIP(c, hipMemsetAsync(dinfo, 0, 4, st));
-  LRN_TRY(potrf_lower(st, LX, n, n, LinvX, cw, dinfo));
+  LRN_TRY(potrf_lower(st, LX, n, n, cw, dinfo));
   hipLaunchKernelGGL(tril_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, LX, n);
   LRN_HIP(c, hipMemcpyAsync(LS, b.S.p, mm, hipMemcpyDeviceToDevice, s2));
   LRN_HIP(c, hipMemsetAsync(dinfoS, 0, 4, s2));
-  LRN_TRY(potrf_lower(s2, LS, n, n, LinvS, two ? cw2 : cw, dinfoS));
+  LRN_TRY(potrf_lower(s2, LS, n, n, cw2, dinfoS));
   hipLaunchKernelGGL(tril_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, LS, n);
   if (two) LRN_HIP(c, hipEventRecord(c->evB, s2));            // LS is final
   // the verdicts first, in the reference's order: X (prepare_W.jl:33), then S (:34) -- nothing else is queued on a failed
@@ -158,7 +156,7 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   struct S2Guard { hipStream_t s; bool on; ~S2Guard() { if (on) (void)hipStreamSynchronize(s); } } guard{s2, two};
   // Si = LS^-T LS^-1   (on the second stream: overlaps everything up to the end of this function)
   hipLaunchKernelGGL(eye_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, Y2, n);
-  LRN_TRY(trsm_left_lower(s2, LS, n, n, LinvS, false, Y2, n, n, two ? tw2 : tw));
+  LRN_TRY(trsm_left_lower(s2, LS, n, n, false, Y2, n, n, two ? tw2 : tw));
   LRN_TRY(gemm_nn(s2, n, Y2, true, Y2, false, b.Si.as<double>(), GEMM_TRI_LOWER));
   hipLaunchKernelGGL(mirror_lower_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, b.Si.as<double>(), n);
   // SVD of CC = LS' LX = U D V' by one-sided Jacobi on CC' = LX' LS: its columns are rotated by
@@ -187,7 +185,7 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
     LRN_HIP(c, hipStreamWaitEvent(s2, c->evA, 0));
   }
   hipLaunchKernelGGL(scale_cols_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, V, b.D.as<double>(), n, 1, Y);
-  LRN_TRY(trsm_left_lower(s2, LX, n, n, LinvX, true, Y, n, n, two ? tw2 : tw));
+  LRN_TRY(trsm_left_lower(s2, LX, n, n, true, Y, n, n, two ? tw2 : tw));
   hipLaunchKernelGGL(transpose_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(32, 8), 0, s2, Y, n, b.Gi.as<double>());
   // G = LX (V D^-1/2)
   hipLaunchKernelGGL(scale_cols_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, V, b.D.as<double>(), n, 0, CC);
@@ -626,13 +624,11 @@ int nt_factor(lrn_ctx* c, LmiBlock& b, int* info, double* minpiv) {
   b.chol_valid = false;
   LRN_TRY(ensure(c, b.LXf, mm));
   LRN_TRY(ensure(c, b.LSf, mm));
-  const size_t linv = chol_linv_doubles(n);
-  LRN_TRY(ensure(c, c->lxbuf, (2 * linv + 2 * (size_t)n * CHOL_NB + 16) * 8));
-  double* LinvX = c->lxbuf.as<double>();
-  double* LinvS = LinvX + linv;
-  double* cw = LinvS + linv;
-  double* cw2 = cw + (size_t)n * CHOL_NB;
-  double* piv = cw2 + (size_t)n * CHOL_NB;
+  const size_t cwd = chol_work_doubles(n);
+  LRN_TRY(ensure(c, c->lxbuf, (2 * cwd + 16) * 8));
+  double* cw = c->lxbuf.as<double>();      // cholesky(X)
+  double* cw2 = cw + cwd;                  // cholesky(S): beside cholesky(X) with two streams
+  double* piv = cw2 + cwd;
   LRN_TRY(ensure(c, c->info_dev, 64));
   int* dinfo = c->info_dev.as<int>();
   int* dinfoS = dinfo + 12;
@@ -652,12 +648,12 @@ int nt_factor(lrn_ctx* c, LmiBlock& b, int* info, double* minpiv) {
   tic(c);
   LRN_HIP(c, hipMemcpyAsync(LX, b.X.p, mm, hipMemcpyDeviceToDevice, st));
   LRN_HIP(c, hipMemsetAsync(dinfo, 0, 4, st));
-  LRN_TRY(potrf_lower(st, LX, n, n, LinvX, cw, dinfo));
+  LRN_TRY(potrf_lower(st, LX, n, n, cw, dinfo));
   hipLaunchKernelGGL(tril_kernel, dim3(ge), dim3(256), 0, st, LX, n);
   hipLaunchKernelGGL(min_pivot_kernel, dim3(1), dim3(256), 0, st, LX, n, piv);
   LRN_HIP(c, hipMemcpyAsync(LS, b.S.p, mm, hipMemcpyDeviceToDevice, s2));
   LRN_HIP(c, hipMemsetAsync(dinfoS, 0, 4, s2));
-  LRN_TRY(potrf_lower(s2, LS, n, n, LinvS, two ? cw2 : cw, dinfoS));
+  LRN_TRY(potrf_lower(s2, LS, n, n, cw2, dinfoS));
   hipLaunchKernelGGL(tril_kernel, dim3(ge), dim3(256), 0, s2, LS, n);
   hipLaunchKernelGGL(min_pivot_kernel, dim3(1), dim3(256), 0, s2, LS, n, piv + 1);
   // the verdicts, in the reference's order (prepare_W.jl:33-34)

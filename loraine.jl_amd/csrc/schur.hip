@@ -463,16 +463,14 @@ static int factor_w(lrn_ctx* c, LmiBlock& b, bool* ok) {
   const int m = b.msz;
   const long mm = (long)m * m;
   *ok = false;
-  const size_t linv = chol_linv_doubles(m);
-  LRN_TRY(ensure(c, c->wchol, (2 * (size_t)mm + linv + (size_t)m * CHOL_NB) * 8));
+  LRN_TRY(ensure(c, c->wchol, (2 * (size_t)mm + chol_work_doubles(m)) * 8));
   double* Lw = c->wchol.as<double>();
   double* Ut = Lw + mm;
-  double* Linv = Ut + mm;
-  double* cw = Linv + linv;
+  double* cw = Ut + mm;
   tic(c);
   LRN_HIP(c, hipMemcpyAsync(Lw, b.W.p, (size_t)mm * 8, hipMemcpyDeviceToDevice, c->stream));
   LRN_HIP(c, hipMemsetAsync(c->info_dev.p, 0, 8, c->stream));
-  LRN_TRY(potrf_lower(c->stream, Lw, m, m, Linv, cw, c->info_dev.as<int>()));
+  LRN_TRY(potrf_lower(c->stream, Lw, m, m, cw, c->info_dev.as<int>()));
   int h_info = 0;
   LRN_HIP(c, hipMemcpyAsync(&h_info, c->info_dev.p, 4, hipMemcpyDeviceToHost, c->stream));
   LRN_HIP(c, hipStreamSynchronize(c->stream));
@@ -1145,8 +1143,7 @@ int schur_factor(lrn_ctx* c, int* info) {
   const int n = c->nvar;
   size_t bytes = (size_t)n * n * 8;
   LRN_TRY(ensure(c, c->L, bytes));
-  LRN_TRY(ensure(c, c->Linv, chol_linv_doubles(n) * 8));
-  LRN_TRY(ensure(c, c->cholwork, (size_t)n * CHOL_NB * 8));
+  LRN_TRY(ensure(c, c->cholwork, chol_work_doubles(n) * 8));
   hipEvent_t a0, a1;
   if (c->profile) { (void)hipEventCreate(&a0); (void)hipEventCreate(&a1); (void)hipEventRecord(a0, c->stream); }
   // H is positive semidefinite by construction; late in a solve its smallest eigenvalues sink below the
@@ -1164,9 +1161,8 @@ int schur_factor(lrn_ctx* c, int* info) {
     if (attempt == 0)
       hipLaunchKernelGGL(get_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->H.as<double>(), n,
                          c->hdiag.as<double>());
-    LRN_TRY(potrf_lower_boost(c->stream, c->L.as<double>(), n, n, c->Linv.as<double>(), c->cholwork.as<double>(),
-                              c->info_dev.as<int>(), attempt == 0 ? c->hdiag.as<double>() : nullptr, c->opt.pivot_boost,
-                              std::max(8, n / 64)));
+    LRN_TRY(potrf_lower_boost(c->stream, c->L.as<double>(), n, n, c->cholwork.as<double>(), c->info_dev.as<int>(),
+                              attempt == 0 ? c->hdiag.as<double>() : nullptr, c->opt.pivot_boost, std::max(8, n / 64)));
     LRN_HIP(c, hipMemcpyAsync(h_two, c->info_dev.p, 8, hipMemcpyDeviceToHost, c->stream));
     LRN_HIP(c, hipStreamSynchronize(c->stream));
     if (h_two[0] == 0) break;
@@ -1196,8 +1192,8 @@ int schur_solve(lrn_ctx* c, const double* h, double* dely) {
   unsigned nb = (unsigned)((n + 255) / 256);
   // position space: hs[p] = h[sigma[p]]
   hipLaunchKernelGGL(gather_vec_kernel, dim3(nb), dim3(256), 0, c->stream, c->v0.as<double>(), sig, c->v1.as<double>(), n);
-  LRN_TRY(potrs_vec(c->stream, c->L.as<double>(), n, n, c->Linv.as<double>(), c->v1.as<double>(), c->v0.as<double>(),
-                    c->v2.as<double>(), c->v3.as<double>()));
+  LRN_TRY(potrs_vec(c->stream, c->L.as<double>(), n, n, c->v1.as<double>(), c->v0.as<double>(), c->v2.as<double>(),
+                    c->v3.as<double>()));
   hipLaunchKernelGGL(scatter_vec_kernel, dim3(nb), dim3(256), 0, c->stream, c->v0.as<double>(), sig, c->v1.as<double>(), n);
   if (c->profile) {
     (void)hipEventRecord(a1, c->stream);
