@@ -65,7 +65,9 @@ int lrn_upload_lowrank(lrn_ctx* ctx, int ilmi, int khat, const int64_t* V_colptr
  * comes from lrn_schur_assemble(mode 1).  LRN_ERR_STATE when no factors were uploaded or when the block's AA has any entry
  * (no constraint may be counted twice).  On a factored block lrn_get_constraint, lrn_matvec / lrn_matvec_partial,
  * lrn_prec_setup, lrn_pcg and modes 0 / -1 of lrn_schur_assemble return LRN_ERR_STATE.  on = 0 takes the declaration back.
- * lrn_get_count: "op_factored" / "op_dense" / "op_sparse" count the operator calls by route; "device_bytes",
+ * lrn_get_count: "op_factored" / "op_dense" / "op_sparse" count the operator calls by route, "op_dense_tri" /
+ * "op_dense_stream" / "op_dense_scalar" the passes over dense constraint data by tier (column tails of symmetric data /
+ * 16-byte loads over both triangles / one element per lane; the tier is decided when the model is uploaded); "device_bytes",
  * "device_bytes_peak" (device memory of this context now / at most) and "adense_bytes" (dense constraint slabs) are state. */
 int lrn_set_factored(lrn_ctx* ctx, int ilmi, int on);
 /* Builder-defined synthetic dense SDP data generated on the device:

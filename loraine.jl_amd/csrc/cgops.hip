@@ -1,11 +1,10 @@
-// CG operator, right-hand side, low-rank preconditioners and device-resident PCG.
-// Replaces MyA / MyM_no / MyM_beta / MyM, Prec_for_CG_beta, Prec_for_CG_tilS_prep,
-// prec_alpha_S! (reference src/Solvers.jl:572-904), makeRHS (src/makeBBBB.jl:221-228) and
-// cg of ConjugateGradients.jl 0.1 (call sites src/predictor_corrector.jl:134,235).
-//
-// Mat-vec  Ax = AA vec(W mat(AA' x) W):  AA' x is a deterministic gather over the stored
-// columns of AA (no atomics), the two msz^3 products run on the FP64 MFMA GEMM, AA vec(.)
-// is one wavefront per constraint.  All vectors live in natural constraint order.
+// The CG recurrence, the low-rank preconditioners and the device-resident PCG.
+// Replaces MyM_no / MyM_beta / MyM, Prec_for_CG_beta, Prec_for_CG_tilS_prep, prec_alpha_S! (reference
+// src/Solvers.jl:572-904) and cg of ConjugateGradients.jl 0.1 (call sites src/predictor_corrector.jl:134,235).
+// This file holds: Prec and symv_rows_kernel, the CG kernels, prec_setup / prec_apply / prec_dense_*, the operator
+// selection (op_select, op_apply), pcg_dev and the extern "C" entry points (lrn_matvec, lrn_matvec_partial, lrn_make_rhs,
+// lrn_prec_*, lrn_pcg).  The operator itself -- MyA, Ax = AA vec(W mat(AA' x) W) -- and every other pass over the
+// constraint data live in dataops.hip.
 //
 // H_alpha apply uses the algebraically identical "ts" form of the SMW formula:
 //   ts = D^-1/2 AA (U (x) Z)   (nvar x k*msz, built once per IP iteration)
@@ -75,35 +74,6 @@ __global__ __launch_bounds__(256) void symv_rows_kernel(const double* __restrict
   }
 }
 
-__global__ void eye_fill_kernel(double* __restrict__ V, int n) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x)
-    V[e] = (e % n == e / n) ? 1.0 : 0.0;
-}
-
-__global__ void transpose_sq_kernel(const double* __restrict__ A, int n, double* __restrict__ B) {
-  __shared__ double tile[32][33];
-  int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-  for (int r = threadIdx.y; r < 32; r += 8) {
-    int i = bx + threadIdx.x, j = by + r;
-    if (i < n && j < n) tile[r][threadIdx.x] = A[(long)i + (long)j * n];
-  }
-  __syncthreads();
-  for (int r = threadIdx.y; r < 32; r += 8) {
-    int i = by + threadIdx.x, j = bx + r;
-    if (i < n && j < n) B[(long)i + (long)j * n] = tile[threadIdx.x][r];
-  }
-}
-
-// lower triangle -> full symmetric (in place)
-__global__ void mirror_lower_full_kernel(double* __restrict__ A, int n) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    int i = (int)(e % n), j = (int)(e / n);
-    if (i < j) A[e] = A[(long)j + (long)i * n];
-  }
-}
-
 void prec_free(lrn_ctx* c) {
   if (!c->prec) return;
   Prec* p = c->prec;
@@ -112,1265 +82,6 @@ void prec_free(lrn_ctx* c) {
     release(*d);
   delete p;
   c->prec = nullptr;
-}
-
-static inline unsigned nb(long n, long cap = 4096) {
-  long b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-// ------------------------------------------------------------------ AA' x  and  AA vec(Z)
-// M[q] = sum_k cq_v[k] * x[cq_j[k]] over the stored columns of AA (sparse constraints):
-// one wavefront per stored column (a column can hold one entry per constraint -- e.g. the
-// shared corner of thetaG11's 1600 edge blocks), fixed lane partition -> deterministic.
-__global__ __launch_bounds__(256) void aat_gather_kernel(const long* __restrict__ cq_q, const long* __restrict__ cq_ptr,
-                                                         const int* __restrict__ cq_j, const double* __restrict__ cq_v,
-                                                         long ncq, const double* __restrict__ x, double* __restrict__ M) {
-  const int lane = threadIdx.x & 63;
-  const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= ncq) return;
-  double s = 0.0;
-  for (long k = cq_ptr[t] + lane; k < cq_ptr[t + 1]; k += 64) s += cq_v[k] * x[cq_j[k]];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) M[cq_q[t]] = s;
-}
-
-// M[q] -= sum_{p<nd} x[sigma[p]] * Adense[p][q]
-__global__ void aat_dense_kernel(const double* __restrict__ Ad, int nd, long mm, const int* __restrict__ sigma,
-                                 const double* __restrict__ x, double* __restrict__ M) {
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < mm; q += (long)gridDim.x * blockDim.x) {
-    double s = 0.0;
-    for (int p = 0; p < nd; ++p) s += x[sigma[p]] * Ad[(long)p * mm + q];
-    M[q] -= s;
-  }
-}
-
-// mat(): (M + M')/2 in place  (kron_etc.jl:13-18)
-__global__ void symmetrize_kernel(double* __restrict__ M, int n) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    int i = (int)(e % n), j = (int)(e / n);
-    if (i < j) {
-      double a = M[e], b = M[(long)j + (long)i * n];
-      double s = (a + b) / 2.0;
-      M[e] = s;
-      M[(long)j + (long)i * n] = s;
-    }
-  }
-}
-
-// the same by 32 x 32 tile pairs (both accesses coalesced; the element-wise kernel above reads M' with stride n: 2 ms at
-// msz 10^4 against 0.7): tile (bi, bj), bi >= bj, and its mirror image are averaged and written back together
-__global__ __launch_bounds__(256) void symmetrize_tiled_kernel(double* __restrict__ M, int n) {
-  __shared__ double ta[32][33], tb[32][33];
-  const int nt = (n + 31) / 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (long t = blockIdx.x; t < (long)nt * nt; t += gridDim.x) {
-    const int ti = (int)(t % nt), tj = (int)(t / nt);
-    if (ti < tj) continue;
-    const int bi = ti * 32, bj = tj * 32;
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int i = bi + tx, j = bj + r;       // tile (bi, bj): element (i, j) -> ta[r][tx]
-      ta[r][tx] = (i < n && j < n) ? M[(long)i + (long)j * n] : 0.0;
-      const int i2 = bj + tx, j2 = bi + r;     // tile (bj, bi): element (i2, j2) -> tb[r][tx]
-      tb[r][tx] = (i2 < n && j2 < n) ? M[(long)i2 + (long)j2 * n] : 0.0;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int i = bi + tx, j = bj + r;
-      if (i < n && j < n && i != j) {
-        const double a = ta[r][tx], b = tb[tx][r];          // M[i,j], M[j,i]
-        M[(long)i + (long)j * n] = (i > j ? a + b : b + a) / 2.0;        // (the pair adds in the order of the lower element first, as symmetrize_kernel)
-      }
-      if (ti != tj) {
-        const int i2 = bj + tx, j2 = bi + r;
-        if (i2 < n && j2 < n) {
-          const double a = tb[r][tx], b = ta[tx][r];        // M[i2,j2] (upper), M[j2,i2] (lower)
-          M[(long)i2 + (long)j2 * n] = (b + a) / 2.0;
-        }
-      }
-    }
-  }
-}
-
-static void symmetrize_dev(hipStream_t st, double* M, int n) {
-  const long total = (long)n * n;
-  if (n >= 512) {
-    const long nt = (n + 31) / 32;
-    hipLaunchKernelGGL(symmetrize_tiled_kernel, dim3((unsigned)std::min<long>(4096, nt * nt)), dim3(256), 0, st, M, n);
-  } else {
-    const long bl = (total + 255) / 256;
-    hipLaunchKernelGGL(symmetrize_kernel, dim3((unsigned)(bl < 1 ? 1 : (bl > 4096 ? 4096 : bl))), dim3(256), 0, st, M, n);
-  }
-}
-
-// out[sigma[p]] += -sum_e a_e Z[r_e,c_e]   (one wavefront per sparse position)
-__global__ __launch_bounds__(256) void aa_times_kernel(const long* __restrict__ ptr, const int* __restrict__ er,
-                                                       const int* __restrict__ ec, const double* __restrict__ ev,
-                                                       const double* __restrict__ Z, int msz, int p_lo, int p_end,
-                                                       const int* __restrict__ sigma, double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int p = p_lo + blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= p_end) return;
-  double s = 0.0;
-  for (long e = ptr[p] + lane; e < ptr[p + 1]; e += 64) s += ev[e] * Z[(long)er[e] + (long)ec[e] * msz];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) out[sigma[p]] -= s;
-}
-
-// out[sigma[p]] += -<Adense[p], Z>   (one workgroup per dense slot)
-__global__ __launch_bounds__(256) void aa_dense_dot_kernel(const double* __restrict__ Ad, long mm,
-                                                           const double* __restrict__ Z, const int* __restrict__ sigma,
-                                                           double* __restrict__ out) {
-  __shared__ double sh[4];
-  const double* a = Ad + (long)blockIdx.x * mm;
-  double s = 0.0;
-  for (long q = threadIdx.x; q < mm; q += 256) s += a[q] * Z[q];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[sigma[blockIdx.x]] -= sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// ---- the passes over the dense constraint data at sizes where they are HBM streams (C4: 4000 matrices of 32 MB; round 3).
-// The one-element-per-thread kernels above keep one 8-byte load per lane in flight and re-read Z from the MALL for every
-// constraint (5.1 TB/s of constraint data, 25 ms per pass).  Here: 16-byte loads, eight of them in flight per lane, and FOUR
-// constraints per workgroup against one read of Z.  msz even (16-byte alignment of every matrix); else the kernels above.
-typedef double v2f64 __attribute__((ext_vector_type(2)));
-
-__global__ __launch_bounds__(256) void aa_dense_dot4_kernel(const double* __restrict__ Ad, long mm, int nd,
-                                                            const double* __restrict__ Z, const int* __restrict__ sigma,
-                                                            double* __restrict__ out) {
-  __shared__ double sh[4][4];
-  const int p0 = blockIdx.x * 4;
-  const long n2 = mm >> 1;
-  const v2f64* z2 = reinterpret_cast<const v2f64*>(Z);
-  const v2f64* a2[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a2[k] = reinterpret_cast<const v2f64*>(Ad + (long)(p0 + k < nd ? p0 + k : p0) * mm);
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  long q = threadIdx.x;
-  for (; q + 256 < n2; q += 512) {
-    const v2f64 z0 = z2[q], z1 = z2[q + 256];
-    v2f64 a0[4], a1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { a0[k] = __builtin_nontemporal_load(a2[k] + q); a1[k] = __builtin_nontemporal_load(a2[k] + q + 256); }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] += (a0[k].x * z0.x + a0[k].y * z0.y) + (a1[k].x * z1.x + a1[k].y * z1.y);
-  }
-  for (; q < n2; q += 256) {
-    const v2f64 z0 = z2[q];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const v2f64 a = a2[k][q]; s[k] += a.x * z0.x + a.y * z0.y; }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_down(s[k], off, 64);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 && p0 + (int)threadIdx.x < nd) {
-    const int k = threadIdx.x;
-    out[sigma[p0 + k]] -= sh[k][0] + sh[k][1] + sh[k][2] + sh[k][3];
-  }
-}
-
-// two products in one pass (aa_times2)
-__global__ __launch_bounds__(256) void aa_dense_dot4x2_kernel(const double* __restrict__ Ad, long mm, int nd,
-                                                              const double* __restrict__ Z1, const double* __restrict__ Z2,
-                                                              const int* __restrict__ sigma, double* __restrict__ out1,
-                                                              double* __restrict__ out2) {
-  __shared__ double sh[8][4];
-  const int p0 = blockIdx.x * 4;
-  const long n2 = mm >> 1;
-  const v2f64* y2 = reinterpret_cast<const v2f64*>(Z1);
-  const v2f64* z2 = reinterpret_cast<const v2f64*>(Z2);
-  const v2f64* a2[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a2[k] = reinterpret_cast<const v2f64*>(Ad + (long)(p0 + k < nd ? p0 + k : p0) * mm);
-  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (long q = threadIdx.x; q < n2; q += 256) {
-    const v2f64 y0 = y2[q], z0 = z2[q];
-    v2f64 a[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = a2[k][q];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      s[k] += a[k].x * y0.x + a[k].y * y0.y;
-      s[4 + k] += a[k].x * z0.x + a[k].y * z0.y;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_down(s[k], off, 64);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 8 && p0 + (int)(threadIdx.x & 3) < nd) {
-    const int k = threadIdx.x;
-    const double v = sh[k][0] + sh[k][1] + sh[k][2] + sh[k][3];
-    if (k < 4) out1[sigma[p0 + k]] -= v;
-    else out2[sigma[p0 + k - 4]] -= v;
-  }
-}
-
-// M[q] -= sum_p x[sigma[p]] Adense[p][q], two entries per lane, eight matrices in flight
-__global__ __launch_bounds__(256) void aat_dense2_kernel(const double* __restrict__ Ad, int nd, long mm,
-                                                         const int* __restrict__ sigma, const double* __restrict__ x,
-                                                         double* __restrict__ M) {
-  const long n2 = mm >> 1;
-  const long q = (long)blockIdx.x * 256 + threadIdx.x;
-  if (q >= n2) return;
-  const v2f64* a2 = reinterpret_cast<const v2f64*>(Ad) + q;
-  v2f64 s0 = {0.0, 0.0}, s1 = {0.0, 0.0};
-  int p = 0;
-  for (; p + 8 <= nd; p += 8) {
-    v2f64 a[8];
-    double xs[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { a[k] = __builtin_nontemporal_load(a2 + (long)(p + k) * n2); xs[k] = x[sigma[p + k]]; }
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) { s0 += xs[k] * a[k]; s1 += xs[k + 1] * a[k + 1]; }
-  }
-  // (rotating the order of the matrices per group of workgroups -- eight addresses 32 MB apart meet the same DRAM banks --
-  // changes nothing: 23.5 ms per pass = 5.4 TB/s either way)
-  for (; p < nd; ++p) s0 += x[sigma[p]] * a2[(long)p * n2];
-  v2f64* m2 = reinterpret_cast<v2f64*>(M) + q;
-  *m2 -= s0 + s1;
-}
-
-// ---- round 4: the same passes over HALF the bytes.  Every A_k is symmetric, so <A_k, Z> = sum_{i>=j} A_k[i,j] w[i,j] with
-// w = Z + Z' below the diagonal, Z on it, and mat(AA'x) is the mirror image of its lower triangle.  Only the column tails
-// rows >= j of each matrix are streamed (they are contiguous in the column-major storage), cut into chunks of 64 x 16 bytes
-// = 128 rows listed in a table built once per matrix side (TriChunk; the tails start at j rounded down to 16 rows so that
-// every chunk is 128-byte aligned: 0.8 % of over-read at msz 2000, covered by zero weights / masked stores).  One wave per
-// chunk; the workgroup's four chunks are consecutive in the table, i.e. mostly one contiguous 4 KB piece of a column.
-struct TriChunk { long off; int col; int nv2; };      // first element (doubles), column, valid 16-byte pairs (<= 64)
-
-// w = tri-weights of Z: Z + Z' strictly below the diagonal, Z on it, zero above
-__global__ void tri_weights_kernel(const double* __restrict__ Z, int n, double* __restrict__ Wt) {
-  __shared__ double tile[32][33];
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;      // output tile rows bx.., columns by..
-  if (bx + 31 < by) {                                          // entirely above the diagonal
-    for (int r = threadIdx.y; r < 32; r += 8) {
-      const int i = bx + threadIdx.x, j = by + r;
-      if (i < n && j < n) Wt[(long)i + (long)j * n] = 0.0;
-    }
-    return;
-  }
-  for (int r = threadIdx.y; r < 32; r += 8) {                  // tile[r][t] = Z[by + t, bx + r]  (the transposed block)
-    const int i = by + threadIdx.x, j = bx + r;
-    if (i < n && j < n) tile[r][threadIdx.x] = Z[(long)i + (long)j * n];
-  }
-  __syncthreads();
-  for (int r = threadIdx.y; r < 32; r += 8) {
-    const int i = bx + threadIdx.x, j = by + r;
-    if (i < n && j < n) {
-      const double a = Z[(long)i + (long)j * n];
-      Wt[(long)i + (long)j * n] = i > j ? a + tile[threadIdx.x][r] : (i == j ? a : 0.0);
-    }
-  }
-}
-
-// upper triangle <- lower triangle
-__global__ void mirror_lower_tiled_kernel(double* __restrict__ A, int n) {
-  __shared__ double tile[32][33];
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;      // source tile rows bx.., columns by.. (on or below the diagonal)
-  if (bx < by) return;
-  for (int r = threadIdx.y; r < 32; r += 8) {
-    const int i = bx + threadIdx.x, j = by + r;
-    if (i < n && j < n) tile[r][threadIdx.x] = A[(long)i + (long)j * n];
-  }
-  __syncthreads();
-  for (int r = threadIdx.y; r < 32; r += 8) {
-    const int i = by + threadIdx.x, j = bx + r;              // destination (i, j) = transposed position
-    if (i < n && j < n && i < j) A[(long)i + (long)j * n] = tile[threadIdx.x][r];
-  }
-}
-
-// out[sigma[p]] -= <A_p, Z> for NZ weight matrices at once (NZ = 1, 2), four constraints per workgroup
-template <int NZ>
-__global__ __launch_bounds__(256) void aa_dense_tri_dot4_kernel(const double* __restrict__ Ad, long mm, int nd,
-                                                                const double* __restrict__ W1, const double* __restrict__ W2,
-                                                                const TriChunk* __restrict__ tab, int nch,
-                                                                const int* __restrict__ sigma, double* __restrict__ out1,
-                                                                double* __restrict__ out2) {
-  __shared__ double sh[4 * NZ][4];
-  const int p0 = blockIdx.x * 4;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const v2f64* a2[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a2[k] = reinterpret_cast<const v2f64*>(Ad + (long)(p0 + k < nd ? p0 + k : p0) * mm);
-  const v2f64* w1 = reinterpret_cast<const v2f64*>(W1);
-  const v2f64* w2 = reinterpret_cast<const v2f64*>(NZ > 1 ? W2 : W1);
-  double s[4 * NZ];
-#pragma unroll
-  for (int k = 0; k < 4 * NZ; ++k) s[k] = 0.0;
-  for (int ch = w; ch < nch; ch += 8) {
-    const TriChunk e0 = tab[ch];
-    const bool two = ch + 4 < nch;
-    const TriChunk e1 = tab[two ? ch + 4 : ch];
-    const bool v0 = lane < e0.nv2, v1 = two && lane < e1.nv2;
-    const long q0 = (e0.off >> 1) + (v0 ? lane : 0), q1 = (e1.off >> 1) + (v1 ? lane : 0);
-    v2f64 a0[4], a1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { a0[k] = __builtin_nontemporal_load(a2[k] + q0); a1[k] = __builtin_nontemporal_load(a2[k] + q1); }
-    v2f64 y0 = w1[q0], y1 = w1[q1];
-    if (!v0) y0 = (v2f64){0.0, 0.0};
-    if (!v1) y1 = (v2f64){0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] += (a0[k].x * y0.x + a0[k].y * y0.y) + (a1[k].x * y1.x + a1[k].y * y1.y);
-    if (NZ > 1) {
-      v2f64 z0 = w2[q0], z1 = w2[q1];
-      if (!v0) z0 = (v2f64){0.0, 0.0};
-      if (!v1) z1 = (v2f64){0.0, 0.0};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s[4 + k] += (a0[k].x * z0.x + a0[k].y * z0.y) + (a1[k].x * z1.x + a1[k].y * z1.y);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4 * NZ; ++k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_down(s[k], off, 64);
-    if (lane == 0) sh[k][w] = s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 * NZ && p0 + (int)(threadIdx.x & 3) < nd) {
-    const int k = threadIdx.x;
-    const double v = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
-    if (k < 4) out1[sigma[p0 + k]] -= v;
-    else out2[sigma[p0 + k - 4]] -= v;
-  }
-}
-
-// lower triangle of M -= sum_p x[sigma[p]] A_p: one wave per chunk, eight matrices in flight per lane
-__global__ __launch_bounds__(256) void aat_dense_tri_kernel(const double* __restrict__ Ad, int nd, long mm, int m,
-                                                            const int* __restrict__ sigma, const double* __restrict__ x,
-                                                            const TriChunk* __restrict__ tab, int nch, double* __restrict__ M) {
-  const int lane = threadIdx.x & 63;
-  const int ch = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (ch >= nch) return;
-  const TriChunk e = tab[ch];
-  if (lane >= e.nv2) return;
-  const long n2 = mm >> 1;
-  const v2f64* a2 = reinterpret_cast<const v2f64*>(Ad) + (e.off >> 1) + lane;
-  v2f64 s0 = {0.0, 0.0}, s1 = {0.0, 0.0};
-  int p = 0;
-  for (; p + 8 <= nd; p += 8) {
-    v2f64 a[8];
-    double xs[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { a[k] = __builtin_nontemporal_load(a2 + (long)(p + k) * n2); xs[k] = x[sigma[p + k]]; }
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) { s0 += xs[k] * a[k]; s1 += xs[k + 1] * a[k + 1]; }
-  }
-  for (; p < nd; ++p) s0 += x[sigma[p]] * a2[(long)p * n2];
-  const v2f64 t = s0 + s1;
-  double* mp = M + e.off + 2 * lane;
-  const int r = (int)(e.off - (long)e.col * m) + 2 * lane;      // row of the first element of the pair
-  if (r >= e.col) mp[0] -= t.x;
-  if (r + 1 >= e.col) mp[1] -= t.y;
-}
-
-// is every dense constraint matrix symmetric?  flag[0] = 1 when a pair differs
-__global__ __launch_bounds__(256) void dense_sym_check_kernel(const double* __restrict__ Ad, int m, int* __restrict__ flag) {
-  const double* A = Ad + (long)blockIdx.x * m * m;
-  bool bad = false;
-  for (long e = threadIdx.x; e < (long)m * m; e += 256) {
-    const int i = (int)(e % m), j = (int)(e / m);
-    if (i > j && A[e] != A[(long)j + (long)i * m]) bad = true;
-  }
-  if (bad) flag[0] = 1;
-}
-
-// row-sharded variants (multi-GPU mat-vec): only entries with r0 <= row < r1; Zg holds the rows
-// [r0,r1) of Z with leading dimension ldz
-__global__ __launch_bounds__(256) void aa_times_rows_kernel(const long* __restrict__ ptr, const int* __restrict__ er,
-                                                            const int* __restrict__ ec, const double* __restrict__ ev,
-                                                            const double* __restrict__ Zg, int ldz, int r0, int r1,
-                                                            int p_lo, int p_end, const int* __restrict__ sigma,
-                                                            double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int p = p_lo + blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= p_end) return;
-  double s = 0.0;
-  for (long e = ptr[p] + lane; e < ptr[p + 1]; e += 64) {
-    int r = er[e];
-    if (r >= r0 && r < r1) s += ev[e] * Zg[(long)(r - r0) + (long)ec[e] * ldz];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) out[sigma[p]] -= s;
-}
-
-__global__ __launch_bounds__(256) void aa_dense_dot_rows_kernel(const double* __restrict__ Ad, int m,
-                                                                const double* __restrict__ Zg, int ldz, int r0, int r1,
-                                                                const int* __restrict__ sigma, double* __restrict__ out) {
-  __shared__ double sh[4];
-  const double* a = Ad + (long)blockIdx.x * m * m;
-  const int nr = r1 - r0;
-  double s = 0.0;
-  for (long q = threadIdx.x; q < (long)nr * m; q += 256) {
-    int r = (int)(q % nr), cc = (int)(q / nr);
-    s += a[(long)(r0 + r) + (long)cc * m] * Zg[(long)r + (long)cc * ldz];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[sigma[blockIdx.x]] -= sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// linear block, two deterministic passes (no floating-point atomics):
-//   t_l = xs_l * sum_i C[i,l] x_i   (by column);   y_i += sum_l C[i,l] t_l   (by row, CSR built at upload)
-__global__ void lin_t_kernel(const long* __restrict__ ptr, const int* __restrict__ row, const double* __restrict__ val,
-                             const double* __restrict__ xs, int nlin, const double* __restrict__ x,
-                             double* __restrict__ tl) {
-  int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l >= nlin) return;
-  double t = 0.0;
-  for (long k = ptr[l]; k < ptr[l + 1]; ++k) t += val[k] * x[row[k]];
-  tl[l] = t * xs[l];
-}
-
-__global__ void lin_rows_kernel(const long* __restrict__ rptr, const int* __restrict__ rcol,
-                                const double* __restrict__ rval, const double* __restrict__ tl, int n,
-                                double* __restrict__ y) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = 0.0;
-  for (long k = rptr[i]; k < rptr[i + 1]; ++k) s += rval[k] * tl[rcol[k]];
-  y[i] += s;
-}
-
-// d_i += sum_l C[i,l]^2 xs_l
-__global__ void lin_diag_kernel(const long* __restrict__ rptr, const int* __restrict__ rcol,
-                                const double* __restrict__ rval, const double* __restrict__ xs, int n,
-                                double* __restrict__ d) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double s = 0.0;
-  for (long k = rptr[i]; k < rptr[i + 1]; ++k) s += rval[k] * rval[k] * xs[rcol[k]];
-  d[i] += s;
-}
-
-static int lin_matvec(lrn_ctx* c, const double* x, double* y) {
-  LRN_TRY(ensure(c, c->redbuf, (size_t)std::max(c->nlin, 64) * 8));
-  double* tl = c->redbuf.as<double>();
-  const unsigned gl = (unsigned)((c->nlin + 255) / 256), gn = (unsigned)((c->nvar + 255) / 256);
-  hipLaunchKernelGGL(lin_t_kernel, dim3(gl), dim3(256), 0, c->stream, c->cl_ptr.as<long>(), c->cl_rown.as<int>(),
-                     c->cl_val.as<double>(), c->lin_xs.as<double>(), c->nlin, x, tl);
-  hipLaunchKernelGGL(lin_rows_kernel, dim3(gn), dim3(256), 0, c->stream, c->cr_ptr.as<long>(), c->cr_col.as<int>(),
-                     c->cr_val.as<double>(), tl, c->nvar, y);
-  return LRN_OK;
-}
-
-
-// ------------------------------------------------------------------ sparse-aware mat-vec
-// When M = mat(AA'x) is sparse (every constraint sparse, e.g. C5: 9 nnz each, 18 per column of M),
-// AA vec(W M W) needs Z = W M W only on the pattern of M.  With N = M W  (N(:,q) = M W(:,q)):
-//   Z[p,q] = W(:,p) . N(:,q)        -- two contiguous columns
-// and N' = W M is a sparse combination of columns of W:  N'(:,r) = sum_s M[s,r] W(:,s).
-// 2 nnz(M) msz + nnz(M) msz flop instead of 4 msz^3; the kernels are bandwidth-bound (L2 / MALL).
-
-__global__ __launch_bounds__(256) void sp_gather_kernel(const long* __restrict__ cq_ptr, const int* __restrict__ cq_j,
-                                                        const double* __restrict__ cq_v, long ncq,
-                                                        const double* __restrict__ x, double* __restrict__ raw) {
-  const int lane = threadIdx.x & 63;
-  const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= ncq) return;
-  double s = 0.0;
-  for (long k = cq_ptr[t] + lane; k < cq_ptr[t + 1]; k += 64) s += cq_v[k] * x[cq_j[k]];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) raw[t] = s;
-}
-
-// mat(): (M + M')/2 on the pattern  (kron_etc.jl:13-18)
-__global__ void sp_symmetrize_kernel(const double* __restrict__ raw, const int* __restrict__ pc_t, long ncq,
-                                     double* __restrict__ Mv) {
-  long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < ncq) Mv[t] = (raw[t] + raw[pc_t[t]]) / 2.0;
-}
-
-// N[r, q] = sum_{t in column r of M} Mv[t] * W[q, row(t)]   for q in [q_lo, q_hi), all r.
-// One thread per q, 16 consecutive r per workgroup: W is read along q (coalesced 2 KB per stored
-// entry), N is written as 128 contiguous bytes per thread.  blockIdx.x walks r (fast) so that the
-// 256 rows of W a q-tile touches (msz * 2 KB) stay in L2 / MALL across the r-tiles.
-__global__ __launch_bounds__(256) void sp_wm_kernel(const long* __restrict__ pc_ptr, const int* __restrict__ pc_r,
-                                                    const double* __restrict__ Mv, const double* __restrict__ W, int m,
-                                                    int q_lo, int q_hi, double* __restrict__ N) {
-  const int q = q_lo + blockIdx.y * 256 + threadIdx.x;
-  const int r0 = blockIdx.x * 16;
-  const bool live = q < q_hi;
-  const double* wq = W + (live ? q : q_lo);
-  double acc[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int r = r0 + i;
-    if (r < m) {
-      const long t1 = pc_ptr[r + 1];
-      for (long t = pc_ptr[r]; t < t1; ++t) acc[i] += Mv[t] * wq[(long)pc_r[t] * m];
-    }
-  }
-  if (!live) return;
-  double* dst = N + (long)q * m + r0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-    if (r0 + i < m) dst[i] = acc[i];
-}
-
-// The same product with the q-tiles dealt to the XCDs (round 3).  Above, blockIdx.x walks the row tiles, so the eight XCDs
-// work on the SAME 256 columns of W at a time and each of their L2s misses on the whole 20 MB slab (msz 10^4): 10.8 GB of
-// L2-miss traffic per mat-vec for 0.8 GB of W.  Here XCD x = blockIdx.x % 8 sweeps all row tiles of q-tile 8 (j / R) + x,
-// j = blockIdx.x / 8, 64 columns wide: the 64 x msz slab (5 MB) it gathers from -- every row 36 times at C5 -- stays in its
-// own L2.  One wave per 4 rows r, lanes over q (512-byte segments of W).
-__global__ __launch_bounds__(256) void sp_wm_xcd_kernel(const long* __restrict__ pc_ptr, const int* __restrict__ pc_r,
-                                                        const double* __restrict__ Mv, const double* __restrict__ W, int m,
-                                                        int q_lo, int q_hi, double* __restrict__ N) {
-  const int R = (m + 15) / 16, Q = (q_hi - q_lo + 63) / 64;
-  const int xcd = blockIdx.x & 7;
-  const long j = blockIdx.x >> 3;
-  const int qt = 8 * (int)(j / R) + xcd, rt = (int)(j % R);
-  if (qt >= Q) return;
-  const int lane = threadIdx.x & 63;
-  const int g = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int q = q_lo + qt * 64 + lane;
-  const bool live = q < q_hi;
-  const double* wq = W + (live ? q : q_lo);
-  const int r0 = rt * 16 + 4 * g;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = r0 + i;
-    if (r >= m) break;
-    const long t0 = pc_ptr[r], t1 = pc_ptr[r + 1];
-    for (long t = t0; t < t1; t += 4) {
-      double w[4], v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const bool ok = t + k < t1;
-        v[k] = ok ? Mv[t + k] : 0.0;
-        w[k] = wq[(long)pc_r[ok ? t + k : t] * m];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc[i] += v[k] * w[k];
-    }
-  }
-  if (!live) return;
-  double* dst = N + (long)q * m + r0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (r0 + i < m) dst[i] = acc[i];
-}
-
-// Zs[t] = W(:,p_t) . N(:,q_t) for the stored entries of pattern column q (one workgroup per column);
-// mirror: only p <= q is computed and copied to the transposed entry (Z is symmetric).
-__global__ __launch_bounds__(256) void sp_dot_kernel(const long* __restrict__ pc_ptr, const int* __restrict__ pc_r,
-                                                     const int* __restrict__ pc_t, const double* __restrict__ W,
-                                                     const double* __restrict__ N, int m, int q_lo, int mirror,
-                                                     double* __restrict__ Zs) {
-  __shared__ double sh[4];
-  const int q = q_lo + blockIdx.x;
-  const double* nq = N + (long)q * m;
-  const long t1 = pc_ptr[q + 1];
-  for (long t = pc_ptr[q]; t < t1; ++t) {
-    const int p = pc_r[t];
-    if (mirror && p > q) break;                 // rows ascending within a column
-    const double* wp = W + (long)p * m;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < m; i += 256) s += wp[i] * nq[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = sh[0] + sh[1] + sh[2] + sh[3];
-      Zs[t] = v;
-      if (mirror && p != q) Zs[pc_t[t]] = v;
-    }
-  }
-}
-
-// ---- the same operator for matrices that sit in L2 (msz < 1500: thetaG11, msz 801, 3 % of the entries of M stored) --
-// round 3.  There the dense route costs two msz^3 products and three passes over msz^2 (97 us per mat-vec at msz 801)
-// for 2 x 2 nnz(M) msz flop of useful work, and the kernels above -- one workgroup per column with a block reduction per
-// entry -- are bound by their serial loops.  Here: the gather and the symmetrisation in one launch (one thread per stored
-// entry, both halves of (M + M') / 2), and ONE WAVE per stored entry for Z[p, q] = W(:, p) . N(:, q).
-__global__ __launch_bounds__(256) void sp_gather_sym_kernel(const long* __restrict__ cq_ptr, const int* __restrict__ cq_j,
-                                                            const double* __restrict__ cq_v, const int* __restrict__ pc_t,
-                                                            long ncq, const double* __restrict__ x, double* __restrict__ Mv) {
-  // one wave per stored entry (a position can be shared by every constraint: thetaG11's corner entry by 1600)
-  const int lane = threadIdx.x & 63;
-  const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= ncq) return;
-  const long u = pc_t[t];
-  double a = 0.0, b = 0.0;
-  for (long k = cq_ptr[t] + lane; k < cq_ptr[t + 1]; k += 64) a += cq_v[k] * x[cq_j[k]];
-  if (u != t)
-    for (long k = cq_ptr[u] + lane; k < cq_ptr[u + 1]; k += 64) b += cq_v[k] * x[cq_j[k]];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
-  // (raw[t] + raw[twin]) / 2 in a fixed order: the twins get the same bits
-  if (lane == 0) Mv[t] = (u == t) ? (a + a) / 2.0 : (t < u ? a + b : b + a) / 2.0;
-}
-
-// N[r, q] for 4 consecutive r per workgroup, one thread per q; the W values of up to 8 stored entries are requested
-// before they are used (one workgroup per CU at this size: nothing else hides the L2 latency).  Columns with more than
-// SP_LONG stored entries (thetaG11: one column of 801 among columns of 7) are left to sp_wm_long_kernel.
-static constexpr int SP_LONG = 64;
-__global__ __launch_bounds__(256) void sp_wm_small_kernel(const long* __restrict__ pc_ptr, const int* __restrict__ pc_r,
-                                                          const double* __restrict__ Mv, const double* __restrict__ W, int m,
-                                                          int q_lo, int q_hi, double* __restrict__ N) {
-  const int q = q_lo + blockIdx.y * 256 + threadIdx.x;
-  const int r0 = blockIdx.x * 4;
-  const bool live = q < q_hi;
-  const double* wq = W + (live ? q : q_lo);
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = r0 + i;
-    if (r >= m) break;
-    const long t0 = pc_ptr[r], t1 = pc_ptr[r + 1];
-    if (t1 - t0 > SP_LONG) continue;
-    for (long t = t0; t < t1; t += 8) {
-      double w[8], v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const bool ok = t + k < t1;
-        v[k] = ok ? Mv[t + k] : 0.0;
-        w[k] = wq[(long)pc_r[ok ? t + k : t] * m];
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) acc[i] += v[k] * w[k];
-    }
-  }
-  if (!live) return;
-  double* dst = N + (long)q * m + r0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (r0 + i < m) {
-      const long cnt = pc_ptr[r0 + i + 1] - pc_ptr[r0 + i];
-      if (cnt <= SP_LONG) dst[i] = acc[i];
-    }
-}
-
-// N[r, q] of a long column r: one wave per q, the lanes over the stored entries (W(:, q) read at the rows of the
-// entries -- ascending, nearly contiguous)
-__global__ __launch_bounds__(256) void sp_wm_long_kernel(const long* __restrict__ pc_ptr, const int* __restrict__ pc_r,
-                                                         const double* __restrict__ Mv, const double* __restrict__ W, int m,
-                                                         int r, int q_lo, int q_hi, double* __restrict__ N) {
-  const int lane = threadIdx.x & 63;
-  const int q = q_lo + blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= q_hi) return;
-  const double* wq = W + (long)q * m;
-  double s = 0.0;
-  for (long t = pc_ptr[r] + lane; t < pc_ptr[r + 1]; t += 64) s += Mv[t] * wq[pc_r[t]];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) N[(long)q * m + r] = s;
-}
-
-__global__ __launch_bounds__(256) void sp_dot_wave_kernel(const long* __restrict__ cq_q, const int* __restrict__ pc_t, long ncq,
-                                                          const double* __restrict__ W, const double* __restrict__ N, int m,
-                                                          int q_lo, int q_hi, int mirror, double* __restrict__ Zs) {
-  const int lane = threadIdx.x & 63;
-  const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= ncq) return;
-  const long key = cq_q[t];
-  const int q = (int)(key / m), p = (int)(key % m);
-  if (q < q_lo || q >= q_hi || (mirror && p > q)) return;
-  const double* wp = W + (long)p * m;
-  const double* nq = N + (long)q * m;
-  double s = 0.0;
-  for (int i = lane; i < m; i += 64) s += wp[i] * nq[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) {
-    Zs[t] = s;
-    if (mirror && p != q) Zs[pc_t[t]] = s;
-  }
-}
-
-// out[sigma[p]] -= sum_e a_e Zs[ent_t[e]]   (entries with column in [c_lo, c_hi))
-__global__ __launch_bounds__(256) void sp_aa_times_kernel(const long* __restrict__ ptr, const int* __restrict__ ec,
-                                                          const double* __restrict__ ev, const int* __restrict__ ent_t,
-                                                          const double* __restrict__ Zs, int c_lo, int c_hi, int p_end,
-                                                          const int* __restrict__ sigma, double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= p_end) return;
-  double s = 0.0;
-  for (long e = ptr[p] + lane; e < ptr[p + 1]; e += 64) {
-    const int cc = ec[e];
-    if (cc >= c_lo && cc < c_hi) s += ev[e] * Zs[ent_t[e]];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) out[sigma[p]] -= s;
-}
-
-// The half-traffic passes (column tails of the symmetric matrices): table of chunks, built once per block
-static int tri_table(lrn_ctx* c, LmiBlock& b) {
-  if (b.tri_nch > 0) return LRN_OK;
-  const int m = b.msz;
-  std::vector<TriChunk> tab;
-  for (int j = 0; j < m; ++j) {
-    const int r0 = j & ~15;
-    for (int r = r0; r < m; r += 128) tab.push_back({(long)j * m + r, j, std::min(64, (m - r) / 2)});
-  }
-  LRN_TRY(ensure(c, b.tri_tab, tab.size() * sizeof(TriChunk)));
-  LRN_TRY(copy_in(c, b.tri_tab.p, tab.data(), tab.size() * sizeof(TriChunk)));
-  b.tri_nch = (int)tab.size();
-  return LRN_OK;
-}
-
-// symmetric dense data (checked once on the device), msz even (16-byte pairs), enough data to be a stream
-static bool dense_tri_ok(lrn_ctx* c, LmiBlock& b) {
-  static const bool off = getenv("LRN_DENSE_PASS_FULL") != nullptr;       // (measurement: the round-3 kernels, both triangles)
-  if (off || b.nd <= 0 || (b.msz & 1) != 0 || b.msz < 256 || ((uintptr_t)b.Adense.p & 15) != 0) return false;
-  if (b.dense_sym < 0) {
-    if (ensure(c, c->info_dev, 64) != LRN_OK) return false;
-    (void)hipMemsetAsync(c->info_dev.p, 0, 4, c->stream);
-    hipLaunchKernelGGL(dense_sym_check_kernel, dim3(b.nd), dim3(256), 0, c->stream, b.Adense.as<double>(), b.msz,
-                       c->info_dev.as<int>());
-    int f = 1;
-    if (copy_out(c, &f, c->info_dev.p, 4) != LRN_OK) return false;
-    (void)hipMemsetAsync(c->info_dev.p, 0, 4, c->stream);
-    b.dense_sym = f == 0 ? 1 : 0;
-  }
-  return b.dense_sym == 1 && tri_table(c, b) == LRN_OK;
-}
-
-// w = tri-weights of Z into slot `which` of the block's weight workspace
-static int tri_weights(lrn_ctx* c, LmiBlock& b, const double* Z, int which, double** out) {
-  const int m = b.msz;
-  LRN_TRY(ensure(c, c->triw, (size_t)2 * m * m * 8));
-  double* Wt = c->triw.as<double>() + (size_t)which * m * m;
-  hipLaunchKernelGGL(tri_weights_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(32, 8), 0, c->stream, Z, m, Wt);
-  *out = Wt;
-  return LRN_OK;
-}
-
-// the 16-byte kernels of the dense passes: every matrix 16-byte aligned (msz even), enough data to be a stream
-static bool dense_stream_ok(const LmiBlock& b, const double* Z) {
-  static const bool off = getenv("LRN_DENSE_PASS_SCALAR") != nullptr;      // (measurement: the one-element-per-lane kernels)
-  return !off && (b.msz & 1) == 0 && b.msz >= 256 && (((uintptr_t)Z | (uintptr_t)b.Adense.p) & 15) == 0;
-}
-
-bool use_sparse_matvec(const lrn_ctx* c, const LmiBlock& b) {
-  if (b.factored) return false;        // (no stored column of AA to walk: the data are the factors)
-  if (!b.sp_ok || c->opt.matvec_sparse == 1) return false;
-  if (c->opt.matvec_sparse == 2) return true;
-  // ~4e-12 ncq msz s against 4 msz^3 / 6e13 s.  Below msz ~ 1500 both routes are bound by their launches and L2: the
-  // wave-per-entry kernels win where a twelfth of M or less is stored
-  if (b.msz < 1500)
-    return b.msz >= 256 && (double)b.ncq * 12.0 < (double)b.msz * (double)b.msz && b.sp_long_cols.size() <= 4;
-  return (double)b.ncq * 60.0 < (double)b.msz * (double)b.msz;
-}
-
-// y += AA vec(W mat(AA'x) W) restricted to the pattern columns [q_lo, q_hi) of Z
-static int matvec_sparse_block(lrn_ctx* c, LmiBlock& b, const double* x, double* y, int q_lo, int q_hi, bool mirror) {
-  const int m = b.msz;
-  hipStream_t st = c->stream;
-  LRN_TRY(ensure(c, c->m1, (size_t)m * m * 8));
-  double* N = c->m1.as<double>();
-  const bool small = m < 1500;        // W and N sit in L2: one wave per stored entry (see sp_dot_wave_kernel)
-  if (small) {
-    hipLaunchKernelGGL(sp_gather_sym_kernel, dim3((unsigned)((b.ncq + 3) / 4)), dim3(256), 0, st, b.cq_ptr.as<long>(),
-                       b.cq_j.as<int>(), b.cq_v.as<double>(), b.pc_t.as<int>(), b.ncq, x, b.Mv.as<double>());
-  } else {
-    hipLaunchKernelGGL(sp_gather_kernel, dim3((unsigned)((b.ncq + 3) / 4)), dim3(256), 0, st, b.cq_ptr.as<long>(),
-                       b.cq_j.as<int>(), b.cq_v.as<double>(), b.ncq, x, b.Zs.as<double>());
-    hipLaunchKernelGGL(sp_symmetrize_kernel, dim3((unsigned)((b.ncq + 255) / 256)), dim3(256), 0, st, b.Zs.as<double>(),
-                       b.pc_t.as<int>(), b.ncq, b.Mv.as<double>());
-  }
-  if (q_hi > q_lo) {
-    if (small) {
-      hipLaunchKernelGGL(sp_wm_small_kernel, dim3((m + 3) / 4, (q_hi - q_lo + 255) / 256), dim3(256), 0, st,
-                         b.pc_ptr.as<long>(), b.pc_r.as<int>(), b.Mv.as<double>(), b.W.as<double>(), m, q_lo, q_hi, N);
-      for (int r : b.sp_long_cols)
-        hipLaunchKernelGGL(sp_wm_long_kernel, dim3((q_hi - q_lo + 3) / 4), dim3(256), 0, st, b.pc_ptr.as<long>(),
-                           b.pc_r.as<int>(), b.Mv.as<double>(), b.W.as<double>(), m, r, q_lo, q_hi, N);
-    } else {
-      static const bool wm_plain = getenv("LRN_SP_WM_PLAIN") != nullptr;      // (measurement: the round-1 tiling)
-      const long R = (m + 15) / 16, Q8 = ((q_hi - q_lo + 63) / 64 + 7) / 8;
-      if (!wm_plain && 8 * Q8 * R < 0x7fffffffL)
-        hipLaunchKernelGGL(sp_wm_xcd_kernel, dim3((unsigned)(8 * Q8 * R)), dim3(256), 0, st, b.pc_ptr.as<long>(),
-                           b.pc_r.as<int>(), b.Mv.as<double>(), b.W.as<double>(), m, q_lo, q_hi, N);
-      else
-      hipLaunchKernelGGL(sp_wm_kernel, dim3((m + 15) / 16, (q_hi - q_lo + 255) / 256), dim3(256), 0, st, b.pc_ptr.as<long>(),
-                         b.pc_r.as<int>(), b.Mv.as<double>(), b.W.as<double>(), m, q_lo, q_hi, N);
-    }
-    // one wave per stored entry at every size (round 3; C5: 1.74 -> 1.16 ms -- the workgroup-per-column kernel exposes the
-    // HBM latency at each of its entries: a block reduction and two barriers between one 80 KB column of W and the next)
-    static const bool dot_wg = getenv("LRN_SP_DOT_WG") != nullptr;           // (measurement: the round-1 kernel)
-    if (small || !dot_wg)
-      hipLaunchKernelGGL(sp_dot_wave_kernel, dim3((unsigned)((b.ncq + 3) / 4)), dim3(256), 0, st, b.cq_q.as<long>(),
-                         b.pc_t.as<int>(), b.ncq, b.W.as<double>(), N, m, q_lo, q_hi, mirror ? 1 : 0, b.Zs.as<double>());
-    else
-      hipLaunchKernelGGL(sp_dot_kernel, dim3(q_hi - q_lo), dim3(256), 0, st, b.pc_ptr.as<long>(), b.pc_r.as<int>(),
-                         b.pc_t.as<int>(), b.W.as<double>(), N, m, q_lo, mirror ? 1 : 0, b.Zs.as<double>());
-    hipLaunchKernelGGL(sp_aa_times_kernel, dim3((b.npos_nz + 3) / 4), dim3(256), 0, st, b.ent_ptr.as<long>(),
-                       b.ent_c.as<int>(), b.ent_v.as<double>(), b.ent_t.as<int>(), b.Zs.as<double>(), q_lo, q_hi, b.npos_nz,
-                       b.sigma_d.as<int>(), y);
-  }
-  return LRN_OK;
-}
-
-__global__ void vec_add_kernel(double* __restrict__ y, const double* __restrict__ t, long n) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) y[e] += t[e];
-}
-
-// multi-GPU: are the passes over the dense constraint matrices split over the ranks?  (communicator present, enough dense
-// constraints for every rank; option "shard_passes" = 0 keeps them replicated)
-static bool dense_passes_sharded(lrn_ctx* c, const LmiBlock& b) {
-  return c->comm && c->world > 1 && c->opt.shard_passes != 0 && b.nd >= 8 * c->world;
-}
-
-int wmw(lrn_ctx* c, LmiBlock& b, double* M, double* P, double* Z) {
-  const int m = b.msz;
-  if (products_sharded(c, c->stream, m)) {      // P = W M' (M symmetric), Z = P W' (W symmetric): column blocks + all-gather
-    LRN_TRY(pgemm_nt(c, c->stream, m, b.W.as<double>(), M, P));
-    return pgemm_nt_sym(c, c->stream, m, P, b.W.as<double>(), Z);
-  }
-  GemmDesc g1;     // P = W M   (M symmetric: read as M[n + k*m] -> direct-to-LDS path)
-  g1.A = b.W.as<double>(); g1.sAm = 1; g1.sAk = m;
-  g1.B = M; g1.sBk = m; g1.sBn = 1;
-  g1.C = P; g1.sCm = 1; g1.sCn = m;
-  g1.M = g1.N = g1.K = m;
-  LRN_TRY(gemm(c->stream, g1));
-  if (m >= 1500) return gemm_nt_sym(c->stream, m, P, b.W.as<double>(), Z);      // Z = P W symmetric: lower tiles + mirror
-  GemmDesc g2;     // Z = P W   (W symmetric)
-  g2.A = P; g2.sAm = 1; g2.sAk = m;
-  g2.B = b.W.as<double>(); g2.sBk = m; g2.sBn = 1;
-  g2.C = Z; g2.sCm = 1; g2.sCn = m;
-  g2.M = g2.N = g2.K = m;
-  return gemm(c->stream, g2);
-}
-
-// AA vec(W M W) for a dense symmetric M when every constraint of the block is sparse (C5: 9 entries each): the entries
-// of Z = W M W are needed on the pattern of the constraints only -- N = M W is one product, Z[p,q] = W(:,p) . N(:,q) one
-// wave per stored entry (the kernels of the pattern-restricted CG operator above) -- instead of the second n^3 product.
-bool wmw_pattern_ok(const lrn_ctx* c, const LmiBlock& b) {
-  return !b.factored && b.sp_ok && b.nd == 0 && b.msz >= c->opt.wmw_pattern_min && b.have_W;
-}
-
-int aa_times_wmw_pattern(lrn_ctx* c, LmiBlock& b, const double* M, double* N, double* y) {
-  const int m = b.msz;
-  LRN_TRY(pgemm_nt(c, c->stream, m, M, b.W.as<double>(), N));                   // N = M W' = M W
-  hipLaunchKernelGGL(sp_dot_wave_kernel, dim3((unsigned)((b.ncq + 3) / 4)), dim3(256), 0, c->stream, b.cq_q.as<long>(),
-                     b.pc_t.as<int>(), b.ncq, b.W.as<double>(), N, m, 0, m, 1, b.Zs.as<double>());
-  hipLaunchKernelGGL(sp_aa_times_kernel, dim3((b.npos_nz + 3) / 4), dim3(256), 0, c->stream, b.ent_ptr.as<long>(),
-                     b.ent_c.as<int>(), b.ent_v.as<double>(), b.ent_t.as<int>(), b.Zs.as<double>(), 0, m, b.npos_nz,
-                     b.sigma_d.as<int>(), y);
-  return LRN_OK;
-}
-
-int ensure_m(lrn_ctx* c, int m) {
-  size_t mm = (size_t)m * m * 8;
-  LRN_TRY(ensure(c, c->m0, mm));
-  LRN_TRY(ensure(c, c->m1, mm));
-  LRN_TRY(ensure(c, c->m2, mm));
-  return LRN_OK;
-}
-
-// ---- factor form of the two data operators (factored blocks, lrn_set_factored): A_k = V_k diag(d_k) V_k' exists only as the
-// dense factor matrix Vd (msz x R, R = nvar khat, column h khat + p = column p of the constraint with H index h) and the
-// weights w (d, 0 in the padding).  With AA = -A:
-//     (AA vec(Z))_k = -sum_p w_kp v_kp' Z v_kp          Q = Z Vd by one FP64 MFMA product, then per column <Q_c, Vd_c>
-//     mat(AA' x)    = -Vd diag(w o (x (x) 1_khat)) Vd'   columns scaled into a workspace, one lower-triangle product, mirrored
-// Q and the scaled copy live in the BG workspace (msz x R, what the mode-1 assembly uses for U).  Every sum has a fixed
-// order: one wave per constraint walks its khat columns in order, lanes stride the rows, one shuffle tree -- no atomics.
-
-// out[nat(h)] -= sum_p w[h kh + p] <Q(:, h kh + p), Vd(:, h kh + p)>   (sigma: H index -> constraint, null = identity)
-__global__ __launch_bounds__(256) void fac_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Vd,
-                                                         const double* __restrict__ w, int m, int kh, int nvar,
-                                                         const int* __restrict__ sigma, double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (h >= nvar) return;
-  double s = 0.0;
-  for (int p = 0; p < kh; ++p) {
-    const long col = (long)h * kh + p;
-    const double wp = w[col];
-    if (wp == 0.0) continue;                       // padding column (wave-uniform)
-    const double* __restrict__ q = Q + col * m;
-    const double* __restrict__ v = Vd + col * m;
-    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-    int r = lane;
-    for (; r + 192 < m; r += 256) {
-      t0 += q[r] * v[r];
-      t1 += q[r + 64] * v[r + 64];
-      t2 += q[r + 128] * v[r + 128];
-      t3 += q[r + 192] * v[r + 192];
-    }
-    for (; r < m; r += 64) t0 += q[r] * v[r];
-    s += wp * ((t0 + t1) + (t2 + t3));
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) out[sigma ? sigma[h] : h] -= s;
-}
-
-// Vs(:, c) = -w[c] x[nat(c / kh)] Vd(:, c)   (one workgroup per factor column)
-__global__ __launch_bounds__(256) void fac_scale_kernel(const double* __restrict__ Vd, const double* __restrict__ w,
-                                                        const double* __restrict__ x, const int* __restrict__ sigma, int m,
-                                                        int kh, double* __restrict__ Vs) {
-  const long col = blockIdx.x;
-  const int h = (int)(col / kh);
-  const double sc = -(w[col] * x[sigma ? sigma[h] : h]);
-  const double* __restrict__ v = Vd + col * m;
-  double* __restrict__ o = Vs + col * m;
-  for (int r = threadIdx.x; r < m; r += 256) o[r] = sc * v[r];
-}
-
-static int fac_workspace(lrn_ctx* c, LmiBlock& b, double** ws) {
-  if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
-  LRN_TRY(ensure(c, c->BG, (size_t)b.msz * (size_t)c->nvar * b.lr_khat * 8));
-  *ws = c->BG.as<double>();
-  return LRN_OK;
-}
-
-// y += AA vec(Z), Z symmetric
-static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
-  const int m = b.msz, kh = b.lr_khat;
-  const long R = (long)c->nvar * kh;
-  double* Q = nullptr;
-  LRN_TRY(fac_workspace(c, b, &Q));
-  GemmDesc g;     // Q = Z Vd, msz x R
-  g.A = Z; g.sAm = 1; g.sAk = m;
-  g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
-  g.C = Q; g.sCm = 1; g.sCn = m;
-  g.M = m; g.N = (int)R; g.K = m;
-  LRN_TRY(gemm(c->stream, g));
-  hipLaunchKernelGGL(fac_coldot_kernel, dim3((c->nvar + 3) / 4), dim3(256), 0, c->stream, Q, b.Vd.as<double>(),
-                     b.v_w.as<double>(), m, kh, c->nvar, c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, y);
-  c->counts["op_factored"] += 1;
-  return LRN_OK;
-}
-
-// M = mat(AA' x), exactly symmetric
-static int aat_to_mat_factored(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
-  const int m = b.msz, kh = b.lr_khat;
-  const long R = (long)c->nvar * kh;
-  double* Vs = nullptr;
-  LRN_TRY(fac_workspace(c, b, &Vs));
-  hipLaunchKernelGGL(fac_scale_kernel, dim3((unsigned)R), dim3(256), 0, c->stream, b.Vd.as<double>(), b.v_w.as<double>(), x,
-                     c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, m, kh, Vs);
-  GemmDesc g;     // M = Vs Vd', the tiles on and below the diagonal
-  g.A = Vs; g.sAm = 1; g.sAk = m;
-  g.B = b.Vd.as<double>(); g.sBk = m; g.sBn = 1;
-  g.C = M; g.sCm = 1; g.sCn = m;
-  g.M = m; g.N = m; g.K = (int)R;
-  g.flags = GEMM_TRI_LOWER;
-  // From 16 x 16 128-tiles on gemm() no longer splits K by itself, but the lower triangle alone (msz 2000: 136 tiles on 512
-  // workgroup slots) leaves most of the chip idle over a long K = R.  K is cut into ks equal parts run as a BATCH of the
-  // same kernel into ks slabs, added in a fixed order.  ks by the round model of gemm_f64.hip (1.85 us per K-step of a
-  // round of 512 workgroups, 1.25 / 2 for a round of up to 256 / 512) plus the pass over the slabs.
-  const long tm = (m + 127) / 128, tiles = tm * (tm + 1) / 2;
-  int ks = 1;
-  static const int forced = getenv("LRN_FAC_SPLIT") ? atoi(getenv("LRN_FAC_SPLIT")) : 0;      // (measurement: ks, 1 = none)
-  if (forced >= 1 && forced <= 16 && R % forced == 0) ks = forced;
-  else if (tm * tm >= 256 && tiles < 512) {
-    double best = 1e300;
-    for (int k : {1, 2, 3, 4, 5, 6, 8}) {
-      if (R % k || (k > 1 && R / k < 512)) continue;
-      const long wg = tiles * k, rem = wg % 512;
-      const double rounds = 2.0 * (double)(wg / 512) + (rem == 0 ? 0.0 : (rem <= 256 ? 1.25 : 2.0));
-      const double us = (double)(R / k) / 16.0 * 1.85 * rounds + (k > 1 ? 5.0 + (double)(k + 1) * m * (double)m * 8.0 / 4.0e6 : 0.0);
-      if (us < best) { best = us; ks = k; }
-    }
-  }
-  if (ks > 1) {
-    const long mm = (long)m * m;
-    LRN_TRY(ensure(c, c->slabs, (size_t)ks * mm * 8));
-    g.C = c->slabs.as<double>();
-    g.K = (int)(R / ks);
-    g.batch = ks;
-    g.bA = (long)(R / ks) * m; g.bB = (long)(R / ks) * m; g.bC = mm;
-    LRN_TRY(gemm(c->stream, g));
-    LRN_TRY(reduce_slabs(c->stream, c->slabs.as<double>(), mm, ks, M, mm, 0.0));
-  } else {
-    LRN_TRY(gemm(c->stream, g));
-  }
-  hipLaunchKernelGGL(mirror_lower_tiled_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(32, 8), 0, c->stream, M, m);
-  c->counts["op_factored"] += 1;
-  return LRN_OK;
-}
-
-// option "profile_ops": one data operator between two events of its own (the phases of the resident loop -- "rhs",
-// "residual_d", "find_step" -- contain other products as well)
-struct OpTimer {
-  lrn_ctx* c;
-  const char* key;
-  hipEvent_t a = nullptr, b = nullptr;
-  OpTimer(lrn_ctx* c_, const char* key_) : c(c_), key(key_) {
-    if (!c->opt.profile_ops) return;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = nullptr; return; }
-    (void)hipEventRecord(a, c->stream);
-  }
-  int done(int rc) {
-    if (a) {
-      (void)hipEventRecord(b, c->stream);
-      (void)hipEventSynchronize(b);
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, a, b);
-      c->timing[key] += ms;
-      c->counts[key] += 1;
-      (void)hipEventDestroy(a);
-      (void)hipEventDestroy(b);
-    }
-    return rc;
-  }
-};
-
-static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);
-static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);
-static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M);
-int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
-  OpTimer t(c, "aa_times");
-  return t.done(aa_times_impl(c, b, Z, y));
-}
-int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
-  OpTimer t(c, "aa_times2");
-  return t.done(aa_times2_impl(c, b, Z1, y1, Z2, y2));
-}
-int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
-  OpTimer t(c, "aat_to_mat");
-  return t.done(aat_to_mat_impl(c, b, x, M));
-}
-
-// y += AA vec(Z)
-static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
-  if (b.factored) return aa_times_factored(c, b, Z, y);
-  if (b.npos_nz > b.nd) c->counts["op_sparse"] += 1;
-  if (b.nd > 0) c->counts["op_dense"] += 1;
-  if (b.npos_nz > b.nd)
-    hipLaunchKernelGGL(aa_times_kernel, dim3((b.npos_nz - b.nd + 3) / 4), dim3(256), 0, c->stream, b.ent_ptr.as<long>(),
-                       b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), Z, b.msz, b.nd, b.npos_nz,
-                       b.sigma_d.as<int>(), y);
-  if (b.nd > 0) {
-    int p0 = 0, p1 = b.nd;
-    if (dense_passes_sharded(c, b)) {
-      // one process per GPU: every pass over the dense constraint data (128 GB at C4: 25 ms at 5.1 TB/s, six of them per IP
-      // iteration in the replicated part of the loop) is split by constraints; the nvar-vector of partial results is summed
-      // by one all-reduce on the library's stream
-      const int per = (b.nd + c->world - 1) / c->world;
-      p0 = std::min(b.nd, c->rank * per);
-      p1 = std::min(b.nd, p0 + per);
-      LRN_TRY(ensure(c, c->commvec, (size_t)c->nvar * 8));
-      LRN_HIP(c, hipMemsetAsync(c->commvec.p, 0, (size_t)c->nvar * 8, c->stream));
-      if (p1 > p0) {
-        if (dense_tri_ok(c, b)) {
-          double* Wt = nullptr;
-          LRN_TRY(tri_weights(c, b, Z, 0, &Wt));
-          hipLaunchKernelGGL(aa_dense_tri_dot4_kernel<1>, dim3((p1 - p0 + 3) / 4), dim3(256), 0, c->stream,
-                             b.Adense.as<double>() + (long)p0 * b.msz * b.msz, (long)b.msz * b.msz, p1 - p0, Wt, Wt,
-                             b.tri_tab.as<TriChunk>(), b.tri_nch, b.sigma_d.as<int>() + p0, c->commvec.as<double>(),
-                             c->commvec.as<double>());
-        } else if (dense_stream_ok(b, Z))
-          hipLaunchKernelGGL(aa_dense_dot4_kernel, dim3((p1 - p0 + 3) / 4), dim3(256), 0, c->stream,
-                             b.Adense.as<double>() + (long)p0 * b.msz * b.msz, (long)b.msz * b.msz, p1 - p0, Z,
-                             b.sigma_d.as<int>() + p0, c->commvec.as<double>());
-        else
-        hipLaunchKernelGGL(aa_dense_dot_kernel, dim3(p1 - p0), dim3(256), 0, c->stream,
-                           b.Adense.as<double>() + (long)p0 * b.msz * b.msz, (long)b.msz * b.msz, Z, b.sigma_d.as<int>() + p0,
-                           c->commvec.as<double>());
-      }
-      LRN_TRY(comm_allreduce(c, c->commvec.as<double>(), c->nvar, 0));
-      hipLaunchKernelGGL(vec_add_kernel, dim3(nb(c->nvar)), dim3(256), 0, c->stream, y, c->commvec.as<double>(), c->nvar);
-      return LRN_OK;
-    }
-    if (dense_tri_ok(c, b)) {
-      double* Wt = nullptr;
-      LRN_TRY(tri_weights(c, b, Z, 0, &Wt));
-      hipLaunchKernelGGL(aa_dense_tri_dot4_kernel<1>, dim3((b.nd + 3) / 4), dim3(256), 0, c->stream, b.Adense.as<double>(),
-                         (long)b.msz * b.msz, b.nd, Wt, Wt, b.tri_tab.as<TriChunk>(), b.tri_nch, b.sigma_d.as<int>(), y, y);
-    } else if (dense_stream_ok(b, Z))
-      hipLaunchKernelGGL(aa_dense_dot4_kernel, dim3((b.nd + 3) / 4), dim3(256), 0, c->stream, b.Adense.as<double>(),
-                         (long)b.msz * b.msz, b.nd, Z, b.sigma_d.as<int>(), y);
-    else
-    hipLaunchKernelGGL(aa_dense_dot_kernel, dim3(b.nd), dim3(256), 0, c->stream, b.Adense.as<double>(),
-                       (long)b.msz * b.msz, Z, b.sigma_d.as<int>(), y);
-  }
-  return LRN_OK;
-}
-
-// out1[sigma[p]] -= <Adense[p], Z1>, out2[sigma[p]] -= <Adense[p], Z2>: ONE pass over the dense constraint data for two
-// products (C4: 128 GB per pass)
-__global__ __launch_bounds__(256) void aa_dense_dot2_kernel(const double* __restrict__ Ad, long mm, const double* __restrict__ Z1,
-                                                            const double* __restrict__ Z2, const int* __restrict__ sigma,
-                                                            double* __restrict__ out1, double* __restrict__ out2) {
-  __shared__ double sh[8];
-  const double* a = Ad + (long)blockIdx.x * mm;
-  double s1 = 0.0, s2 = 0.0;
-  for (long q = threadIdx.x; q < mm; q += 256) { const double v = a[q]; s1 += v * Z1[q]; s2 += v * Z2[q]; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = s1; sh[4 + (threadIdx.x >> 6)] = s2; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    out1[sigma[blockIdx.x]] -= sh[0] + sh[1] + sh[2] + sh[3];
-    out2[sigma[blockIdx.x]] -= sh[4] + sh[5] + sh[6] + sh[7];
-  }
-}
-
-// y1 += AA vec(Z1), y2 += AA vec(Z2) with the dense constraint data read once
-static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
-  if (b.factored || b.nd <= 0 || dense_passes_sharded(c, b)) {      // (the sharded pass is 1/world of the data already; factor form: two products)
-    LRN_TRY(aa_times_impl(c, b, Z1, y1));
-    return aa_times_impl(c, b, Z2, y2);
-  }
-  c->counts["op_dense"] += 1;
-  if (b.npos_nz > b.nd) {
-    c->counts["op_sparse"] += 1;
-    for (int h = 0; h < 2; ++h)
-      hipLaunchKernelGGL(aa_times_kernel, dim3((b.npos_nz - b.nd + 3) / 4), dim3(256), 0, c->stream, b.ent_ptr.as<long>(),
-                         b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), h ? Z2 : Z1, b.msz, b.nd, b.npos_nz,
-                         b.sigma_d.as<int>(), h ? y2 : y1);
-  }
-  if (dense_tri_ok(c, b)) {
-    double *W1 = nullptr, *W2 = nullptr;
-    LRN_TRY(tri_weights(c, b, Z1, 0, &W1));
-    LRN_TRY(tri_weights(c, b, Z2, 1, &W2));
-    hipLaunchKernelGGL(aa_dense_tri_dot4_kernel<2>, dim3((b.nd + 3) / 4), dim3(256), 0, c->stream, b.Adense.as<double>(),
-                       (long)b.msz * b.msz, b.nd, W1, W2, b.tri_tab.as<TriChunk>(), b.tri_nch, b.sigma_d.as<int>(), y1, y2);
-  } else if (dense_stream_ok(b, Z1) && dense_stream_ok(b, Z2))
-    hipLaunchKernelGGL(aa_dense_dot4x2_kernel, dim3((b.nd + 3) / 4), dim3(256), 0, c->stream, b.Adense.as<double>(),
-                       (long)b.msz * b.msz, b.nd, Z1, Z2, b.sigma_d.as<int>(), y1, y2);
-  else
-  hipLaunchKernelGGL(aa_dense_dot2_kernel, dim3(b.nd), dim3(256), 0, c->stream, b.Adense.as<double>(), (long)b.msz * b.msz,
-                     Z1, Z2, b.sigma_d.as<int>(), y1, y2);
-  return LRN_OK;
-}
-
-// M = mat(AA' x)  (symmetrised msz x msz, kron_etc.jl:13-18)
-static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
-  if (b.factored) return aat_to_mat_factored(c, b, x, M);
-  const int m = b.msz;
-  const long mm = (long)m * m;
-  if (b.ncq > 0) c->counts["op_sparse"] += 1;
-  if (b.nd > 0) c->counts["op_dense"] += 1;
-  LRN_HIP(c, hipMemsetAsync(M, 0, (size_t)mm * 8, c->stream));
-  if (b.ncq > 0)
-    hipLaunchKernelGGL(aat_gather_kernel, dim3((unsigned)((b.ncq + 3) / 4)), dim3(256), 0, c->stream, b.cq_q.as<long>(),
-                       b.cq_ptr.as<long>(), b.cq_j.as<int>(), b.cq_v.as<double>(), b.ncq, x, M);
-  // symmetric dense data: the sparse part is symmetrised first, the dense constraints are added to the LOWER triangle only
-  // (half the bytes of the pass) and the result is mirrored -- the same matrix up to the order of the additions
-  const bool tri = b.nd > 0 && dense_tri_ok(c, b);
-  if (tri && b.ncq > 0) symmetrize_dev(c->stream, M, m);
-  if (b.nd > 0) {
-    int p0 = 0, p1 = b.nd;
-    double* Tm = M;
-    const bool sharded = dense_passes_sharded(c, b);
-    if (sharded) {
-      // this rank's constraints into a zeroed buffer, one all-reduce of the msz x msz partial sums, then added to M
-      const int per = (b.nd + c->world - 1) / c->world;
-      p0 = std::min(b.nd, c->rank * per);
-      p1 = std::min(b.nd, p0 + per);
-      LRN_TRY(ensure(c, c->commmat, (size_t)mm * 8));
-      Tm = c->commmat.as<double>();
-      LRN_HIP(c, hipMemsetAsync(Tm, 0, (size_t)mm * 8, c->stream));
-    }
-    if (p1 > p0) {
-      const double* Ap0 = b.Adense.as<double>() + (long)p0 * mm;
-      const int* sg = b.sigma_d.as<int>() + p0;
-      if (tri)
-        hipLaunchKernelGGL(aat_dense_tri_kernel, dim3((unsigned)((b.tri_nch + 3) / 4)), dim3(256), 0, c->stream, Ap0, p1 - p0,
-                           mm, m, sg, x, b.tri_tab.as<TriChunk>(), b.tri_nch, Tm);
-      else if (dense_stream_ok(b, Tm))
-        hipLaunchKernelGGL(aat_dense2_kernel, dim3((unsigned)((mm / 2 + 255) / 256)), dim3(256), 0, c->stream, Ap0, p1 - p0, mm,
-                           sg, x, Tm);
-      else
-        hipLaunchKernelGGL(aat_dense_kernel, dim3(nb(mm)), dim3(256), 0, c->stream, Ap0, p1 - p0, mm, sg, x, Tm);
-    }
-    if (sharded) {
-      LRN_TRY(comm_allreduce(c, Tm, mm, 0));
-      hipLaunchKernelGGL(vec_add_kernel, dim3(nb(mm)), dim3(256), 0, c->stream, M, Tm, mm);
-    }
-  }
-  if (tri)
-    hipLaunchKernelGGL(mirror_lower_tiled_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(32, 8), 0, c->stream, M, m);
-  else
-    symmetrize_dev(c->stream, M, m);
-  return LRN_OK;
-}
-
-int matvec_dev(lrn_ctx* c, const double* x, double* y) {
-  const int n = c->nvar;
-  LRN_HIP(c, hipMemsetAsync(y, 0, (size_t)n * 8, c->stream));
-  for (auto& b : c->lmi) {
-    if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set");
-    const int m = b.msz;
-    if (use_sparse_matvec(c, b)) {
-      LRN_TRY(matvec_sparse_block(c, b, x, y, 0, m, true));
-      continue;
-    }
-    LRN_TRY(ensure_m(c, m));
-    double* M = c->m0.as<double>();
-    LRN_TRY(aat_to_mat(c, b, x, M));
-    LRN_TRY(wmw(c, b, M, c->m1.as<double>(), c->m2.as<double>()));
-    LRN_TRY(aa_times(c, b, c->m2.as<double>(), y));
-  }
-  if (c->nlin > 0) LRN_TRY(lin_matvec(c, x, y));
-  LRN_HIP(c, hipGetLastError());
-  return LRN_OK;
-}
-
-// Partial mat-vec of rank `rank` of `world`: rows R_g of Z = W M W (row blocks of msz/world),
-// y_g = AA[:, idx(R_g)] vec(Z[R_g,:]); the caller all-reduces y_g over the ranks
-// (one all-reduce of an nvar-vector per mat-vec).  The C_lin term is added by rank 0.
-int matvec_partial_dev(lrn_ctx* c, const double* x, double* y, int rank, int world) {
-  const int n = c->nvar;
-  LRN_HIP(c, hipMemsetAsync(y, 0, (size_t)n * 8, c->stream));
-  for (auto& b : c->lmi) {
-    if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set");
-    const int m = b.msz;
-    const int per = (m + world - 1) / world;
-    const int r0 = std::min(m, rank * per), r1 = std::min(m, r0 + per);
-    if (r1 <= r0) continue;
-    const int nr = r1 - r0;
-    if (use_sparse_matvec(c, b)) {       // shard the pattern columns of Z instead of its rows
-      LRN_TRY(matvec_sparse_block(c, b, x, y, r0, r1, false));
-      continue;
-    }
-    LRN_TRY(ensure_m(c, m));
-    double* M = c->m0.as<double>();
-    LRN_TRY(aat_to_mat(c, b, x, M));              // replicated: sparse, cheap
-    GemmDesc g1;                                  // P_g = W[R_g,:] M
-    g1.A = b.W.as<double>() + r0; g1.sAm = 1; g1.sAk = m;
-    g1.B = M; g1.sBk = m; g1.sBn = 1;             // M symmetric
-    g1.C = c->m1.as<double>(); g1.sCm = 1; g1.sCn = nr;
-    g1.M = nr; g1.N = m; g1.K = m;
-    LRN_TRY(gemm(c->stream, g1));
-    GemmDesc g2;                                  // Z_g = P_g W
-    g2.A = c->m1.as<double>(); g2.sAm = 1; g2.sAk = nr;
-    g2.B = b.W.as<double>(); g2.sBk = m; g2.sBn = 1;
-    g2.C = c->m2.as<double>(); g2.sCm = 1; g2.sCn = nr;
-    g2.M = nr; g2.N = m; g2.K = m;
-    LRN_TRY(gemm(c->stream, g2));
-    if (b.npos_nz > b.nd)
-      hipLaunchKernelGGL(aa_times_rows_kernel, dim3((b.npos_nz - b.nd + 3) / 4), dim3(256), 0, c->stream,
-                         b.ent_ptr.as<long>(), b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(),
-                         c->m2.as<double>(), nr, r0, r1, b.nd, b.npos_nz, b.sigma_d.as<int>(), y);
-    if (b.nd > 0)
-      hipLaunchKernelGGL(aa_dense_dot_rows_kernel, dim3(b.nd), dim3(256), 0, c->stream, b.Adense.as<double>(), m,
-                         c->m2.as<double>(), nr, r0, r1, b.sigma_d.as<int>(), y);
-  }
-  if (c->nlin > 0 && rank == 0) LRN_TRY(lin_matvec(c, x, y));
-  LRN_HIP(c, hipGetLastError());
-  return LRN_OK;
 }
 
 // ------------------------------------------------------------------ vector kernels (single workgroup)
@@ -1732,8 +443,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     LRN_TRY(copy_out(c, &hd, c->info_dev.p, 4));
     if (hd != 0) { if (info) *info = hd; return LRN_OK; }
   } else if (c->nlin > 0)
-    hipLaunchKernelGGL(lin_diag_kernel, dim3(nb(n)), dim3(256), 0, st, c->cr_ptr.as<long>(), c->cr_col.as<int>(),
-                       c->cr_val.as<double>(), c->lin_xs.as<double>(), n, P->d.as<double>());
+    lin_diag(c, P->d.as<double>());
   if (kind == 1) {
     LRN_TRY(ensure(c, P->ts, (size_t)n * ksz * 8));
     int col0 = 0;
@@ -1823,7 +533,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     if (P->has_inv) {
       LRN_TRY(ensure(c, P->Sm, (size_t)ksz * ksz * 8));
       LRN_HIP(c, hipMemcpyAsync(P->Sm.p, P->cholS.p, (size_t)ksz * ksz * 8, hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(mirror_lower_full_kernel, dim3(nb((long)ksz * ksz)), dim3(256), 0, st, P->Sm.as<double>(), ksz);
+      mirror_lower(st, P->Sm.as<double>(), ksz);
     }
     LRN_TRY(ensure(c, P->workS, chol_work_doubles(ksz) * 8));
     LRN_HIP(c, hipMemsetAsync(c->info_dev.p, 0, 4, st));
@@ -1837,10 +547,10 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       double* Li = c->m0.as<double>();
       double* LiT = c->m1.as<double>();
       LRN_TRY(ensure(c, P->workS, (chol_work_doubles(ksz) + (size_t)CHOL_NB * ksz) * 8));
-      hipLaunchKernelGGL(eye_fill_kernel, dim3(nb((long)ksz * ksz)), dim3(256), 0, st, Li, ksz);
+      eye_mat(st, Li, ksz);
       LRN_TRY(trsm_left_lower(st, P->cholS.as<double>(), ksz, ksz, false, Li, ksz, ksz,
                               P->workS.as<double>() + chol_work_doubles(ksz)));
-      hipLaunchKernelGGL(transpose_sq_kernel, dim3((ksz + 31) / 32, (ksz + 31) / 32), dim3(32, 8), 0, st, Li, ksz, LiT);
+      transpose_mat(st, Li, ksz, LiT);
       LRN_TRY(gemm_nt_sym(st, ksz, LiT, LiT, P->Ainv.as<double>(), 1.0));      // L^-T L^-1
     }
     LRN_TRY(ensure(c, P->y, (size_t)(ksz + 64) * 8));
@@ -2142,7 +852,10 @@ extern "C" int lrn_make_rhs(lrn_ctx* c, const double* Rp, const double* const* R
     LmiBlock& b = c->lmi[il];
     if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set");
     LRN_TRY(ensure_m(c, b.msz));
-    LRN_TRY(copy_in(c, c->m0.p, RdS[il], (size_t)b.msz * b.msz * 8));
+    // wmw reads its middle factor transposed (everywhere else it is symmetric): it gets (Rd+S)', so that a Rd+S that is
+    // not symmetric still gives W (Rd+S) W -- with constraint matrices that are not symmetric either the two differ
+    LRN_TRY(copy_in(c, c->m1.p, RdS[il], (size_t)b.msz * b.msz * 8));
+    transpose_mat(c->stream, c->m1.as<double>(), b.msz, c->m0.as<double>());
     LRN_TRY(wmw(c, b, c->m0.as<double>(), c->m1.as<double>(), c->m2.as<double>()));
     LRN_TRY(aa_times(c, b, c->m2.as<double>(), c->v1.as<double>()));
   }

@@ -23,8 +23,11 @@ struct LmiBlock {
   lrn::DBuf ent_r, ent_c;   // int32 [nent]
   lrn::DBuf ent_v;          // double [nent]   value of A_j (= -AA)
   lrn::DBuf Adense;         // double [nd * msz^2], slot s = position s
-  int dense_sym = -1;       // every dense constraint matrix is exactly symmetric: -1 not checked yet, 0 no, 1 yes
-  lrn::DBuf tri_tab;        // chunk table of the half-traffic passes over the dense data (cgops.hip::TriChunk)
+  // route of the passes over Adense, set where Adense is filled (dataops.hip::dense_route_setup) and reset with it:
+  // tri = column tails only (symmetric data), stream = 16-byte loads over both triangles, scalar = one element per lane
+  enum DenseRoute { DENSE_SCALAR = 0, DENSE_STREAM, DENSE_TRI };
+  DenseRoute dense_route = DENSE_SCALAR;
+  lrn::DBuf tri_tab;        // DENSE_TRI: chunk table of the column tails (dataops.hip::TriChunk), tri_nch entries
   int tri_nch = 0;
   lrn::DBuf hidx;           // int32 [nvar] position -> row/col index of the Schur matrix
   lrn::DBuf sigma_d, ipos_d; // int32 [nvar] device copies of sigma / ipos
@@ -34,7 +37,7 @@ struct LmiBlock {
   lrn::DBuf cq_j;           // int32 constraint (natural index)
   lrn::DBuf cq_v;           // double AA value
   // sparsity pattern of mat(AA'x) = the stored columns above, when no constraint is stored dense and
-  // the pattern is symmetric: sparse-aware mat-vec (cgops.hip, Z = W M W only where AA needs it)
+  // the pattern is symmetric: sparse-aware mat-vec (dataops.hip, Z = W M W only where AA needs it)
   bool sp_ok = false;
   std::vector<int> sp_long_cols;   // pattern columns with more than 64 stored entries (small-msz sparse mat-vec)
   lrn::DBuf pc_ptr;         // int64 [msz+1] pattern column -> range of stored columns
@@ -72,7 +75,7 @@ struct LmiBlock {
   lrn::DBuf Vd;             // dense copy of the rank-k factors, msz x (nvar * lr_khat) (dense U product, assembly from W)
   bool have_Vd = false;
   // factored block (lrn_set_factored): the factors ARE the constraint data -- AA has no entry, AA vec(.) and mat(AA' .) go
-  // through Vd (cgops.hip, "factor form"), the Schur matrix through mode 1 only
+  // through Vd (dataops.hip, "factor form"), the Schur matrix through mode 1 only
   bool factored = false;
 };
 

@@ -19,11 +19,6 @@
 
 namespace lrn {
 
-static inline unsigned nbk(long n, long cap = 4096) {
-  long b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 // out = a*A + b*B + c*C (null pointers skipped), n elements
 __global__ void lin3_kernel(double* __restrict__ out, double a, const double* __restrict__ A, double b,
                             const double* __restrict__ B, double c, const double* __restrict__ C, long n) {
@@ -203,7 +198,7 @@ static void sym_half(hipStream_t st, const double* M, double* out, int n) {
     hipLaunchKernelGGL(symadd_kernel, dim3((unsigned)std::min<long>(1024, nt * nt)), dim3(256), 0, st, SlabSrc{M, 0, 1}, n, 0.5, out,
                        (const double*)nullptr, (double*)nullptr);
   } else {
-    hipLaunchKernelGGL(sym_kernel, dim3(nbk((long)n * n)), dim3(256), 0, st, M, out, n);
+    hipLaunchKernelGGL(sym_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, M, out, n);
   }
 }
 
@@ -463,7 +458,7 @@ extern "C" int lrn_ip_residual_d(lrn_ctx* c, const double* y) {
     LRN_TRY(ensure_resident(c, b));
     const long mm_ = (long)b.msz * b.msz;
     LRN_TRY(aat_to_mat(c, b, c->v0.as<double>(), b.t0.as<double>()));
-    hipLaunchKernelGGL(lin3_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.Rd.as<double>(), 1.0, b.Cd.as<double>(),
+    hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.Rd.as<double>(), 1.0, b.Cd.as<double>(),
                        -1.0, b.S.as<double>(), -1.0, b.t0.as<double>(), mm_);
   }
   toc(c, "residual_d");
@@ -478,7 +473,7 @@ extern "C" int lrn_ip_rhs_pred(lrn_ctx* c, double* out) {
   for (auto& b : c->lmi) {
     LRN_TRY(ensure_resident(c, b));
     const long mm_ = (long)b.msz * b.msz;
-    hipLaunchKernelGGL(lin3_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.Rd.as<double>(),
+    hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.Rd.as<double>(),
                        1.0, b.S.as<double>(), 0.0, (const double*)nullptr, mm_);
     LRN_TRY(wmw(c, b, b.t0.as<double>(), b.t1.as<double>(), b.t2.as<double>()));
     LRN_TRY(aa_times(c, b, b.t2.as<double>(), c->v1.as<double>()));
@@ -497,7 +492,7 @@ extern "C" int lrn_ip_rhs_pred2(lrn_ctx* c, double* aax_out, double* out) {
   for (auto& b : c->lmi) {
     LRN_TRY(ensure_resident(c, b));
     const long mm_ = (long)b.msz * b.msz;
-    hipLaunchKernelGGL(lin3_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.Rd.as<double>(),
+    hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.Rd.as<double>(),
                        1.0, b.S.as<double>(), 0.0, (const double*)nullptr, mm_);
     if (wmw_pattern_ok(c, b)) {          // every constraint sparse: W M W only where AA reads it (one product instead of two)
       LRN_TRY(aa_times(c, b, b.X.as<double>(), c->v2.as<double>()));
@@ -526,15 +521,15 @@ extern "C" int lrn_ip_rhs_corr(lrn_ctx* c, double sigma_mu, double* out) {
       // G (G'RdG + D - sigma_mu/D - RNT) G' = W Rd W + X - sigma_mu Si - G RNT G'
       if (wmw_pattern_ok(c, b)) {        // AA vec(W Rd W) on the pattern, AA vec(X - sigma_mu Si - G RNT G') by itself
         LRN_TRY(aa_times_wmw_pattern(c, b, b.Rd.as<double>(), b.t1.as<double>(), c->v1.as<double>()));
-        hipLaunchKernelGGL(lin3_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.X.as<double>(), -sigma_mu,
+        hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.X.as<double>(), -sigma_mu,
                            b.Si.as<double>(), -1.0, b.Qm.as<double>(), mm_);
         LRN_TRY(aa_times(c, b, b.t0.as<double>(), c->v1.as<double>()));
         continue;
       }
       LRN_TRY(wmw(c, b, b.Rd.as<double>(), b.t1.as<double>(), b.t2.as<double>()));
-      hipLaunchKernelGGL(lin3_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.t2.as<double>(), 1.0,
+      hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.t2.as<double>(), 1.0,
                          b.X.as<double>(), -sigma_mu, b.Si.as<double>(), mm_);
-      hipLaunchKernelGGL(lin3_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.t2.as<double>(), 1.0, b.t0.as<double>(), -1.0,
+      hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t2.as<double>(), 1.0, b.t0.as<double>(), -1.0,
                          b.Qm.as<double>(), 0.0, (const double*)nullptr, mm_);
       LRN_TRY(aa_times(c, b, b.t2.as<double>(), c->v1.as<double>()));
       continue;
@@ -543,7 +538,7 @@ extern "C" int lrn_ip_rhs_corr(lrn_ctx* c, double sigma_mu, double* out) {
     // t1 = G' Rd G
     LRN_TRY(mm(c, m, G, true, b.Rd.as<double>(), false, b.t0.as<double>()));
     LRN_TRY(mm(c, m, b.t0.as<double>(), false, G, false, b.t1.as<double>()));
-    hipLaunchKernelGGL(corr_inner_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.t1.as<double>(), b.D.as<double>(),
+    hipLaunchKernelGGL(corr_inner_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t1.as<double>(), b.D.as<double>(),
                        b.RNT.as<double>(), sigma_mu, b.t0.as<double>(), m);
     // my_kron(G,G,inner) = vec(G inner G')
     LRN_TRY(mm(c, m, G, false, b.t0.as<double>(), false, b.t1.as<double>()));
@@ -566,7 +561,7 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
     LRN_TRY(ensure_resident(c, b));
     const int m = b.msz;
     const long mm_ = (long)m * m;
-    const unsigned g = nbk(mm_);
+    const unsigned g = nb(mm_);
     double *t0 = b.t0.as<double>(), *t1 = b.t1.as<double>(), *t2 = b.t2.as<double>();
     double *G = b.G.as<double>(), *Gi = b.Gi.as<double>();
     // delS = Rd - mat(AA' dely)                                   (:252)
@@ -653,7 +648,7 @@ extern "C" int lrn_ip_update(lrn_ctx* c, int predict, const double* alpha, const
     LRN_TRY(ensure_resident(c, b));
     const int m = b.msz;
     const long mm_ = (long)m * m;
-    const unsigned g = nbk(mm_);
+    const unsigned g = nb(mm_);
     double *t0 = b.t0.as<double>(), *t1 = b.t1.as<double>(), *t2 = b.t2.as<double>();
     if (predict) {
       hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, b.Xn.as<double>(), 1.0, b.X.as<double>(), alpha[il],
@@ -815,7 +810,7 @@ extern "C" int lrn_synthetic_dense_problem(lrn_ctx* c, uint64_t seed, double* b_
   for (auto& v : Q) v = gauss();
   for (auto& v : y0) v = gauss() / std::sqrt((double)n);
   LRN_TRY(copy_in(c, b.t1.p, Q.data(), Q.size() * 8));
-  hipLaunchKernelGGL(synth_x0_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), b.t1.as<double>(), m, r);
+  hipLaunchKernelGGL(synth_x0_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), b.t1.as<double>(), m, r);
   // b = AA vec(X0)
   LRN_HIP(c, hipMemsetAsync(c->v1.p, 0, (size_t)n * 8, c->stream));
   LRN_TRY(aa_times(c, b, b.t0.as<double>(), c->v1.as<double>()));
@@ -823,7 +818,7 @@ extern "C" int lrn_synthetic_dense_problem(lrn_ctx* c, uint64_t seed, double* b_
   // C = I + mat(AA' y0)
   LRN_TRY(copy_in(c, c->v0.p, y0.data(), (size_t)n * 8));
   LRN_TRY(aat_to_mat(c, b, c->v0.as<double>(), b.t0.as<double>()));
-  hipLaunchKernelGGL(eye_add_kernel, dim3(nbk(mm_)), dim3(256), 0, c->stream, b.Cd.as<double>(), b.t0.as<double>(), 1.0, m);
+  hipLaunchKernelGGL(eye_add_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.Cd.as<double>(), b.t0.as<double>(), 1.0, m);
   if (normC) {
     LRN_TRY(ensure(c, c->redout, 64 * 8));
     LRN_TRY(dot_dev(c, b.Cd.as<double>(), nullptr, mm_, c->redout.as<double>()));

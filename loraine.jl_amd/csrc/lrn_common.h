@@ -30,6 +30,12 @@ __host__ __device__ inline int shard_global_block(int rank, int lb, int world) {
   return lb * world + ((lb & 1) ? world - 1 - rank : rank);
 }
 
+// workgroups of 256 threads for a grid-stride loop over n elements, at most `cap`
+static inline unsigned nb(long n, long cap = 4096) {
+  long b = (n + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
 // ---------------------------------------------------------------- device buffer
 struct DBuf {
   void* p = nullptr;

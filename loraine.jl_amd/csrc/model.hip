@@ -4,6 +4,7 @@
 #include <numeric>
 
 #include "ctx.h"
+#include "ops.h"
 
 namespace lrn {
 
@@ -169,6 +170,8 @@ using namespace lrn;
 
 static void free_block(LmiBlock& b) {
   release(b.tri_tab);
+  b.tri_nch = 0;
+  b.dense_route = LmiBlock::DENSE_SCALAR;      // (Adense goes below)
   for (DBuf* d : {&b.ent_ptr, &b.ent_r, &b.ent_c, &b.ent_v, &b.Adense, &b.hidx, &b.sigma_d, &b.ipos_d, &b.cq_q, &b.cq_ptr, &b.cq_j, &b.cq_v, &b.pc_ptr, &b.pc_r, &b.pc_t, &b.ent_t, &b.Mv, &b.Zs, &b.b_ptr, &b.b_col,
                   &b.b_val, &b.X, &b.S, &b.W, &b.G, &b.Gi, &b.Si, &b.D, &b.DDsi, &b.Vprev, &b.Cd, &b.Rd, &b.delX, &b.delS, &b.Xn, &b.Sn, &b.RNT,
                   &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd, &b.v_ptr, &b.v_col, &b.v_val, &b.v_w, &b.Vd})
@@ -360,7 +363,7 @@ extern "C" int lrn_upload_model(lrn_ctx* c, int nlmi, int nvar, const int64_t* m
           LRN_TRY(copy_in(c, b.pc_t.p, pt.data(), (size_t)nq * 4));
           LRN_TRY(copy_in(c, b.ent_t.p, et.data(), (size_t)b.nent * 4));
           b.sp_ok = true;
-          // columns of the pattern with many entries (sp_wm_long_kernel, cgops.hip)
+          // columns of the pattern with many entries (sp_wm_long_kernel, dataops.hip)
           b.sp_long_cols.clear();
           for (long q = 0; q < m; ++q)
             if (pcp[q + 1] - pcp[q] > 64) b.sp_long_cols.push_back((int)q);
@@ -389,6 +392,7 @@ extern "C" int lrn_upload_model(lrn_ctx* c, int nlmi, int nvar, const int64_t* m
                          b.ent_ptr.as<long>(), b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(),
                          b.Adense.as<double>(), m);
     }
+    LRN_TRY(dense_route_setup(c, b, false));
     // rank-one factors, rows reordered to H index order
     b.has_B = false;
     if (B_colptr && B_colptr[il] && B_rowval && B_nzval) {
@@ -519,7 +523,6 @@ extern "C" int lrn_synthetic_dense_model(lrn_ctx* c, int msz, int nvar, uint64_t
   b.nnz.assign(nvar, (long)msz * msz);
   b.qA = b.nd = b.q_wave = b.npos_nz = nvar;
   b.sp_ok = false;
-  b.dense_sym = 1;          // (R_k + R_k')/2 from one Philox draw per unordered index pair: symmetric by construction
   b.nent = 0;
   std::vector<long> ptr(nvar + 1, 0);
   LRN_TRY(ensure(c, b.ent_ptr, (size_t)(nvar + 1) * 8));
@@ -540,6 +543,7 @@ extern "C" int lrn_synthetic_dense_model(lrn_ctx* c, int msz, int nvar, uint64_t
     hipLaunchKernelGGL(synth_dense_kernel, dim3(4096), dim3(256), 0, c->stream, b.Adense.as<double>(), msz,
                        k0, nk, seed);
   }
+  LRN_TRY(dense_route_setup(c, b, true));     // (R_k + R_k')/2 from one Philox draw per unordered index pair: symmetric by construction
   LRN_TRY(alloc_common(c));
   LRN_HIP(c, hipStreamSynchronize(c->stream));
   return LRN_OK;
@@ -629,7 +633,7 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
 }
 
 // on = 1: the factors of lrn_upload_lowrank ARE the constraint data of block ilmi (A_k = V_k diag(d_k) V_k', AA = -A as
-// everywhere): AA vec(.) and mat(AA' .) of the resident path run in factor form (cgops.hip), the Schur matrix comes from
+// everywhere): AA vec(.) and mat(AA' .) of the resident path run in factor form (dataops.hip), the Schur matrix comes from
 // mode 1.  The block's AA must be without entries -- no constraint may be counted twice.  on = 0 takes the declaration back.
 extern "C" int lrn_set_factored(lrn_ctx* c, int ilmi, int on) {
   if (!c) return LRN_ERR_ARG;

@@ -1,4 +1,5 @@
-// Shared device-side operations (cgops.hip / prepw.hip) used by the resident IP step.
+// Device-side operations shared between translation units: the data operators (dataops.hip), the NT scaling (prepw.hip),
+// the Lanczos searches (lz.hip) and a few helper launches.
 #pragma once
 #include "ctx.h"
 namespace lrn {
@@ -11,6 +12,13 @@ bool wmw_pattern_ok(const lrn_ctx* c, const LmiBlock& b);
 int aa_times_wmw_pattern(lrn_ctx* c, LmiBlock& b, const double* M, double* N, double* y);
 int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);   // both, one pass over dense data
 int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M);        // M = mat(AA' x)
+// route of the passes over the dense constraint data of b, decided once b.Adense is filled (model.hip): the symmetry check
+// on the device and the chunk table of the column tails; sym_known: the data are symmetric by construction, no check
+int dense_route_setup(lrn_ctx* c, LmiBlock& b, bool sym_known);
+int matvec_dev(lrn_ctx* c, const double* x, double* y);                     // y = AA vec(W mat(AA' x) W) (+ the C_lin term): MyA
+int matvec_partial_dev(lrn_ctx* c, const double* x, double* y, int rank, int world);   // the rows of Z of one rank; the caller all-reduces
+int lin_matvec(lrn_ctx* c, const double* x, double* y);                     // y += C_lin diag(xs) C_lin' x
+void lin_diag(lrn_ctx* c, double* d);                                       // d_i += sum_l C_lin[i,l]^2 xs_l
 int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info);                    // NT scaling from b.X, b.S (SVD route)
 // eigen-free NT scaling from b.X, b.S: W, Si, the Cholesky factors and K^(+-1/2); *converged = false: nothing usable, take
 // the SVD route
@@ -50,4 +58,8 @@ int eigmin_dev(lrn_ctx* c, const double* M, int n, double* lam, int* steps_out, 
 int eigmin_certified(lrn_ctx* c, const double* M, int n, double* lam);
 int eigmin_certified_pair(lrn_ctx* c, const double* M1, const double* M2, int n, double* lam1, double* lam2);
 void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I (ipstep.hip)
+// n x n helpers (prepw.hip)
+void eye_mat(hipStream_t st, double* V, int n);                            // V = I
+void mirror_lower(hipStream_t st, double* A, int n);                       // upper triangle <- lower triangle, in place
+void transpose_mat(hipStream_t st, const double* A, int n, double* B);     // B = A'
 }  // namespace lrn

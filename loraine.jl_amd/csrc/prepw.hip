@@ -76,9 +76,14 @@ __global__ __launch_bounds__(256) void coldot_rsqrt_kernel(const double* __restr
   if (threadIdx.x == 0) out[blockIdx.x] = 1.0 / sqrt(sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
-static inline unsigned nb2(long n) {
-  long b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+void eye_mat(hipStream_t st, double* V, int n) {
+  hipLaunchKernelGGL(eye_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, V, n);
+}
+void mirror_lower(hipStream_t st, double* A, int n) {
+  hipLaunchKernelGGL(mirror_lower_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, A, n);
+}
+void transpose_mat(hipStream_t st, const double* A, int n, double* B) {
+  hipLaunchKernelGGL(transpose_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(32, 8), 0, st, A, n, B);
 }
 
 static int gemm_nn(hipStream_t st, int n, const double* A, bool tA, const double* B, bool tB, double* C, int flags = 0) {
@@ -134,11 +139,11 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   LRN_HIP(c, hipMemcpyAsync(LX, b.X.p, mm, hipMemcpyDeviceToDevice, st));
   LRN_HIP(c, hipMemsetAsync(dinfo, 0, 4, st));
   LRN_TRY(potrf_lower(st, LX, n, n, cw, dinfo));
-  hipLaunchKernelGGL(tril_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, LX, n);
+  hipLaunchKernelGGL(tril_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, LX, n);
   LRN_HIP(c, hipMemcpyAsync(LS, b.S.p, mm, hipMemcpyDeviceToDevice, s2));
   LRN_HIP(c, hipMemsetAsync(dinfoS, 0, 4, s2));
   LRN_TRY(potrf_lower(s2, LS, n, n, cw2, dinfoS));
-  hipLaunchKernelGGL(tril_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, LS, n);
+  hipLaunchKernelGGL(tril_kernel, dim3(nb((long)n * n)), dim3(256), 0, s2, LS, n);
   if (two) LRN_HIP(c, hipEventRecord(c->evB, s2));            // LS is final
   // the verdicts first, in the reference's order: X (prepare_W.jl:33), then S (:34) -- nothing else is queued on a failed
   // factor (no output is touched, every pass of the host's +1e-5 I loop costs the two factorisations only), and both
@@ -155,10 +160,10 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   // from here on an error return must not leave the second stream writing the shared scratch
   struct S2Guard { hipStream_t s; bool on; ~S2Guard() { if (on) (void)hipStreamSynchronize(s); } } guard{s2, two};
   // Si = LS^-T LS^-1   (on the second stream: overlaps everything up to the end of this function)
-  hipLaunchKernelGGL(eye_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, Y2, n);
+  eye_mat(s2, Y2, n);
   LRN_TRY(trsm_left_lower(s2, LS, n, n, false, Y2, n, n, two ? tw2 : tw));
   LRN_TRY(gemm_nn(s2, n, Y2, true, Y2, false, b.Si.as<double>(), GEMM_TRI_LOWER));
-  hipLaunchKernelGGL(mirror_lower_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, b.Si.as<double>(), n);
+  mirror_lower(s2, b.Si.as<double>(), n);
   // SVD of CC = LS' LX = U D V' by one-sided Jacobi on CC' = LX' LS: its columns are rotated by
   // U and converge to V D, so V = (columns / D) needs no accumulation of rotations -- the rounds
   // are bandwidth-bound (every round streams the whole matrix), this removes the V half of it.
@@ -175,7 +180,7 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   toc(c, "prepw_gemm");
   tic(c);
   LRN_TRY(jacobi_svd(c, CC, nullptr, b.D.as<double>(), n, &sweeps, false));
-  hipLaunchKernelGGL(scale_cols_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, CC, b.D.as<double>(), n, 2, V);
+  hipLaunchKernelGGL(scale_cols_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, CC, b.D.as<double>(), n, 2, V);
   c->counts["svd_sweeps"] = sweeps;
   toc(c, "prepw_svd");
   tic(c);
@@ -184,22 +189,22 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
     LRN_HIP(c, hipEventRecord(c->evA, st));
     LRN_HIP(c, hipStreamWaitEvent(s2, c->evA, 0));
   }
-  hipLaunchKernelGGL(scale_cols_kernel, dim3(nb2((long)n * n)), dim3(256), 0, s2, V, b.D.as<double>(), n, 1, Y);
+  hipLaunchKernelGGL(scale_cols_kernel, dim3(nb((long)n * n)), dim3(256), 0, s2, V, b.D.as<double>(), n, 1, Y);
   LRN_TRY(trsm_left_lower(s2, LX, n, n, true, Y, n, n, two ? tw2 : tw));
-  hipLaunchKernelGGL(transpose_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(32, 8), 0, s2, Y, n, b.Gi.as<double>());
+  transpose_mat(s2, Y, n, b.Gi.as<double>());
   // G = LX (V D^-1/2)
-  hipLaunchKernelGGL(scale_cols_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, V, b.D.as<double>(), n, 0, CC);
+  hipLaunchKernelGGL(scale_cols_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, V, b.D.as<double>(), n, 0, CC);
   LRN_TRY(gemm_nn(st, n, LX, false, CC, false, b.G.as<double>()));
   if (c->opt.jacobi_warm) {          // U = LS' G D^-1/2  (G = LS^-T U D^1/2) for the next warm start
     LRN_TRY(ensure(c, b.Vprev, mm));
     LRN_TRY(gemm_nn(st, n, LS, true, b.G.as<double>(), false, CC));
-    hipLaunchKernelGGL(scale_cols_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, CC, b.D.as<double>(), n, 0,
+    hipLaunchKernelGGL(scale_cols_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, CC, b.D.as<double>(), n, 0,
                        b.Vprev.as<double>());
     b.have_Vprev = true;
   }
   // W = G G'
   LRN_TRY(gemm_nn(st, n, b.G.as<double>(), false, b.G.as<double>(), true, b.W.as<double>(), GEMM_TRI_LOWER));
-  hipLaunchKernelGGL(mirror_lower_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, b.W.as<double>(), n);
+  mirror_lower(st, b.W.as<double>(), n);
   // DDsi = 1/sqrt(diag(G' S G))
   LRN_TRY(gemm_nn(st, n, b.S.as<double>(), false, b.G.as<double>(), false, CC));
   hipLaunchKernelGGL(coldot_rsqrt_kernel, dim3(n), dim3(256), 0, st, b.G.as<double>(), CC, n, b.DDsi.as<double>());
@@ -593,14 +598,14 @@ int pgemm_nt(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* B
   }
   LRN_TRY(comm_allgather_cols(c, C, n, cb));
   c->counts["pgemm_sharded"] += 1;
-  if (Ct) hipLaunchKernelGGL(transpose_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(32, 8), 0, st, C, n, Ct);
+  if (Ct) transpose_mat(st, C, n, Ct);
   return LRN_OK;
 }
 
 int pgemm_nt_sym(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha, int tri) {
   if (!products_sharded(c, st, n)) return gemm_nt_sym(st, n, A, Bm, C, alpha, tri);
   LRN_TRY(pgemm_nt(c, st, n, A, Bm, C, 0, alpha, nullptr));
-  hipLaunchKernelGGL(sym_inplace_kernel, dim3(nb2((long)n * n)), dim3(256), 0, st, C, n);
+  hipLaunchKernelGGL(sym_inplace_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, C, n);
   return LRN_OK;
 }
 
@@ -639,7 +644,7 @@ int nt_factor(lrn_ctx* c, LmiBlock& b, int* info, double* minpiv) {
   }
   hipStream_t s2 = c->opt.prepw_streams ? c->stream2 : st;
   const bool two = s2 != st;
-  const unsigned ge = nb2((long)nn);
+  const unsigned ge = nb((long)nn);
   double *LX = b.LXf.as<double>(), *LS = b.LSf.as<double>();
   if (two) {
     LRN_HIP(c, hipEventRecord(c->evA, st));
@@ -718,19 +723,18 @@ int prepare_w_ns(lrn_ctx* c, LmiBlock& b, int* info, bool* converged) {
   const bool shp = products_sharded(c, st, n);
   hipStream_t s2 = (c->opt.prepw_streams && !shp) ? c->stream2 : st;
   const bool two = s2 != st;
-  const unsigned ge = nb2((long)nn);
+  const unsigned ge = nb((long)nn);
   if (two) {
     LRN_HIP(c, hipEventRecord(c->evA, st));
     LRN_HIP(c, hipStreamWaitEvent(s2, c->evA, 0));
   }
   tic(c);
-  const dim3 tg((n + 31) / 32, (n + 31) / 32), tb(32, 8);
   double* LSt = Zta;                                 // (free until the first Newton-Schulz step, which st orders after its reader)
-  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, s2, LS, n, LSt);
+  transpose_mat(s2, LS, n, LSt);
   if (two) LRN_HIP(c, hipEventRecord(c->evB, s2));
   // (round 4: S^-1 no longer through L_S^-1 -- a triangular solve with msz right-hand sides, 436 ms of a 2 s iteration at
   // msz 10^4 -- but from what the iteration produces anyway: K = L_X' S L_X  =>  S^-1 = L_X K^-1 L_X', see the end)
-  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, st, LX, n, LXt);
+  transpose_mat(st, LX, n, LXt);
   // K = CC' CC with CC = L_S' L_X (prepare_W.jl:39) -- NOT L_X' S L_X: with cond(X), cond(S) at 1e10 the entries of
   // |L_X'| |S| |L_X| are 1e10 times those of K and the explicit product has no correct digit left (measured: the
   // Newton-Schulz iteration then diverges); through the factors the error is that of CC itself, which the SVD shares
@@ -767,7 +771,7 @@ int prepare_w_ns(lrn_ctx* c, LmiBlock& b, int* info, bool* converged) {
   double ell = std::sqrt(ell2);
   double *Yc = Y, *Ytc = Yt0, *Zc = Z, *Ztc = Zt0;        // current set (Y, Y', Z, Z')
   double *Yn = Ya, *Ytn = Yta, *Zn = Za, *Ztn = Zta;      // next set
-  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, st, Yc, n, Ytc);
+  transpose_mat(st, Yc, n, Ytc);
   bool z_is_eye = true;
   int k = 0;
   // the transposed twin of a product: stored by the GEMM epilogue (8-byte scattered stores: 61 against 35 us at msz 800 on
@@ -782,7 +786,7 @@ int prepare_w_ns(lrn_ctx* c, LmiBlock& b, int* info, bool* converged) {
       return LRN_OK;
     }
     LRN_TRY(pgemm_nt(c, sx, n, A, Bm, C, 0, 1.0));
-    hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, sx, C, n, Ct);
+    transpose_mat(sx, C, n, Ct);
     return LRN_OK;
   };
   // Y T and T Z are independent: the second one on a third stream, so that two workgroups share every CU where one

@@ -677,6 +677,7 @@ def test_dense_passes_over_the_column_tails(dev, msz, nvar, mixed):
     try:
         _upload(dev, model)
         dev.set_scaling(0, W, G)
+        dev.reset_timing()
         AAd = model.AA[0].toarray()
         # makeRHS with a non-symmetric Rd + S: h = Rp + AA vec(W (Rd+S) W)
         RdS = rng.standard_normal((msz, msz))
@@ -689,6 +690,109 @@ def test_dense_passes_over_the_column_tails(dev, msz, nvar, mixed):
         x = rng.standard_normal(n)
         Mx = (AAd.T @ x).reshape(msz, msz, order="F"); Mx = 0.5 * (Mx + Mx.T)
         assert relerr(dev.matvec(x), AAd @ (W @ Mx @ W).reshape(-1, order="F")) < 1e-12
+        # all three passes took the column-tail tier
+        assert dev.count("op_dense_tri") == 3 and dev.count("op_dense") == 3
+        assert dev.count("op_dense_stream") == 0 and dev.count("op_dense_scalar") == 0
     finally:
         dev.set_option("dense_threshold", -1)
         dev.set_option("matvec_h", 0)
+
+
+_TIERS = ("op_dense_tri", "op_dense_stream", "op_dense_scalar")
+
+
+def _tier_model(msz, nvar, symmetric):
+    """The dense model of the test above; `symmetric` False: the same with ONE off-diagonal entry of one A_k changed
+    (AA row k = -vec(A_k)), so that the check on the device has to say "not symmetric"."""
+    model = _dense_model(msz, nvar, 7)
+    if not symmetric:
+        AA = model.AA[0].toarray()
+        AA[nvar // 2, 3 + 17 * msz] += 0.25                 # A_k[3, 17]; A_k[17, 3] stays
+        model.AA[0] = sp.csr_matrix(AA)
+    return model
+
+
+@pytest.mark.parametrize("symmetric", [True, False], ids=["sym", "asym"])
+@pytest.mark.parametrize("msz,nvar", [(256, 9), (256, 21), (258, 9), (258, 21), (257, 9), (257, 21)])
+def test_dense_pass_tiers(dev, msz, nvar, symmetric):
+    """Every tier of the passes over dense constraint data -- tri (symmetric data, msz even >= 256: column tails), stream
+    (the same sizes, data not exactly symmetric: 16-byte loads over both triangles), scalar (everything else) -- computes
+    AA vec(Z) and mat(AA'x), with one and with two weight matrices per pass, and the counters name the tier that ran.
+    msz 256: the smallest stream / tri size; 258: msz^2 / 2 is no multiple of 512 (tail of the unrolled loop, column
+    tails that end inside a chunk); 257: odd -> scalar.  nvar 9, 21: nd % 4 = 1 (last workgroup with one live constraint),
+    one and two full groups of the 8-deep loop of mat(AA'x) plus a remainder.  For data that are not symmetric mat() is
+    (M + M')/2 as in the oracle (kron_etc.jl:13-18)."""
+    rng = np.random.default_rng(msz + nvar)
+    model = _tier_model(msz, nvar, symmetric)
+    n = model.n
+    W, G = _spd(msz, 9)
+    AAd = model.AA[0].toarray()
+    vecF = lambda M: M.reshape(-1, order="F")
+    matF = lambda v: (lambda M: 0.5 * (M + M.T))(v.reshape(msz, msz, order="F"))
+    expect = "op_dense_scalar" if msz % 2 else ("op_dense_tri" if symmetric else "op_dense_stream")
+    dev.set_option("dense_threshold", 1000)
+    try:
+        _upload(dev, model)
+        dev.set_scaling(0, W, G)
+        dev.reset_timing()
+        # makeRHS with a non-symmetric Rd + S: h = Rp + AA vec(W (Rd+S) W)
+        RdS = rng.standard_normal((msz, msz))
+        Rp = rng.standard_normal(n)
+        h = dev.make_rhs(Rp, [RdS])
+        e = relerr(h, Rp + AAd @ vecF(W @ RdS @ W))
+        print(f"make_rhs {e:.3e}")
+        assert e < 1e-12
+        # MyA through the dense route: mat(AA'x), two products, AA vec(.)
+        dev.set_option("matvec_h", 1)
+        x = rng.standard_normal(n)
+        e = relerr(dev.matvec(x), AAd @ vecF(W @ matF(AAd.T @ x) @ W))
+        print(f"matvec {e:.3e}")
+        assert e < 1e-12
+        # resident form: the single products (ip_aa_x, ip_rhs_pred) against the pair kernels (ip_rhs_pred2) and NumPy
+        X = np.eye(msz) + 0.3 * (lambda Q: Q @ Q.T)(rng.standard_normal((msz, msz)) / np.sqrt(msz))
+        S = np.eye(msz) + 0.3 * (lambda Q: Q @ Q.T)(rng.standard_normal((msz, msz)) / np.sqrt(msz))
+        Cm = rng.standard_normal((msz, msz)) / np.sqrt(msz); Cm = 0.5 * (Cm + Cm.T)
+        y = rng.standard_normal(n)
+        dev.ip_set_c(0, Cm)
+        dev.ip_set_iterate(0, X, S)
+        assert dev.ip_prepare_w(0) == 0
+        dev.ip_residual_d(y)
+        aax1 = dev.ip_aa_x()
+        rhs1 = dev.ip_rhs_pred()
+        aax2, rhs2 = dev.ip_rhs_pred2()
+        Wd = dev.dbg_get_block(0, "W")[0]
+        Rd = Cm - S - matF(AAd.T @ y)
+        errs = dict(pair_aax=relerr(aax2, aax1), pair_rhs=relerr(rhs2, rhs1), aax=relerr(aax1, AAd @ vecF(X)),
+                    rhs=relerr(rhs1, AAd @ vecF(Wd @ (Rd + S) @ Wd)), Rd=relerr(dev.dbg_get_block(0, "Rd")[0], Rd))
+        print(" ".join(f"{k} {v:.3e}" for k, v in errs.items()))
+        assert max(errs.values()) < 1e-12
+        # the tier: make_rhs, matvec (two passes), residual_d, aa_x, rhs_pred, rhs_pred2 = seven passes, all on one route
+        cnt = {k: dev.count(k) for k in _TIERS}
+        print(cnt)
+        assert dev.count("op_dense") == 7
+        assert cnt == {k: (7 if k == expect else 0) for k in _TIERS}
+    finally:
+        dev.set_option("dense_threshold", -1)
+        dev.set_option("matvec_h", 0)
+
+
+def test_dense_route_is_decided_at_upload(dev):
+    """The symmetry check and the chunk table of the column tails belong to the upload: the first pass after it already
+    takes the tri tier and gives the bits of the second."""
+    msz, nvar = 256, 9
+    model = _dense_model(msz, nvar, 7)
+    W, G = _spd(msz, 9)
+    rng = np.random.default_rng(3)
+    RdS = rng.standard_normal((msz, msz))
+    Rp = rng.standard_normal(model.n)
+    dev.set_option("dense_threshold", 1000)
+    try:
+        _upload(dev, model)
+        dev.set_scaling(0, W, G)
+        dev.reset_timing()
+        h1 = dev.make_rhs(Rp, [RdS])
+        h2 = dev.make_rhs(Rp, [RdS])
+        assert np.array_equal(h1, h2)
+        assert dev.count("op_dense_tri") == 2 and dev.count("op_dense_stream") == 0 and dev.count("op_dense_scalar") == 0
+    finally:
+        dev.set_option("dense_threshold", -1)
