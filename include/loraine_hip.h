@@ -326,6 +326,11 @@ int lrn_hbm_copy_peak(lrn_ctx* ctx, int64_t bytes, double* gbps);
 int lrn_dbg_gemm(lrn_ctx* ctx, int transA, int transB, int M, int N, int K, double alpha,
                  const double* A, int lda, const double* B, int ldb, double beta, double* C,
                  int ldc, int flags, int ksplit);
+/* What lrn_dbg_gemm would launch for the same arguments, decided on the host alone (no context, no device): out6 =
+ * { kernel, tile side, grid x, grid z, dynamic LDS bytes, split-K slabs }.  kernel: 0 nothing, 1 / 2 register-staged
+ * 64 / 128 tile, 3 direct-to-LDS 128 tile, 4 64-tile DMA pipeline, 5 K-segment, 6 / 7 / 8 K-contiguous 128 / 160 / strip. */
+int lrn_dbg_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, double beta, int ldc, int flags,
+                      int ksplit, int* out6);
 int lrn_dbg_mfma_probe(lrn_ctx* ctx, const double* A16x4, const double* B4x16, double* D16x16);
 int lrn_dbg_potrf(lrn_ctx* ctx, int n, double* A, int* info);
 int lrn_dbg_potrs(lrn_ctx* ctx, int n, const double* A, const double* b, double* x, int* info);

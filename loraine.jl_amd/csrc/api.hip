@@ -508,6 +508,34 @@ int lrn_dbg_gemm(lrn_ctx* c, int transA, int transB, int M, int N, int K, double
   return rc;
 }
 
+int lrn_dbg_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, double beta, int ldc, int flags, int ksplit,
+                      int* out6) {
+  if (!out6) return LRN_ERR_ARG;
+  // the descriptor of lrn_dbg_gemm over operands that are never touched (16-byte aligned, as device allocations are)
+  alignas(16) static double dummy[2];
+  GemmDesc g;
+  g.A = dummy; g.B = dummy; g.C = dummy;
+  g.M = M; g.N = N; g.K = K;
+  if (!transA) { g.sAm = 1; g.sAk = lda; } else { g.sAm = lda; g.sAk = 1; }
+  if (!transB) { g.sBk = 1; g.sBn = ldb; } else { g.sBk = ldb; g.sBn = 1; }
+  g.flags = flags;
+  if (ksplit > 1 || (flags & GEMM_KSEG_TRI)) {
+    g.sCm = 1; g.sCn = M; g.ksplit = ksplit < 1 ? 1 : ksplit; g.sCs = (long)M * N;
+    if (flags & GEMM_KSEG_TRI) {
+      int ld = 1;
+      while ((long)(ld + 1) * (ld + 1) <= K) ++ld;
+      g.kseg_ld = ld; g.kseg_cols = ld;
+    }
+  } else {
+    g.sCm = 1; g.sCn = ldc; g.beta = beta;
+  }
+  GemmPlanInfo info;
+  const int rc = gemm_plan_info(g, &info);
+  const int v[6] = {info.kernel, info.tile, info.grid_x, info.grid_z, info.dyn_lds, info.slabs};
+  for (int i = 0; i < 6; ++i) out6[i] = v[i];
+  return rc;
+}
+
 int lrn_dbg_mfma_probe(lrn_ctx* c, const double* A, const double* B, double* D) {
   if (!c || !A || !B || !D) return LRN_ERR_ARG;
   LRN_HIP(c, hipSetDevice(c->device));

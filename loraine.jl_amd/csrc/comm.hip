@@ -87,7 +87,7 @@ int comm_allgather(lrn_ctx* c, const double* send, double* recv, long count) {
 }
 
 // Column blocks of an n x n column-major matrix, in place: rank r holds columns [r cb, min(n, (r + 1) cb)) and receives
-// the others (the sharded n^3 products of the resident path, prepw.hip::pgemm_nt).  RCCL: one broadcast per rank inside a
+// the others (the sharded n^3 products of the resident path, products.hip::pgemm_nt).  RCCL: one broadcast per rank inside a
 // group (the last block may be narrower); host transport: packed through the equal-count all-gather callback.
 int comm_allgather_cols(lrn_ctx* c, double* C, int n, int cb) {
   Comm* m = c->comm;

@@ -20,8 +20,10 @@
 #include "lrn_common.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <map>
 #include <mutex>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -291,12 +293,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmParams p) {
       }
 }
 
-template <int BM, int BN, bool KSEG, bool EPI>
-static void launch4(hipStream_t st, const GemmParams& p, bool akc, bool bkc, dim3 grid) {
-  if (akc && bkc) hipLaunchKernelGGL((gemm_f64_kernel<BM, BN, true, true, KSEG, EPI>), grid, dim3(256), 0, st, p);
-  else if (akc) hipLaunchKernelGGL((gemm_f64_kernel<BM, BN, true, false, KSEG, EPI>), grid, dim3(256), 0, st, p);
-  else if (bkc) hipLaunchKernelGGL((gemm_f64_kernel<BM, BN, false, true, KSEG, EPI>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((gemm_f64_kernel<BM, BN, false, false, KSEG, EPI>), grid, dim3(256), 0, st, p);
+using GemmFn = void (*)(GemmParams);
+// the instantiation for operands that are K-contiguous (unit K stride, not also unit stride along the tile) or not
+template <int BT, bool KSEG, bool EPI>
+static GemmFn reg_kernel(const GemmDesc& d) {
+  const bool akc = (d.sAk == 1 && d.sAm != 1), bkc = (d.sBk == 1 && d.sBn != 1);
+  if (akc) return bkc ? gemm_f64_kernel<BT, BT, true, true, KSEG, EPI> : gemm_f64_kernel<BT, BT, true, false, KSEG, EPI>;
+  return bkc ? gemm_f64_kernel<BT, BT, false, true, KSEG, EPI> : gemm_f64_kernel<BT, BT, false, false, KSEG, EPI>;
+}
+template <int BT>
+static GemmFn reg_kernel(const GemmDesc& d, bool epi) {
+  if (d.flags & GEMM_KSEG_TRI) return reg_kernel<BT, true, false>(d);
+  return epi ? reg_kernel<BT, false, true>(d) : reg_kernel<BT, false, false>(d);
 }
 
 // ------------------------------------------------------------------ direct-to-LDS variant
@@ -1018,6 +1026,47 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kseg_lds_kernel(GemmParams p)
     }
 }
 
+// ------------------------------------------------------------------ host side: plan, then launch
+// plan_gemm() makes every decision of a product -- orientation, validation, K ranges, tile lists, kernel, grid -- without a
+// HIP call or an allocation (it runs for every product; the launch chains of the small solves are host-bound);
+// launch_gemm() fetches the tile lists and issues the one launch of the plan.
+enum GemmKernel : int {
+  GK_NONE = 0,        // nothing to launch (empty product, no tile of the requested class)
+  GK_REG64,           // gemm_f64_kernel<64, 64, ...>: register-staged, any strides, any epilogue
+  GK_REG128,          // gemm_f64_kernel<128, 128, ...>
+  GK_LDS,             // gemm_f64_lds_kernel: 128-tile, operands straight into LDS
+  GK_MID,             // gemm_f64_mid_kernel: 64-tile, three-stage LDS DMA pipeline
+  GK_KSEG,            // gemm_f64_kseg_lds_kernel<false, 4, 4>: GEMM_KSEG_TRI
+  GK_KFLAT128,        // gemm_f64_kseg_lds_kernel<true, 4, 4>: GEMM_KFLAT
+  GK_KFLAT160,        // gemm_f64_kseg_lds_kernel<true, 5, 5>: GEMM_KFLAT | GEMM_TILE160
+  GK_KFLAT_STRIP,     // gemm_f64_kseg_lds_kernel<true, 4, 5>: the last 128 + r rows of tile_class 5
+};
+
+// what get_tile_list is asked for; n: entries of the list, padding included
+struct TileListKey {
+  int tilesM, tilesN, tri, short_sel;
+  bool edge_m, edge_n, diag;
+  int n;
+};
+
+struct GemmPlan {
+  GemmKernel kernel;
+  int tile_m, tile_n;     // workgroup tile
+  dim3 grid;
+  unsigned dyn_lds;
+  bool epi;               // the kernel instantiation with the epilogues (flags, C2)
+  int slabs;              // split-K factor chosen for gemm() / gemm_slabs(): p.d then writes `slabs` slabs, 1 = none
+  int nlists;
+  TileListKey lists[2];   // -> p.tile_list, p.tile_list2
+  GemmParams p;           // oriented descriptor, K ranges, list lengths, tile origin
+};
+
+// gemm() has no context to report into: the reason of its last failure on this thread, appended by
+// lrn_last_error (api.hip) so that a bare LRN_ERR_ARG from deep inside a driver is not a stale message
+static thread_local const char* tls_gemm_error = nullptr;
+const char* gemm_last_error() { return tls_gemm_error; }
+static int gemm_fail(int code, const char* why) { tls_gemm_error = why; return code; }
+
 static bool kseg_lds_path_ok(const GemmDesc& d) {
   if (d.sAk != 1 || d.sBk != 1 || d.beta != 0.0) return false;
   if ((d.flags & GEMM_KFLAT) ? ((d.kflat_total & 15) || (d.kflat_diag & 15)) : (d.kseg_ld & 15)) return false;
@@ -1031,10 +1080,8 @@ static bool lds_path_ok(const GemmDesc& d) {
   if (d.sAm != 1 || d.sBn != 1 || d.ksplit != 1) return false;
   if (d.flags & GEMM_SQUARE_BLOCKSUM) return false;        // (its epilogue is the generic kernel's)
   // (round 4: rows that are only 8-byte aligned -- odd leading dimensions -- are fine: the 16-byte DMA was measured correct
-  // from them on gfx950, tools/probe_unaligned_dma.py and test_gpu_blocks.py; LRN_LDS_ALIGNED=1 restores the old rule)
-  static const bool aligned_only = getenv("LRN_LDS_ALIGNED") != nullptr;
-  if (d.sAk < d.M || d.sBk < d.N || (aligned_only && ((d.sAk & 1) || (d.sBk & 1)))) return false;
-  if (aligned_only && (((uintptr_t)d.A & 15) || ((uintptr_t)d.B & 15) || (d.bA & 1) || (d.bB & 1))) return false;
+  // from them on gfx950, tools/probe_unaligned_dma.py and test_gpu_blocks.py)
+  if (d.sAk < d.M || d.sBk < d.N) return false;
   // short-K products (Cholesky panel / trailing updates) stay on the generic kernel: the DMA
   // pipeline needs a long K loop to pay off, and it keeps this kernel's profile = the assembly GEMMs
   if (d.K < 256) return false;
@@ -1043,6 +1090,15 @@ static bool lds_path_ok(const GemmDesc& d) {
   return true;
 }
 
+// a plain mid-size product, or its split-K slabs (gemm_maybe_slabs below): three-stage LDS DMA pipeline
+static bool mid_path_ok(const GemmDesc& d, bool epi) {
+  const bool tri = d.flags & (GEMM_TRI_LOWER | GEMM_TRI_UPPER);
+  return !epi && d.batch == 1 && d.beta == 0.0 && d.sAm == 1 && d.sBn == 1 && d.K >= 64 && d.sCn == 1 && d.sAk >= d.M &&
+         d.sBk >= d.N && !(d.flags & ~(GEMM_SMALL_TILE | GEMM_TRI_LOWER | GEMM_TRI_UPPER)) &&
+         (!tri || (d.M == d.N && d.ksplit > 1)) && (double)d.K * (double)std::max(d.sAk, d.sBk) * 8.0 < 2.0e9;
+}
+
+// ---- tile lists
 // (tm, tn) enumeration: 8x8 super-tiles (tm fastest inside), only the tiles a TRI flag keeps.
 // Consecutive list entries share operand panels, and the XCD swizzle hands each XCD a
 // contiguous run of the list, so co-resident workgroups of one L2 re-use panels.
@@ -1051,47 +1107,45 @@ static bool lds_path_ok(const GemmDesc& d) {
 // tiles when `diag` (GEMM_DIAG_*).  The K-contiguous rank-k update runs them as two launches: its workgroups are all
 // equally long and advance in lock-step through K (that is where its L2 hits come from); shorter workgroups mixed in
 // break the step -- measured at C4: 496 -> 520 ms although 7 % of the MFMAs were skipped.
-static const int2* get_tile_list(int tilesM, int tilesN, int tri, int* count, int short_sel = 0, bool edge_m = false,
-                                 bool edge_n = false, bool diag = false, int korder = 0) {
-  struct Key {
-    int a, b, c;
-    bool operator<(const Key& o) const { return a != o.a ? a < o.a : (b != o.b ? b < o.b : c < o.c); }
-  };
-  tri |= short_sel << 8 | (edge_m ? 1 << 12 : 0) | (edge_n ? 1 << 13 : 0) | (diag ? 1 << 14 : 0) | korder << 16;
-  struct Val { int2* dev; int n; };
-  static std::map<Key, Val> cache[16];
+static bool tile_in_list(const TileListKey& k, int tm, int tn) {
+  if (k.tri == GEMM_TRI_LOWER && tn > tm) return false;
+  if (k.tri == GEMM_TRI_UPPER && tm > tn) return false;
+  const bool shrt = (k.edge_m && tm == k.tilesM - 1) || (k.edge_n && tn == k.tilesN - 1) || (k.diag && tm == tn);
+  return !((k.short_sel == 1 && shrt) || (k.short_sel == 2 && !shrt));
+}
+
+// The kernels take blockIdx.x % 8 for the XCD of a workgroup (flat id % 8 in hardware): true for every z-slice of
+// the grid only if the list length is a multiple of 8 -- the lists are padded with entries whose workgroups exit at once.
+static TileListKey tile_list_key(int tilesM, int tilesN, int tri, int short_sel = 0, bool edge_m = false, bool edge_n = false,
+                                 bool diag = false) {
+  TileListKey k{tilesM, tilesN, tri & (GEMM_TRI_LOWER | GEMM_TRI_UPPER), short_sel, edge_m, edge_n, diag, 0};
+  if (!k.tri && !short_sel) k.n = tilesM * tilesN;      // (every plain product: no walk over its tiles)
+  else
+    for (int tn = 0; tn < tilesN; ++tn)
+      for (int tm = 0; tm < tilesM; ++tm) k.n += tile_in_list(k, tm, tn);
+  k.n = (k.n + 7) & ~7;
+  return k;
+}
+
+// the list on the current device, built and uploaded at its first use
+static const int2* get_tile_list(const TileListKey& k) {
+  static std::map<std::tuple<int, int, int>, int2*> cache[16];
   static std::mutex mu;                       // contexts on several host threads share the cache
   std::lock_guard<std::mutex> lock(mu);
   int dev = 0;
   (void)hipGetDevice(&dev);
   auto& cm = cache[dev & 15];
-  Key k{tilesM, tilesN, tri};
-  auto it = cm.find(k);
-  if (it != cm.end()) { *count = it->second.n; return it->second.dev; }
+  const std::tuple<int, int, int> key{k.tilesM, k.tilesN, k.tri | k.short_sel << 8 | k.edge_m << 12 | k.edge_n << 13 | k.diag << 14};
+  auto it = cm.find(key);
+  if (it != cm.end()) return it->second;
   std::vector<int2> v;
   const int GS = 8;
-  for (int sn = 0; sn < tilesN; sn += GS)
-    for (int sm = 0; sm < tilesM; sm += GS)
-      for (int tn = sn; tn < sn + GS && tn < tilesN; ++tn)
-        for (int tm = sm; tm < sm + GS && tm < tilesM; ++tm) {
-          if ((tri & 3) == GEMM_TRI_LOWER && tn > tm) continue;
-          if ((tri & 3) == GEMM_TRI_UPPER && tm > tn) continue;
-          const bool shrt = (edge_m && tm == tilesM - 1) || (edge_n && tn == tilesN - 1) || (diag && tm == tn);
-          if ((short_sel == 1 && shrt) || (short_sel == 2 && !shrt)) continue;
-          v.push_back(make_int2(tm, tn));
-        }
-  if (korder) {
-    // (measurement, LRN_TILE_ORDER: the tiles of a triangular-K product by K length -- korder 1 / 2: K grows with tn / tm
-    // downwards -- longest, shortest, second longest, second shortest, ...)
-    std::vector<int2> srt = v, mix;
-    std::stable_sort(srt.begin(), srt.end(), [&](const int2& a, const int2& b) { return korder == 1 ? a.y < b.y : a.x < b.x; });
-    for (size_t i = 0, j = srt.size(); i < j;) {
-      mix.push_back(srt[i++]);
-      if (i < j) mix.push_back(srt[--j]);
-    }
-    v.swap(mix);
-  }
-  if (short_sel == 2 && diag) {
+  for (int sn = 0; sn < k.tilesN; sn += GS)
+    for (int sm = 0; sm < k.tilesM; sm += GS)
+      for (int tn = sn; tn < sn + GS && tn < k.tilesN; ++tn)
+        for (int tm = sm; tm < sm + GS && tm < k.tilesM; ++tm)
+          if (tile_in_list(k, tm, tn)) v.push_back(make_int2(tm, tn));
+  if (k.short_sel == 2 && k.diag) {
     // every XCD walks one contiguous run of the list: deal the diagonal tiles (10 of 16 blocks per wave) and the
     // edge tiles (a quarter of the rows) alternately, so that the runs are equally long
     std::vector<int2> dg, ed, mix;
@@ -1102,66 +1156,28 @@ static const int2* get_tile_list(int tilesM, int tilesN, int tri, int* count, in
     }
     v.swap(mix);
   }
-  // The kernels take blockIdx.x % 8 for the XCD of a workgroup (flat id % 8 in hardware): true for every z-slice of
-  // the grid only if the list length is a multiple of 8 -- pad with entries whose workgroups exit at once.
-  const int n_real = (int)v.size();
-  while (n_real > 0 && (v.size() & 7)) v.push_back(make_int2(-1, -1));
-  Val val{nullptr, (int)v.size()};
-  if (hipMalloc(&val.dev, sizeof(int2) * (v.size() + 1)) != hipSuccess) { *count = 0; return nullptr; }
-  (void)hipMemcpy(val.dev, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice);
-  cm[k] = val;
-  *count = val.n;
-  return val.dev;
+  v.resize((size_t)k.n, make_int2(-1, -1));
+  int2* devp = nullptr;
+  if (hipMalloc(&devp, sizeof(int2) * (v.size() + 1)) != hipSuccess) return nullptr;
+  (void)hipMemcpy(devp, v.data(), sizeof(int2) * v.size(), hipMemcpyHostToDevice);
+  cm[key] = devp;
+  return devp;
 }
 
-// gemm() has no context to report into: the reason of its last failure on this thread, appended by
-// lrn_last_error (api.hip) so that a bare LRN_ERR_ARG from deep inside a driver is not a stale message
-static thread_local const char* tls_gemm_error = nullptr;
-const char* gemm_last_error() { return tls_gemm_error; }
-static int gemm_fail(int code, const char* why) { tls_gemm_error = why; return code; }
-
-static int gemm_impl(hipStream_t st, const GemmDesc& din);
-// hipFuncSetAttribute is per device: one process may drive several (one context per GPU)
-static bool big_tile_attr_ok() {
-  static bool done[64] = {false}, ok[64] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  if (!done[dev]) {
-    ok[dev] = hipFuncSetAttribute((const void*)gemm_f64_kseg_lds_kernel<true, 5, 5>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 160 * BK * 8) == hipSuccess &&
-              hipFuncSetAttribute((const void*)gemm_f64_kseg_lds_kernel<true, 4, 5>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 160) * BK * 8) == hipSuccess;
-    done[dev] = true;
-  }
-  return ok[dev];
+// ---- cost model of gemm_f64_mid_kernel (us; round 4, calibrated at msz 640 .. 1400, tools/gemm_nt_times.py): a CU shares
+// its MFMA pipe between the workgroups it holds (three fit), one K-tile of one workgroup costs 0.515 us of it, 1.5 x that
+// when the workgroup is alone on its CU.  `workgroups` equally long workgroups of `ktiles` K-tiles on the 256 CUs:
+static double mid_kernel_us(long workgroups, double ktiles) {
+  const long per_cu = (workgroups + 255) / 256;
+  return (double)per_cu * ktiles * 0.515 * (per_cu == 1 ? 1.5 : 1.0);
 }
 
 // ---- mid-size products (round 3): a plain product whose 64 x 64 tiles do not fill the chip (msz ~ 800: 169 tiles on 256 CUs,
 // one workgroup per CU, one wave per SIMD) is bound by the latency of its global loads -- 45 us for 801^3 where the MFMAs
 // need 21.  Splitting K over 2-4 workgroups per tile puts several workgroups on every CU (their loads overlap each other's
-// MFMAs); the slabs are added in a fixed order by reduce_slabs.  Slab memory: one buffer per stream (products on different
-// streams run concurrently), grown on demand, kept for the life of the process.
-#include <map>
-#include <mutex>
-static double* split_slabs(hipStream_t st, size_t bytes) {
-  static std::mutex mu;
-  static std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> cache;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lk(mu);
-  auto& e = cache[{dev, st}];
-  if (e.second < bytes) {
-    if (e.first) { (void)hipStreamSynchronize(st); (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
-    if (hipMalloc(&e.first, bytes) != hipSuccess) { e.first = nullptr; return nullptr; }
-    e.second = bytes;
-  }
-  return static_cast<double*>(e.first);
-}
-
+// MFMAs); the slabs are added in a fixed order by reduce_slabs.
 static int auto_split_factor(const GemmDesc& d) {
-  static const int forced = getenv("LRN_GEMM_SPLIT") ? atoi(getenv("LRN_GEMM_SPLIT")) : -1;    // 0 / 1: off; k: k slabs
-  if (forced == 0 || forced == 1) return 1;
-  // (flags: none, or GEMM_TRI_LOWER alone -- a symmetric product of which only the lower 64-tiles are wanted, gemm_slabs)
+  // (flags: none, or GEMM_TRI_LOWER alone -- a symmetric product of which only the lower 64-tiles are wanted)
   const bool tril = d.flags == GEMM_TRI_LOWER && d.M == d.N;
   if (d.ksplit > 1 || d.batch != 1 || (d.flags != 0 && !tril) || d.C2 || d.K < 256 || d.M < 128 || d.N < 128) return 1;
   const long t128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
@@ -1169,138 +1185,50 @@ static int auto_split_factor(const GemmDesc& d) {
   const long tm64 = (d.M + 63) / 64;
   const long t64 = tril ? tm64 * (tm64 + 1) / 2 : tm64 * ((d.N + 63) / 64);
   // C dense and contiguous (reduce_slabs adds flat vectors)
-  const long a = d.sCm < 0 ? -d.sCm : d.sCm, b = d.sCn < 0 ? -d.sCn : d.sCn;
+  const long a = std::labs(d.sCm), b = std::labs(d.sCn);
   if (!((a == 1 && b == d.M) || (b == 1 && a == d.N))) return 1;
-  if (forced > 1) return forced > 8 ? 8 : forced;
-  // Round 4: the factor that minimises a small cost model of gemm_f64_mid_kernel (us; calibrated at msz 640 .. 1400,
-  // tools/gemm_nt_times.py): a CU shares its MFMA pipe between the workgroups it holds (three fit), one K-tile of one
-  // workgroup costs 0.515 us of it (1.5 x that when the workgroup is alone on its CU), plus launch and epilogue, plus -- for
-  // slabs -- the pass that adds them ((ks + 1) M N doubles at 4 TB/s and a launch).
+  // Round 4: the factor that minimises the kernel's cost plus launch and epilogue, plus -- for slabs -- the pass that adds
+  // them ((ks + 1) M N doubles at 4 TB/s and a launch).
   int best = 1;
   double best_us = 1e300;
   for (int ks = 1; ks <= (tril ? 6 : 4); ++ks) {
     if (ks > 1 && d.K / ks < 96) break;
-    const long wgs = t64 * ks;
-    const long per_cu = (wgs + 255) / 256;
-    const double ktiles = std::ceil((double)d.K / 16.0 / ks);
-    double us = (double)per_cu * ktiles * 0.515 * (per_cu == 1 ? 1.5 : 1.0) + 5.0;
+    double us = mid_kernel_us(t64 * ks, std::ceil((double)d.K / 16.0 / ks)) + 5.0;
     if (ks > 1) us += 4.0 + (double)(ks + 1) * (double)d.M * (double)d.N * 8.0 / 4.0e6;
     if (us < best_us) { best_us = us; best = ks; }
   }
   return best;
 }
 
-static int gemm_maybe_slabs(hipStream_t st, const GemmDesc& din, SlabSrc* out) {
-  tls_gemm_error = nullptr;            // (a stale reason must not be appended to a later, unrelated error)
-  const int ks = auto_split_factor(din);
-  if (din.flags == GEMM_TRI_LOWER && out && (ks < 2 || din.beta != 0.0)) {
-    out->p = nullptr; out->stride = 0; out->n = 0;     // (lower tiles as slabs or not at all: the caller takes its other route)
-    return LRN_OK;
+// Orient so that the kernel's n (lane-contiguous in the MFMA result) is the contiguous dimension of C: C^T = B^T A^T.
+static bool orient(GemmDesc& d) {
+  if (std::labs(d.sCm) >= std::labs(d.sCn)) return false;
+  static const int pairs[4][2] = {{GEMM_KFROM_N, GEMM_KFROM_M}, {GEMM_KTO_N, GEMM_KTO_M}, {GEMM_TRI_LOWER, GEMM_TRI_UPPER},
+                                  {GEMM_DIAG_LOWER, GEMM_DIAG_UPPER}};
+  for (const auto& pr : pairs) {
+    if (d.flags & pr[0]) d.flags = (d.flags & ~pr[0]) | pr[1];
+    else if (d.flags & pr[1]) d.flags = (d.flags & ~pr[1]) | pr[0];
   }
-  if (ks > 1) {
-    const size_t mn = (size_t)din.M * din.N;
-    double* slabs = split_slabs(st, mn * ks * 8);
-    if (slabs) {
-      GemmDesc d2 = din;
-      d2.C = slabs; d2.sCs = (long)mn; d2.ksplit = ks; d2.beta = 0.0;
-      d2.flags |= GEMM_SMALL_TILE;
-      const int rc2 = gemm_impl(st, d2);
-      if (rc2 != LRN_OK) { if (!tls_gemm_error) tls_gemm_error = "kernel launch failed"; return rc2; }
-      if (out && din.beta == 0.0) {
-        out->p = slabs; out->stride = (long)mn; out->n = ks;
-        return LRN_OK;
-      }
-      if (out) { out->p = din.C; out->stride = 0; out->n = 1; }
-      return reduce_slabs(st, slabs, (long)mn, ks, din.C, (long)mn, din.beta);
-    }
-  }
-  if (out) { out->p = din.C; out->stride = 0; out->n = 1; }
-  const int rc = gemm_impl(st, din);
-  if (rc != LRN_OK && !tls_gemm_error) tls_gemm_error = "kernel launch failed";
-  return rc;
+  d.flags &= ~GEMM_DIAG_LOWER_Z;                 // (a hint for the unswapped orientation only)
+  std::swap(d.A, d.B);
+  std::swap(d.bA, d.bB);
+  std::swap(d.sAm, d.sBn);
+  std::swap(d.sAk, d.sBk);
+  std::swap(d.sCm, d.sCn);
+  std::swap(d.M, d.N);
+  return true;
 }
 
-int gemm(hipStream_t st, const GemmDesc& din) { return gemm_maybe_slabs(st, din, nullptr); }
-int gemm_slabs(hipStream_t st, const GemmDesc& din, SlabSrc* out) { return gemm_maybe_slabs(st, din, out); }
-
-static int gemm_impl(hipStream_t st, const GemmDesc& din) {
-  GemmParams p;
-  p.d = din;
+// the K ranges of the splits: p.kchunk (plain), p.kcols (GEMM_KSEG_TRI), p.kcols / p.kcols2 (GEMM_KFLAT)
+static int plan_k_ranges(GemmParams& p) {
   GemmDesc& d = p.d;
-  if (d.M <= 0 || d.N <= 0 || d.batch <= 0) return LRN_OK;
-  if (d.ksplit < 1) d.ksplit = 1;
-  if (d.ksplit > MAX_KSPLIT) return gemm_fail(LRN_ERR_ARG, "gemm: d.ksplit > MAX_KSPLIT");
-  // Orient so that the kernel's n (lane-contiguous in the MFMA result) is the contiguous
-  // dimension of C: C^T = B^T A^T.
-  long asCm = d.sCm < 0 ? -d.sCm : d.sCm, asCn = d.sCn < 0 ? -d.sCn : d.sCn;
-  bool swapped = false;
-  if (asCm < asCn) {
-    swapped = true;
-    if (d.flags & GEMM_KFROM_N) d.flags = (d.flags & ~GEMM_KFROM_N) | GEMM_KFROM_M;
-    else if (d.flags & GEMM_KFROM_M) d.flags = (d.flags & ~GEMM_KFROM_M) | GEMM_KFROM_N;
-    if (d.flags & GEMM_KTO_N) d.flags = (d.flags & ~GEMM_KTO_N) | GEMM_KTO_M;
-    else if (d.flags & GEMM_KTO_M) d.flags = (d.flags & ~GEMM_KTO_M) | GEMM_KTO_N;
-    std::swap(d.A, d.B);
-    std::swap(d.bA, d.bB);
-    long sAm = d.sBn, sAk = d.sBk, sBk = d.sAk, sBn = d.sAm;
-    d.sAm = sAm; d.sAk = sAk; d.sBk = sBk; d.sBn = sBn;
-    std::swap(d.sCm, d.sCn);
-    std::swap(d.M, d.N);
-    if (d.flags & GEMM_TRI_LOWER) d.flags = (d.flags & ~GEMM_TRI_LOWER) | GEMM_TRI_UPPER;
-    else if (d.flags & GEMM_TRI_UPPER) d.flags = (d.flags & ~GEMM_TRI_UPPER) | GEMM_TRI_LOWER;
-    if (d.flags & GEMM_DIAG_LOWER) d.flags = (d.flags & ~GEMM_DIAG_LOWER) | GEMM_DIAG_UPPER;
-    else if (d.flags & GEMM_DIAG_UPPER) d.flags = (d.flags & ~GEMM_DIAG_UPPER) | GEMM_DIAG_LOWER;
-    d.flags &= ~GEMM_DIAG_LOWER_Z;                 // (a hint for the unswapped orientation only)
-  }
-  const bool tri = d.flags & (GEMM_TRI_LOWER | GEMM_TRI_UPPER);
-  const bool kflat = d.flags & GEMM_KFLAT;
-  const bool kseg = (d.flags & GEMM_KSEG_TRI) || kflat;
-  const bool kfrom = d.flags & (GEMM_KFROM_N | GEMM_KFROM_M | GEMM_KTO_N | GEMM_KTO_M);   // triangular K ranges
-  if ((d.flags & GEMM_C_MIRROR) && (d.M != d.N || !tri || d.beta != 0.0)) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & GEMM_C_MIRROR) && (d.M != d.N || !tri || d.beta != 0.0)");
-  // triangular K ranges: the operand that is triangular spans K (a trailing sub-block may be narrower in the other
-  // dimension: columns [c0, c1) of a product with the trailing block of the factor)
-  if (kfrom && (d.ksplit != 1 || kseg)) return gemm_fail(LRN_ERR_ARG, "gemm: kfrom && (d.ksplit != 1 || kseg)");
-  if ((d.flags & (GEMM_KFROM_N | GEMM_KTO_N)) && d.N > d.K) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & (GEMM_KFROM_N | GEMM_KTO_N)) && d.N > d.K");
-  if ((d.flags & (GEMM_KFROM_M | GEMM_KTO_M)) && d.M > d.K) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & (GEMM_KFROM_M | GEMM_KTO_M)) && d.M > d.K");
-  if ((d.flags & GEMM_SQUARE_BLOCKSUM) &&
-      (!d.blk_w || d.blk_k < 1 || d.blk_k > 16 || (d.blk_k & (d.blk_k - 1)) || d.M % d.blk_k || d.N % d.blk_k ||
-       d.ksplit != 1 || d.batch != 1 || kseg || kfrom || d.C2 ||
-       (d.flags & (GEMM_SQUARE | GEMM_OFFDIAG_X2 | GEMM_C_PACKED | GEMM_C_MIRROR))))
-    return gemm_fail(LRN_ERR_ARG, "gemm: GEMM_SQUARE_BLOCKSUM needs blk_w, blk_k in {1, 2, 4, 8, 16} dividing M and N, one "
-                                  "unsplit, unbatched product and no other epilogue");
-  if ((d.flags & GEMM_C_PACKED) && (d.pk_off & 15)) return gemm_fail(LRN_ERR_ARG, "gemm: GEMM_C_PACKED needs pk_off % 16 == 0 (block width of the packed layout)");
-  if ((d.flags & GEMM_C_PACKED) && (!swapped || d.pk_m <= 0 || d.beta != 0.0)) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & GEMM_C_PACKED) && (!swapped || d.pk_m <= 0 || d.beta != 0.0)");
-  // tile choice: 128x128 unless the problem is too small to fill the chip with it
-  long t128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch * d.ksplit;
-  static const int mid_mode = getenv("LRN_GEMM_MID") ? atoi(getenv("LRN_GEMM_MID")) : 1;      // (measurement knob; 0: off)
-  bool small = (d.flags & GEMM_SMALL_TILE) ||
-               (t128 < 256 && !(d.flags & (GEMM_OFFDIAG_X2 | GEMM_C_PACKED | GEMM_C_MIRROR)) && !kseg && !kfrom);
-  // (measurement, LRN_GEMM_MID=2: plain products of up to 1024 128-tiles on the 64-tile DMA kernel as well)
-  if (mid_mode == 2 && t128 < 1024 && d.flags == 0 && !d.C2 && d.batch == 1 && d.beta == 0.0) small = true;
-  // Round 4: one plain product of 256 .. 1023 128-tiles (msz 2000 .. 4000) does not fill whole rounds of the 512 workgroup
-  // slots with 128-tiles -- msz 3000: 576 tiles, the 64 of the second round run alone on their CUs, 1226 us where the
-  // 64-tile DMA kernel (2209 tiles on 768 slots) takes 1011.  Both kernels priced by the round model that fits
-  // tools/gemm_nt_times.py (its decisions match the measurements at msz 2100 .. 3800); the 128-tile kernel keeps the tie.
-  if (mid_mode == 1 && !small && t128 >= 256 && t128 < 1024 && d.flags == 0 && !d.C2 && d.batch == 1 && d.ksplit == 1 &&
-      d.beta == 0.0 && d.sAm == 1 && d.sBn == 1 && d.sCn == 1 && d.M == d.N) {
-    const double ks = (double)((d.K + BK - 1) / BK);
-    const long full = t128 / 512, rem = t128 % 512;
-    const double big_us = ks * 1.85 * (2.0 * full + (rem == 0 ? 0.0 : (rem <= 256 ? 1.25 : 2.0)));
-    const long t64 = (long)((d.M + 63) / 64) * ((d.N + 63) / 64);
-    const long mfull = t64 / 768, mrem = t64 % 768, per_cu = (mrem + 255) / 256;
-    const double mid_us = mfull * 3.0 * ks * 0.515 + (mrem ? per_cu * ks * 0.515 * (per_cu == 1 ? 1.5 : 1.0) : 0.0);
-    if (mid_us * 1.08 < big_us * 1.03) small = true;
-  }
-  const bool big = kflat && (d.flags & GEMM_TILE160);       // 160 x 160 tile of the K-contiguous rank-k update
-  const int BMv = small ? 64 : (big ? 160 : 128);
-  p.tilesM = (d.M + BMv - 1) / BMv;
-  p.tilesN = (d.N + BMv - 1) / BMv;
-  if (kflat) {
+  p.kchunk = 0;
+  if (d.flags & GEMM_KFLAT) {
     // chunk (16 doubles) boundaries per split: kflat_nsd splits over the diagonal region, the rest over
     // the strictly-lower region (the caller weights their slabs by 2)
     if (d.kflat_total <= 0 || d.kflat_diag <= 0 || d.kflat_diag > d.kflat_total || d.kflat_nsd < 1 ||
         d.kflat_nsd > d.ksplit || d.kflat_cstride < 16 || (d.kflat_cstride & 1) || !kseg_lds_path_ok(d)) return gemm_fail(LRN_ERR_ARG, "gemm: d.kflat_total <= 0 || d.kflat_diag <= 0 || d.kflat_diag > d.kflat_total || d.kflat_nsd < 1 || d.kflat_nsd > d.ksplit || d.kflat_cstride < 16 || (d.kflat_cstride & 1) || !kseg_lds_path_ok(d)");
-      d.K = (int)(d.kflat_total > 0x7fffffff ? 0x7fffffff : d.kflat_total);
+    d.K = (int)(d.kflat_total > 0x7fffffff ? 0x7fffffff : d.kflat_total);
     const long cd = d.kflat_diag / BK, ct = d.kflat_total / BK;
     // split s walks the chunks [kcols[s], kcols2[s])
     if (d.kflat_kb && d.kflat_ke) {
@@ -1318,8 +1246,7 @@ static int gemm_impl(hipStream_t st, const GemmDesc& din) {
         p.kcols2[nsd + s] = (int)(cd + (ct - cd) * (s + 1) / nso);
       }
     }
-    p.kchunk = 0;
-  } else if (kseg) {
+  } else if (d.flags & GEMM_KSEG_TRI) {
     if (d.kseg_ld <= 0 || d.kseg_cols <= 0) return gemm_fail(LRN_ERR_ARG, "gemm: d.kseg_ld <= 0 || d.kseg_cols <= 0");
     d.K = d.kseg_ld * d.kseg_cols;
     // balance splits by segment length sum
@@ -1333,43 +1260,117 @@ static int gemm_impl(hipStream_t st, const GemmDesc& din) {
       if (accw >= total * s / d.ksplit) p.kcols[s++] = c + 1;
     }
     for (; s <= d.ksplit; ++s) p.kcols[s] = d.kseg_cols;
-    p.kchunk = 0;
   } else {
     long per = (d.K + d.ksplit - 1) / d.ksplit;
     per = ((per + BK - 1) / BK) * BK;
     if (per < BK) per = BK;
     p.kchunk = (int)per;
   }
-  int ntile = 0;
+  return LRN_OK;
+}
+
+// 128-tile or 64-tile for a product that is not K-contiguous
+static bool want_small_tile(const GemmDesc& d, bool kseg, bool kfrom) {
+  // tile choice: 128x128 unless the problem is too small to fill the chip with it
+  const long t128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch * d.ksplit;
+  if ((d.flags & GEMM_SMALL_TILE) ||
+      (t128 < 256 && !(d.flags & (GEMM_OFFDIAG_X2 | GEMM_C_PACKED | GEMM_C_MIRROR)) && !kseg && !kfrom))
+    return true;
+  // Round 4: one plain product of 256 .. 1023 128-tiles (msz 2000 .. 4000) does not fill whole rounds of the 512 workgroup
+  // slots with 128-tiles -- msz 3000: 576 tiles, the 64 of the second round run alone on their CUs, 1226 us where the
+  // 64-tile DMA kernel (2209 tiles on 768 slots) takes 1011.  Both kernels priced by the round model that fits
+  // tools/gemm_nt_times.py (its decisions match the measurements at msz 2100 .. 3800); the 128-tile kernel keeps the tie.
+  if (t128 >= 256 && t128 < 1024 && d.flags == 0 && !d.C2 && d.batch == 1 && d.ksplit == 1 && d.beta == 0.0 && d.sAm == 1 &&
+      d.sBn == 1 && d.sCn == 1 && d.M == d.N) {
+    const double ktiles = (double)((d.K + BK - 1) / BK);
+    const long full = t128 / 512, rem = t128 % 512;
+    const double big_us = ktiles * 1.85 * (2.0 * full + (rem == 0 ? 0.0 : (rem <= 256 ? 1.25 : 2.0)));
+    const long t64 = (long)((d.M + 63) / 64) * ((d.N + 63) / 64), mrem = t64 % 768;      // whole rounds of 768 slots, and the last
+    const double mid_us = mid_kernel_us(t64 - mrem, ktiles) + mid_kernel_us(mrem, ktiles);
+    if (mid_us * 1.08 < big_us * 1.03) return true;
+  }
+  return false;
+}
+
+// The kernel of an oriented, validated product; `small`: want_small_tile.  Every route once; why a route is closed to a
+// product stands in its *_path_ok.
+static GemmKernel choose_kernel(const GemmDesc& d, bool small, bool epi) {
+  if (d.flags & GEMM_KFLAT) {        // K-contiguous rank-k update, GEMM3' (kseg_lds_path_ok is checked with its K ranges)
+    if (d.tile_class == 5) return GK_KFLAT_STRIP;
+    return (d.flags & GEMM_TILE160) ? GK_KFLAT160 : GK_KFLAT128;
+  }
+  const bool kseg = d.flags & GEMM_KSEG_TRI;
+  if (kseg && kseg_lds_path_ok(d)) return GK_KSEG;                    // GEMM3: K segments by DMA
+  if (!kseg && !small && lds_path_ok(d)) return GK_LDS;               // 128 tiles, operands straight into LDS
+  if (!kseg && small && mid_path_ok(d, epi)) return GK_MID;           // 64 tiles, three-stage DMA pipeline
+  return small ? GK_REG64 : GK_REG128;                                // everything else: any strides, any epilogue
+}
+
+// the two lists of a K-contiguous launch that walks the regular tiles of every split first and the short ones last
+// (GemmParams::tile_list2)
+static void plan_two_lists(GemmPlan* plan, int tilesM, int tilesN, int tri, bool em, bool en, bool dg) {
+  GemmParams& p = plan->p;
+  plan->nlists = 2;
+  plan->lists[0] = tile_list_key(tilesM, tilesN, tri, 1, em, en, dg);
+  plan->lists[1] = tile_list_key(tilesM, tilesN, tri, 2, em, en, dg);
+  const bool only_short = plan->lists[0].n == 0;      // (only short tiles: they are the first list)
+  if (only_short) plan->lists[0] = plan->lists[1];
+  p.n1 = plan->lists[0].n;
+  p.n2 = only_short ? 0 : plan->lists[1].n;
+}
+
+// slabs: the split-K factor of gemm() / gemm_slabs() -- 0: auto_split_factor decides; k > 1: the plan writes k slabs of
+// M N doubles each (the caller points plan->p.d.C at them)
+static int plan_gemm(const GemmDesc& din, GemmPlan* plan, int slabs = 0) {
+  *plan = GemmPlan{};
+  plan->slabs = slabs > 0 ? slabs : auto_split_factor(din);
+  GemmParams& p = plan->p;
+  p.d = din;
+  GemmDesc& d = p.d;
+  if (plan->slabs > 1) {
+    d.sCs = (long)din.M * din.N; d.ksplit = plan->slabs; d.beta = 0.0;
+    d.flags |= GEMM_SMALL_TILE;
+  }
+  if (d.M <= 0 || d.N <= 0 || d.batch <= 0) return LRN_OK;
+  if (!d.A || !d.B || (!d.C && plan->slabs == 1)) return gemm_fail(LRN_ERR_ARG, "gemm: null A, B or C");
+  if (d.ksplit < 1) d.ksplit = 1;
+  if (d.ksplit > MAX_KSPLIT) return gemm_fail(LRN_ERR_ARG, "gemm: d.ksplit > MAX_KSPLIT");
+  const bool swapped = orient(d);
+  const bool kflat = d.flags & GEMM_KFLAT;
+  const bool kseg = (d.flags & GEMM_KSEG_TRI) || kflat;
+  const bool kfrom = d.flags & (GEMM_KFROM_N | GEMM_KFROM_M | GEMM_KTO_N | GEMM_KTO_M);   // triangular K ranges
+  const int trif = d.flags & (GEMM_TRI_LOWER | GEMM_TRI_UPPER);
+  if ((d.flags & GEMM_C_MIRROR) && (d.M != d.N || !trif || d.beta != 0.0)) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & GEMM_C_MIRROR) && (d.M != d.N || !tri || d.beta != 0.0)");
+  // triangular K ranges: the operand that is triangular spans K (a trailing sub-block may be narrower in the other
+  // dimension: columns [c0, c1) of a product with the trailing block of the factor)
+  if (kfrom && (d.ksplit != 1 || kseg)) return gemm_fail(LRN_ERR_ARG, "gemm: kfrom && (d.ksplit != 1 || kseg)");
+  if ((d.flags & (GEMM_KFROM_N | GEMM_KTO_N)) && d.N > d.K) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & (GEMM_KFROM_N | GEMM_KTO_N)) && d.N > d.K");
+  if ((d.flags & (GEMM_KFROM_M | GEMM_KTO_M)) && d.M > d.K) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & (GEMM_KFROM_M | GEMM_KTO_M)) && d.M > d.K");
+  if ((d.flags & GEMM_SQUARE_BLOCKSUM) &&
+      (!d.blk_w || d.blk_k < 1 || d.blk_k > 16 || (d.blk_k & (d.blk_k - 1)) || d.M % d.blk_k || d.N % d.blk_k ||
+       d.ksplit != 1 || d.batch != 1 || kseg || kfrom || d.C2 ||
+       (d.flags & (GEMM_SQUARE | GEMM_OFFDIAG_X2 | GEMM_C_PACKED | GEMM_C_MIRROR))))
+    return gemm_fail(LRN_ERR_ARG, "gemm: GEMM_SQUARE_BLOCKSUM needs blk_w, blk_k in {1, 2, 4, 8, 16} dividing M and N, one "
+                                  "unsplit, unbatched product and no other epilogue");
+  if ((d.flags & GEMM_C_PACKED) && (d.pk_off & 15)) return gemm_fail(LRN_ERR_ARG, "gemm: GEMM_C_PACKED needs pk_off % 16 == 0 (block width of the packed layout)");
+  if ((d.flags & GEMM_C_PACKED) && (!swapped || d.pk_m <= 0 || d.beta != 0.0)) return gemm_fail(LRN_ERR_ARG, "gemm: (d.flags & GEMM_C_PACKED) && (!swapped || d.pk_m <= 0 || d.beta != 0.0)");
+  const bool small = want_small_tile(d, kseg, kfrom);
+  const bool big = kflat && (d.flags & GEMM_TILE160);       // 160 x 160 tile of the K-contiguous rank-k update
+  const int BMv = small ? 64 : (big ? 160 : 128);
+  p.tilesM = (d.M + BMv - 1) / BMv;
+  p.tilesN = (d.N + BMv - 1) / BMv;
+  if (const int rc = plan_k_ranges(p); rc != LRN_OK) return rc;
   if (d.tile_class >= 4 && !kflat) return gemm_fail(LRN_ERR_ARG, "gemm: tile_class 4 / 5 are for the K-contiguous rank-k update");
   if (d.tile_class != 0 && small) return gemm_fail(LRN_ERR_ARG, "gemm: tile_class needs the 128 tile");
-  p.tile_list2 = nullptr;
-  p.n1 = 0;
   p.n2 = -1;
+  plan->epi = (d.flags & (GEMM_OFFDIAG_X2 | GEMM_SQUARE | GEMM_SQUARE_BLOCKSUM | GEMM_C_PACKED | GEMM_C_MIRROR)) || d.C2;
+  plan->tile_m = plan->tile_n = BMv;
+  const GemmKernel kernel = choose_kernel(d, small, plan->epi);
+  const bool em = (d.M % BMv) != 0, en = (d.N % BMv) != 0, dg = (d.flags & (GEMM_DIAG_LOWER | GEMM_DIAG_UPPER)) != 0;
   if (d.tile_class == 3) {
     if (!kflat || d.batch != 1) return gemm_fail(LRN_ERR_ARG, "gemm: tile_class 3 is for the K-contiguous rank-k update");
-    const int trif = d.flags & (GEMM_TRI_LOWER | GEMM_TRI_UPPER);
-    const bool em = (d.M % BMv) != 0, en = (d.N % BMv) != 0, dg = (d.flags & (GEMM_DIAG_LOWER | GEMM_DIAG_UPPER)) != 0;
-    int c1 = 0, c2 = 0;
-    p.tile_list = get_tile_list(p.tilesM, p.tilesN, trif, &c1, 1, em, en, dg);
-    p.tile_list2 = get_tile_list(p.tilesM, p.tilesN, trif, &c2, 2, em, en, dg);
-    if (!p.tile_list || !p.tile_list2) return gemm_fail(LRN_ERR_NOMEM, "gemm: tile list allocation failed");
-    p.n1 = c1;
-    p.n2 = c2;
-    if (c1 + c2 == 0) return LRN_OK;
-    if (c1 == 0) { p.tile_list = p.tile_list2; p.n1 = c2; p.n2 = 0; }     // (only short tiles: they are the first list)
-    const long wgs = 8L * d.ksplit * ((p.n1 >> 3) + (p.n2 >> 3));
-    if (wgs > 0x7fffffffL) return gemm_fail(LRN_ERR_ARG, "gemm: grid too large");
-    dim3 grid1((unsigned)wgs, 1, 1);
-    if (big) {
-      if (!big_tile_attr_ok()) return gemm_fail(LRN_ERR_HIP, "gemm: 80 KB of dynamic LDS refused");
-      hipLaunchKernelGGL((gemm_f64_kseg_lds_kernel<true, 5, 5>), grid1, dim3(256), 2 * 2 * 160 * BK * 8, st, p);
-    } else {
-      hipLaunchKernelGGL((gemm_f64_kseg_lds_kernel<true, 4, 4>), grid1, dim3(256), 2 * 2 * 128 * BK * 8, st, p);
-    }
-    return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-  }
-  if (d.tile_class == 4 || d.tile_class == 5) {
+    plan_two_lists(plan, p.tilesM, p.tilesN, trif, em, en, dg);
+  } else if (d.tile_class == 4 || d.tile_class == 5) {
     // The symmetric rank-k update with a LAST TILE ROW OF HEIGHT 128 + r, r = M % 128 in (0, 32] (nvar = 4000 = 30 x 128 +
     // 160): instead of a row of edge tiles that hold r of 128 rows -- each costs 0.7 of a full tile, bound by its panel
     // traffic -- the last 128 + r rows are tiled on their own by 128 x 160 tiles (<true, 4, 5>), the diagonal corner
@@ -1379,127 +1380,188 @@ static int gemm_impl(hipStream_t st, const GemmDesc& din) {
     // streams the leading part loses its lock-step (measured at C4: 502 against 488 ms as one launch with edge tiles,
     // 486 as two launches in sequence with a corner launch of its own, which this form saves).
     const int rem = d.M % 128;
-    if (!kflat || d.batch != 1 || big || d.M != d.N || rem == 0 || rem > 32 || d.M < 288 ||
-        (d.flags & (GEMM_TRI_LOWER | GEMM_TRI_UPPER)) != GEMM_TRI_UPPER || !(d.flags & GEMM_DIAG_UPPER) ||
-        (d.flags & GEMM_NO_SKIP))
+    if (d.batch != 1 || big || d.M != d.N || rem == 0 || rem > 32 || d.M < 288 || trif != GEMM_TRI_UPPER ||
+        !(d.flags & GEMM_DIAG_UPPER) || (d.flags & GEMM_NO_SKIP))
       return gemm_fail(LRN_ERR_ARG, "gemm: tile_class 4 needs the symmetric K-contiguous update with M % 128 in (0, 32]");
-    if (!big_tile_attr_ok()) return gemm_fail(LRN_ERR_HIP, "gemm: 80 KB of dynamic LDS refused");
     const int Mm = d.M - 128 - rem, tmain = Mm / 128;
     if (d.tile_class == 4) {   // leading part: regular tiles of every split first, its diagonal tiles last (as tile_class 3)
-      GemmParams pm = p;
-      pm.d.M = Mm; pm.d.N = Mm;
-      pm.tilesM = tmain; pm.tilesN = tmain;
-      int c1 = 0, c2 = 0;
-      pm.tile_list = get_tile_list(tmain, tmain, GEMM_TRI_UPPER, &c1, 1, false, false, true);
-      pm.tile_list2 = get_tile_list(tmain, tmain, GEMM_TRI_UPPER, &c2, 2, false, false, true);
-      if (!pm.tile_list || !pm.tile_list2) return gemm_fail(LRN_ERR_NOMEM, "gemm: tile list allocation failed");
-      pm.n1 = c1;
-      pm.n2 = c2;
-      if (c1 == 0) { pm.tile_list = pm.tile_list2; pm.n1 = c2; pm.n2 = 0; }
-      const long wgs = 8L * d.ksplit * ((pm.n1 >> 3) + (pm.n2 >> 3));
-      if (wgs > 0x7fffffffL) return gemm_fail(LRN_ERR_ARG, "gemm: grid too large");
-      if (wgs > 0)
-        hipLaunchKernelGGL((gemm_f64_kseg_lds_kernel<true, 4, 4>), dim3((unsigned)wgs, 1, 1), dim3(256),
-                           2 * 2 * 128 * BK * 8, st, pm);
+      d.M = d.N = Mm;
+      p.tilesM = p.tilesN = tmain;
+      plan_two_lists(plan, tmain, tmain, GEMM_TRI_UPPER, false, false, true);
     } else {   // strip: all rows x the last 128 + r columns (entries below the diagonal of the corner are computed and never read)
-      GemmParams ps = p;
-      ps.d.flags &= ~(GEMM_TRI_LOWER | GEMM_TRI_UPPER | GEMM_DIAG_LOWER | GEMM_DIAG_UPPER);
-      ps.m_org = 0; ps.n_org = Mm;
-      ps.tilesM = tmain + 2; ps.tilesN = 1;
-      int cnt = 0;
-      ps.tile_list = get_tile_list(tmain + 2, 1, 0, &cnt);
-      if (!ps.tile_list || cnt <= 0) return gemm_fail(LRN_ERR_NOMEM, "gemm: tile list allocation failed");
-      hipLaunchKernelGGL((gemm_f64_kseg_lds_kernel<true, 4, 5>), dim3(cnt, 1, d.ksplit), dim3(256),
-                         2 * (128 + 160) * BK * 8, st, ps);
+      d.flags &= ~(GEMM_TRI_LOWER | GEMM_TRI_UPPER | GEMM_DIAG_LOWER | GEMM_DIAG_UPPER);
+      p.n_org = Mm;
+      p.tilesM = tmain + 2; p.tilesN = 1;
+      plan->tile_n = 160;
+      plan->nlists = 1;
+      plan->lists[0] = tile_list_key(tmain + 2, 1, 0);
     }
-    return hipGetLastError() == hipSuccess ? LRN_OK : gemm_fail(LRN_ERR_HIP, "gemm: launch failed");
-  }
-  static const int tile_order = getenv("LRN_TILE_ORDER") ? atoi(getenv("LRN_TILE_ORDER")) : 0;      // (measurement knob)
-  const int korder = (tile_order && d.tile_class == 0 && d.batch > 1) ? ((d.flags & GEMM_KFROM_N) ? 1 : (d.flags & GEMM_KFROM_M) ? 2 : 0) : 0;
-  p.tile_list = get_tile_list(p.tilesM, p.tilesN, d.flags & (GEMM_TRI_LOWER | GEMM_TRI_UPPER), &ntile, d.tile_class,
-                              d.tile_class != 0 && (d.M % BMv) != 0, d.tile_class != 0 && (d.N % BMv) != 0,
-                              d.tile_class != 0 && (d.flags & (GEMM_DIAG_LOWER | GEMM_DIAG_UPPER)) != 0, korder);
-  if (d.tile_class != 0 && p.tile_list && ntile == 0) return LRN_OK;      // nothing of that class
-  if (!p.tile_list || ntile <= 0) return gemm_fail(LRN_ERR_NOMEM, "gemm: tile list allocation failed");
-  (void)tri;
-  const bool akc = (d.sAk == 1 && d.sAm != 1);
-  const bool bkc = (d.sBk == 1 && d.sBn != 1);
-  dim3 grid(ntile, 1, d.batch * d.ksplit);
-  if (grid.z > 65535) return gemm_fail(LRN_ERR_ARG, "gemm: grid.z > 65535");
-  const bool epi = (d.flags & (GEMM_OFFDIAG_X2 | GEMM_SQUARE | GEMM_SQUARE_BLOCKSUM | GEMM_C_PACKED | GEMM_C_MIRROR)) || d.C2;
-  if (d.C2 && (d.M != d.N || d.batch != 1 || d.ksplit != 1 || kseg)) return gemm_fail(LRN_ERR_ARG, "gemm: C2 needs a square, unbatched, unsplit product");
-  if (kflat) {
-    if (big) {
-      if (!big_tile_attr_ok()) return gemm_fail(LRN_ERR_HIP, "gemm: 80 KB of dynamic LDS refused");
-      hipLaunchKernelGGL((gemm_f64_kseg_lds_kernel<true, 5, 5>), grid, dim3(256), 2 * 2 * 160 * BK * 8, st, p);
-    } else {
-      hipLaunchKernelGGL((gemm_f64_kseg_lds_kernel<true, 4, 4>), grid, dim3(256), 2 * 2 * 128 * BK * 8, st, p);
-    }
-    return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-  }
-  if (kseg && kseg_lds_path_ok(d)) {
-    hipLaunchKernelGGL((gemm_f64_kseg_lds_kernel<false, 4, 4>), grid, dim3(256), 2 * 2 * 128 * BK * 8, st, p);
-    return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-  }
-  if (!small && !kseg && lds_path_ok(d)) {
-    const unsigned dyn = (d.flags & GEMM_LAB_ONE_WG) ? 24576u : 0u;        // (measurement only)
-    if (dyn) {
-      (void)hipFuncSetAttribute((const void*)gemm_f64_lds_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-      (void)hipFuncSetAttribute((const void*)gemm_f64_lds_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    }
-    if (d.flags & GEMM_DYN_MASKS) {
-      if (epi) hipLaunchKernelGGL((gemm_f64_lds_kernel<true, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((gemm_f64_lds_kernel<false, true>), grid, dim3(256), 0, st, p);
-    } else {
-      if (epi) hipLaunchKernelGGL((gemm_f64_lds_kernel<true, false>), grid, dim3(256), dyn, st, p);
-      else hipLaunchKernelGGL((gemm_f64_lds_kernel<false, false>), grid, dim3(256), dyn, st, p);
-    }
-    return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-  }
-  if (small && mid_mode != 0 && !kseg && !epi && d.batch == 1 && d.beta == 0.0 && d.sAm == 1 && d.sBn == 1 && d.K >= 64 &&
-      d.sCn == 1 && d.sAk >= d.M && d.sBk >= d.N && !(d.flags & ~(GEMM_SMALL_TILE | GEMM_TRI_LOWER | GEMM_TRI_UPPER)) &&
-      (!tri || (d.M == d.N && d.ksplit > 1)) &&
-      (double)d.K * (double)std::max(d.sAk, d.sBk) * 8.0 < 2.0e9) {
-    // a plain mid-size product, or its split-K slabs (gemm() below): three-stage LDS DMA pipeline
-    static const char* trace_path = getenv("LRN_MID_TRACE");       // (measurement: clocks of the workgroups of launch #40)
-    static int trace_launch = 0;
-    unsigned long long* tb = nullptr;
-    // (every tile of the grid, or its lower / upper triangle; the real entries come first in the list)
-    p.n1 = (tri ? p.tilesM * (p.tilesM + 1) / 2 : p.tilesM * p.tilesN) * d.ksplit;
-    grid = dim3((unsigned)((p.n1 + 7) & ~7), 1, 1);
-    const size_t tw = 8 * (size_t)grid.x * grid.z;
-    if (trace_path && ++trace_launch == 40 && hipMalloc(&tb, tw * 8) == hipSuccess) {
-      (void)hipMemsetAsync(tb, 0, tw * 8, st);
-      p.d.lab_trace = tb;
-    }
-    hipLaunchKernelGGL(gemm_f64_mid_kernel, grid, dim3(256), 0, st, p);
-    if (tb) {
-      std::vector<unsigned long long> h(tw);
-      (void)hipStreamSynchronize(st);
-      (void)hipMemcpy(h.data(), tb, tw * 8, hipMemcpyDeviceToHost);
-      if (FILE* f = fopen(trace_path, "wb")) { fwrite(h.data(), 8, tw, f); fclose(f); }
-      (void)hipFree(tb);
-    }
-    return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
-  }
-  if (small) {
-    if (kseg) launch4<64, 64, true, false>(st, p, akc, bkc, grid);
-    else if (epi) launch4<64, 64, false, true>(st, p, akc, bkc, grid);
-    else launch4<64, 64, false, false>(st, p, akc, bkc, grid);
   } else {
-    if (kseg) launch4<128, 128, true, false>(st, p, akc, bkc, grid);
-    else if (epi) launch4<128, 128, false, true>(st, p, akc, bkc, grid);
-    else launch4<128, 128, false, false>(st, p, akc, bkc, grid);
+    plan->nlists = 1;
+    plan->lists[0] = tile_list_key(p.tilesM, p.tilesN, trif, d.tile_class, d.tile_class != 0 && em, d.tile_class != 0 && en,
+                                   d.tile_class != 0 && dg);
   }
+  if (plan->lists[0].n == 0) return LRN_OK;      // no tile (of that class)
+  if (plan->nlists == 2) {
+    const long wgs = 8L * d.ksplit * ((p.n1 >> 3) + (p.n2 >> 3));
+    if (wgs > 0x7fffffffL) return gemm_fail(LRN_ERR_ARG, "gemm: grid too large");
+    plan->grid = dim3((unsigned)wgs, 1, 1);
+  } else {
+    plan->grid = dim3(plan->lists[0].n, 1, d.batch * d.ksplit);
+    if (plan->grid.z > 65535) return gemm_fail(LRN_ERR_ARG, "gemm: grid.z > 65535");
+  }
+  if (d.C2 && (d.M != d.N || d.batch != 1 || d.ksplit != 1 || kseg)) return gemm_fail(LRN_ERR_ARG, "gemm: C2 needs a square, unbatched, unsplit product");
+  if (kernel == GK_KSEG) plan->dyn_lds = 2 * 2 * 128 * BK * 8;
+  else if (kernel > GK_KSEG) plan->dyn_lds = 2 * (plan->tile_m + plan->tile_n) * BK * 8;      // two stages of both panels
+  else if (kernel == GK_LDS && (d.flags & (GEMM_LAB_ONE_WG | GEMM_DYN_MASKS)) == GEMM_LAB_ONE_WG) plan->dyn_lds = 24576;   // (measurement only)
+  else if (kernel == GK_MID) {
+    // (every tile of the grid, or its lower / upper triangle; the real entries come first in the list)
+    p.n1 = (trif ? p.tilesM * (p.tilesM + 1) / 2 : p.tilesM * p.tilesN) * d.ksplit;
+    plan->grid = dim3((unsigned)((p.n1 + 7) & ~7), 1, 1);
+  }
+  plan->kernel = kernel;
+  return LRN_OK;
+}
+
+// more than 64 KB of dynamic LDS (the 160-wide tiles) is asked for once per kernel and device -- hipFuncSetAttribute is per
+// device, and one process may drive several (one context per GPU)
+static bool big_lds_ok(const GemmPlan& plan, GemmFn fn) {
+  static signed char state[64][2];      // 0: not asked yet, 1: granted, -1: refused
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  signed char& s = state[dev][plan.kernel == GK_KFLAT_STRIP];
+  if (!s) s = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.dyn_lds) == hipSuccess ? 1 : -1;
+  return s > 0;
+}
+
+// LRN_MID_TRACE=file (measurement, tools/mid_trace.py): the clocks of the workgroups of the 40th launch of the mid kernel
+// (GemmDesc::lab_trace, 8 words per workgroup) written to the file
+static const char* const mid_trace_path = getenv("LRN_MID_TRACE");
+static unsigned long long* mid_trace_begin(hipStream_t st, GemmPlan& plan) {
+  static int trace_launch = 0;
+  unsigned long long* tb = nullptr;
+  const size_t bytes = 64 * (size_t)plan.grid.x * plan.grid.z;
+  if (!mid_trace_path || ++trace_launch != 40 || hipMalloc(&tb, bytes) != hipSuccess) return nullptr;
+  (void)hipMemsetAsync(tb, 0, bytes, st);
+  plan.p.d.lab_trace = tb;
+  return tb;
+}
+static void mid_trace_end(hipStream_t st, const GemmPlan& plan, unsigned long long* tb) {
+  const size_t words = 8 * (size_t)plan.grid.x * plan.grid.z;
+  std::vector<unsigned long long> h(words);
+  (void)hipStreamSynchronize(st);
+  (void)hipMemcpy(h.data(), tb, words * 8, hipMemcpyDeviceToHost);
+  if (FILE* f = fopen(mid_trace_path, "wb")) { fwrite(h.data(), 8, words, f); fclose(f); }
+  (void)hipFree(tb);
+}
+
+static GemmFn kernel_fn(const GemmPlan& plan) {
+  const GemmDesc& d = plan.p.d;
+  switch (plan.kernel) {
+    case GK_KFLAT160: return gemm_f64_kseg_lds_kernel<true, 5, 5>;
+    case GK_KFLAT_STRIP: return gemm_f64_kseg_lds_kernel<true, 4, 5>;
+    case GK_KFLAT128: return gemm_f64_kseg_lds_kernel<true, 4, 4>;
+    case GK_KSEG: return gemm_f64_kseg_lds_kernel<false, 4, 4>;
+    case GK_LDS:
+      if (d.flags & GEMM_DYN_MASKS) return plan.epi ? gemm_f64_lds_kernel<true, true> : gemm_f64_lds_kernel<false, true>;
+      return plan.epi ? gemm_f64_lds_kernel<true, false> : gemm_f64_lds_kernel<false, false>;
+    case GK_MID: return gemm_f64_mid_kernel;
+    case GK_REG64: return reg_kernel<64>(d, plan.epi);
+    default: return reg_kernel<128>(d, plan.epi);
+  }
+}
+
+static int launch_gemm(hipStream_t st, GemmPlan& plan) {
+  if (plan.kernel == GK_NONE) return LRN_OK;
+  GemmParams& p = plan.p;
+  p.tile_list = get_tile_list(plan.lists[0]);
+  p.tile_list2 = plan.nlists == 2 ? get_tile_list(plan.lists[1]) : nullptr;
+  if (!p.tile_list || (plan.nlists == 2 && !p.tile_list2)) return gemm_fail(LRN_ERR_NOMEM, "gemm: tile list allocation failed");
+  const GemmFn fn = kernel_fn(plan);
+  if ((plan.kernel == GK_KFLAT160 || plan.kernel == GK_KFLAT_STRIP) && !big_lds_ok(plan, fn)) return gemm_fail(LRN_ERR_HIP, "gemm: 80 KB of dynamic LDS refused");
+  if (plan.kernel == GK_LDS && plan.dyn_lds)      // (GEMM_LAB_ONE_WG, measurement only)
+    (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.dyn_lds);
+  unsigned long long* trace = plan.kernel == GK_MID ? mid_trace_begin(st, plan) : nullptr;
+  hipLaunchKernelGGL(fn, plan.grid, dim3(256), plan.dyn_lds, st, p);
+  if (trace) mid_trace_end(st, plan, trace);
   return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
 }
 
+// Slab memory of the split mid-size products: one buffer per stream (products on different streams run concurrently),
+// grown on demand, kept for the life of the process.
+static double* split_slabs(hipStream_t st, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lk(mu);
+  auto& e = cache[{dev, st}];
+  if (e.second < bytes) {
+    if (e.first) { (void)hipStreamSynchronize(st); (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
+    if (hipMalloc(&e.first, bytes) != hipSuccess) { e.first = nullptr; return nullptr; }
+    e.second = bytes;
+  }
+  return static_cast<double*>(e.first);
+}
+
+static int gemm_maybe_slabs(hipStream_t st, const GemmDesc& din, SlabSrc* out) {
+  tls_gemm_error = nullptr;            // (a stale reason must not be appended to a later, unrelated error)
+  GemmPlan plan;
+  int rc = plan_gemm(din, &plan);
+  // GEMM_TRI_LOWER through gemm_slabs: the lower tiles as slabs or not at all (out->n = 0: the caller takes its other route)
+  const bool lower_only = din.flags == GEMM_TRI_LOWER && out;
+  const size_t mn = (size_t)din.M * din.N;
+  double* slabs = nullptr;
+  if (plan.slabs > 1 && !(lower_only && din.beta != 0.0)) {
+    slabs = split_slabs(st, mn * plan.slabs * 8);
+    if (slabs) plan.p.d.C = slabs;
+    else if (!lower_only) rc = plan_gemm(din, &plan, 1);      // (no memory for the slabs: the unsplit product)
+  }
+  if (lower_only && !slabs) {
+    tls_gemm_error = nullptr;
+    out->p = nullptr; out->stride = 0; out->n = 0;
+    return LRN_OK;
+  }
+  if (rc == LRN_OK) rc = launch_gemm(st, plan);
+  if (rc != LRN_OK) {
+    if (!tls_gemm_error) tls_gemm_error = "kernel launch failed";
+    return rc;
+  }
+  if (slabs && out && din.beta == 0.0) {
+    out->p = slabs; out->stride = (long)mn; out->n = plan.slabs;
+    return LRN_OK;
+  }
+  if (out) { out->p = din.C; out->stride = 0; out->n = 1; }
+  if (!slabs) return LRN_OK;
+  // (a product of lower tiles alone: the slabs hold nothing above them, and C keeps what it held there)
+  const int tri = din.flags != GEMM_TRI_LOWER ? 0 : (std::labs(din.sCm) == 1 ? GEMM_TRI_LOWER : GEMM_TRI_UPPER);
+  return reduce_slabs(st, slabs, (long)mn, plan.slabs, din.C, (long)mn, din.beta, tri, din.M);
+}
+
+int gemm(hipStream_t st, const GemmDesc& din) { return gemm_maybe_slabs(st, din, nullptr); }
+int gemm_slabs(hipStream_t st, const GemmDesc& din, SlabSrc* out) { return gemm_maybe_slabs(st, din, out); }
+
+int gemm_plan_info(const GemmDesc& d, GemmPlanInfo* info) {
+  tls_gemm_error = nullptr;
+  GemmPlan plan;
+  const int rc = plan_gemm(d, &plan);
+  *info = GemmPlanInfo{(int)plan.kernel, plan.tile_m, (int)plan.grid.x, (int)plan.grid.z, (int)plan.dyn_lds, plan.slabs};
+  return rc;
+}
+
 // ------------------------------------------------------------------ slab reduction
+// TRI: the flat vectors are ld x ld column-major matrices of which only the 64-tiles on and below (GEMM_TRI_LOWER) or on
+// and above (GEMM_TRI_UPPER) the diagonal are summed and stored; the other entries of `out` are left as they are
+template <bool TRI>
 __global__ void reduce_slabs_kernel(const double* __restrict__ slabs, long stride, int nslab,
-                                    double* __restrict__ out, long n, double beta) {
+                                    double* __restrict__ out, long n, double beta, int tri, int ld) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long step = (long)gridDim.x * blockDim.x;
   for (; i < n; i += step) {
+    if (TRI) {
+      const long r = (i % ld) >> 6, c = (i / ld) >> 6;
+      if (tri == GEMM_TRI_LOWER ? r < c : r > c) continue;
+    }
     double s = 0.0;
     for (int k = 0; k < nslab; ++k) s += slabs[(long)k * stride + i];
     out[i] = (beta != 0.0 ? beta * out[i] : 0.0) + s;
@@ -1507,12 +1569,12 @@ __global__ void reduce_slabs_kernel(const double* __restrict__ slabs, long strid
 }
 
 int reduce_slabs(hipStream_t st, const double* slabs, long stride, int nslab, double* out,
-                 long n, double beta) {
+                 long n, double beta, int tri, int ld) {
   if (n <= 0) return LRN_OK;
   long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)blocks), dim3(256), 0, st, slabs, stride,
-                     nslab, out, n, beta);
+  hipLaunchKernelGGL(tri && ld > 0 ? reduce_slabs_kernel<true> : reduce_slabs_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st,
+                     slabs, stride, nslab, out, n, beta, tri, ld);
   return hipGetLastError() == hipSuccess ? LRN_OK : LRN_ERR_HIP;
 }
 

@@ -113,16 +113,6 @@ __global__ __launch_bounds__(256) void dot_final_kernel(const double* __restrict
   if (threadIdx.x == 0) *out = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-static int mm(lrn_ctx* c, int n, const double* A, bool tA, const double* B, bool tB, double* C) {
-  GemmDesc g;
-  g.A = A; g.B = B; g.C = C;
-  g.M = g.N = g.K = n;
-  if (!tA) { g.sAm = 1; g.sAk = n; } else { g.sAm = n; g.sAk = 1; }
-  if (!tB) { g.sBk = 1; g.sBn = n; } else { g.sBk = n; g.sBn = 1; }
-  g.sCm = 1; g.sCn = n;
-  return gemm(c->stream, g);
-}
-
 static int dot_dev(lrn_ctx* c, const double* A, const double* B, long n, double* out_dev) {
   const int np = (int)std::min<long>(1024, (n + 255) / 256);
   LRN_TRY(ensure(c, c->redbuf, (size_t)(np + 64) * 8));
@@ -181,17 +171,6 @@ __device__ __forceinline__ double block_sum_parts(const double* __restrict__ par
 }
 
 // out = (M + M') / 2: the tiled kernel above from msz 512 on (the element-wise one reads M' with stride n)
-// C = alpha A Bm' for a consumer that can add split-K slabs while it reads: below msz 1500 on one rank the product may come
-// back as slabs (src->n > 1, C untouched); otherwise it is in C
-static int prod_slabs(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha, int tri,
-                      SlabSrc* src) {
-  if (n >= 1500 || products_sharded(c, st, n)) {
-    src->p = C; src->stride = 0; src->n = 1;
-    return pgemm_nt(c, st, n, A, Bm, C, tri, alpha);
-  }
-  return gemm_nt_slabs(st, n, A, Bm, C, alpha, src);
-}
-
 static void sym_half(hipStream_t st, const double* M, double* out, int n) {
   if (n >= 512) {
     const long nt = (n + 31) / 32;
@@ -536,13 +515,13 @@ extern "C" int lrn_ip_rhs_corr(lrn_ctx* c, double sigma_mu, double* out) {
     }
     double* G = b.G.as<double>();
     // t1 = G' Rd G
-    LRN_TRY(mm(c, m, G, true, b.Rd.as<double>(), false, b.t0.as<double>()));
-    LRN_TRY(mm(c, m, b.t0.as<double>(), false, G, false, b.t1.as<double>()));
+    LRN_TRY(gemm_nn(c->stream, m, G, true, b.Rd.as<double>(), false, b.t0.as<double>()));
+    LRN_TRY(gemm_nn(c->stream, m, b.t0.as<double>(), false, G, false, b.t1.as<double>()));
     hipLaunchKernelGGL(corr_inner_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t1.as<double>(), b.D.as<double>(),
                        b.RNT.as<double>(), sigma_mu, b.t0.as<double>(), m);
     // my_kron(G,G,inner) = vec(G inner G')
-    LRN_TRY(mm(c, m, G, false, b.t0.as<double>(), false, b.t1.as<double>()));
-    LRN_TRY(mm(c, m, b.t1.as<double>(), false, G, true, b.t2.as<double>()));
+    LRN_TRY(gemm_nn(c->stream, m, G, false, b.t0.as<double>(), false, b.t1.as<double>()));
+    LRN_TRY(gemm_nn(c->stream, m, b.t1.as<double>(), false, G, true, b.t2.as<double>()));
     LRN_TRY(aa_times(c, b, b.t2.as<double>(), c->v1.as<double>()));
   }
   toc(c, "rhs");
@@ -577,7 +556,7 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
       LRN_TRY(pgemm_nt(c, c->stream, m, b.LXt.as<double>(), b.delS.as<double>(), t0, GEMM_KFROM_M));    // L_X' upper triangular
       // (both second products are symmetric in exact arithmetic: from msz 1500 on the lower tiles + mirror, half the work;
       // below, the full product and the average of the two triangles)
-      if (m >= 1500) {
+      if (m >= BIG_TILE_MIN_N) {
         LRN_TRY(pgemm_nt_sym(c, c->stream, m, t0, b.LXt.as<double>(), b.Bs.as<double>(), 1.0, GEMM_KFROM_N));
       } else {
         SlabSrc prod;
@@ -586,7 +565,7 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
                            (double*)nullptr);
       }
       LRN_TRY(pgemm_nt(c, c->stream, m, b.Zh.as<double>(), b.Bs.as<double>(), t0));
-      if (m >= 1500) {
+      if (m >= BIG_TILE_MIN_N) {
         LRN_TRY(pgemm_nt_sym(c, c->stream, m, t0, b.Zh.as<double>(), t3, 1.0 / b.ns_c));
       } else {
         SlabSrc prod;
@@ -613,17 +592,17 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
       // delX = mat(sigma_mu Si - X - W delS W + G RNT G')          (:257)
       hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, t0, sigma_mu, b.Si.as<double>(), -1.0,
                          b.X.as<double>(), -1.0, t2, mm_);
-      LRN_TRY(mm(c, m, G, false, b.RNT.as<double>(), false, t1));
-      LRN_TRY(mm(c, m, t1, false, G, true, t2));
+      LRN_TRY(gemm_nn(c->stream, m, G, false, b.RNT.as<double>(), false, t1));
+      LRN_TRY(gemm_nn(c->stream, m, t1, false, G, true, t2));
       hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, t0, 1.0, t0, 1.0, t2, 0.0, (const double*)nullptr, mm_);
     }
     sym_half(c->stream, t0, b.delX.as<double>(), m);
     // step lengths: eigmin of DDsi-scaled G' delS G and Gi delX Gi'   (:263-291)
-    LRN_TRY(mm(c, m, Gi, false, b.delX.as<double>(), false, t0));
-    LRN_TRY(mm(c, m, t0, false, Gi, true, t1));
+    LRN_TRY(gemm_nn(c->stream, m, Gi, false, b.delX.as<double>(), false, t0));
+    LRN_TRY(gemm_nn(c->stream, m, t0, false, Gi, true, t1));
     hipLaunchKernelGGL(scale_sym_kernel, dim3(g), dim3(256), 0, c->stream, t1, b.DDsi.as<double>(), t2, m);
-    LRN_TRY(mm(c, m, G, true, b.delS.as<double>(), false, t0));
-    LRN_TRY(mm(c, m, t0, false, G, false, t1));
+    LRN_TRY(gemm_nn(c->stream, m, G, true, b.delS.as<double>(), false, t0));
+    LRN_TRY(gemm_nn(c->stream, m, t0, false, G, false, t1));
     hipLaunchKernelGGL(scale_sym_kernel, dim3(g), dim3(256), 0, c->stream, t1, b.DDsi.as<double>(), t3, m);
     LRN_TRY(eigmin_certified_pair(c, t2, t3, m, &lamX, &lamS));
     alpha[il] = lamX > -1e-6 ? 0.99 : std::min(1.0, -tau / lamX);
@@ -685,9 +664,9 @@ extern "C" int lrn_ip_update(lrn_ctx* c, int predict, const double* alpha, const
         b.nt_free = false;
       }
       // RNT = -(Gi delX delS G + its transpose) ./ (D_i + D_j)     (:308-309)
-      LRN_TRY(mm(c, m, b.Gi.as<double>(), false, b.delX.as<double>(), false, t0));
-      LRN_TRY(mm(c, m, t0, false, b.delS.as<double>(), false, t1));
-      LRN_TRY(mm(c, m, t1, false, b.G.as<double>(), false, t2));
+      LRN_TRY(gemm_nn(c->stream, m, b.Gi.as<double>(), false, b.delX.as<double>(), false, t0));
+      LRN_TRY(gemm_nn(c->stream, m, t0, false, b.delS.as<double>(), false, t1));
+      LRN_TRY(gemm_nn(c->stream, m, t1, false, b.G.as<double>(), false, t2));
       hipLaunchKernelGGL(rnt_kernel, dim3(g), dim3(256), 0, c->stream, t2, b.D.as<double>(), b.RNT.as<double>(), m);
     } else {
       b.chol_valid = false;

@@ -178,8 +178,13 @@ __device__ __forceinline__ double slab_sum(const SlabSrc& s, long e) {
 int gemm_slabs(hipStream_t st, const GemmDesc& d, SlabSrc* out);
 const char* gemm_last_error();   // reason of this thread's last gemm() failure, or null
 // out[i] = beta*out[i] + sum_s slabs[s*stride + i]   (i < n), fixed summation order
+// tri (GEMM_TRI_LOWER / GEMM_TRI_UPPER) with ld > 0: the vectors are ld x ld column-major matrices and only the 64 x 64 tiles
+// on and below / on and above the diagonal are summed and stored (the slabs of a triangular product hold no others)
 int reduce_slabs(hipStream_t st, const double* slabs, long stride, int nslab, double* out,
-                 long n, double beta);
+                 long n, double beta, int tri = 0, int ld = 0);
+// what gemm() would launch for d, decided without touching a device (lrn_dbg_gemm_plan; tests/test_gemm_plan_cpu.py)
+struct GemmPlanInfo { int kernel, tile, grid_x, grid_z, dyn_lds, slabs; };
+int gemm_plan_info(const GemmDesc& d, GemmPlanInfo* info);
 // FP64 MFMA issue-rate probe: returns achieved TFLOP/s of a register-only MFMA loop.
 int mfma_f64_peak(hipStream_t st, double* tflops);
 // debug: one 16x16x4 MFMA with explicit operands (checks the lane maps)

@@ -1,5 +1,5 @@
 // Device-side operations shared between translation units: the data operators (dataops.hip), the NT scaling (prepw.hip),
-// the Lanczos searches (lz.hip) and a few helper launches.
+// the n x n products (products.hip), the Lanczos searches (lz.hip) and a few helper launches.
 #pragma once
 #include "ctx.h"
 namespace lrn {
@@ -26,7 +26,15 @@ int prepare_w_ns(lrn_ctx* c, LmiBlock& b, int* info, bool* converged);
 // Cholesky factors of b.X, b.S into b.LXf, b.LSf (two streams); info = 0, 1 (X not PD), 2 (S not PD) as prepare_W.jl:33-34;
 // minpiv[2] (may be null): smallest pivots L_ii^2 (upper bounds of the smallest eigenvalues).  Sets b.chol_valid.
 int nt_factor(lrn_ctx* c, LmiBlock& b, int* info, double* minpiv);
-// C = alpha A Bm' (n x n, column-major): the arrangement the direct-to-LDS GEMM kernel takes
+// ---- products.hip: n x n products, column-major
+// Border between the two routes of these products: from this side on the 128-tile direct-to-LDS kernel fills the chip (a
+// symmetric product as lower tiles + mirror, triangular-K hints taken); below it the product runs on 64-tiles, split into
+// slabs where that pays, and its consumers add the slabs while they read (at msz 800 the 28 lower tiles of 128 take 121 us,
+// the full product on 64-tiles 35 us)
+constexpr int BIG_TILE_MIN_N = 1500;
+// C = op(A) op(B), op = transpose where tA / tB
+int gemm_nn(hipStream_t st, int n, const double* A, bool tA, const double* B, bool tB, double* C, int flags = 0);
+// C = alpha A Bm': the arrangement the direct-to-LDS GEMM kernel takes
 int gemm_nt(hipStream_t st, int n, const double* A, const double* Bm, double* C, int flags = 0, double alpha = 1.0,
             double* Ct = nullptr);     // Ct: the transposed result as well
 // the same, a mid-size product left as its split-K slabs for a consumer that adds them while it reads (lrn_common.h, SlabSrc;
@@ -34,17 +42,23 @@ int gemm_nt(hipStream_t st, int n, const double* A, const double* Bm, double* C,
 int gemm_nt_slabs(hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha, SlabSrc* src);
 // C and its transposed twin Ct from one pass over the slabs of a product (or over C itself when the product was not split)
 void slabs_to_c_and_ct(hipStream_t st, const SlabSrc& src, int n, double* C, double* Ct);
+// P = A Bm' symmetrised (not stored) -> T = a (3 I - a^2 P) / 2, partial sums of ||I - P||_F^2 in part[0 .. *npart)
+int gemm_nt_sym_ns(hipStream_t st, int n, const double* A, const double* Bm, double* scratchC, double a, double* T, double* part,
+                   int* npart);
 // the same for a product that is symmetric in exact arithmetic; C comes back exactly symmetric
 int gemm_nt_sym(hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha = 1.0, int tri = 0);
 // The same products for the resident path of a sharded run (one process per GPU): when the communicator has more than one
 // rank, `st` is the context's stream and n >= option shard_products_min, this rank computes its block of columns and the
 // blocks are all-gathered in place (csrc/comm.hip) -- every rank ends with the same bits; otherwise the plain product.
 bool products_sharded(const lrn_ctx* c, hipStream_t st, int n);
-// tri: GEMM_KFROM_M / GEMM_KFROM_N / GEMM_KTO_M / GEMM_KTO_N when op(A) / op(B) is triangular with stored zeros (prepw.hip)
+// tri: GEMM_KFROM_M / GEMM_KFROM_N / GEMM_KTO_M / GEMM_KTO_N when op(A) / op(B) is triangular with stored zeros
 int pgemm_nt(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* C, int tri = 0,
              double alpha = 1.0, double* Ct = nullptr);
 int pgemm_nt_sym(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha = 1.0,
                  int tri = 0);
+// pgemm_nt for a consumer that can add split-K slabs while it reads (src->n > 1: the product is in the slabs, C untouched)
+int prod_slabs(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha, int tri,
+               SlabSrc* src);
 // k largest eigenpairs (ascending), smallest eigenvalue and trace of a dense symmetric matrix
 int lanczos_extremes(lrn_ctx* c, const double* M, int n, int k, double* lam_top, double* U_top, double* lam_min,
                      double* trace, int* steps_out);

@@ -86,18 +86,6 @@ void transpose_mat(hipStream_t st, const double* A, int n, double* B) {
   hipLaunchKernelGGL(transpose_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(32, 8), 0, st, A, n, B);
 }
 
-static int gemm_nn(hipStream_t st, int n, const double* A, bool tA, const double* B, bool tB, double* C, int flags = 0) {
-  GemmDesc g;
-  g.A = A; g.B = B; g.C = C;
-  g.M = g.N = g.K = n;
-  if (!tA) { g.sAm = 1; g.sAk = n; } else { g.sAm = n; g.sAk = 1; }
-  if (!tB) { g.sBk = 1; g.sBn = n; } else { g.sBk = n; g.sBn = 1; }
-  g.sCm = 1; g.sCn = n;
-  g.flags = flags;
-  return gemm(st, g);
-}
-
-
 int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   const int n = b.msz;
   const size_t mm = (size_t)n * n * 8;
@@ -327,288 +315,6 @@ __global__ __launch_bounds__(256) void sum_sqrt_kernel(const double* __restrict_
   if (threadIdx.x == 0) *out = sqrt(sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
-// C = alpha A Bm'  (all n x n column-major): both operands contiguous along the result's dimensions -> direct-to-LDS kernel
-int gemm_nt(hipStream_t st, int n, const double* A, const double* Bm, double* C, int flags, double alpha, double* Ct) {
-  GemmDesc g;
-  g.A = A; g.sAm = 1; g.sAk = n;
-  g.B = Bm; g.sBk = n; g.sBn = 1;
-  g.C = C; g.sCm = 1; g.sCn = n;
-  g.C2 = Ct;
-  g.M = g.N = g.K = n;
-  g.alpha = alpha;
-  g.flags = flags;
-  return gemm(st, g);
-}
-
-int gemm_nt_slabs(hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha, SlabSrc* src) {
-  GemmDesc g;
-  g.A = A; g.sAm = 1; g.sAk = n;
-  g.B = Bm; g.sBk = n; g.sBn = 1;
-  g.C = C; g.sCm = 1; g.sCn = n;
-  g.M = g.N = g.K = n;
-  g.alpha = alpha;
-  return gemm_slabs(st, g, src);
-}
-
-// C = sum of the slabs, Ct = its transpose: 32 x 32 tiles through LDS (round 4: the slab addition of a mid-size product and
-// the transpose pass that followed it were two launches and two trips through memory)
-__global__ __launch_bounds__(256) void slabs_transpose_kernel(SlabSrc src, int n, double* __restrict__ C, double* __restrict__ Ct) {
-  __shared__ double tile[32][33];
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int r = ty; r < 32; r += 8) {
-    const int i = bx + tx, j = by + r;
-    if (i < n && j < n) {
-      const long e = (long)i + (long)j * n;
-      const double v = slab_sum(src, e);
-      tile[r][tx] = v;
-      if (src.n > 1 || src.p != C) C[e] = v;
-    }
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int i = by + tx, j = bx + r;      // Ct[i][j] = C[j][i]
-    if (i < n && j < n) Ct[(long)i + (long)j * n] = tile[tx][r];
-  }
-}
-
-void slabs_to_c_and_ct(hipStream_t st, const SlabSrc& src, int n, double* C, double* Ct) {
-  hipLaunchKernelGGL(slabs_transpose_kernel, dim3((n + 31) / 32, (n + 31) / 32), dim3(256), 0, st, src, n, C, Ct);
-}
-
-// C = (S + S') / 2 for S = the sum of the slabs (or C itself, in place): the tile pair (bi, bj), (bj, bi) by one workgroup.
-// T != null: the Newton-Schulz pass on P = C in the same sweep -- T = a (3 I - a^2 P) / 2 and this workgroup's share of
-// ||I - P||_F^2 in part[blockIdx.x] (ns_t_kernel's work; C may then be null: nobody reads P itself)
-__global__ __launch_bounds__(256) void slabs_sym_kernel(SlabSrc src, int n, double* __restrict__ C, double a, double* __restrict__ T,
-                                                        double* __restrict__ part) {
-  __shared__ double ta[32][33], tb[32][33];
-  __shared__ double sh[4];
-  const int nt = (n + 31) / 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  // pair index -> (bi <= bj)
-  int bj = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-  while ((long)(bj + 1) * (bj + 2) / 2 <= (long)blockIdx.x) ++bj;
-  while ((long)bj * (bj + 1) / 2 > (long)blockIdx.x) --bj;
-  const int bi = (int)(blockIdx.x - (long)bj * (bj + 1) / 2);
-  if (bj >= nt) return;
-  const int oi = bi * 32, oj = bj * 32;
-  for (int r = ty; r < 32; r += 8) {
-    const int i = oi + tx, j = oj + r;       // tile (bi, bj): element (i, j)
-    ta[r][tx] = (i < n && j < n) ? slab_sum(src, (long)i + (long)j * n) : 0.0;
-    const int i2 = oj + tx, j2 = oi + r;     // tile (bj, bi): element (i2, j2)
-    tb[r][tx] = (i2 < n && j2 < n) ? slab_sum(src, (long)i2 + (long)j2 * n) : 0.0;
-  }
-  __syncthreads();
-  const double a3 = 0.5 * a * a * a, a1 = 1.5 * a;
-  double acc = 0.0;
-  for (int r = ty; r < 32; r += 8) {
-    const int i = oi + tx, j = oj + r;
-    if (i < n && j < n) {
-      const double v = 0.5 * (ta[r][tx] + tb[tx][r]);
-      if (C) C[(long)i + (long)j * n] = v;
-      if (T) {
-        const double rr = (i == j ? 1.0 : 0.0) - v;
-        acc += rr * rr;
-        T[(long)i + (long)j * n] = (i == j ? a1 : 0.0) - a3 * v;
-      }
-    }
-    const int i2 = oj + tx, j2 = oi + r;
-    if (bi != bj && i2 < n && j2 < n) {
-      const double v = 0.5 * (tb[r][tx] + ta[tx][r]);
-      if (C) C[(long)i2 + (long)j2 * n] = v;
-      if (T) {
-        acc += v * v;                                  // (off the diagonal: the residual entry is -v)
-        T[(long)i2 + (long)j2 * n] = -a3 * v;
-      }
-    }
-  }
-  if (!T || !part) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// The same from slabs that hold only the LOWER 64-tiles of the product (rows i, columns j with i / 64 >= j / 64; gemm_slabs
-// with GEMM_TRI_LOWER: half the MFMA work).  The pair of 32-tiles (bi <= bj) is filled from the lower one, (bj, bi): C over
-// there = the sum, C over here = its transpose; inside a diagonal 32-tile the lower triangle is mirrored.  The result is
-// the product's lower triangle mirrored -- exactly symmetric, NOT the average of the two triangles that slabs_sym_kernel
-// forms (the form the products of msz >= 1500 have had since round 3: lower tiles + mirror).
-__global__ __launch_bounds__(256) void slabs_symlow_kernel(SlabSrc src, int n, double* __restrict__ C, double a, double* __restrict__ T,
-                                                           double* __restrict__ part) {
-  __shared__ double tl[32][33];
-  __shared__ double sh[4];
-  const int nt = (n + 31) / 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  int bj = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-  while ((long)(bj + 1) * (bj + 2) / 2 <= (long)blockIdx.x) ++bj;
-  while ((long)bj * (bj + 1) / 2 > (long)blockIdx.x) --bj;
-  const int bi = (int)(blockIdx.x - (long)bj * (bj + 1) / 2);
-  if (bj >= nt) return;
-  const int oi = bi * 32, oj = bj * 32;          // lower tile: rows oj .., columns oi ..
-  for (int r = ty; r < 32; r += 8) {
-    const int i = oj + tx, j = oi + r;           // element (i, j) of the lower tile, i fastest
-    tl[r][tx] = (i < n && j < n) ? slab_sum(src, (long)i + (long)j * n) : 0.0;
-  }
-  __syncthreads();
-  const double a3 = 0.5 * a * a * a, a1 = 1.5 * a;
-  double acc = 0.0;
-  for (int r = ty; r < 32; r += 8) {
-    {   // the lower tile itself: element (oj + tx, oi + r)
-      const int i = oj + tx, j = oi + r;
-      if (i < n && j < n) {
-        const double v = (bi == bj && tx < r) ? tl[tx][r] : tl[r][tx];       // diagonal tile: (i, j) above the diagonal <- (j, i)
-        if (C) C[(long)i + (long)j * n] = v;
-        if (T) {
-          const double rr = (i == j ? 1.0 : 0.0) - v;
-          acc += rr * rr;
-          T[(long)i + (long)j * n] = (i == j ? a1 : 0.0) - a3 * v;
-        }
-      }
-    }
-    if (bi != bj) {   // its mirror image: element (oi + tx, oj + r) = lower (oj + r, oi + tx)
-      const int i = oi + tx, j = oj + r;
-      if (i < n && j < n) {
-        const double v = tl[tx][r];
-        if (C) C[(long)i + (long)j * n] = v;
-        if (T) {
-          acc += v * v;
-          T[(long)i + (long)j * n] = -a3 * v;
-        }
-      }
-    }
-  }
-  if (!T || !part) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// the lower 64-tiles of C = alpha A Bm' as split-K slabs (src->n == 0: not available for this size -- take the full product)
-static int gemm_nt_lower_slabs(hipStream_t st, int n, const double* A, const double* Bm, double alpha, SlabSrc* src) {
-  static const bool off = getenv("LRN_SYM_LOWER_OFF") != nullptr;      // (measurement knob)
-  src->p = nullptr; src->stride = 0; src->n = 0;
-  if (off) return LRN_OK;
-  GemmDesc g;
-  g.A = A; g.sAm = 1; g.sAk = n;
-  g.B = Bm; g.sBk = n; g.sBn = 1;
-  g.C = nullptr; g.sCm = 1; g.sCn = n;
-  g.M = g.N = g.K = n;
-  g.alpha = alpha;
-  g.flags = GEMM_TRI_LOWER;
-  return gemm_slabs(st, g, src);
-}
-
-// P = A Bm' symmetrised (not stored) -> T = a (3 I - a^2 P) / 2, partial sums of ||I - P||_F^2 in part[0 .. *npart): the
-// Newton-Schulz step's first product with its element-wise pass folded into the slab addition (msz < 1500, one rank)
-int gemm_nt_sym_ns(hipStream_t st, int n, const double* A, const double* Bm, double* scratchC, double a, double* T, double* part,
-                   int* npart) {
-  SlabSrc src;
-  const long nt = (n + 31) / 32;
-  *npart = (int)(nt * (nt + 1) / 2);
-  LRN_TRY(gemm_nt_lower_slabs(st, n, A, Bm, 1.0, &src));
-  if (src.n > 0) {
-    hipLaunchKernelGGL(slabs_symlow_kernel, dim3((unsigned)*npart), dim3(256), 0, st, src, n, (double*)nullptr, a, T, part);
-    return LRN_OK;
-  }
-  LRN_TRY(gemm_nt_slabs(st, n, A, Bm, scratchC, 1.0, &src));
-  hipLaunchKernelGGL(slabs_sym_kernel, dim3((unsigned)*npart), dim3(256), 0, st, src, n, (double*)nullptr, a, T, part);
-  return LRN_OK;
-}
-
-// (M + M')/2 in place
-__global__ void sym_inplace_kernel(double* __restrict__ M, int n) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    int i = (int)(e % n), j = (int)(e / n);
-    if (i < j) {
-      const long f = (long)j + (long)i * n;
-      const double v = 0.5 * (M[e] + M[f]);
-      M[e] = v;
-      M[f] = v;
-    }
-  }
-}
-
-// C = alpha A Bm' for a product that is symmetric in exact arithmetic, returned exactly symmetric: lower tiles + mirror on
-// the 128-tile direct-to-LDS kernel where that fills the chip, the plain product and a symmetrising pass below (at msz 800
-// the 28 lower tiles of 128 take 121 us, the full product on 64-tiles 35 us)
-// upper := lower inside the 128 x 128 diagonal tiles (GEMM_C_MIRROR mirrors the tiles below the diagonal only)
-__global__ __launch_bounds__(256) void mirror_diag_tiles_kernel(double* __restrict__ C, int n) {
-  const int t0 = blockIdx.x * 128;
-  for (int e = threadIdx.x; e < 128 * 128; e += 256) {
-    const int i = t0 + (e & 127), j = t0 + (e >> 7);
-    if (i < n && j < n && i < j) C[(long)i + (long)j * n] = C[(long)j + (long)i * n];
-  }
-}
-
-int gemm_nt_sym(hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha, int tri) {
-  if (n >= 1500) {
-    LRN_TRY(gemm_nt(st, n, A, Bm, C, GEMM_TRI_LOWER | GEMM_C_MIRROR | ((n & 1) ? 0 : tri), alpha));
-    hipLaunchKernelGGL(mirror_diag_tiles_kernel, dim3((n + 127) / 128), dim3(256), 0, st, C, n);
-    return LRN_OK;
-  }
-  SlabSrc src;
-  const long nt = (n + 31) / 32;
-  LRN_TRY(gemm_nt_lower_slabs(st, n, A, Bm, alpha, &src));
-  if (src.n > 0) {      // (round 4: lower 64-tiles only + mirror, as the products of msz >= 1500)
-    hipLaunchKernelGGL(slabs_symlow_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, src, n, C, 0.0, (double*)nullptr,
-                       (double*)nullptr);
-    return LRN_OK;
-  }
-  LRN_TRY(gemm_nt_slabs(st, n, A, Bm, C, alpha, &src));
-  hipLaunchKernelGGL(slabs_sym_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, src, n, C, 0.0, (double*)nullptr,
-                     (double*)nullptr);
-  return LRN_OK;
-}
-
-bool products_sharded(const lrn_ctx* c, hipStream_t st, int n) {
-  return c->comm && c->world > 1 && c->opt.shard_products != 0 && st == c->stream && n >= c->opt.shard_products_min;
-}
-
-static int shard_cols(const lrn_ctx* c, int n, int* c0, int* c1) {
-  const int cb = (((n + c->world - 1) / c->world) + 15) & ~15;      // 16-column granularity: aligned operand pointers
-  *c0 = std::min(n, c->rank * cb);
-  *c1 = std::min(n, *c0 + cb);
-  return cb;
-}
-
-// `tri`: which operand is triangular with explicit zeros in its other triangle (GEMM_KFROM_M / _N: zero for k < m / k < n,
-// GEMM_KTO_M / _N: zero for k > m / k > n; one flag) -- the K loop of every tile then covers only the range where that
-// operand is not zero: half the work of the products with L_X, L_X', L_S^-T (bitwise the same sums: the skipped terms
-// are exact zeros).  Taken where the 128-tile kernel runs (n >= 1500, even); the sharded product ignores it.
-static inline int tri_hint(int n, int tri) { return (n >= 1500 && (n & 1) == 0) ? tri : 0; }
-
-int pgemm_nt(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* C, int tri, double alpha,
-             double* Ct) {
-  if (!products_sharded(c, st, n)) return gemm_nt(st, n, A, Bm, C, tri_hint(n, tri), alpha, Ct);
-  int c0, c1;
-  const int cb = shard_cols(c, n, &c0, &c1);
-  if (c1 > c0) {
-    GemmDesc g;                      // C[:, c0:c1] = alpha A Bm[c0:c1, :]'
-    g.A = A; g.sAm = 1; g.sAk = n;
-    g.B = Bm + c0; g.sBk = n; g.sBn = 1;
-    g.C = C + (long)c0 * n; g.sCm = 1; g.sCn = n;
-    g.M = n; g.N = c1 - c0; g.K = n;
-    g.alpha = alpha;
-    LRN_TRY(gemm(st, g));
-  }
-  LRN_TRY(comm_allgather_cols(c, C, n, cb));
-  c->counts["pgemm_sharded"] += 1;
-  if (Ct) transpose_mat(st, C, n, Ct);
-  return LRN_OK;
-}
-
-int pgemm_nt_sym(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* C, double alpha, int tri) {
-  if (!products_sharded(c, st, n)) return gemm_nt_sym(st, n, A, Bm, C, alpha, tri);
-  LRN_TRY(pgemm_nt(c, st, n, A, Bm, C, 0, alpha, nullptr));
-  hipLaunchKernelGGL(sym_inplace_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, C, n);
-  return LRN_OK;
-}
-
 // smallest pivot of a Cholesky factor: out = min_i L_ii^2
 __global__ __launch_bounds__(256) void min_pivot_kernel(const double* __restrict__ L, int n, double* __restrict__ out) {
   __shared__ double sh[4];
@@ -807,7 +513,7 @@ int prepare_w_ns(lrn_ctx* c, LmiBlock& b, int* info, bool* converged) {
     // device) -- and T is its own transposed twin
     const double* Pk = Yc;                                // Z = I: P = Y (exactly symmetric)
     int np_k = npart;
-    if (!z_is_eye && n < 1500 && !products_sharded(c, st, n)) {
+    if (!z_is_eye && n < BIG_TILE_MIN_N && !products_sharded(c, st, n)) {
       // (mid sizes: symmetrisation, T and the residual in the pass that adds the product's slabs)
       LRN_TRY(gemm_nt_sym_ns(st, n, Zc, Ytc, Pm, a, Tm, part, &np_k));
     } else {
@@ -876,7 +582,7 @@ int prepare_w_ns(lrn_ctx* c, LmiBlock& b, int* info, bool* converged) {
   LRN_TRY(pgemm_nt(c, st, n, LX, Ztc, Pm, GEMM_KTO_M, 1.0));                             // (L_X lower triangular)
   LRN_TRY(pgemm_nt_sym(c, st, n, Pm, LX, b.W.as<double>(), 1.0 / std::sqrt(b.ns_c), GEMM_KTO_N));
   // (K/c)^-1 = Zh^2: the sigma_mu S^-1 term of the corrector in the L_X basis
-  if (n >= 1500) LRN_TRY(pgemm_nt_sym(c, st, n, Zc, Ztc, b.Ki.as<double>(), 1.0));       // symmetric: lower tiles + mirror
+  if (n >= BIG_TILE_MIN_N) LRN_TRY(pgemm_nt_sym(c, st, n, Zc, Ztc, b.Ki.as<double>(), 1.0));       // symmetric: lower tiles + mirror
   else LRN_TRY(pgemm_nt(c, st, n, Zc, Ztc, b.Ki.as<double>(), 0, 1.0));
   // Si = S^-1 = L_X K^-1 L_X' = L_X Ki L_X' / c  (prepare_W.jl:68): two products with the triangular factor, nothing inverted
   LRN_TRY(pgemm_nt(c, st, n, LX, b.Ki.as<double>(), Pm, GEMM_KTO_M, 1.0));               // L_X Ki'  (Ki symmetric)

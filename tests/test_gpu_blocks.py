@@ -126,6 +126,18 @@ def test_gemm_tri_flags_and_square(dev):
     assert relerr(C[il], ref[il]) < 1e-13
     # strictly-upper tiles (64- or 128-granular) are untouched
     assert np.array_equal(C[0, n - 1], C0[0, n - 1])
+    # the same contract where GEMM_TRI_LOWER alone is split into slabs of lower 64-tiles (tests/test_gemm_plan_cpu.py: 5 slabs
+    # at 801, 2 at 129 -- the smallest side the split admits, one tile row below the first): the slab addition must leave
+    # the 64-tiles above the diagonal alone as well
+    for n, K in ((801, 801), (129, 256)):
+        A = rng.standard_normal((n, K))
+        C0 = rng.standard_normal((n, n))
+        C = dev.dbg_gemm(A, A, False, True, alpha=1.0, beta=0.0, Cin=C0, flags=_capi.GEMM_TRI_LOWER)
+        il = np.tril_indices(n)
+        assert relerr(C[il], (A @ A.T)[il]) < 1e-13
+        t = np.arange(n) // 64
+        above = t[:, None] < t[None, :]
+        assert np.array_equal(C[above], C0[above])
 
 
 @pytest.mark.parametrize("m", [300, 320])     # 320: K-contiguous direct-to-LDS kernel (msz % 16 == 0)

@@ -1,5 +1,5 @@
 """Time of plain NT products C = A B' (the form of every product of the NT scaling / Lyapunov / step-length code) by matrix
-side, back to back on the device (LRN_DBG_GEMM_REPS).  LRN_GEMM_MID=0: without the mid-size slab kernel."""
+side, back to back on the device (LRN_DBG_GEMM_REPS)."""
 import os, sys
 os.environ.setdefault("LRN_DBG_GEMM_REPS", "50")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
