@@ -55,16 +55,26 @@ int lrn_upload_model(lrn_ctx* ctx, int nlmi, int nvar, const int64_t* msizes,
  * with d in {+1, -1}, every constraint padded to khat columns (khat = 1, 2, 4, 8 or 16; padding columns empty, weight 0).
  * V: (nvar * khat) x msz CSC, 1-based, row k * khat + p = column p of V_k (the orientation of B above); d: nvar * khat
  * weights in the same order.  Call after lrn_upload_model / lrn_synthetic_dense_model; lrn_schur_assemble(mode 1) uses
- * them.  AA stays what every other entry point reads (unless the block is declared factored, below). */
+ * them.  AA stays what every other entry point reads (unless the block is declared factored, below).  If some constraint
+ * with entries in AA has no factor column of non-zero weight, the factors do not cover the block: mode 1 then assembles a
+ * block that is not declared factored from the entries of its AA (the general assembly; lrn_get_count "lowrank_from_entries"). */
 int lrn_upload_lowrank(lrn_ctx* ctx, int ilmi, int khat, const int64_t* V_colptr, const int64_t* V_rowval,
                        const double* V_nzval, const double* d);
 /* Factored block (after lrn_upload_model and lrn_upload_lowrank): on = 1 declares that the factors ARE the constraint data
  * of block ilmi -- its AA was uploaded without entries, no A_k exists as a matrix on host or device.  AA vec(.) and
  * mat(AA' .) of the resident path (lrn_ip_*) then run in factor form: Q = Z Vd by one FP64 MFMA product and a column dot
  * per constraint; M = -Vd diag(w o x) Vd' by one lower-triangle product, mirrored (exactly symmetric).  The Schur matrix
- * comes from lrn_schur_assemble(mode 1).  LRN_ERR_STATE when no factors were uploaded or when the block's AA has any entry
- * (no constraint may be counted twice).  On a factored block lrn_get_constraint, lrn_matvec / lrn_matvec_partial,
- * lrn_prec_setup, lrn_pcg and modes 0 / -1 of lrn_schur_assemble return LRN_ERR_STATE.  on = 0 takes the declaration back.
+ * comes from lrn_schur_assemble(mode 1).
+ * Hybrid block: the AA may hold the rows of a few STORED constraints (sparse or dense, -vec(A) as everywhere) provided the
+ * factor columns of those constraints all have weight 0 -- every constraint is exactly one of the two.  The stored rows go
+ * through the stored-entry kernels (sparse tier, dense slots) beside the factor form; mode 1 adds H_SS by the general
+ * assembly over the stored rows and the cross terms H_sj = sum_p d_jp y_jp' A_s y_jp from Y = W Vd (one pass over Y, fixed
+ * order, no atomics; option "fac_cross_lds").  One GPU only: mode 1 returns LRN_ERR_STATE for a hybrid block under world > 1.
+ * LRN_ERR_STATE when no factors were uploaded or when a constraint of the block has both a stored row and a factor column
+ * of non-zero weight ("has entries": no constraint may be counted twice; a fully materialised AA with factors is refused as
+ * before).  On a factored block lrn_matvec / lrn_matvec_partial, lrn_prec_setup, lrn_pcg and modes 0 / -1 of
+ * lrn_schur_assemble return LRN_ERR_STATE, and so does lrn_get_constraint for a factored constraint (a stored constraint of
+ * a hybrid block is returned).  on = 0 takes the declaration back.
  * lrn_get_count: "op_factored" / "op_dense" / "op_sparse" count the operator calls by route, "op_dense_tri" /
  * "op_dense_stream" / "op_dense_scalar" the passes over dense constraint data by tier (column tails of symmetric data /
  * 16-byte loads over both triangles / one element per lane; the tier is decided when the model is uploaded); "device_bytes",
@@ -126,7 +136,9 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * 1 = the better conditioned equivalent Lyapunov equation (Yh/s + s Zh) R + R (.) = C/s + s Zh C Zh, 0 = Yh R + R Yh = C),
  * "ns_lanczos" / "ns_lanczos_min" (1: scale and schedule of the Newton-Schulz iteration from a 24-step Lanczos run on K for
  * blocks of side >= ns_lanczos_min = 1500), "lowrank_form" (rank-k assembly, mode 1: U = G'V by a gather over the factor
- * entries (0), one dense MFMA product (1), or by the factors' density (-1, default)), "profile_ops" (measurement: every
+ * entries (0), one dense MFMA product (1), or by the factors' density (-1, default)), "fac_cross_lds" (cross terms of a
+ * hybrid factored block: each column of Y staged in LDS (1, columns of up to 64 KiB), gathered from global memory (0), or LDS
+ * up to 32 KiB per column (-1, default); the same bits either way), "profile_ops" (measurement: every
  * AA vec(.) / mat(AA' .) timed by itself under "aa_times" / "aa_times2" / "aat_to_mat"; synchronises, not for solves), "comm_fail_ensure" (test hook: the next exchange of this rank fails its buffer
  * allocation), "lz_res_limit" (ticks of the 100 MHz wall clock a workgroup of a resident Lanczos launch waits for its peers
  * before the launch gives up; default 2 000 000 = 20 ms, clamped to [1000, 2 000 000]: the option shortens the wait, it

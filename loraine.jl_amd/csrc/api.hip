@@ -116,6 +116,7 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "comm_fail_ensure")) lrn::comm_inject_ensure_failure(c);      // test hook (tests/test_gpu_comm.py)
   else if (!strcmp(key, "pcg_lookahead")) c->opt.pcg_lookahead = std::max(0, std::min(8, (int)value));
   else if (!strcmp(key, "lowrank_form")) c->opt.lowrank_form = std::max(-1, std::min(1, (int)value));
+  else if (!strcmp(key, "fac_cross_lds")) c->opt.fac_cross_lds = std::max(-1, std::min(1, (int)value));
   else if (!strcmp(key, "jacobi_cross")) c->opt.jacobi_cross = (int)value;
   else if (!strcmp(key, "jacobi_early")) c->opt.jacobi_early = value;
   else if (!strcmp(key, "eigmin_pair")) c->opt.eigmin_pair = (int)value;

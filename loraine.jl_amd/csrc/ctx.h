@@ -55,6 +55,8 @@ struct LmiBlock {
   bool has_V = false;
   long vnnz = 0;
   lrn::DBuf v_ptr, v_col, v_val, v_w;
+  bool v_partial = false;   // some constraint with stored entries has no weighted factor column: the factors are not the whole
+                            // block.  Not factored: mode 1 assembles the block from its entries (AA is complete); factored: hybrid
   // --- NT scaling state (device, msz x msz col-major)
   lrn::DBuf X, S, W, G, Gi, Si, D, DDsi;
   lrn::DBuf Vprev;          // right singular vectors of the previous prepare_W (Jacobi warm start)
@@ -74,9 +76,12 @@ struct LmiBlock {
   bool have_Bd = false;     // dense copy of the rank-one factors (rank-one assembly from W)
   lrn::DBuf Vd;             // dense copy of the rank-k factors, msz x (nvar * lr_khat) (dense U product, assembly from W)
   bool have_Vd = false;
-  // factored block (lrn_set_factored): the factors ARE the constraint data -- AA has no entry, AA vec(.) and mat(AA' .) go
-  // through Vd (dataops.hip, "factor form"), the Schur matrix through mode 1 only
+  // factored block (lrn_set_factored): the factors ARE the constraint data -- AA vec(.) and mat(AA' .) go through Vd
+  // (dataops.hip, "factor form"), the Schur matrix through mode 1 only.  Pure: AA has no entry.  Hybrid: a few constraints
+  // are stored instead (rows of AA, positions [0, npos_nz) as everywhere) and have weight-0 factor columns; every constraint
+  // is exactly one of the two.  The stored-entry kernels serve the stored part, schur.hip::assemble_cross the mixed terms
   bool factored = false;
+  bool hybrid() const { return factored && npos_nz > 0; }
 };
 
 struct lrn_ctx;
@@ -141,6 +146,8 @@ struct LrnOptions {
   int matvec_h = 0;               // CG operator through the assembled Schur matrix (hop.hip): 0 auto (cost model), 1 never
                                   // (the matrix-free MyA always), 2 always
   int pcg_lookahead = 2;          // lrn_pcg: iterations the host queues beyond the one whose convergence test it has read
+  int fac_cross_lds = -1;         // cross terms of a hybrid factored block: the column of Y staged in LDS (1, where it fits), read from
+                                  // global memory (0), by the column length (-1)
   int lowrank_form = -1;          // rank-k assembly: U = G' V (or W V) by a sparse gather (0), one dense MFMA product (1), by the
                                   // factors' density (-1)
 };
@@ -198,6 +205,7 @@ struct lrn_ctx {
   // assembly workspaces
   lrn::DBuf P, P2, T, slabs, Hd, BG;
   lrn::DBuf m0, m1, m2, cgbuf;   // msz^2 work matrices (mat-vec / rhs), PCG vectors
+  lrn::DBuf facY, facM;          // hybrid factored block: Y = W Vd when U is G' Vd (msz x nvar khat); the stored part of mat(AA' x)
   int T_m = 0;                 // matrix side and block the T workspace was last laid out for
   const void* T_owner = nullptr;
   int T_layout = 0;            // 0: msz^2 per matrix, lower tiles (T_k = W A_k W); 1: packed lower tiles (L' A_k L)

@@ -905,6 +905,8 @@ int ensure_m(lrn_ctx* c, int m) {
 //     mat(AA' x)    = -Vd diag(w o (x (x) 1_khat)) Vd'   columns scaled into a workspace, one lower-triangle product, mirrored
 // Q and the scaled copy live in the BG workspace (msz x R, what the mode-1 assembly uses for U).  Every sum has a fixed
 // order: one wave per constraint walks its khat columns in order, lanes stride the rows, one shuffle tree -- no atomics.
+// A hybrid block adds the rows of its few stored constraints through the stored-entry kernels (aa_times_impl,
+// aat_to_mat_impl); their factor columns have weight 0 and contribute nothing here.
 
 // out[nat(h)] -= sum_p w[h kh + p] <Q(:, h kh + p), Vd(:, h kh + p)>   (sigma: H index -> constraint, null = identity)
 __global__ __launch_bounds__(256) void fac_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Vd,
@@ -1066,7 +1068,7 @@ int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
 
 // y += AA vec(Z)
 static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
-  if (b.factored) return aa_times_factored(c, b, Z, y);
+  if (b.factored) LRN_TRY(aa_times_factored(c, b, Z, y));      // (a hybrid block goes on with its stored rows; a pure one has none)
   if (b.npos_nz > b.nd) c->counts["op_sparse"] += 1;
   if (b.nd > 0) c->counts["op_dense"] += 1;
   if (b.npos_nz > b.nd)
@@ -1107,8 +1109,22 @@ static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1,
 }
 
 // M = mat(AA' x)  (symmetrised msz x msz, kron_etc.jl:13-18)
+static int aat_to_mat_stored(lrn_ctx* c, LmiBlock& b, const double* x, double* M);
 static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
-  if (b.factored) return aat_to_mat_factored(c, b, x, M);
+  if (!b.factored) return aat_to_mat_stored(c, b, x, M);
+  LRN_TRY(aat_to_mat_factored(c, b, x, M));
+  if (!b.hybrid()) return LRN_OK;
+  // hybrid: the stored rows through the stored-entry kernels into a matrix of their own, then one elementwise sum -- both
+  // terms are exactly symmetric, so the sum is
+  const long mm = (long)b.msz * b.msz;
+  LRN_TRY(ensure(c, c->facM, (size_t)mm * 8));
+  LRN_TRY(aat_to_mat_stored(c, b, x, c->facM.as<double>()));
+  hipLaunchKernelGGL(vec_add_kernel, dim3(nb(mm)), dim3(256), 0, c->stream, M, c->facM.as<double>(), mm);
+  return LRN_OK;
+}
+
+// ... from the stored entries of AA: the sparse tier by stored columns, the dense slots by passes over Adense
+static int aat_to_mat_stored(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
   const int m = b.msz;
   const long mm = (long)m * m;
   if (b.ncq > 0) c->counts["op_sparse"] += 1;

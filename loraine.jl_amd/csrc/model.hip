@@ -182,7 +182,7 @@ void lrn_free_model(lrn_ctx* c) {
   for (auto& b : c->lmi) free_block(b);
   c->lmi.clear();
   for (DBuf* d : {&c->cl_ptr, &c->cl_row, &c->cl_val, &c->lin_xs, &c->H, &c->L, &c->cholwork,
-                  &c->v0, &c->v1, &c->v2, &c->v3, &c->P, &c->P2, &c->T, &c->slabs, &c->Hd, &c->BG, &c->m0, &c->m1, &c->m2, &c->cgbuf, &c->cl_rown,
+                  &c->v0, &c->v1, &c->v2, &c->v3, &c->P, &c->P2, &c->T, &c->slabs, &c->Hd, &c->BG, &c->m0, &c->m1, &c->m2, &c->cgbuf, &c->facY, &c->facM, &c->cl_rown,
                   &c->hdiag, &c->wchol, &c->lp_r, &c->lp_c, &c->lp_ptr, &c->lp_l, &c->lp_w, &c->cr_ptr, &c->cr_col, &c->cr_val})
     release(*d);
   c->T_m = 0;
@@ -552,10 +552,10 @@ extern "C" int lrn_synthetic_dense_model(lrn_ctx* c, int msz, int nvar, uint64_t
 extern "C" int lrn_get_constraint(lrn_ctx* c, int ilmi, int k, double* A_out) {
   if (!c || ilmi < 0 || ilmi >= c->nlmi || k < 0 || k >= c->nvar || !A_out) return LRN_ERR_ARG;
   LmiBlock& b = c->lmi[ilmi];
-  if (b.factored)
+  int pos = b.ipos[k];
+  if (b.factored && pos >= b.npos_nz)          // (a stored constraint of a hybrid block is returned like any other)
     return set_error(c, LRN_ERR_STATE, "lrn_get_constraint: block %d is factored (lrn_set_factored): no constraint matrix is stored", ilmi);
   size_t mm = (size_t)b.msz * b.msz * 8;
-  int pos = b.ipos[k];
   if (pos < b.nd) return copy_out(c, A_out, b.Adense.as<double>() + (size_t)pos * b.msz * b.msz, mm);
   LRN_TRY(ensure(c, c->scratch, mm));
   LRN_HIP(c, hipMemsetAsync(c->scratch.p, 0, mm, c->stream));
@@ -563,6 +563,34 @@ extern "C" int lrn_get_constraint(lrn_ctx* c, int ilmi, int k, double* A_out) {
                      b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), pos,
                      c->scratch.as<double>(), b.msz);
   return copy_out(c, A_out, c->scratch.p, mm);
+}
+
+// A constraint of a factored block is stored (rows of AA) or factored, never both: the first stored position whose factor
+// columns carry a non-zero weight, or -1.  w: the weights in H index order (host).
+static int stored_and_factored(const lrn_ctx* c, const LmiBlock& b, const double* w) {
+  for (int p = 0; p < b.npos_nz; ++p) {
+    const long h = c->pos_space ? p : b.sigma[p];
+    for (int q = 0; q < b.lr_khat; ++q)
+      if (w[h * b.lr_khat + q] != 0.0) return p;
+  }
+  return -1;
+}
+
+// Does a constraint with stored entries have no weighted factor column?  Then the factors do not represent the whole block
+// (a materialised block some of whose constraints were given as matrices only): mode 1 assembles it from its entries.
+static bool factors_partial(const lrn_ctx* c, const LmiBlock& b, const double* w) {
+  for (int p = 0; p < b.npos_nz; ++p) {
+    const long h = c->pos_space ? p : b.sigma[p];
+    bool any = false;
+    for (int q = 0; q < b.lr_khat && !any; ++q) any = w[h * b.lr_khat + q] != 0.0;
+    if (!any) return true;
+  }
+  return false;
+}
+
+static int has_entries_error(lrn_ctx* c, const LmiBlock& b, int ilmi) {
+  return set_error(c, LRN_ERR_STATE, "lrn_set_factored: the AA of block %d has entries (%ld): a factored block takes its "
+                                     "constraints from the factors alone, or each one from a stored row or from factors, never both", ilmi, b.nent);
 }
 
 // Rank-k factors of the constraints of block ilmi (datarank >= 1): A_k = V_k diag(d_k) V_k', V as an (nvar * khat) x msz
@@ -627,6 +655,11 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
   b.lr_khat = khat;
   b.vnnz = nnz;
   b.has_V = true;
+  b.v_partial = factors_partial(c, b, wh.data());
+  if (b.factored && stored_and_factored(c, b, wh.data()) >= 0) {      // (new factors that overlap the stored rows of a hybrid block)
+    b.factored = false;
+    return has_entries_error(c, b, ilmi);
+  }
   if (b.factored) LRN_TRY(lowrank_dense_factors(c, b));      // (new factors of a factored block: its operators read Vd)
   LRN_HIP(c, hipStreamSynchronize(c->stream));
   return LRN_OK;
@@ -634,7 +667,9 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
 
 // on = 1: the factors of lrn_upload_lowrank ARE the constraint data of block ilmi (A_k = V_k diag(d_k) V_k', AA = -A as
 // everywhere): AA vec(.) and mat(AA' .) of the resident path run in factor form (dataops.hip), the Schur matrix comes from
-// mode 1.  The block's AA must be without entries -- no constraint may be counted twice.  on = 0 takes the declaration back.
+// mode 1.  The block's AA is without entries, or holds the rows of a few STORED constraints whose factor columns all have
+// weight 0 (a hybrid block: stored-entry kernels + factor form, cross terms in schur.hip) -- no constraint may be counted
+// twice.  on = 0 takes the declaration back.
 extern "C" int lrn_set_factored(lrn_ctx* c, int ilmi, int on) {
   if (!c) return LRN_ERR_ARG;
   if (ilmi < 0 || ilmi >= c->nlmi) return set_error(c, LRN_ERR_ARG, "lrn_set_factored: block %d of %d", ilmi, c->nlmi);
@@ -646,9 +681,11 @@ extern "C" int lrn_set_factored(lrn_ctx* c, int ilmi, int on) {
   }
   if (!b.has_V)
     return set_error(c, LRN_ERR_STATE, "lrn_set_factored: no factors were uploaded for block %d (lrn_upload_lowrank)", ilmi);
-  if (b.nent > 0 || b.nd > 0 || b.npos_nz > 0 || b.ncq > 0)
-    return set_error(c, LRN_ERR_STATE, "lrn_set_factored: the AA of block %d has entries (%ld): a factored block takes its "
-                                       "constraints from the factors alone", ilmi, b.nent);
+  if (b.npos_nz > 0) {
+    std::vector<double> w((size_t)c->nvar * b.lr_khat);
+    LRN_HIP(c, hipMemcpy(w.data(), b.v_w.p, w.size() * 8, hipMemcpyDeviceToHost));
+    if (stored_and_factored(c, b, w.data()) >= 0) return has_entries_error(c, b, ilmi);
+  }
   LRN_TRY(lowrank_dense_factors(c, b));
   b.factored = true;
   LRN_HIP(c, hipStreamSynchronize(c->stream));

@@ -1058,6 +1058,150 @@ static int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
   return LRN_OK;
 }
 
+// ---- hybrid factored block: a few constraints S are stored (positions [0, npos_nz)), the others F are factors.  H has three
+// parts: H_FF by assemble_lowrank (the stored positions have weight-0 columns and receive + 0), H_SS by assemble_dense /
+// assemble_sparse over the stored positions, and the cross terms, with Y = W Vd (msz x R, column hidx[j] khat + p):
+//     H_sj = tr(A_s W A_j W) = sum_p d_jp y_jp' A_s y_jp            (A_s from ent_v = +A, d from v_w = +d: the signs agree)
+// a sparse quadratic form per column of Y, nnz(A_s) R multiply-adds per stored constraint.
+//
+// fac_cross_kernel: workgroup (x, y) owns the factored position j = p_f + x and the 32 sparse-tier stored positions
+// s0 + 32 y ..; wave v takes the stored positions s0 + 32 y + 4 t + v, t < 8, and keeps their sums in registers.  The khat
+// columns of Y of position j are staged in LDS one at a time (LDS: msz * 8 bytes, up to 32 KiB -- five workgroups per CU) or,
+// for longer columns, gathered from global memory by the same code; lanes stride the entry list of A_s, one shuffle tree
+// adds in a fixed order, the sum is weighted by d_jp and added over p in order.  Each workgroup writes its 32 entries of the
+// lower triangle of H exactly once, += because the blocks of a model share H.  No atomics: two assemblies give the same bits.
+template <bool LDS>
+__global__ __launch_bounds__(256) void fac_cross_kernel(const long* __restrict__ ptr, const int* __restrict__ er,
+                                                        const int* __restrict__ ec, const double* __restrict__ ev,
+                                                        const double* __restrict__ Y, const double* __restrict__ w, int m, int kh,
+                                                        int s_lo, int s_hi, int p_f, int p_end,
+                                                        const int* __restrict__ hidx, double* __restrict__ H, int ldh) {
+  extern __shared__ double ycol[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = p_f + blockIdx.x;
+  if (j >= p_end) return;                        // (whole workgroup)
+  const int hj = hidx[j];
+  const int sb = s_lo + blockIdx.y * 32 + wave;
+  double acc[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) acc[t] = 0.0;
+  for (int p = 0; p < kh; ++p) {
+    const long col = (long)hj * kh + p;
+    const double wp = w[col];
+    if (wp == 0.0) continue;                     // padding column (uniform over the workgroup)
+    const double* __restrict__ yg = Y + col * m;
+    if (LDS) {
+      __syncthreads();                           // the waves are done with the previous column
+      for (int r = threadIdx.x; r < m; r += 256) ycol[r] = yg[r];
+      __syncthreads();
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int sp = sb + 4 * t;                 // wave-uniform
+      if (sp >= s_hi) continue;
+      double q = 0.0;
+      for (long e = ptr[sp] + lane; e < ptr[sp + 1]; e += 64) {
+        const int r = er[e], cc = ec[e];
+        q += ev[e] * (LDS ? ycol[r] * ycol[cc] : yg[r] * yg[cc]);
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
+      acc[t] += wp * q;
+    }
+  }
+  if (lane != 0) return;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const int sp = sb + 4 * t;
+    if (sp >= s_hi) continue;
+    const int hs = hidx[sp];
+    const int rr = hs > hj ? hs : hj, cc = hs > hj ? hj : hs;
+    H[(long)rr + (long)cc * ldh] += acc[t];
+  }
+}
+
+// stored constraint in dense slot s: Q = A_s Y is one product, H_sj = sum_p d_jp <Q(:, jp), Y(:, jp)> one wave per factored
+// position j (the column dot of dataops.hip::fac_coldot_kernel), written once
+__global__ __launch_bounds__(256) void fac_cross_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Y,
+                                                               const double* __restrict__ w, int m, int kh, int s, int p_f,
+                                                               int p_end, const int* __restrict__ hidx, double* __restrict__ H,
+                                                               int ldh) {
+  const int lane = threadIdx.x & 63;
+  const int j = p_f + blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= p_end) return;
+  const int hj = hidx[j];
+  double acc = 0.0;
+  for (int p = 0; p < kh; ++p) {
+    const long col = (long)hj * kh + p;
+    const double wp = w[col];
+    if (wp == 0.0) continue;
+    const double* __restrict__ q = Q + col * m;
+    const double* __restrict__ y = Y + col * m;
+    double t = 0.0;
+    for (int r = lane; r < m; r += 64) t += q[r] * y[r];
+    acc += wp * t;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if (lane != 0) return;
+  const int hs = hidx[s];
+  const int rr = hs > hj ? hs : hj, cc = hs > hj ? hj : hs;
+  H[(long)rr + (long)cc * ldh] += acc;
+}
+
+static int assemble_cross(lrn_ctx* c, LmiBlock& b) {
+  const int n = c->nvar, m = b.msz, kh = b.lr_khat;
+  const long R = (long)n * kh;
+  if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");
+  const int nf = n - b.npos_nz;
+  if (nf <= 0) return LRN_OK;
+  // Y = W Vd: what assemble_lowrank left in BG when only W exists, one more product into a workspace of its own otherwise
+  const double* Y = c->BG.as<double>();
+  tic(c);
+  if (b.have_G) {
+    LRN_TRY(ensure(c, c->facY, (size_t)m * R * 8));
+    GemmDesc g;
+    g.A = b.W.as<double>(); g.sAm = 1; g.sAk = m;
+    g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
+    g.C = c->facY.as<double>(); g.sCm = 1; g.sCn = m;
+    g.M = m; g.N = (int)R; g.K = m;
+    LRN_TRY(gemm(c->stream, g));
+    Y = c->facY.as<double>();
+  }
+  toc(c, "hybrid_y");
+  tic(c);
+  if (b.npos_nz > b.nd) {
+    const size_t cap = c->opt.fac_cross_lds == 1 ? 65536 : 32768;      // bytes of one column: forced / by default
+    const bool lds = c->opt.fac_cross_lds != 0 && (size_t)m * 8 <= cap;
+    const dim3 grid((unsigned)nf, (unsigned)((b.npos_nz - b.nd + 31) / 32));
+#define LRN_CROSS_LAUNCH(L, SH)                                                                                        \
+  hipLaunchKernelGGL(fac_cross_kernel<L>, grid, dim3(256), SH, c->stream, b.ent_ptr.as<long>(), b.ent_r.as<int>(),    \
+                     b.ent_c.as<int>(), b.ent_v.as<double>(), Y, b.v_w.as<double>(), m, kh, b.nd, b.npos_nz, b.npos_nz, n, \
+                     b.hidx.as<int>(), c->H.as<double>(), n)
+    if (lds) LRN_CROSS_LAUNCH(true, (size_t)m * 8);
+    else LRN_CROSS_LAUNCH(false, 0);
+#undef LRN_CROSS_LAUNCH
+    c->counts[lds ? "hybrid_cross_lds" : "hybrid_cross_global"] += 1;
+  }
+  if (b.nd > 0) {
+    LRN_TRY(ensure(c, c->P, (size_t)m * R * 8));
+    double* Q = c->P.as<double>();
+    for (int s = 0; s < b.nd; ++s) {
+      GemmDesc g;     // Q = A_s Y
+      g.A = b.Adense.as<double>() + (long)s * m * m; g.sAm = 1; g.sAk = m;
+      g.B = Y; g.sBk = 1; g.sBn = m;
+      g.C = Q; g.sCm = 1; g.sCn = m;
+      g.M = m; g.N = (int)R; g.K = m;
+      LRN_TRY(gemm(c->stream, g));
+      hipLaunchKernelGGL(fac_cross_coldot_kernel, dim3((nf + 3) / 4), dim3(256), 0, c->stream, Q, Y, b.v_w.as<double>(), m, kh,
+                         s, b.npos_nz, n, b.hidx.as<int>(), c->H.as<double>(), n);
+    }
+    c->counts["hybrid_cross_dense"] += 1;
+  }
+  toc(c, "hybrid_cross");
+  return LRN_OK;
+}
+
 int schur_assemble(lrn_ctx* c, int mode) {
   const int n = c->nvar;
   if (n <= 0) return set_error(c, LRN_ERR_STATE, "no model uploaded");
@@ -1073,6 +1217,10 @@ int schur_assemble(lrn_ctx* c, int mode) {
     if (b.factored && mode != 1)
       return set_error(c, LRN_ERR_STATE, "lrn_schur_assemble: mode %d on a factored block (lrn_set_factored): its constraints "
                                          "exist as factors only, mode 1 assembles from them", mode);
+  for (const auto& b : c->lmi)
+    if (b.hybrid() && c->world > 1)
+      return set_error(c, LRN_ERR_STATE, "lrn_schur_assemble: mode 1 on a factored block with stored constraints runs on one "
+                                         "GPU (the cross terms are not sharded)");
   LRN_HIP(c, hipMemsetAsync(c->H.p, 0, (size_t)n * n * 8, c->stream));
   c->H_partial = false;
   c->H_owned_only = false;
@@ -1081,8 +1229,23 @@ int schur_assemble(lrn_ctx* c, int mode) {
       LRN_TRY(assemble_rank1(c, b));
       continue;
     }
+    if (mode == 1 && !b.factored && b.has_V && b.v_partial) {
+      // factors for some constraints only, and the block is not factored: its AA holds every constraint (a hybrid model the
+      // host materialised), the factors do not -- the general assembly over the entries is the exact one
+      if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");
+      if (b.nd > 0) LRN_TRY(assemble_dense(c, b));
+      if (b.npos_nz > b.nd) LRN_TRY(assemble_sparse(c, b));
+      c->counts["lowrank_from_entries"] += 1;
+      continue;
+    }
     if (mode == 1) {
+      if (b.hybrid()) {     // H_SS from the stored entries, then H_FF and the cross terms (see assemble_cross)
+        if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");
+        if (b.nd > 0) LRN_TRY(assemble_dense(c, b));
+        if (b.npos_nz > b.nd) LRN_TRY(assemble_sparse(c, b));
+      }
       LRN_TRY(assemble_lowrank(c, b));
+      if (b.hybrid()) LRN_TRY(assemble_cross(c, b));
       continue;
     }
     if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");

@@ -40,6 +40,10 @@ class MyModel:
     from_factors: bool = False     # built by build_factored_model (some or all blocks may have been materialised)
     factored_blocks: list = field(default_factory=list)
     aa_fro: list = field(default_factory=list)
+    # hybrid factored block: a few constraints are STORED matrices instead of factors -- stored[i] = {k: A_i,k+1 (csc)} (0-based
+    # k; {} for a pure or a materialised block).  AA[i] then holds the rows of the stored constraints only, lowrank[i]
+    # weight-0 columns for them, aa_fro[i] both parts; A[i] stays [F_0]
+    stored: list = field(default_factory=list)
 
 
 def _rank_one_rows(blockA, n):
@@ -230,8 +234,25 @@ def factors_fro(V, d, khat, n, chunk=256):
     return float(np.sqrt(max(tot, 0.0)))
 
 
+def _stored_matrix(item, m, where):
+    """A stored constraint: symmetric m x m, SciPy sparse or a 2-D array -> csc without explicit zeros, or ValueError."""
+    if not sp.issparse(item):
+        item = np.asarray(item, dtype=np.float64)
+        if item.ndim != 2:
+            raise ValueError(f"{where}: a stored constraint is a 2-D matrix, got {item.ndim} dimension(s)")
+    if item.shape != (m, m):
+        raise ValueError(f"{where}: stored matrix is {item.shape}, the block has side {m}")
+    A = sp.csc_matrix(item, dtype=np.float64)
+    A.eliminate_zeros()
+    skew = abs(A - A.T)
+    if skew.nnz and skew.max() > 1e-12 * abs(A).max():
+        raise ValueError(f"{where}: stored matrix is not symmetric (max |A - A'| = {skew.max():.3e})")
+    return A
+
+
 def _check_factors(F0, factors, n):
-    """factors[i][k] = (V, d) -> dense (m x r) V and d per constraint, or ValueError."""
+    """factors[i][k] = (V, d) -> dense (m x r) V and d per constraint, or a symmetric m x m matrix (a stored constraint) -> csc;
+    ValueError otherwise."""
     if len(factors) != len(F0):
         raise ValueError(f"factors for {len(factors)} LMI blocks, F0 has {len(F0)}")
     out = []
@@ -242,7 +263,11 @@ def _check_factors(F0, factors, n):
         if len(blk) != n:
             raise ValueError(f"block {i + 1}: factors of {len(blk)} constraints, b has {n} entries")
         facs = []
-        for j, (V, d) in enumerate(blk):
+        for j, item in enumerate(blk):
+            if sp.issparse(item) or isinstance(item, np.ndarray):
+                facs.append(_stored_matrix(item, m, f"block {i + 1}, constraint {j + 1}"))
+                continue
+            V, d = item
             V = np.asarray(V.toarray() if sp.issparse(V) else V, dtype=np.float64)
             if V.ndim == 1:
                 V = V.reshape(-1, 1)
@@ -261,33 +286,44 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
     """A model given by F_0 (per block), b, optional linear rows and the factors alone: A_ik = V diag(d) V' with
     factors[i][k] = (V (m_i x r, r <= 16, dense or sparse), d (+-1)).  No A_ik is formed for a factored block: its AA is
     an n x m^2 matrix without entries (nzA = 0, identity sigmaA) and `lowrank` carries the data.
+    factors[i][k] may instead be a symmetric m_i x m_i matrix (SciPy sparse or a 2-D array): constraint k of block i is
+    STORED.  A block with both kinds is hybrid: its AA holds the rows -vec(A) of the stored constraints only, nzA / sigmaA /
+    qA follow the rule of _prepare_A (stable sort by nnz, descending: the stored constraints take the first positions, the
+    factored ones follow in their natural order), `lowrank` pads the stored constraints with weight-0 columns, `stored`
+    keeps the matrices.
     factored_form: 1 = every block factored; -1 = a block whose factors are so small that the sparse path serves it --
-    sum_k nnz(V_k V_k') <= kappa * n, i.e. on average at most `datasparsity` entries per constraint, the count below which
-    the reference treats a constraint as sparse -- is materialised (sparse AA built from the factors, the existing
-    path) and stays un-factored."""
+    sum_k nnz(V_k V_k') <= kappa * (number of factored constraints), i.e. on average at most `datasparsity` entries per
+    constraint, the count below which the reference treats a constraint as sparse -- is materialised (sparse AA built from
+    the factors, stored matrices taken as they are, the existing path) and stays un-factored."""
     n = len(b)
     if factored_form not in (-1, 1):
         raise ValueError(f"factored_form = {factored_form} (-1 auto, 1 always factored)")
-    facs_all = _check_factors(F0, factors, n)
+    items_all = _check_factors(F0, factors, n)
     nlmi = len(F0)
-    A, AA, C, lowrank, fblocks, aa_fro = [], [], [], [], [], []
+    A, AA, C, lowrank, fblocks, aa_fro, stored = [], [], [], [], [], [], []
     nzA = np.zeros((n, nlmi), dtype=np.int64)
     sigmaA = np.zeros((n, nlmi), dtype=np.int64)
     qA = np.zeros((2, nlmi), dtype=np.int64)
-    for i, facs in enumerate(facs_all):
+    for i, items in enumerate(items_all):
         if sp.issparse(F0[i]):
             F = sp.csc_matrix(F0[i])
             F.eliminate_zeros()
         else:
             F = np.asarray(F0[i], dtype=np.float64)            # (a dense F_0 stays dense: C is then a dense array too)
         m = F.shape[0]
+        st = {k: it for k, it in enumerate(items) if sp.issparse(it)}
+        none = (np.zeros((m, 0)), np.zeros(0))                 # a stored constraint has no factor column
+        facs = [none if k in st else it for k, it in enumerate(items)]
         lr = pad_factors(facs, n, m)
         lowrank.append(lr)
         supp = [int(np.count_nonzero(np.any(V != 0.0, axis=1))) for V, _ in facs]
-        small = sum(s * s for s in supp) <= kappa * n
+        small = sum(s * s for s in supp) <= kappa * (n - len(st))
         if factored_form == -1 and small:
             blk = [sp.csc_matrix(F)]
-            for (V, d), s in zip(facs, supp):
+            for k, ((V, d), s) in enumerate(zip(facs, supp)):
+                if k in st:
+                    blk.append(st[k])
+                    continue
                 rows = np.nonzero(np.any(V != 0.0, axis=1))[0]
                 sub = (V[rows] * d) @ V[rows].T
                 Ak = sp.coo_matrix((sub.ravel(), (np.repeat(rows, s), np.tile(rows, s))), shape=(m, m)).tocsc()
@@ -298,6 +334,17 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
             nzA[:, i], sigmaA[:, i], qA[:, i] = nz[:, 0], sg[:, 0], q[:, 0]
             fblocks.append(False)
             aa_fro.append(float(sp.linalg.norm(AAi[0])))
+            stored.append({})
+        elif st:
+            empty = sp.csc_matrix((m, m))
+            AAi, _, _, nz, sg, q = _prepare_A([[empty] + [st.get(k, empty) for k in range(n)]], 0, kappa, n)
+            A.append([F])
+            AA.append(AAi[0])
+            C.append(sp.csc_matrix(-F) if sp.issparse(F) else -F)
+            nzA[:, i], sigmaA[:, i], qA[:, i] = nz[:, 0], sg[:, 0], q[:, 0]
+            fblocks.append(True)
+            aa_fro.append(float(np.hypot(factors_fro(*lr, n), sp.linalg.norm(AAi[0]))))
+            stored.append(st)
         else:
             A.append([F])
             AA.append(sp.csr_matrix((n, m * m)))
@@ -305,13 +352,14 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
             sigmaA[:, i] = np.arange(n)
             fblocks.append(True)
             aa_fro.append(factors_fro(*lr, n))
+            stored.append({})
     if C_lin is None or C_lin.shape[1] == 0:
         C_lin = sp.csr_matrix((n, 0))
         d_lin = np.zeros(0)
     msizes = np.array([blk[0].shape[0] for blk in A], dtype=np.int64)
     return MyModel(A, AA, [], C, nzA, sigmaA, qA, np.asarray(b, float), float(b_const), np.asarray(d_lin, float),
                    sp.csr_matrix(C_lin), n, msizes, int(C_lin.shape[1]), nlmi, lowrank, "",
-                   any(fblocks), True, fblocks, aa_fro)
+                   any(fblocks), True, fblocks, aa_fro, stored)
 
 
 def _tokens(line):

@@ -83,6 +83,9 @@ class Optimizer:
         factors[i][k] = (V, d) with A_i,k+1 = V diag(d) V' (V msz x r, r <= 16, d = +-1, dense or sparse).  No A_ik, no
         row of AA and no dense constraint slab is ever formed, on the host or on the device; implies datarank = the
         largest rank (at least 1) and needs kit = 0 and the resident solver (ValueError otherwise).
+        factors[i][k] may instead be a symmetric msz x msz matrix (SciPy sparse or a 2-D array): that constraint is stored
+        as a matrix -- a trace row, a few sparse side constraints among thousands of factored ones (a hybrid block; the
+        others stay factors, nothing else is materialised).
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
         if not self.resident:

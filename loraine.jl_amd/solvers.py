@@ -196,7 +196,7 @@ class MySolver:
             if self.initpoint == 0:
                 eps_, eta_ = 1.0, float(m.n)
             else:
-                # (||AA_i||_F: of a factored block from its factors, model.factors_fro)
+                # (||AA_i||_F: of a factored block from its factors, model.factors_fro, and the stored rows of a hybrid one)
                 naa = m.aa_fro[i] if getattr(m, "factored", False) and m.factored_blocks[i] else _fro(m.AA[i])
                 f = np.linalg.norm(b2) / (1.0 + naa)
                 eps_ = math.sqrt(s) * max(1.0, math.sqrt(s) * f)

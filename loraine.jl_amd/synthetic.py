@@ -124,9 +124,12 @@ class FactoredLowRankProblem:
     dense msz x krank with N(0, 1/msz) entries, d = +-1.  The optimum is planted the way LowRankProblem plants its own:
     X* = Q diag(lam) Q' (rank xrank, trace sqrt(msz) -- see the warning there), S* = I - Q Q', y* ~ 0.1 N(0,1),
     b_k = <M_k, X*> = -sum_p d_kp |lam^1/2 Q' v_kp|^2,  C = S* + sum_k y*_k M_k = S* - Vall diag(y* (x) d) Vall'.
-    Everything is formed from products of V: no msz x msz matrix per constraint exists at any point."""
+    Everything is formed from products of V: no msz x msz matrix per constraint exists at any point.
+    stored (optional): [(k, A)] -- constraint k is the symmetric sparse matrix A instead of its factors (a hybrid block: a
+    trace row, a few sparse side constraints); b, C and F0 include it, factors() returns A in place k.  The draws do not
+    depend on it, so the factored constraints are those of the problem without it."""
 
-    def __init__(self, msz, nvar, krank=2, xrank=4, seed=20250616, xtrace=None):
+    def __init__(self, msz, nvar, krank=2, xrank=4, seed=20250616, xtrace=None, stored=None):
         rng = np.random.default_rng(seed)
         self.msz, self.nvar, self.krank, self.xrank = int(msz), int(nvar), int(krank), int(xrank)
         self.V = rng.standard_normal((nvar, msz, krank)) / np.sqrt(msz)
@@ -137,15 +140,28 @@ class FactoredLowRankProblem:
         QV = np.einsum("ma,kmp->kap", Q, self.V)                                  # Q' V_k
         self.b = -np.einsum("kp,a,kap,kap->k", self.d, self.lam, QV, QV)
         self.ystar = 0.1 * rng.standard_normal(nvar)
+        self.stored = {}
+        for k, Ak in (stored or []):
+            Ak = sp.csc_matrix(Ak, dtype=np.float64)
+            if not 0 <= int(k) < self.nvar or Ak.shape != (self.msz, self.msz):
+                raise ValueError(f"stored constraint {k}: index out of range or matrix {Ak.shape} not {self.msz} x {self.msz}")
+            self.stored[int(k)] = Ak
+            self.b[int(k)] = -float(np.sum(self.lam * np.einsum("ma,ma->a", Q, Ak @ Q)))      # -<A_k, X*>
         self.optimum = float(self.b @ self.ystar)
 
     def factors(self):
-        return [[(self.V[k], self.d[k]) for k in range(self.nvar)]]
+        return [[self.stored[k] if k in self.stored else (self.V[k], self.d[k]) for k in range(self.nvar)]]
 
     def C_dense(self):
         m = self.msz
         Vall = self.V.transpose(1, 0, 2).reshape(m, -1)                           # column k * krank + p = column p of V_k
-        Cd = np.eye(m) - self.Q @ self.Q.T - (Vall * (self.ystar[:, None] * self.d).ravel()) @ Vall.T
+        wgt = self.ystar[:, None] * self.d
+        if self.stored:
+            wgt = wgt.copy()
+            wgt[list(self.stored)] = 0.0
+        Cd = np.eye(m) - self.Q @ self.Q.T - (Vall * wgt.ravel()) @ Vall.T
+        for k, Ak in self.stored.items():
+            Cd -= self.ystar[k] * Ak.toarray()
         return np.asfortranarray(0.5 * (Cd + Cd.T))
 
     def F0(self):
@@ -153,4 +169,6 @@ class FactoredLowRankProblem:
 
     def constraint(self, k):
         """A_k as a dense matrix (tests at small size / the CPU oracle)."""
+        if k in self.stored:
+            return self.stored[k].toarray()
         return (self.V[k] * self.d[k]) @ self.V[k].T
