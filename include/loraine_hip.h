@@ -148,7 +148,17 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * run (run 0 / 1 of a pair in lock-step; a launch of a single run has run 0 only) keeps its publication of ONE step (step 0:
  * the first of the launch, 1: a middle one, 2: the last) to itself.  Its peers' wait runs into lz_res_limit, all workgroups
  * return normally, the host repeats the run with one launch per step; lrn_get_count("lz_test_withheld") goes up when the armed
- * launch is queued and, like "lz_no_persist", survives reset_timing; 0 disarms), "reset_timing".
+ * launch is queued and, like "lz_no_persist", survives reset_timing; 0 disarms),
+ * "cg_lowrank" (the CG path -- lrn_matvec, lrn_prec_setup, lrn_pcg -- from the rank-k factors of lrn_upload_lowrank: 0, default
+ * = never, every route and every bit as without factors; 1 = always, for every COVERED block: one that is not declared
+ * factored and whose factors reach every constraint that has entries; -1 = a static cost model decides per piece.  The
+ * pieces: the assembled-matrix operator ("matvec_h") assembles H in mode 1 when every LMI block is covered; the matrix-free
+ * operator takes mat(AA' x) and AA vec(W M W) of a covered block in the factor form of factored blocks; lrn_prec_setup forms
+ * the block of ts = D^-1/2 AA (U (x) Z) of a covered block as P = L' Vd, T = Vd' Um and one weighted, transposing pass over P
+ * instead of one pass over every A_k per eigenvector.  Everything else that reads AA -- lrn_make_rhs, lrn_ip_*, the general
+ * assembly -- stays on the entries.  Factored and hybrid blocks keep refusing the CG entry points.  With world > 1
+ * (lrn_set_shard, lrn_comm_init) the option is ignored and the entry routes run: the factor routes are not sharded and have
+ * only been run on one GPU), "reset_timing".
  * Counters of this path (lrn_get_count): "lz_resident_launches" (resident launches queued), "lz_persist_abort" (those that
  * gave up), and the STATE "lz_no_persist" (0 / 1, survives reset_timing: a resident launch of this context has given up, all
  * Lanczos steps are launched one by one from then on). */
@@ -322,7 +332,10 @@ int lrn_comm_allreduce(lrn_ctx* ctx, double* buf, int64_t count, int op);
  * "CG predictor" / "CG corrector" (src/predictor_corrector.jl:130,234) = pcg, "find step corrector" (:243). */
 int lrn_get_timing(lrn_ctx* ctx, const char* key, double* ms);
 /* launch / event counters of the same phases; "shard_bs" returns the column-block width of the Schur
- * sharding in effect (option "shard_bs": 0 = auto, two 128-aligned blocks per rank) */
+ * sharding in effect (option "shard_bs": 0 = auto, two 128-aligned blocks per rank).  Option "cg_lowrank":
+ * "hop_assemble_lowrank" (assemblies of the CG operator's H in mode 1; "hop_assemble" counts them too), "op_factored_cg"
+ * (blocks the matrix-free CG operator took in factor form, per application), "prec_ts_factored" (STATE: the blocks whose
+ * part of ts came from the factors in the last lrn_prec_setup) */
 int64_t lrn_get_count(lrn_ctx* ctx, const char* key);
 /* FP64 MFMA issue-rate probe (TFLOP/s of a register-only v_mfma_f64_16x16x4_f64 loop; an 8 ms warm-up launch and 43 ms
  * timed, so that the clock's ramp after an idle period is not what is measured: 77.3-77.8 on an MI355X) */

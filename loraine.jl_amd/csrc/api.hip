@@ -116,6 +116,10 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "comm_fail_ensure")) lrn::comm_inject_ensure_failure(c);      // test hook (tests/test_gpu_comm.py)
   else if (!strcmp(key, "pcg_lookahead")) c->opt.pcg_lookahead = std::max(0, std::min(8, (int)value));
   else if (!strcmp(key, "lowrank_form")) c->opt.lowrank_form = std::max(-1, std::min(1, (int)value));
+  else if (!strcmp(key, "cg_lowrank")) {      // (the operator choice is taken again; an H of the other mode is not reused)
+    c->opt.cg_lowrank = std::max(-1, std::min(1, (int)value));
+    c->hop_version = -1;
+  }
   else if (!strcmp(key, "fac_cross_lds")) c->opt.fac_cross_lds = std::max(-1, std::min(1, (int)value));
   else if (!strcmp(key, "jacobi_cross")) c->opt.jacobi_cross = (int)value;
   else if (!strcmp(key, "jacobi_early")) c->opt.jacobi_early = value;

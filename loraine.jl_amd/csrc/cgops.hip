@@ -43,6 +43,7 @@ struct Prec {
   // -- inside lrn_pcg the seven launches of the SMW apply become one pass over nvar (nvar + 1) / 2 doubles (symv_lower)
   bool has_dense = false;
   DBuf Minv, T1;
+  DBuf Tf;       // ts from the rank-k factors: T = Vd' Um, (nvar khat) x erank
 };
 
 // y = alpha M x + beta z for a symmetric n x n matrix, 16 rows per workgroup, x staged in LDS (n <= 8192): one launch
@@ -78,7 +79,7 @@ void prec_free(lrn_ctx* c) {
   if (!c->prec) return;
   Prec* p = c->prec;
   for (DBuf* d : {&p->d, &p->ts, &p->cholS, &p->workS, &p->y, &p->y2, &p->y3, &p->y4, &p->zpart, &p->E, &p->Um,
-                  &p->AU, &p->sig, &p->LD, &p->workD, &p->Cd, &p->Sm, &p->Ainv, &p->Minv, &p->T1})
+                  &p->AU, &p->sig, &p->LD, &p->workD, &p->Cd, &p->Sm, &p->Ainv, &p->Minv, &p->T1, &p->Tf})
     release(*d);
   delete p;
   c->prec = nullptr;
@@ -308,6 +309,52 @@ __global__ __launch_bounds__(256) void au_dense_kernel(const double* __restrict_
   }
 }
 
+// ts of H_alpha from the rank-k factors of a covered block (option "cg_lowrank").  With A_j = sum_p w_hp v_hp v_hp' (h the H
+// index of constraint j, the one the factor columns are stored in), L the Cholesky factor of 2 W - Um Um' and u_a column a
+// of Um, the entry route forms  ts[j, a m + r] = -(L' A_j u_a)[r] / sqrt(d_j)  by one pass over every A_j per eigenvector.
+// Here  P = L' Vd  (m x R, one MFMA product for ALL eigenvectors) and  T = Vd' Um  (R x erank) come first, and
+//     ts[j, col0 + a m + r] = -(1 / sqrt(d_j)) sum_p w[h kh + p] T[h kh + p, a] P[r, h kh + p]
+// is what this kernel does: a weighted sum of the kh columns of P of each constraint, in the order p = 0 .. kh - 1 (no
+// atomics: two setups give the same bits), written TRANSPOSED -- P is contiguous along r, ts along j.
+// Workgroup tile: 64 constraints (natural rows j0 .. j0 + 63 of ts) x 64 rows r of P, eigenvector a = blockIdx.z.  Wave w
+// takes the constraints j0 + w, j0 + w + 4, ..: its 64 lanes read 64 consecutive doubles of each column of P (512 B per
+// load, coalesced whatever the order of h = ipos[j]) with the coefficient w T as a wave-uniform scalar, and store the sums
+// as row jl of an LDS tile of 64 x 65 doubles (33 280 bytes; ds_write_b64 of consecutive addresses).  After the barrier lane
+// l of wave w reads tile[l][rr], rr = w, w + 4, .. -- a stride of 65 doubles = 130 banks, 2 l mod 64 over a 32-lane half:
+// conflict-free, where 64 would be a 32-way conflict -- and the wave writes 64 consecutive rows j of one column of ts.
+static constexpr int FTS_TILE = 64;
+__global__ __launch_bounds__(256) void fac_ts_kernel(const double* __restrict__ Pm, const double* __restrict__ T,
+                                                     const double* __restrict__ w, const int* __restrict__ ipos,
+                                                     const double* __restrict__ d, int m, int kh, long R, int nvar,
+                                                     double* __restrict__ ts) {
+  __shared__ double tile[FTS_TILE][FTS_TILE + 1];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int j0 = blockIdx.x * FTS_TILE, r0 = blockIdx.y * FTS_TILE, a = blockIdx.z;
+  const double* __restrict__ Ta = T + (long)a * R;
+  const int r = r0 + lane;
+  for (int jl = wv; jl < FTS_TILE; jl += 4) {
+    const int j = j0 + jl;
+    double s = 0.0;
+    if (j < nvar) {                                  // (wave-uniform)
+      const long c0 = (long)(ipos ? ipos[j] : j) * kh;
+      for (int p = 0; p < kh; ++p) {
+        const double wp = w[c0 + p];
+        if (wp == 0.0) continue;                     // padding column
+        const double cf = wp * Ta[c0 + p];
+        if (r < m) s += cf * Pm[(c0 + p) * m + r];
+      }
+    }
+    tile[jl][lane] = s;
+  }
+  __syncthreads();
+  const int j = j0 + lane;
+  if (j >= nvar) return;
+  const double sc = -1.0 / sqrt(d[j]);
+  double* __restrict__ out = ts + (long)a * m * nvar + j;
+  for (int rr = wv; rr < FTS_TILE && r0 + rr < m; rr += 4) out[(long)(r0 + rr) * nvar] = sc * tile[lane][rr];
+}
+
 // Cd[i, l] = C_lin[i, l] * sqrt(xs_l)   (dense nvar x nlin image of the linear block)
 __global__ void lin_dense_kernel(const long* __restrict__ ptr, const int* __restrict__ row, const double* __restrict__ val,
                                  const double* __restrict__ xs, int nlin, int n, double* __restrict__ Cd) {
@@ -344,6 +391,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
   P->kind = kind;
   P->erank = erank;
   P->has_dense = false;
+  c->counts["prec_ts_factored"] = 0;
   const int n = c->nvar;
   hipStream_t st = c->stream;
   if (kind == 0) return LRN_OK;
@@ -447,6 +495,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
   if (kind == 1) {
     LRN_TRY(ensure(c, P->ts, (size_t)n * ksz * 8));
     int col0 = 0;
+    long ts_factored = 0;      // blocks whose part of ts came from the factors ("prec_ts_factored", of the LAST setup)
     for (int il = 0; il < c->nlmi; ++il) {
       LmiBlock& b = c->lmi[il];
       const int m = b.msz, k = erank;
@@ -493,6 +542,33 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       }
       if (h != 0) { if (info) *info = h; return LRN_OK; }
       hipLaunchKernelGGL(tril2_kernel, dim3(nb((long)m * m)), dim3(256), 0, st, Zf, m);
+      if (cg_lowrank_ts(c, b, k)) {
+        // from the rank-k factors: P = L' Vd and T = Vd' Um, then fac_ts_kernel (the whole nvar x k m block, every element once)
+        const int kh = b.lr_khat;
+        const long R = (long)n * kh;
+        LRN_TRY(lowrank_dense_factors(c, b));
+        LRN_TRY(ensure(c, c->BG, (size_t)m * R * 8));
+        LRN_TRY(ensure(c, P->Tf, (size_t)R * k * 8));
+        GemmDesc gp;     // P = L' Vd, m x R (the upper triangle of Zf is zero: tril2_kernel)
+        gp.A = Zf; gp.sAm = m; gp.sAk = 1;
+        gp.B = b.Vd.as<double>(); gp.sBk = 1; gp.sBn = m;
+        gp.C = c->BG.as<double>(); gp.sCm = 1; gp.sCn = m;
+        gp.M = m; gp.N = (int)R; gp.K = m;
+        LRN_TRY(gemm(st, gp));
+        GemmDesc gt;     // T = Vd' Um, R x k
+        gt.A = b.Vd.as<double>(); gt.sAm = m; gt.sAk = 1;
+        gt.B = Um; gt.sBk = 1; gt.sBn = m;
+        gt.C = P->Tf.as<double>(); gt.sCm = 1; gt.sCn = R;
+        gt.M = (int)R; gt.N = k; gt.K = m;
+        LRN_TRY(gemm(st, gt));
+        hipLaunchKernelGGL(fac_ts_kernel, dim3((n + FTS_TILE - 1) / FTS_TILE, (m + FTS_TILE - 1) / FTS_TILE, k), dim3(256), 0, st,
+                           c->BG.as<double>(), P->Tf.as<double>(), b.v_w.as<double>(),
+                           c->pos_space ? b.ipos_d.as<int>() : (const int*)nullptr, P->d.as<double>(), m, kh, R, n,
+                           P->ts.as<double>() + (size_t)col0 * n);
+        ++ts_factored;
+        col0 += k * m;
+        continue;
+      }
       // ts[:, block a] = (D^-1/2 AU_a) Z
       LRN_TRY(ensure(c, P->AU, (size_t)n * m * 8));
       for (int a = 0; a < k; ++a) {
@@ -514,6 +590,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       }
       col0 += k * m;
     }
+    c->counts["prec_ts_factored"] = ts_factored;
     if (P->has_LD)      // ts = L_D^-1 t   (the reference: AAAATtau \ t, Solvers.jl:767)
       LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, false, P->ts.as<double>(), ksz, n,
                               P->workD.as<double>() + chol_work_doubles(n)));

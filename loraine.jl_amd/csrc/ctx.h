@@ -150,6 +150,10 @@ struct LrnOptions {
                                   // global memory (0), by the column length (-1)
   int lowrank_form = -1;          // rank-k assembly: U = G' V (or W V) by a sparse gather (0), one dense MFMA product (1), by the
                                   // factors' density (-1)
+  int cg_lowrank = 0;             // CG path (kit = 1) from the rank-k factors of a covered block (cg_lowrank_covered): 0 never (the
+                                  // entry routes, bit for bit), 1 always, -1 the static cost model of hop.hip decides per piece --
+                                  // the mode of the assembled-matrix operator, the form of the matrix-free operator, the route
+                                  // of the H_alpha setup.  Ignored with world > 1
 };
 
 struct lrn_ctx {
@@ -266,6 +270,10 @@ int symv_lower(lrn_ctx* c, const double* A_dev, int n, const int* idx, const dou
                double* qpart = nullptr, int* nq = nullptr, bool sharded = false);
 bool hop_worthwhile(lrn_ctx* c, long expected_iters);
 int hop_prepare(lrn_ctx* c);
+// option "cg_lowrank" (hop.hip): the factors of a block are its whole constraint data and the block still has its entries
+inline bool cg_lowrank_covered(const LmiBlock& b) { return !b.factored && b.has_V && !b.v_partial; }
+bool cg_lowrank_operator(const lrn_ctx* c, const LmiBlock& b);   // matrix-free operator of this block in factor form?
+bool cg_lowrank_ts(const lrn_ctx* c, const LmiBlock& b, int erank);   // ts of H_alpha for this block from the factors?
 }  // namespace lrn
 
 #define LRN_HIP(c, expr)                                                                   \

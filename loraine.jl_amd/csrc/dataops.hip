@@ -1050,24 +1050,28 @@ struct OpTimer {
   }
 };
 
-static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);
+static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form = false);
 static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);
-static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M);
-int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
+static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_form = false);
+// factor_form (the CG operator under option "cg_lowrank", matvec_dev): a block that is NOT factored goes through its factors
+// all the same -- they cover every constraint (cg_lowrank_covered), so the entries are left alone.  A parameter of the call:
+// every other caller keeps the entries of such a block
+int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form) {
   OpTimer t(c, "aa_times");
-  return t.done(aa_times_impl(c, b, Z, y));
+  return t.done(aa_times_impl(c, b, Z, y, factor_form));
 }
 int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
   OpTimer t(c, "aa_times2");
   return t.done(aa_times2_impl(c, b, Z1, y1, Z2, y2));
 }
-int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
+int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_form) {
   OpTimer t(c, "aat_to_mat");
-  return t.done(aat_to_mat_impl(c, b, x, M));
+  return t.done(aat_to_mat_impl(c, b, x, M, factor_form));
 }
 
 // y += AA vec(Z)
-static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
+static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form) {
+  if (factor_form && !b.factored) return aa_times_factored(c, b, Z, y);
   if (b.factored) LRN_TRY(aa_times_factored(c, b, Z, y));      // (a hybrid block goes on with its stored rows; a pure one has none)
   if (b.npos_nz > b.nd) c->counts["op_sparse"] += 1;
   if (b.nd > 0) c->counts["op_dense"] += 1;
@@ -1110,7 +1114,8 @@ static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1,
 
 // M = mat(AA' x)  (symmetrised msz x msz, kron_etc.jl:13-18)
 static int aat_to_mat_stored(lrn_ctx* c, LmiBlock& b, const double* x, double* M);
-static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
+static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_form) {
+  if (factor_form && !b.factored) return aat_to_mat_factored(c, b, x, M);
   if (!b.factored) return aat_to_mat_stored(c, b, x, M);
   LRN_TRY(aat_to_mat_factored(c, b, x, M));
   if (!b.hybrid()) return LRN_OK;
@@ -1164,15 +1169,21 @@ int matvec_dev(lrn_ctx* c, const double* x, double* y) {
   for (auto& b : c->lmi) {
     if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set");
     const int m = b.msz;
-    if (use_sparse_matvec(c, b)) {
+    // option "cg_lowrank": both data operators of a covered block from its rank-k factors (Vd built on first use, as mode 1 does)
+    const bool fac = cg_lowrank_operator(c, b);
+    if (!fac && use_sparse_matvec(c, b)) {
       LRN_TRY(matvec_sparse_block(c, b, x, y, 0, m, true));
       continue;
     }
+    if (fac) {
+      LRN_TRY(lowrank_dense_factors(c, b));
+      c->counts["op_factored_cg"] += 1;
+    }
     LRN_TRY(ensure_m(c, m));
     double* M = c->m0.as<double>();
-    LRN_TRY(aat_to_mat(c, b, x, M));
+    LRN_TRY(aat_to_mat(c, b, x, M, fac));
     LRN_TRY(wmw(c, b, M, c->m1.as<double>(), c->m2.as<double>()));
-    LRN_TRY(aa_times(c, b, c->m2.as<double>(), y));
+    LRN_TRY(aa_times(c, b, c->m2.as<double>(), y, fac));
   }
   if (c->nlin > 0) LRN_TRY(lin_matvec(c, x, y));
   LRN_HIP(c, hipGetLastError());

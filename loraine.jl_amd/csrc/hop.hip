@@ -229,23 +229,64 @@ int hop_apply(lrn_ctx* c, const double* x, double* y, double* qpart, int* nq) {
 
 // ------------------------------------------------------------------ cost model (static: the choice must not depend on
 // measured times, or two runs of one problem would differ at rounding level)
+//
+// Option "cg_lowrank" (0 never, 1 always, -1 by the terms below): a COVERED block (cg_lowrank_covered: not factored, factors
+// for every constraint that has entries) can serve each piece of the CG path from its rank-k factors instead of its
+// entries -- the assembly of H in mode 1, the matrix-free operator in factor form, ts of H_alpha (cgops.hip::fac_ts_kernel).
+// The three terms est_assemble_s(., 1), est_operator_block_s(., ., true) and est_ts_s(., ., ., true) carry rates measured at
+// msz 2000 / nvar 4000 / rank 2 (DESIGN.md sections 10, 11, 14).  With world > 1 the option is ignored and the entry routes
+// run: the factor routes are not sharded, and no multi-GPU machine was there to test anything else.
+static bool cg_lowrank_on(const lrn_ctx* c) { return c->opt.cg_lowrank != 0 && c->world <= 1; }
+
+static double est_operator_block_s(const lrn_ctx* c, const LmiBlock& b, bool factors) {
+  const double m = b.msz;
+  if (factors) {      // Q = Z Vd (2 m^2 R flop) and the lower triangle of Vs Vd' (m^2 R), the two products of wmw; as many launches
+    const double R = (double)c->nvar * b.lr_khat;       // as the entry route (section 11: 1.35 + 0.89 ms for 9.6e10 flop)
+    return 3.0 * m * m * R / 4.0e13 + 4.0 * m * m * m / 5.0e13 + 40e-6;
+  }
+  if (use_sparse_matvec(c, b))
+    return (b.msz < 1500 ? 30e-6 : 10e-6) + (double)b.ncq * m * 1.43e-12;      // pattern route (C5: 2.58 ms, C3: 36 us)
+  return 4.0 * m * m * m / 5.0e13 + (double)b.nd * m * m * 8.0 / 6.0e12 + 40e-6;      // two products + two passes over the column tails
+}
+
+bool cg_lowrank_operator(const lrn_ctx* c, const LmiBlock& b) {
+  if (!cg_lowrank_on(c) || !cg_lowrank_covered(b)) return false;
+  return c->opt.cg_lowrank == 1 || est_operator_block_s(c, b, true) < est_operator_block_s(c, b, false);
+}
+
 static double est_operator_s(const lrn_ctx* c) {
   double t = 0.0;
-  for (const auto& b : c->lmi) {
-    const double m = b.msz;
-    if (use_sparse_matvec(c, b))
-      t += (b.msz < 1500 ? 30e-6 : 10e-6) + (double)b.ncq * m * 1.43e-12;      // pattern route (C5: 2.58 ms, C3: 36 us)
-    else
-      t += 4.0 * m * m * m / 5.0e13 + (double)b.nd * m * m * 8.0 / 6.0e12 + 40e-6;      // two products + two passes over the column tails
-  }
+  for (const auto& b : c->lmi) t += est_operator_block_s(c, b, cg_lowrank_operator(c, b));
   return t;
 }
 
-static double est_assemble_s(const lrn_ctx* c) {
+// ts of H_alpha for one block and `erank` eigenvectors.  Entries: per eigenvector one pass over the dense slabs (one
+// workgroup per slab, a column-strided walk: 1e12 B/s), the sparse entries, AU zeroed and multiplied by Z (2 nvar m^2 flop).
+// Factors: P = L' Vd once (2 m^2 R flop), T = Vd' Um, then per eigenvector one pass over P and one over the block of ts.
+static double est_ts_s(const lrn_ctx* c, const LmiBlock& b, int erank, bool factors) {
+  const double m = b.msz, n = c->nvar, k = erank;
+  if (factors) {
+    const double R = n * b.lr_khat;
+    return 2.0 * m * m * R / 4.0e13 + 2.0 * m * R * k / 1.0e13 + k * (m * R + m * n) * 8.0 / 3.0e12 + 20e-6;      // three launches in all
+  }
+  return k * ((double)b.nd * m * m * 8.0 / 1.0e12 + (double)(b.nent) * 2.0e-10 + n * m * 8.0 / 3.0e12 + 2.0 * n * m * m / 4.0e13 + 25e-6);
+}
+
+bool cg_lowrank_ts(const lrn_ctx* c, const LmiBlock& b, int erank) {
+  if (!cg_lowrank_on(c) || !cg_lowrank_covered(b)) return false;
+  return c->opt.cg_lowrank == 1 || est_ts_s(c, b, erank, true) < est_ts_s(c, b, erank, false);
+}
+
+static double est_assemble_s(const lrn_ctx* c, int mode) {
   const double n = c->nvar;
   double t = n * n * 8.0 / 4.0e12 + 100e-6;
   for (const auto& b : c->lmi) {
     const double m = b.msz, nd = b.nd;
+    if (mode == 1) {      // U = G' Vd and the blocked square of U' U on its lower triangle (section 10: 1.28e11 flop in 3.78 ms)
+      const double R = n * b.lr_khat;
+      t += (2.0 * R * m * m + 0.5 * R * R * m) / 3.4e13;
+      continue;
+    }
     if (b.nd > 0) t += (4.0 / 3.0 * nd * m * m * m + 0.5 * nd * nd * m * m + nd * (n - nd) * m * m * 0.5) / 6.0e13;
     double s1 = 0.0, s2 = 0.0;       // sum over sparse pairs of nnz_i nnz_j = ((sum nnz)^2 + sum nnz^2) / 2
     for (int p = b.nd; p < b.npos_nz; ++p) { s1 += (double)b.nnz[p]; s2 += (double)b.nnz[p] * (double)b.nnz[p]; }
@@ -253,6 +294,16 @@ static double est_assemble_s(const lrn_ctx* c) {
     t += std::max(0.5 * (s1 * s1 + s2) * 4.0e-12, 0.5 * ns * (ns + 1.0) * 5.0e-11);      // C5: 2e8 pairs of 9 x 9 in 66 ms
   }
   return t;
+}
+
+// The mode hop_prepare assembles H in: 1 (from the factors) when every LMI block is covered and the option allows it --
+// always under cg_lowrank = 1, where it is estimated cheaper under -1 --, else 0
+static int hop_mode(const lrn_ctx* c) {
+  if (!cg_lowrank_on(c) || c->lmi.empty()) return 0;
+  for (const auto& b : c->lmi)
+    if (!cg_lowrank_covered(b)) return 0;
+  if (c->opt.cg_lowrank == 1) return 1;
+  return est_assemble_s(c, 1) < est_assemble_s(c, 0) ? 1 : 0;
 }
 
 static double est_symv_s(const lrn_ctx* c) {
@@ -269,14 +320,15 @@ bool hop_worthwhile(lrn_ctx* c, long expected_iters) {
     if (!b.have_W) return false;
   if (c->opt.matvec_h == 2) return true;
   const double gain = (double)expected_iters * (est_operator_s(c) - est_symv_s(c));
-  return gain > 1.2 * est_assemble_s(c);
+  return gain > 1.2 * est_assemble_s(c, hop_mode(c));
 }
 
 // Make c->H the Schur matrix of the current scaling (general mode: the map MyA applies).  One process per GPU: every
 // rank enters the status reduction; column blocks are NOT exchanged (each rank multiplies the columns it assembled),
 // partial sums of the factor path are all-reduced as in lrn_schur_assemble.
 int hop_prepare(lrn_ctx* c) {
-  if (c->have_H && !c->H_shifted && !c->H_partial && c->H_version == c->scal_version && c->H_mode == 0) return LRN_OK;
+  const int mode = hop_mode(c);      // (a matrix assembled in the other mode is the same map but not the same bits: not reused)
+  if (c->have_H && !c->H_shifted && !c->H_partial && c->H_version == c->scal_version && c->H_mode == mode) return LRN_OK;
   const bool sharded = c->comm && c->world > 1;
   int rc;
   if (sharded) {
@@ -284,9 +336,10 @@ int hop_prepare(lrn_ctx* c) {
     rc = schur_assemble(c, 0);
     rc = comm_schur_exchange(c, rc, /*gather_blocks=*/false);
   } else {
-    rc = schur_assemble(c, 0);
+    rc = schur_assemble(c, mode);
   }
   if (rc == LRN_OK) c->counts["hop_assemble"] += 1;
+  if (rc == LRN_OK && mode == 1) c->counts["hop_assemble_lowrank"] += 1;
   return rc;
 }
 

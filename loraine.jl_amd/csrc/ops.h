@@ -6,12 +6,12 @@ namespace lrn {
 bool use_sparse_matvec(const lrn_ctx* c, const LmiBlock& b);                // the pattern-restricted form of MyA serves this block
 int ensure_m(lrn_ctx* c, int m);                                            // c->m0..m2 >= msz^2
 int wmw(lrn_ctx* c, LmiBlock& b, double* M, double* P, double* Z);          // Z = W M W (M symmetric)
-int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);          // y += AA vec(Z)
+int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form = false);          // y += AA vec(Z)
 // y += AA vec(W M W) through the entries of W M W the (all sparse) constraints read: N (work) = M W, then dots on the pattern
 bool wmw_pattern_ok(const lrn_ctx* c, const LmiBlock& b);
 int aa_times_wmw_pattern(lrn_ctx* c, LmiBlock& b, const double* M, double* N, double* y);
 int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);   // both, one pass over dense data
-int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M);        // M = mat(AA' x)
+int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_form = false);        // M = mat(AA' x)
 // route of the passes over the dense constraint data of b, decided once b.Adense is filled (model.hip): the symmetry check
 // on the device and the chunk table of the column tails; sym_known: the data are symmetric by construction, no check
 int dense_route_setup(lrn_ctx* c, LmiBlock& b, bool sym_known);

@@ -119,16 +119,21 @@ class MySolver:
             self.dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes,
                                   B=model.B if len(model.B) else None,
                                   C_lin=model.C_lin if model.nlin else None)    # [GPU] one-time
-        # datarank = k >= 1 (kit = 0): the Schur matrix from the rank-k factors of the data (mode 1); a model whose data has
-        # no such form (or k > 16) takes the general path, as the reference's docs promise (docs/src/Loraine_options.md)
+        # datarank = k >= 1: the rank-k factors of the data go to the device; a model whose data has no such form (or
+        # k > 16) takes the general path, as the reference's docs promise (docs/src/Loraine_options.md).  kit = 0: the Schur
+        # matrix from the factors (mode 1).  kit = 1: the CG path from them wherever the library's cost model finds that
+        # cheaper (option cg_lowrank = -1: H of the assembled-matrix operator, the matrix-free operator, ts of H_alpha)
         self.lowrank = False
-        if self.datarank >= 1 and self.kit == 0 and model.nlmi > 0:
+        if self.datarank >= 1 and model.nlmi > 0:
             if model.lowrank:
                 for i, (V, d, khat) in enumerate(model.lowrank):
                     self.dev.upload_lowrank(i, khat, V, d)                      # [GPU] one-time
                     if getattr(model, "factored", False) and model.factored_blocks[i]:
                         self.dev.set_factored(i)                                # [GPU] the factors are the data
                 self.lowrank = True
+                if self.kit == 1:
+                    self.dev.set_option("cg_lowrank", -1)
+                    self._say(f" ---The CG path uses the rank-{self.datarank} factors of the data (cg_lowrank = -1)")
             else:
                 self._say(f" ---No rank-{self.datarank} factors ({model.lowrank_note}), setting datarank = 0")
                 self.datarank = 0
