@@ -356,6 +356,15 @@ int lrn_dbg_gemm(lrn_ctx* ctx, int transA, int transB, int M, int N, int K, doub
  * 64 / 128 tile, 3 direct-to-LDS 128 tile, 4 64-tile DMA pipeline, 5 K-segment, 6 / 7 / 8 K-contiguous 128 / 160 / strip. */
 int lrn_dbg_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, double beta, int ldc, int flags,
                       int ksplit, int* out6);
+/* What the Cholesky path of lrn_schur_assemble decides before its launches for a block of side msz with nd dense constraints on
+ * rank `rank` of `world` (csrc/schur_plan.h), on the host alone (no context, no device).  pcap_hint: the GEMM1'/GEMM2' batch the
+ * memory test found room for; opts6 = option values { p_batch, gemm3_tile, gemm3_ksplit, gemm3_sched, gemm3_strip, gemm_no_skip }.
+ * out10 = { c0, c1 (this rank's columns of the matrix variable; -1, -1: an idle rank), doubles per P block, its leading
+ * dimension, matrices per GEMM1'/GEMM2' launch, GEMM3' tile side, number of GEMM3' launches, tile class of the first, of the
+ * second, split-K slabs }; kb, ke, weights (64 entries each): the K-chunk range [kb, ke) and the slab weight (1 / 2) of every
+ * split; shares3 = this rank's share of the useful work of GEMM1', GEMM2', GEMM3'. */
+int lrn_dbg_schur_chol_plan(int msz, int nd, int rank, int world, int64_t pcap_hint, const int* opts6, int64_t* out10, int* kb,
+                            int* ke, int* weights, double* shares3);
 int lrn_dbg_mfma_probe(lrn_ctx* ctx, const double* A16x4, const double* B4x16, double* D16x16);
 int lrn_dbg_potrf(lrn_ctx* ctx, int n, double* A, int* info);
 int lrn_dbg_potrs(lrn_ctx* ctx, int n, const double* A, const double* b, double* x, int* info);

@@ -3,6 +3,7 @@
 
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
+#include "schur_plan.h"
 
 using namespace lrn;
 
@@ -539,6 +540,22 @@ int lrn_dbg_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int 
   const int v[6] = {info.kernel, info.tile, info.grid_x, info.grid_z, info.dyn_lds, info.slabs};
   for (int i = 0; i < 6; ++i) out6[i] = v[i];
   return rc;
+}
+
+int lrn_dbg_schur_chol_plan(int msz, int nd, int rank, int world, int64_t pcap_hint, const int* opts6, int64_t* out10, int* kb,
+                            int* ke, int* weights, double* shares3) {
+  if (!opts6 || !out10 || !kb || !ke || !weights || !shares3 || msz < 1 || nd < 1 || world < 1 || rank < 0 || rank >= world)
+    return LRN_ERR_ARG;
+  CholPlanOpts o;
+  o.p_batch = opts6[0]; o.gemm3_tile = opts6[1]; o.gemm3_ksplit = opts6[2];
+  o.gemm3_sched = opts6[3]; o.gemm3_strip = opts6[4]; o.gemm_no_skip = opts6[5];
+  const CholPlan p = plan_chol(msz, nd, rank, world, (long)pcap_hint, o);
+  const int64_t v[10] = {p.idle ? -1 : p.c0, p.idle ? -1 : p.c1, p.p_elems, p.ldp, p.P_cap, p.t160 ? 160 : 128,
+                         p.ncls,             p.cls[0],           p.cls[1],  p.nslab};
+  for (int i = 0; i < 10; ++i) out10[i] = v[i];
+  for (int s = 0; s < p.nslab; ++s) { kb[s] = p.kb[s]; ke[s] = p.ke[s]; weights[s] = (int)p.sw.w[s]; }
+  shares3[0] = p.gemm1_share; shares3[1] = p.gemm2_share; shares3[2] = p.gemm3_share;
+  return LRN_OK;
 }
 
 int lrn_dbg_mfma_probe(lrn_ctx* c, const double* A, const double* B, double* D) {

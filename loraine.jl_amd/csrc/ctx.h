@@ -79,7 +79,7 @@ struct LmiBlock {
   // factored block (lrn_set_factored): the factors ARE the constraint data -- AA vec(.) and mat(AA' .) go through Vd
   // (dataops.hip, "factor form"), the Schur matrix through mode 1 only.  Pure: AA has no entry.  Hybrid: a few constraints
   // are stored instead (rows of AA, positions [0, npos_nz) as everywhere) and have weight-0 factor columns; every constraint
-  // is exactly one of the two.  The stored-entry kernels serve the stored part, schur.hip::assemble_cross the mixed terms
+  // is exactly one of the two.  The stored-entry kernels serve the stored part, schur_factored.hip::assemble_cross the mixed terms
   bool factored = false;
   bool hybrid() const { return factored && npos_nz > 0; }
 };
@@ -262,6 +262,7 @@ int schur_factor(lrn_ctx* c, int* info);
 int schur_solve(lrn_ctx* c, const double* h, double* dely);
 int schur_add_diag(lrn_ctx* c, double eps);
 int schur_get(lrn_ctx* c, double* Hout);
+// schur_factored.hip
 int lowrank_dense_factors(lrn_ctx* c, LmiBlock& b);     // b.Vd from the uploaded rank-k factors (once per upload)
 // hop.hip: the CG operator through the assembled matrix
 // y = H x; qpart (may be null): receives *nq partial sums of x'y (*nq = 0: not formed, e.g. sharded)

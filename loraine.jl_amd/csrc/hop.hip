@@ -4,7 +4,7 @@
 // the nvar x nvar matrix H of src/makeBBBB.jl:67-218 for every IP iteration.  It is the same linear map: Ax = H x.
 // On an MI355X H fits up to nvar ~ 1.5e5 and its assembly is cheap next to hundreds of operator applications (C5: 66 ms
 // against 729 applications of 2.6 ms), so when the cost model below says so the operator of lrn_pcg / lrn_matvec is
-//   assemble H once per NT scaling (the kit=0 kernels of schur.hip), then  y = H x  per CG iteration
+//   assemble H once per NT scaling (the kit=0 kernels of schur*.hip), then  y = H x  per CG iteration
 // as ONE pass over the LOWER triangle: 4 nvar^2 bytes per application, the HBM roofline of the CG iteration.
 //
 // symv_lower_tiles_kernel: workgroup tile = 128 K rows x 128 columns of the lower triangle (column-major: a wave reads

@@ -92,7 +92,7 @@ enum : int {
 
 // ---------------------------------------------------------------- packed lower layout
 // A symmetric msz x msz matrix of which only the 16x16 blocks on and below the diagonal are kept
-// (schur.hip, Cholesky path: At_k = L' A_k L).  S = msz rounded up to 16, column c lies in block column
+// (schur_dense.hip, Cholesky path: At_k = L' A_k L).  S = msz rounded up to 16, column c lies in block column
 // q = c / 16.  Flat index space:
 //   [0, Kd)   Kd = 16 msz: column c at 16 c holds rows 16q .. 16q+15 (the diagonal block, both triangles)
 //   [Kd, Kp)  column c: rows 16(q+1) .. S-1, contiguous

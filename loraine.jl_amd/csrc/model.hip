@@ -595,7 +595,7 @@ static int has_entries_error(lrn_ctx* c, const LmiBlock& b, int ilmi) {
 
 // Rank-k factors of the constraints of block ilmi (datarank >= 1): A_k = V_k diag(d_k) V_k', V as an (nvar * khat) x msz
 // CSC (1-based; row k * khat + p = column p of V_k, the orientation of B in lrn_upload_model), d[nvar * khat].  Stored as
-// CSR by factor column in H index order (schur.hip::assemble_lowrank).  Host or device arrays.
+// CSR by factor column in H index order (schur_factored.hip::assemble_lowrank).  Host or device arrays.
 extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t* V_colptr, const int64_t* V_rowval,
                                   const double* V_nzval, const double* d) {
   if (!c) return LRN_ERR_ARG;
@@ -668,7 +668,7 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
 // on = 1: the factors of lrn_upload_lowrank ARE the constraint data of block ilmi (A_k = V_k diag(d_k) V_k', AA = -A as
 // everywhere): AA vec(.) and mat(AA' .) of the resident path run in factor form (dataops.hip), the Schur matrix comes from
 // mode 1.  The block's AA is without entries, or holds the rows of a few STORED constraints whose factor columns all have
-// weight 0 (a hybrid block: stored-entry kernels + factor form, cross terms in schur.hip) -- no constraint may be counted
+// weight 0 (a hybrid block: stored-entry kernels + factor form, cross terms in schur_factored.hip) -- no constraint may be counted
 // twice.  on = 0 takes the declaration back.
 extern "C" int lrn_set_factored(lrn_ctx* c, int ilmi, int on) {
   if (!c) return LRN_ERR_ARG;

@@ -1,5 +1,5 @@
 // Device-side operations shared between translation units: the data operators (dataops.hip), the NT scaling (prepw.hip),
-// the n x n products (products.hip), the Lanczos searches (lz.hip) and a few helper launches.
+// the n x n products (products.hip), the Lanczos searches (lz.hip), the parts of the Schur assembly and a few helper launches.
 #pragma once
 #include "ctx.h"
 namespace lrn {
@@ -71,6 +71,20 @@ int eigmin_dev(lrn_ctx* c, const double* M, int n, double* lam, int* steps_out, 
 // lambda_min certified by Cholesky tests; _pair: of two matrices of the same size, their Lanczos runs side by side
 int eigmin_certified(lrn_ctx* c, const double* M, int n, double* lam);
 int eigmin_certified_pair(lrn_ctx* c, const double* M1, const double* M2, int n, double* lam1, double* lam2);
+// ---- Schur assembly (schur.hip drives; its launch decisions: schur_plan.h)
+// address of the entry (hi, hj) of H in its authoritative lower triangle, either order of the two indices
+__device__ __forceinline__ long h_lower(int hi, int hj, int ldh) {
+  int rr = hi > hj ? hi : hj, cc = hi > hj ? hj : hi;
+  return (long)rr + (long)cc * ldh;
+}
+// schur_dense.hip: the dense owners of a block (positions < nd) -- Cholesky path, or W / via-L path with the gather against
+// sparse partners; whether the next assembly of the block would take the Cholesky path, and its batch hint
+int assemble_dense(lrn_ctx* c, LmiBlock& b);
+bool chol_path_applicable(lrn_ctx* c, LmiBlock& b, long* pcap_out);
+// schur_factored.hip: rank-one data (mode -1), rank-k data (mode 1), cross terms of a hybrid factored block
+int assemble_rank1(lrn_ctx* c, LmiBlock& b);
+int assemble_lowrank(lrn_ctx* c, LmiBlock& b);
+int assemble_cross(lrn_ctx* c, LmiBlock& b);
 void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I (ipstep.hip)
 // n x n helpers (prepw.hip)
 void eye_mat(hipStream_t st, double* V, int n);                            // V = I

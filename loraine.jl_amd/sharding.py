@@ -85,7 +85,7 @@ def _packed_off_base(c, S):
 
 
 def column_range_cost(msz, nd, c0, c1):
-    """`col_range_cost` of csrc/schur.hip: what the columns [c0, c1) of the matrix variable cost a rank on the Cholesky
+    """`col_range_cost` of csrc/schur_plan.h: what the columns [c0, c1) of the matrix variable cost a rank on the Cholesky
     path, in ms.  The products run on the trailing blocks with the 128-tile grid anchored at c0: GEMM1' tile column j
     has (ntm - j) tiles of K = M - 128 j, GEMM2' tile (i, j), i >= j, has K = M - 128 i (whole tiles, the last tile
     column may be partly empty); GEMM3' costs exactly the packed length of the range.  Constants: least-squares fit to
@@ -111,8 +111,8 @@ def column_range_cost(msz, nd, c0, c1):
 
 
 def column_range(msz, nd, rank, world):
-    """Executable specification of `col_runs` (csrc/schur.hip): the columns [c0, c1) of the matrix variable a rank owns
-    on the Cholesky path, or None for a rank left idle (more ranks than 16-column units).  With W = L L', column c of
+    """Executable specification of `col_runs` (csrc/schur_plan.h; tests/test_schur_plan_cpu.py compares the two): the
+    columns [c0, c1) of the matrix variable a rank owns on the Cholesky path, or None for a rank left idle (more ranks than 16-column units).  With W = L L', column c of
     At_k = L' A_k L needs only columns >= c of L and A_k and <At_i, At_j> is a sum over columns, so a rank computes ITS
     columns of every At_k and its share of every inner product; the ranks' partial Schur matrices are added by one
     all-reduce.  Every rank gets one contiguous range with ends at multiples of 16 (the block width of the packed

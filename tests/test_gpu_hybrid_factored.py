@@ -1,6 +1,6 @@
 """Hybrid factored blocks on the MI355X: most constraints of a block are factors, a few are stored matrices (identity, a
 handful of entries, tridiagonal, dense).  The data operators and the mode-1 Schur matrix (H_FF + H_SS + the cross terms of
-schur.hip::fac_cross_kernel) against the same data fully materialised (mode 0) and against NumPy from the definition;
+schur_factored.hip::fac_cross_kernel) against the same data fully materialised (mode 0) and against NumPy from the definition;
 bit-reproducibility, exact symmetry, both forms of the cross kernel, G given or W only; two blocks with C_lin rows; error
 paths; planted solves through Optimizer.load_factored_model against load_model and the oracle.
 

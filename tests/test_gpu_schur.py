@@ -375,7 +375,7 @@ def test_chol_path_two_blocks_and_switching(dev):
         dev.set_option("schur_chol", -1)
 
 
-@pytest.mark.parametrize("msz,nvar,world", [(260, 300, 2), (260, 300, 3), (260, 300, 5), (1000, 160, 3), (1000, 160, 8)])
+@pytest.mark.parametrize("msz,nvar,world", [(40, 24, 5), (260, 300, 2), (260, 300, 3), (260, 300, 5), (1000, 160, 3), (1000, 160, 8)])
 def test_chol_path_column_split_partial_sums(dev, msz, nvar, world):
     """world > 1 on the Cholesky path: the ranks split the columns of the matrix variable in 16-column units (all
     three GEMMs shard, tile grids anchored at the range start) and hold partial sums of the whole Schur matrix;

@@ -135,7 +135,7 @@ def test_world2_gloo_sharded_pcg(tmp_path):
 
 def partial_schur_dense(Amats, W, rank, world):
     """NumPy restatement of one rank's partial sum on the Cholesky path: H_g[i,j] = sum over the rank's columns c of
-    <At_i[:,c], At_j[:,c]>, At_k = L' A_k L (csrc/schur.hip::assemble_dense_chol)."""
+    <At_i[:,c], At_j[:,c]>, At_k = L' A_k L (csrc/schur_dense.hip::assemble_dense_chol)."""
     from loraine_jl_amd import sharding
     L = np.linalg.cholesky(W)
     rng_ = sharding.column_range(W.shape[0], len(Amats), rank, world)
