@@ -156,9 +156,26 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * operator takes mat(AA' x) and AA vec(W M W) of a covered block in the factor form of factored blocks; lrn_prec_setup forms
  * the block of ts = D^-1/2 AA (U (x) Z) of a covered block as P = L' Vd, T = Vd' Um and one weighted, transposing pass over P
  * instead of one pass over every A_k per eigenvector.  Everything else that reads AA -- lrn_make_rhs, lrn_ip_*, the general
- * assembly -- stays on the entries.  Factored and hybrid blocks keep refusing the CG entry points.  With world > 1
+ * assembly -- stays on the entries.  Factored and hybrid blocks keep refusing the CG entry points (see "cg_factored").  With world > 1
  * (lrn_set_shard, lrn_comm_init) the option is ignored and the entry routes run: the factor routes are not sharded and have
- * only been run on one GPU), "reset_timing".
+ * only been run on one GPU),
+ * "cg_factored" (0, default: lrn_matvec, lrn_prec_setup and lrn_pcg return LRN_ERR_STATE for a factored block, as they always
+ * have; 1: lrn_matvec, lrn_prec_setup, lrn_prec_apply and lrn_pcg accept pure and hybrid factored blocks and models that mix
+ * them with stored-entry blocks -- the matrix-free operator runs in factor form, the assembled-matrix operator assembles H in
+ * mode 1, ts of H_alpha comes from the factors (P = L' Vd, T = Vd' Um, one transposing pass) and, for the stored constraints
+ * of a hybrid block, from their entries on a compact npos_nz x msz buffer.  lrn_matvec_partial and every call under world > 1
+ * keep returning LRN_ERR_STATE for a factored block: the factor routes are not sharded and were run on one GPU only),
+ * "hop_max_mb" (budget of the assembled-matrix operator in MiB: when nvar^2 * 8 bytes exceed it H is not assembled, even under
+ * "matvec_h" = 2, and the matrix-free operator runs; -1, default: no limit for a model without a factored block, and for one
+ * with a factored block the free device memory minus the mode-1 workspace), "fac_op_scaled" (under "cg_factored", pure
+ * factored blocks, matrix-free operator: 1 = Y = W Vd once per NT scaling and W mat(AA' x) W = -Y diag(w o x) Y' per
+ * application, no W M W product; 0 = the composition mat(AA' x) -> W M W -> AA vec(.); -1, default = cost model, which is
+ * "off" until the form has been measured faster), "fac_quadform" (under "cg_factored", pure and hybrid factored blocks, inside
+ * the matrix-free operator only: 1 = AA vec(Z) of the factor part by the fused quadratic form of facops.hip, Q = Z Vd never
+ * stored; 0 = Q and the column dots; -1, default = cost model, "off" likewise), "reset_timing".
+ * Counters of these options: "op_factored_scaled" (blocks per application through Y), "op_quadform_fused" (blocks per
+ * application through the fused kernel), "fac_scaled_y" (products Y = W Vd), "hop_over_budget" (operator choices that found H
+ * above the budget), "prec_ts_stored_rows" (rows of ts filled from stored entries in the LAST lrn_prec_setup).
  * Counters of this path (lrn_get_count): "lz_resident_launches" (resident launches queued), "lz_persist_abort" (those that
  * gave up), and the STATE "lz_no_persist" (0 / 1, survives reset_timing: a resident launch of this context has given up, all
  * Lanczos steps are launched one by one from then on). */

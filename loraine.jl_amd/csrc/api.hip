@@ -121,6 +121,10 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
     c->opt.cg_lowrank = std::max(-1, std::min(1, (int)value));
     c->hop_version = -1;
   }
+  else if (!strcmp(key, "cg_factored")) { c->opt.cg_factored = value != 0.0 ? 1 : 0; c->hop_version = -1; }
+  else if (!strcmp(key, "hop_max_mb")) { c->opt.hop_max_mb = value < 0.0 ? -1.0 : value; c->hop_version = -1; }
+  else if (!strcmp(key, "fac_op_scaled")) { c->opt.fac_op_scaled = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }
+  else if (!strcmp(key, "fac_quadform")) { c->opt.fac_quadform = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }
   else if (!strcmp(key, "fac_cross_lds")) c->opt.fac_cross_lds = std::max(-1, std::min(1, (int)value));
   else if (!strcmp(key, "jacobi_cross")) c->opt.jacobi_cross = (int)value;
   else if (!strcmp(key, "jacobi_early")) c->opt.jacobi_early = value;

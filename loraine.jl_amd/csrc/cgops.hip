@@ -283,30 +283,43 @@ __global__ void tril2_kernel(double* __restrict__ A, int n) {
     if ((int)(e % n) < (int)(e / n)) A[e] = 0.0;
 }
 
-// AU[j, r] += -a_e * Um[c, a] / sqrt(d_j), j = sigma[p]   (one thread per sparse position)
+// AU[j, r] += -a_e * Um[c, a] / sqrt(d_j), j = sigma[p]   (one thread per sparse position).  compact (the stored rows of a
+// hybrid factored block): AU has ld rows and row p holds position p, scaled by its own d_j all the same
 __global__ void au_sparse_kernel(const long* __restrict__ ptr, const int* __restrict__ er, const int* __restrict__ ec,
                                  const double* __restrict__ ev, int p_lo, int p_end, const int* __restrict__ sigma,
-                                 const double* __restrict__ Ucol, const double* __restrict__ d, int nvar,
-                                 double* __restrict__ AU) {
+                                 const double* __restrict__ Ucol, const double* __restrict__ d, int ld,
+                                 double* __restrict__ AU, int compact) {
   int p = p_lo + blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= p_end) return;
   int j = sigma[p];
   double sc = -1.0 / sqrt(d[j]);
-  for (long e = ptr[p]; e < ptr[p + 1]; ++e) AU[(long)j + (long)er[e] * nvar] += sc * ev[e] * Ucol[ec[e]];
+  const long row = compact ? p : j;
+  for (long e = ptr[p]; e < ptr[p + 1]; ++e) AU[row + (long)er[e] * ld] += sc * ev[e] * Ucol[ec[e]];
 }
 
-// dense slot p: AU[sigma[p], r] = -(A_p u)[r] / sqrt(d)
+// dense slot p: AU[sigma[p], r] = -(A_p u)[r] / sqrt(d)   (compact: row p, as above)
 __global__ __launch_bounds__(256) void au_dense_kernel(const double* __restrict__ Ad, int m, const int* __restrict__ sigma,
                                                        const double* __restrict__ Ucol, const double* __restrict__ d,
-                                                       int nvar, double* __restrict__ AU) {
+                                                       int ld, double* __restrict__ AU, int compact) {
   const double* A = Ad + (long)blockIdx.x * m * m;
   int j = sigma[blockIdx.x];
   double sc = -1.0 / sqrt(d[j]);
+  const long row = compact ? blockIdx.x : j;
   for (int r = threadIdx.x; r < m; r += 256) {
     double s = 0.0;
     for (int cidx = 0; cidx < m; ++cidx) s += A[(long)r + (long)cidx * m] * Ucol[cidx];
-    AU[(long)j + (long)r * nvar] = sc * s;
+    AU[row + (long)r * ld] = sc * s;
   }
+}
+
+// ts[sigma[p], col] = C[p, col] for the np stored positions of a hybrid factored block: the rows fac_ts_kernel left at zero
+// (weight-0 factor columns) get their values from the entries, each element written once
+__global__ void ts_store_rows_kernel(const double* __restrict__ C, int np, int m, const int* __restrict__ sigma, int nvar,
+                                     double* __restrict__ ts) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)np * m) return;
+  const int p = (int)(e % np), r = (int)(e / np);
+  ts[(long)sigma[p] + (long)r * nvar] = C[e];
 }
 
 // ts of H_alpha from the rank-k factors of a covered block (option "cg_lowrank").  With A_j = sum_p w_hp v_hp v_hp' (h the H
@@ -392,6 +405,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
   P->erank = erank;
   P->has_dense = false;
   c->counts["prec_ts_factored"] = 0;
+  c->counts["prec_ts_stored_rows"] = 0;
   const int n = c->nvar;
   hipStream_t st = c->stream;
   if (kind == 0) return LRN_OK;
@@ -496,6 +510,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     LRN_TRY(ensure(c, P->ts, (size_t)n * ksz * 8));
     int col0 = 0;
     long ts_factored = 0;      // blocks whose part of ts came from the factors ("prec_ts_factored", of the LAST setup)
+    long ts_stored = 0;        // rows of ts filled from the stored entries of hybrid blocks ("prec_ts_stored_rows", ditto)
     for (int il = 0; il < c->nlmi; ++il) {
       LmiBlock& b = c->lmi[il];
       const int m = b.msz, k = erank;
@@ -542,7 +557,8 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       }
       if (h != 0) { if (info) *info = h; return LRN_OK; }
       hipLaunchKernelGGL(tril2_kernel, dim3(nb((long)m * m)), dim3(256), 0, st, Zf, m);
-      if (cg_lowrank_ts(c, b, k)) {
+      // a factored block (option "cg_factored") has no choice to make: there are no entries to take ts from
+      if (b.factored || cg_lowrank_ts(c, b, k)) {
         // from the rank-k factors: P = L' Vd and T = Vd' Um, then fac_ts_kernel (the whole nvar x k m block, every element once)
         const int kh = b.lr_khat;
         const long R = (long)n * kh;
@@ -566,6 +582,34 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
                            c->pos_space ? b.ipos_d.as<int>() : (const int*)nullptr, P->d.as<double>(), m, kh, R, n,
                            P->ts.as<double>() + (size_t)col0 * n);
         ++ts_factored;
+        if (b.hybrid()) {
+          // the stored constraints have weight-0 columns: their rows came out as zeros.  (D^-1/2 A_s u_a)' Z for these npos_nz
+          // rows alone, on a compact npos_nz x msz buffer -- nothing here has nvar rows -- then each row to its natural place
+          const int np = b.npos_nz;
+          LRN_TRY(ensure(c, P->AU, (size_t)2 * np * m * 8));
+          double* AUc = P->AU.as<double>();
+          double* Cc = AUc + (size_t)np * m;
+          for (int a = 0; a < k; ++a) {
+            LRN_HIP(c, hipMemsetAsync(AUc, 0, (size_t)np * m * 8, st));
+            const double* Ucol = Um + (size_t)a * m;
+            if (b.npos_nz > b.nd)
+              hipLaunchKernelGGL(au_sparse_kernel, dim3(nb(b.npos_nz - b.nd)), dim3(256), 0, st, b.ent_ptr.as<long>(),
+                                 b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), b.nd, b.npos_nz,
+                                 b.sigma_d.as<int>(), Ucol, P->d.as<double>(), np, AUc, 1);
+            if (b.nd > 0)
+              hipLaunchKernelGGL(au_dense_kernel, dim3(b.nd), dim3(256), 0, st, b.Adense.as<double>(), m, b.sigma_d.as<int>(),
+                                 Ucol, P->d.as<double>(), np, AUc, 1);
+            GemmDesc g;
+            g.A = AUc; g.sAm = 1; g.sAk = np;
+            g.B = Zf; g.sBk = 1; g.sBn = m;
+            g.C = Cc; g.sCm = 1; g.sCn = np;
+            g.M = np; g.N = m; g.K = m;
+            LRN_TRY(gemm(st, g));
+            hipLaunchKernelGGL(ts_store_rows_kernel, dim3(nb((long)np * m)), dim3(256), 0, st, Cc, np, m, b.sigma_d.as<int>(), n,
+                               P->ts.as<double>() + (size_t)(col0 + a * m) * n);
+          }
+          ts_stored += np;
+        }
         col0 += k * m;
         continue;
       }
@@ -577,10 +621,10 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
         if (b.npos_nz > b.nd)
           hipLaunchKernelGGL(au_sparse_kernel, dim3(nb(b.npos_nz - b.nd)), dim3(256), 0, st, b.ent_ptr.as<long>(),
                              b.ent_r.as<int>(), b.ent_c.as<int>(), b.ent_v.as<double>(), b.nd, b.npos_nz,
-                             b.sigma_d.as<int>(), Ucol, P->d.as<double>(), n, P->AU.as<double>());
+                             b.sigma_d.as<int>(), Ucol, P->d.as<double>(), n, P->AU.as<double>(), 0);
         if (b.nd > 0)
           hipLaunchKernelGGL(au_dense_kernel, dim3(b.nd), dim3(256), 0, st, b.Adense.as<double>(), m, b.sigma_d.as<int>(),
-                             Ucol, P->d.as<double>(), n, P->AU.as<double>());
+                             Ucol, P->d.as<double>(), n, P->AU.as<double>(), 0);
         GemmDesc g;
         g.A = P->AU.as<double>(); g.sAm = 1; g.sAk = n;
         g.B = Zf; g.sBk = 1; g.sBn = m;
@@ -591,6 +635,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       col0 += k * m;
     }
     c->counts["prec_ts_factored"] = ts_factored;
+    c->counts["prec_ts_stored_rows"] = ts_stored;
     if (P->has_LD)      // ts = L_D^-1 t   (the reference: AAAATtau \ t, Solvers.jl:767)
       LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, false, P->ts.as<double>(), ksz, n,
                               P->workD.as<double>() + chol_work_doubles(n)));
@@ -886,12 +931,19 @@ int pcg_dev(lrn_ctx* c, const double* b, double tol, int maxit, double* x, int* 
 
 using namespace lrn;
 
-// the CG side (mat-vec, H_alpha, PCG) reads the entries of AA: not for factored blocks
-static int no_factored(lrn_ctx* c, const char* what) {
+// the CG side (mat-vec, H_alpha, PCG) reads the entries of AA: not for factored blocks -- unless option "cg_factored" is set:
+// then the operator runs in factor form (dataops.hip) or through H assembled in mode 1 (hop.hip) and ts of H_alpha comes from
+// the factors.  One GPU only (partial: lrn_matvec_partial; world > 1: any call) -- the factor routes are not sharded
+static int no_factored(lrn_ctx* c, const char* what, bool partial = false) {
   for (size_t il = 0; il < c->lmi.size(); ++il)
-    if (c->lmi[il].factored)
+    if (c->lmi[il].factored) {
+      if (c->opt.cg_factored != 0 && (partial || c->world > 1))
+        return set_error(c, LRN_ERR_STATE, "%s: block %d is factored (lrn_set_factored): option cg_factored runs on one GPU "
+                                           "(world = %d) and not through lrn_matvec_partial", what, (int)il, c->world);
+      if (c->opt.cg_factored != 0) return LRN_OK;
       return set_error(c, LRN_ERR_STATE, "%s: block %d is factored (lrn_set_factored): the CG path needs the constraint "
                                          "matrices, factored data is solved with kit = 0", what, (int)il);
+    }
   return LRN_OK;
 }
 
@@ -912,7 +964,7 @@ extern "C" int lrn_matvec(lrn_ctx* c, const double* x, double* Ax) {
 
 extern "C" int lrn_matvec_partial(lrn_ctx* c, const double* x, double* Ax_partial) {
   if (!c || !x || !Ax_partial) return LRN_ERR_ARG;
-  LRN_TRY(no_factored(c, "lrn_matvec_partial"));
+  LRN_TRY(no_factored(c, "lrn_matvec_partial", true));
   LRN_HIP(c, hipSetDevice(c->device));
   const int n = c->nvar;
   LRN_TRY(copy_in(c, c->v0.p, x, (size_t)n * 8));

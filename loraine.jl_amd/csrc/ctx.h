@@ -82,6 +82,9 @@ struct LmiBlock {
   // is exactly one of the two.  The stored-entry kernels serve the stored part, schur_factored.hip::assemble_cross the mixed terms
   bool factored = false;
   bool hybrid() const { return factored && npos_nz > 0; }
+  // option "fac_op_scaled" (pure factored block): Y = W Vd (msz x nvar khat) of the scaling `Ys_version` (dataops.hip::fac_scaled_y)
+  lrn::DBuf Ys;
+  long Ys_version = -1;
 };
 
 struct lrn_ctx;
@@ -154,6 +157,15 @@ struct LrnOptions {
                                   // entry routes, bit for bit), 1 always, -1 the static cost model of hop.hip decides per piece --
                                   // the mode of the assembled-matrix operator, the form of the matrix-free operator, the route
                                   // of the H_alpha setup.  Ignored with world > 1
+  int cg_factored = 0;            // CG path (lrn_matvec, lrn_prec_setup, lrn_prec_apply, lrn_pcg) on factored blocks: 0 refused (the
+                                  // state error of cgops.hip::no_factored), 1 accepted on one GPU -- pure, hybrid and mixed models
+  double hop_max_mb = -1.0;       // budget of the assembled-matrix operator in MiB: H (nvar^2 * 8 bytes) above it is not assembled
+                                  // ("hop_over_budget").  -1: none for a model without a factored block; with one, the free device
+                                  // memory minus the mode-1 workspace
+  int fac_op_scaled = -1;         // matrix-free operator of a pure factored block through Y = W Vd (no W M W product): 1, the
+                                  // composition mat(AA' x) -> W M W -> AA vec(.): 0, cost model (hop.hip::fac_op_scaled_on): -1
+  int fac_quadform = -1;          // AA vec(Z) of a factored block inside the CG operator by the fused quadratic form of facops.hip
+                                  // (Q = Z Vd never stored): 1, Q and fac_coldot_kernel: 0, cost model: -1
 };
 
 struct lrn_ctx {
@@ -275,6 +287,13 @@ int hop_prepare(lrn_ctx* c);
 inline bool cg_lowrank_covered(const LmiBlock& b) { return !b.factored && b.has_V && !b.v_partial; }
 bool cg_lowrank_operator(const lrn_ctx* c, const LmiBlock& b);   // matrix-free operator of this block in factor form?
 bool cg_lowrank_ts(const lrn_ctx* c, const LmiBlock& b, int erank);   // ts of H_alpha for this block from the factors?
+// option "cg_factored": the CG path accepts factored blocks (one GPU only)
+inline bool cg_factored_on(const lrn_ctx* c) { return c->opt.cg_factored != 0 && c->world <= 1; }
+bool fac_op_scaled_on(const lrn_ctx* c, const LmiBlock& b);      // hop.hip: operator of this pure factored block through Y = W Vd?
+bool fac_quadform_on(const lrn_ctx* c, const LmiBlock& b);       // hop.hip: AA vec(Z) of this factored block by the fused kernel?
+// facops.hip: out[nat(h)] -= sum_p w[h kh + p] v_c' Z v_c over the kh factor columns c = h kh + p of every constraint
+int fac_quadform(lrn_ctx* c, const double* Z, const double* Vd, const double* w, int m, int kh, int nvar, const int* sigma,
+                 double* out);
 }  // namespace lrn
 
 #define LRN_HIP(c, expr)                                                                   \

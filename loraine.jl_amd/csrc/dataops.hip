@@ -957,10 +957,17 @@ static int fac_workspace(lrn_ctx* c, LmiBlock& b, double** ws) {
   return LRN_OK;
 }
 
-// y += AA vec(Z), Z symmetric
-static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y) {
+// y += AA vec(Z), Z symmetric.  fused (option "fac_quadform", the CG operator only): facops.hip, Q never stored
+static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused = false) {
   const int m = b.msz, kh = b.lr_khat;
   const long R = (long)c->nvar * kh;
+  if (fused) {
+    if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
+    LRN_TRY(fac_quadform(c, Z, b.Vd.as<double>(), b.v_w.as<double>(), m, kh, c->nvar,
+                         c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, y));
+    c->counts["op_factored"] += 1;
+    return LRN_OK;
+  }
   double* Q = nullptr;
   LRN_TRY(fac_workspace(c, b, &Q));
   GemmDesc g;     // Q = Z Vd, msz x R
@@ -975,17 +982,18 @@ static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y
   return LRN_OK;
 }
 
-// M = mat(AA' x), exactly symmetric
-static int aat_to_mat_factored(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
+// M = mat(AA' x) = -F diag(w o x) F' with F = Vd, exactly symmetric.  F = Y = W Vd (option "fac_op_scaled") gives W mat(AA' x) W
+static int aat_to_mat_factored(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const double* F = nullptr) {
   const int m = b.msz, kh = b.lr_khat;
   const long R = (long)c->nvar * kh;
   double* Vs = nullptr;
   LRN_TRY(fac_workspace(c, b, &Vs));
-  hipLaunchKernelGGL(fac_scale_kernel, dim3((unsigned)R), dim3(256), 0, c->stream, b.Vd.as<double>(), b.v_w.as<double>(), x,
+  if (!F) F = b.Vd.as<double>();
+  hipLaunchKernelGGL(fac_scale_kernel, dim3((unsigned)R), dim3(256), 0, c->stream, F, b.v_w.as<double>(), x,
                      c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, m, kh, Vs);
-  GemmDesc g;     // M = Vs Vd', the tiles on and below the diagonal
+  GemmDesc g;     // M = Vs F', the tiles on and below the diagonal
   g.A = Vs; g.sAm = 1; g.sAk = m;
-  g.B = b.Vd.as<double>(); g.sBk = m; g.sBn = 1;
+  g.B = F; g.sBk = m; g.sBn = 1;
   g.C = M; g.sCm = 1; g.sCn = m;
   g.M = m; g.N = m; g.K = (int)R;
   g.flags = GEMM_TRI_LOWER;
@@ -1050,15 +1058,16 @@ struct OpTimer {
   }
 };
 
-static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form = false);
+static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form = false, bool fused = false);
 static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);
 static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_form = false);
 // factor_form (the CG operator under option "cg_lowrank", matvec_dev): a block that is NOT factored goes through its factors
 // all the same -- they cover every constraint (cg_lowrank_covered), so the entries are left alone.  A parameter of the call:
 // every other caller keeps the entries of such a block
-int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form) {
+// fused (option "fac_quadform", matvec_dev only): the factor part of a factored block by the fused quadratic form
+int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form, bool fused) {
   OpTimer t(c, "aa_times");
-  return t.done(aa_times_impl(c, b, Z, y, factor_form));
+  return t.done(aa_times_impl(c, b, Z, y, factor_form, fused));
 }
 int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
   OpTimer t(c, "aa_times2");
@@ -1070,9 +1079,9 @@ int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_
 }
 
 // y += AA vec(Z)
-static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form) {
+static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form, bool fused) {
   if (factor_form && !b.factored) return aa_times_factored(c, b, Z, y);
-  if (b.factored) LRN_TRY(aa_times_factored(c, b, Z, y));      // (a hybrid block goes on with its stored rows; a pure one has none)
+  if (b.factored) LRN_TRY(aa_times_factored(c, b, Z, y, fused));      // (a hybrid block goes on with its stored rows; a pure one has none)
   if (b.npos_nz > b.nd) c->counts["op_sparse"] += 1;
   if (b.nd > 0) c->counts["op_dense"] += 1;
   if (b.npos_nz > b.nd)
@@ -1163,12 +1172,49 @@ static int aat_to_mat_stored(lrn_ctx* c, LmiBlock& b, const double* x, double* M
   return LRN_OK;
 }
 
+// Y = W Vd of a pure factored block (option "fac_op_scaled"), once per NT scaling: with it
+//     W mat(AA' x) W = -W Vd diag(w o x) Vd' W = -Y diag(w o x) Y',
+// the scaled copy, lower-triangle product and mirror of aat_to_mat_factored on Y instead of Vd -- no W M W product
+static int fac_scaled_y(lrn_ctx* c, LmiBlock& b) {
+  if (b.Ys_version == c->scal_version && b.Ys.p) return LRN_OK;
+  if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
+  OpTimer t(c, "fac_scaled_y");
+  const int m = b.msz;
+  const long R = (long)c->nvar * b.lr_khat;
+  LRN_TRY(ensure(c, b.Ys, (size_t)m * R * 8));
+  GemmDesc g;
+  g.A = b.W.as<double>(); g.sAm = 1; g.sAk = m;
+  g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
+  g.C = b.Ys.as<double>(); g.sCm = 1; g.sCn = m;
+  g.M = m; g.N = (int)R; g.K = m;
+  LRN_TRY(gemm(c->stream, g));
+  b.Ys_version = c->scal_version;
+  c->counts["fac_scaled_y"] += 1;
+  return t.done(LRN_OK);
+}
+
 int matvec_dev(lrn_ctx* c, const double* x, double* y) {
   const int n = c->nvar;
   LRN_HIP(c, hipMemsetAsync(y, 0, (size_t)n * 8, c->stream));
   for (auto& b : c->lmi) {
     if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set");
     const int m = b.msz;
+    // option "cg_factored": a factored block inside the CG operator.  Two routes are parameters of THIS call (every other
+    // caller of aa_times / aat_to_mat keeps its route and bits): the scaled factors Y = W Vd of a pure block, and the fused
+    // quadratic form for the factor part of AA vec(.) (a hybrid block's stored rows still go through aa_times_kernel)
+    const bool fused = b.factored && fac_quadform_on(c, b);
+    if (b.factored && fac_op_scaled_on(c, b)) {
+      LRN_TRY(fac_scaled_y(c, b));
+      LRN_TRY(ensure_m(c, m));
+      double* N = c->m0.as<double>();
+      {
+        OpTimer t(c, "aat_to_mat");
+        LRN_TRY(t.done(aat_to_mat_factored(c, b, x, N, b.Ys.as<double>())));
+      }
+      LRN_TRY(aa_times(c, b, N, y, false, fused));
+      c->counts["op_factored_scaled"] += 1;
+      continue;
+    }
     // option "cg_lowrank": both data operators of a covered block from its rank-k factors (Vd built on first use, as mode 1 does)
     const bool fac = cg_lowrank_operator(c, b);
     if (!fac && use_sparse_matvec(c, b)) {
@@ -1183,7 +1229,7 @@ int matvec_dev(lrn_ctx* c, const double* x, double* y) {
     double* M = c->m0.as<double>();
     LRN_TRY(aat_to_mat(c, b, x, M, fac));
     LRN_TRY(wmw(c, b, M, c->m1.as<double>(), c->m2.as<double>()));
-    LRN_TRY(aa_times(c, b, c->m2.as<double>(), y, fac));
+    LRN_TRY(aa_times(c, b, c->m2.as<double>(), y, fac, fused));
   }
   if (c->nlin > 0) LRN_TRY(lin_matvec(c, x, y));
   LRN_HIP(c, hipGetLastError());

@@ -242,7 +242,12 @@ static double est_operator_block_s(const lrn_ctx* c, const LmiBlock& b, bool fac
   const double m = b.msz;
   if (factors) {      // Q = Z Vd (2 m^2 R flop) and the lower triangle of Vs Vd' (m^2 R), the two products of wmw; as many launches
     const double R = (double)c->nvar * b.lr_khat;       // as the entry route (section 11: 1.35 + 0.89 ms for 9.6e10 flop)
-    return 3.0 * m * m * R / 4.0e13 + 4.0 * m * m * m / 5.0e13 + 40e-6;
+    double t = 3.0 * m * m * R / 4.0e13 + 40e-6;
+    if (!(b.factored && fac_op_scaled_on(c, b))) t += 4.0 * m * m * m / 5.0e13;      // (Y = W Vd: no W M W product)
+    // hybrid block: its stored rows on top, twice (mat(AA' x) and AA vec(.)) -- the sparse tier at the pattern rate, the
+    // dense slots as one pass over the slabs each
+    if (b.hybrid()) t += 2.0 * ((double)b.nent * 1.43e-12 + (double)b.nd * m * m * 8.0 / 6.0e12) + 20e-6;
+    return t;
   }
   if (use_sparse_matvec(c, b))
     return (b.msz < 1500 ? 30e-6 : 10e-6) + (double)b.ncq * m * 1.43e-12;      // pattern route (C5: 2.58 ms, C3: 36 us)
@@ -256,8 +261,29 @@ bool cg_lowrank_operator(const lrn_ctx* c, const LmiBlock& b) {
 
 static double est_operator_s(const lrn_ctx* c) {
   double t = 0.0;
-  for (const auto& b : c->lmi) t += est_operator_block_s(c, b, cg_lowrank_operator(c, b));
+  for (const auto& b : c->lmi) t += est_operator_block_s(c, b, b.factored || cg_lowrank_operator(c, b));
   return t;
+}
+
+// Options "fac_op_scaled" and "fac_quadform" (1 on, 0 off, -1 cost model), both inside matvec_dev and under "cg_factored"
+// only.  The -1 branches choose a form only where it was MEASURED no slower than the parent's composition on one box
+// (msz 320 / nvar 640 / rank 2, msz 2000 / nvar 4000 / rank 2, msz 256 / nvar 32768 / rank 1).
+// Scaled factors: faster per application at all three shapes (0.077 -> 0.055, 2.73 -> 2.02, 0.430 -> 0.399 ms); Y = W Vd
+// costs 0.02 / 1.27 / 0.09 ms per scaling, the gain of one to three applications -- on from msz 256 (the smallest side
+// measured) when the previous scaling saw at least four operator applications (cg_prev_iters, constant within a scaling).
+bool fac_op_scaled_on(const lrn_ctx* c, const LmiBlock& b) {
+  if (!cg_factored_on(c) || !b.factored || b.hybrid()) return false;      // (a hybrid block keeps the composition)
+  if (c->opt.fac_op_scaled >= 0) return c->opt.fac_op_scaled == 1;
+  return b.msz >= 256 && c->cg_prev_iters >= 4;
+}
+
+// Fused quadratic form: slower at msz 320 and 2000, no slower only at msz 256 / R = 32768 -- the regime it was written for
+// (m / 16 flop per byte of the Q round trip below the FP64 balance); -1 is on for msz <= 256 and R >= 32768, nothing else
+// has been measured
+bool fac_quadform_on(const lrn_ctx* c, const LmiBlock& b) {
+  if (!cg_factored_on(c) || !b.factored) return false;
+  if (c->opt.fac_quadform >= 0) return c->opt.fac_quadform == 1;
+  return b.msz <= 256 && (long)c->nvar * b.lr_khat >= 32768;
 }
 
 // ts of H_alpha for one block and `erank` eigenvectors.  Entries: per eigenvector one pass over the dense slabs (one
@@ -282,10 +308,16 @@ static double est_assemble_s(const lrn_ctx* c, int mode) {
   double t = n * n * 8.0 / 4.0e12 + 100e-6;
   for (const auto& b : c->lmi) {
     const double m = b.msz, nd = b.nd;
-    if (mode == 1) {      // U = G' Vd and the blocked square of U' U on its lower triangle (section 10: 1.28e11 flop in 3.78 ms)
+    // mode 1 of a block with factors for every constraint (covered, or factored); a block beside a factored one that has
+    // none takes the general assembly over its entries inside mode 1 (schur.hip): the mode-0 terms below
+    if (mode == 1 && (b.factored || cg_lowrank_covered(b))) {
+      // U = G' Vd and the blocked square of U' U on its lower triangle (section 10: 1.28e11 flop in 3.78 ms)
       const double R = n * b.lr_khat;
       t += (2.0 * R * m * m + 0.5 * R * R * m) / 3.4e13;
-      continue;
+      if (!b.hybrid()) continue;
+      // hybrid: Y = W Vd once more when G exists, the cross terms -- nnz(A_s) R multiply-adds per stored constraint at the
+      // pair rate below, one product A_s Y per dense slot -- and H_SS over the stored positions by the mode-0 terms
+      t += 2.0 * R * m * m / 3.4e13 + (double)b.nent * R * 4.0e-12 + nd * 2.0 * R * m * m / 3.4e13;
     }
     if (b.nd > 0) t += (4.0 / 3.0 * nd * m * m * m + 0.5 * nd * nd * m * m + nd * (n - nd) * m * m * 0.5) / 6.0e13;
     double s1 = 0.0, s2 = 0.0;       // sum over sparse pairs of nnz_i nnz_j = ((sum nnz)^2 + sum nnz^2) / 2
@@ -296,9 +328,17 @@ static double est_assemble_s(const lrn_ctx* c, int mode) {
   return t;
 }
 
+static bool any_factored(const lrn_ctx* c) {
+  for (const auto& b : c->lmi)
+    if (b.factored) return true;
+  return false;
+}
+
 // The mode hop_prepare assembles H in: 1 (from the factors) when every LMI block is covered and the option allows it --
-// always under cg_lowrank = 1, where it is estimated cheaper under -1 --, else 0
+// always under cg_lowrank = 1, where it is estimated cheaper under -1 --, else 0.  And 1 whenever a block is factored
+// (option "cg_factored"): mode 0 refuses such a block, mode 1 handles every block kind, the cross terms of a hybrid one included
 static int hop_mode(const lrn_ctx* c) {
+  if (cg_factored_on(c) && any_factored(c)) return 1;
   if (!cg_lowrank_on(c) || c->lmi.empty()) return 0;
   for (const auto& b : c->lmi)
     if (!cg_lowrank_covered(b)) return 0;
@@ -311,6 +351,23 @@ static double est_symv_s(const lrn_ctx* c) {
   return n * n * 4.0 / 4.5e12 + 12e-6;
 }
 
+// Bytes H may take (option "hop_max_mb"): the option in MiB; -1 = no limit for a model without a factored block (the
+// behaviour before the option existed), and for one with a factored block the free device memory plus what H and the
+// mode-1 workspaces already hold (they are reused), minus the mode-1 workspace: U (and Y, Q of a hybrid block), msz x R each
+static double hop_budget_bytes(const lrn_ctx* c) {
+  if (c->opt.hop_max_mb >= 0.0) return c->opt.hop_max_mb * 1048576.0;
+  if (!(cg_factored_on(c) && any_factored(c))) return 1e300;
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 1e300;
+  double need = 0.0;
+  for (const auto& b : c->lmi) {
+    const double mr = (double)b.msz * (double)c->nvar * b.lr_khat * 8.0;
+    need = std::max(need, mr * (b.hybrid() ? (b.nd > 0 ? 3.0 : 2.0) : 1.0));
+  }
+  const double held = (double)c->H.bytes + (double)c->BG.bytes + (double)c->facY.bytes + (double)c->P.bytes;
+  return (double)fr + held - need;
+}
+
 // Decide, once per NT scaling, whether lrn_pcg / lrn_matvec go through the assembled matrix.  expected_iters: operator
 // applications the caller expects under this scaling (the CG iterations of the previous IP iteration).
 bool hop_worthwhile(lrn_ctx* c, long expected_iters) {
@@ -318,6 +375,13 @@ bool hop_worthwhile(lrn_ctx* c, long expected_iters) {
   if (c->world > 1 && (!c->comm || !hop_shardable(c))) return false;      // (lrn_set_shard alone: the caller exchanges H itself)
   for (const auto& b : c->lmi)
     if (!b.have_W) return false;
+  // option "hop_max_mb": H above the budget is not assembled, whatever else says so -- factored models reach nvar where
+  // nvar^2 doubles do not fit, and an automatic choice must not end in an allocation error
+  const double hbytes = (double)c->nvar * (double)c->nvar * 8.0;
+  if (hbytes > hop_budget_bytes(c)) {
+    c->counts["hop_over_budget"] += 1;
+    return false;
+  }
   if (c->opt.matvec_h == 2) return true;
   const double gain = (double)expected_iters * (est_operator_s(c) - est_symv_s(c));
   return gain > 1.2 * est_assemble_s(c, hop_mode(c));

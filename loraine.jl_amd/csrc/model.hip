@@ -174,7 +174,7 @@ static void free_block(LmiBlock& b) {
   b.dense_route = LmiBlock::DENSE_SCALAR;      // (Adense goes below)
   for (DBuf* d : {&b.ent_ptr, &b.ent_r, &b.ent_c, &b.ent_v, &b.Adense, &b.hidx, &b.sigma_d, &b.ipos_d, &b.cq_q, &b.cq_ptr, &b.cq_j, &b.cq_v, &b.pc_ptr, &b.pc_r, &b.pc_t, &b.ent_t, &b.Mv, &b.Zs, &b.b_ptr, &b.b_col,
                   &b.b_val, &b.X, &b.S, &b.W, &b.G, &b.Gi, &b.Si, &b.D, &b.DDsi, &b.Vprev, &b.Cd, &b.Rd, &b.delX, &b.delS, &b.Xn, &b.Sn, &b.RNT,
-                  &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd, &b.v_ptr, &b.v_col, &b.v_val, &b.v_w, &b.Vd})
+                  &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd, &b.v_ptr, &b.v_col, &b.v_val, &b.v_w, &b.Vd, &b.Ys})
     release(*d);
 }
 
@@ -652,6 +652,7 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
   LRN_TRY(copy_in(c, b.v_w.p, wh.data(), (size_t)R * 8));
   release(b.Vd);                 // (the dense copy is rebuilt from these factors on first use)
   b.have_Vd = false;
+  b.Ys_version = -1;             // (and Y = W Vd of option "fac_op_scaled" with it)
   b.lr_khat = khat;
   b.vnnz = nnz;
   b.has_V = true;

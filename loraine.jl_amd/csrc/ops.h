@@ -6,7 +6,7 @@ namespace lrn {
 bool use_sparse_matvec(const lrn_ctx* c, const LmiBlock& b);                // the pattern-restricted form of MyA serves this block
 int ensure_m(lrn_ctx* c, int m);                                            // c->m0..m2 >= msz^2
 int wmw(lrn_ctx* c, LmiBlock& b, double* M, double* P, double* Z);          // Z = W M W (M symmetric)
-int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form = false);          // y += AA vec(Z)
+int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form = false, bool fused = false);          // y += AA vec(Z)
 // y += AA vec(W M W) through the entries of W M W the (all sparse) constraints read: N (work) = M W, then dots on the pattern
 bool wmw_pattern_ok(const lrn_ctx* c, const LmiBlock& b);
 int aa_times_wmw_pattern(lrn_ctx* c, LmiBlock& b, const double* M, double* N, double* y);

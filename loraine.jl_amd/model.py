@@ -44,6 +44,17 @@ class MyModel:
     # k; {} for a pure or a materialised block).  AA[i] then holds the rows of the stored constraints only, lowrank[i]
     # weight-0 columns for them, aa_fro[i] both parts; A[i] stays [F_0]
     stored: list = field(default_factory=list)
+    # Optimizer.load_factored_model(..., cg=True): the CG path (kit = 1) is allowed on this factored model -- the solver sets
+    # the library option cg_factored = 1 (operator in factor form or through H of mode 1, ts of H_alpha from the factors)
+    factored_cg: bool = False
+
+
+def check_factored_kit(model, kit):
+    """The host's check of kit against a factored model, callable before any device exists: kit = 1 needs the model to say so
+    (load_factored_model(..., cg=True)); ValueError otherwise, with the text the default has always had."""
+    if getattr(model, "factored", False) and int(kit) != 0 and not getattr(model, "factored_cg", False):
+        raise ValueError("a factored model (load_factored_model) needs kit = 0: the CG path reads the constraint "
+                         "matrices, which do not exist")
 
 
 def _rank_one_rows(blockA, n):

@@ -12,7 +12,7 @@ calls a JuMP user makes:
 import numpy as np
 
 from . import solvers
-from .model import MyModel, build_factored_model, build_model, model_from_sdpa
+from .model import MyModel, build_factored_model, build_model, check_factored_kit, model_from_sdpa
 
 # MOI.TerminationStatus values used by the reference (MOI_wrapper.jl:252-265)
 OPTIMIZE_NOT_CALLED = "OPTIMIZE_NOT_CALLED"
@@ -78,11 +78,14 @@ class Optimizer:
         self._pending = ("arrays", (A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense), factors))
         return self
 
-    def load_factored_model(self, F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factored_form=-1):
+    def load_factored_model(self, F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factored_form=-1,
+                            cg=False):
         """The same problem given by its factors alone: F0[i] the constant matrix of block i (the A[i][0] of load_model),
         factors[i][k] = (V, d) with A_i,k+1 = V diag(d) V' (V msz x r, r <= 16, d = +-1, dense or sparse).  No A_ik, no
         row of AA and no dense constraint slab is ever formed, on the host or on the device; implies datarank = the
         largest rank (at least 1) and needs kit = 0 and the resident solver (ValueError otherwise).
+        cg=True admits kit = 1 as well (opt-in): the CG operator runs from the factors or through H assembled from them, ts of
+        H_alpha comes from the factors (library option cg_factored); one GPU only.
         factors[i][k] may instead be a symmetric msz x msz matrix (SciPy sparse or a 2-D array): that constraint is stored
         as a matrix -- a trace row, a few sparse side constraints among thousands of factored ones (a hybrid block; the
         others stay factors, nothing else is materialised).
@@ -92,7 +95,7 @@ class Optimizer:
             raise ValueError("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
                              "multiplies by AA")
         self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
-                                      int(factored_form)))
+                                      int(factored_form), bool(cg)))
         return self
 
     def _copy_to(self):
@@ -103,12 +106,11 @@ class Optimizer:
             model = model_from_sdpa(payload, datarank=drank, kappa=kappa)
             self.max_sense = False
         elif kind == "factored":
-            F0, factors, b, b_const, d_lin, C_lin, max_sense, form = payload
+            F0, factors, b, b_const, d_lin, C_lin, max_sense, form, cg = payload
             self.max_sense = max_sense
             model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
-            if model.factored and int(self.options.get("kit", 0)) != 0:
-                raise ValueError("a factored model (load_factored_model) needs kit = 0: the CG path reads the constraint "
-                                 "matrices, which do not exist")
+            model.factored_cg = bool(cg) and model.factored
+            check_factored_kit(model, self.options.get("kit", 0))
         else:
             A, b, b_const, d_lin, C_lin, max_sense, factors = payload
             self.max_sense = max_sense

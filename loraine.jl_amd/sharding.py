@@ -230,6 +230,9 @@ class DistributedHotPath:
 
     def __init__(self, solver, rank, world, group=None):
         self.rank, self.world, self.group = int(rank), int(world), group
+        if int(world) > 1 and solver.kit == 1 and getattr(solver.model, "factored", False):
+            raise ValueError("a factored model under kit = 1 (load_factored_model(..., cg=True)) runs on one GPU: the factor "
+                             "routes of the CG path are not sharded")
         solver.dist = self
         # the C library shards Schur columns in sigma-position space, which exists for one LMI block;
         # multi-block problems assemble replicated (every rank the whole matrix, no exchange)

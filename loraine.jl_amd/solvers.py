@@ -19,7 +19,7 @@ import scipy.linalg as sla
 import scipy.sparse as sp
 
 from .device import Device
-from .model import MyModel
+from .model import MyModel, check_factored_kit
 
 # src/Solvers.jl:169-185
 DEFAULT_OPTIONS = {
@@ -103,9 +103,8 @@ class MySolver:
         if getattr(model, "factored", False):
             # the constraints exist as factors only: direct solver on the resident path (the CG path reads the entries
             # of AA in H_alpha, the NumPy host loop multiplies by AA)
-            if self.kit != 0:
-                raise ValueError("a factored model (load_factored_model) needs kit = 0: the CG path reads the constraint "
-                                 "matrices, which do not exist")
+            # -- unless the model was loaded with cg=True: then kit = 1 runs from the factors (option cg_factored below)
+            check_factored_kit(model, self.kit)
             if not self._resident:
                 raise ValueError("a factored model (load_factored_model) needs the resident solver "
                                  "(Optimizer(resident=True)): the NumPy host loop multiplies by AA")
@@ -131,6 +130,11 @@ class MySolver:
                     if getattr(model, "factored", False) and model.factored_blocks[i]:
                         self.dev.set_factored(i)                                # [GPU] the factors are the data
                 self.lowrank = True
+                if getattr(model, "factored", False):
+                    # kit = 1 was checked above: the model allows it.  kit = 0 on a device another solve used: the default
+                    self.dev.set_option("cg_factored", 1 if self.kit == 1 else 0)
+                    if self.kit == 1:
+                        self._say(" ---The CG path runs from the factors of the factored blocks (cg_factored = 1)")
                 if self.kit == 1:
                     self.dev.set_option("cg_lowrank", -1)
                     self._say(f" ---The CG path uses the rank-{self.datarank} factors of the data (cg_lowrank = -1)")
@@ -533,7 +537,9 @@ class MySolver:
                             prec_setup=d.timing("prec_setup"), pcg=d.timing("pcg"), svd=d.timing("prepw_svd")),
                 svd_sweeps=d.count("svd_sweeps"), find_step_ms=d.timing("find_step"),
                 rhs_ms=d.timing("rhs"), residual_d_ms=d.timing("residual_d"), stats_ms=d.timing("stats"),
-                hop_assemble=d.count("hop_assemble"), hop_matvec=d.count("hop_matvec"),
+                hop_assemble=d.count("hop_assemble"), hop_over_budget=d.count("hop_over_budget"),
+                op_factored_scaled=d.count("op_factored_scaled"), op_quadform_fused=d.count("op_quadform_fused"),
+                prec_ts_stored_rows=d.count("prec_ts_stored_rows"), hop_matvec=d.count("hop_matvec"),
                 prec_lanczos_steps=d.count("prec_lanczos_steps"), lanczos_plain=d.count("lanczos_plain"),
                 prec_dense_build=d.count("prec_dense_build"),
                 ns_steps=d.count("ns_steps"), lyap_steps=d.count("lyap_steps"), lyap_ms=d.timing("lyap"),
