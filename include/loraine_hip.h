@@ -80,6 +80,22 @@ int lrn_upload_lowrank(lrn_ctx* ctx, int ilmi, int khat, const int64_t* V_colptr
  * 16-byte loads over both triangles / one element per lane; the tier is decided when the model is uploaded); "device_bytes",
  * "device_bytes_peak" (device memory of this context now / at most) and "adense_bytes" (dense constraint slabs) are state. */
 int lrn_set_factored(lrn_ctx* ctx, int ilmi, int on);
+/* Diagonal parts of a factored block (after lrn_set_factored(ilmi, 1)): constraint rows[s] (0-based, as k of
+ * lrn_get_constraint) of block ilmi is A = diag(a_s) + V D V' with a_s = column s of `a` (msz x nrows, column-major) and V, D
+ * its factor columns (all of weight 0 for a purely diagonal constraint, e.g. a trace row: a_s = 1).  Host or device arrays.
+ * nrows = 0 clears the diagonal parts; lrn_set_factored(ilmi, 0) and lrn_upload_model drop them, lrn_upload_lowrank keeps
+ * them.  LRN_ERR_STATE when the block is not factored or when a row is a stored constraint of a hybrid block (it has entries:
+ * put the diagonal into the stored matrix); LRN_ERR_ARG for a row out of range or listed twice.
+ * The data operators subtract sum_i a_si Z_ii / add -sum_s x_s a_s to the diagonal of mat(AA' x) after the factor form; mode 1
+ * of lrn_schur_assemble adds H_DD = Ad' (W o W) Ad, the cross terms Ad' (Y o Y) with Y = W Vd (weighted, summed over khat) and
+ * a_k' diag(W A_s W) for the stored rows of a hybrid block -- dense products with one operand squared entrywise, no entry list
+ * (option "diag_sq_mfma"), fixed order, no atomics.  With diagonal rows in any block lrn_matvec, lrn_matvec_partial,
+ * lrn_prec_setup, lrn_prec_apply and lrn_pcg return LRN_ERR_STATE also under "cg_factored" = 1 (ts of H_alpha does not hold
+ * the diagonal parts), and mode 1 returns LRN_ERR_STATE under world > 1.
+ * lrn_get_count: "diag_rows" (state: diagonal rows of all blocks), "op_diag" (operator calls that added a diagonal part),
+ * "schur_diag" (assemblies of a block with diagonal rows), "diag_sq_rows" / "diag_sq_mfma" (squared-operand products by form),
+ * "diag_stored_cross" (cross terms with stored rows); timing keys under "profile": "diag_dd", "diag_cross", "diag_stored". */
+int lrn_upload_diag(lrn_ctx* ctx, int ilmi, int64_t nrows, const int64_t* rows, const double* a);
 /* Builder-defined synthetic dense SDP data generated on the device:
  * A_k = (R_k + R_k')/2, R_k iid N(0,1) from a counter-based Philox stream; nlmi = 1. */
 int lrn_synthetic_dense_model(lrn_ctx* ctx, int msz, int nvar, uint64_t seed);
@@ -172,7 +188,9 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * application, no W M W product; 0 = the composition mat(AA' x) -> W M W -> AA vec(.); -1, default = cost model, which is
  * "off" until the form has been measured faster), "fac_quadform" (under "cg_factored", pure and hybrid factored blocks, inside
  * the matrix-free operator only: 1 = AA vec(Z) of the factor part by the fused quadratic form of facops.hip, Q = Z Vd never
- * stored; 0 = Q and the column dots; -1, default = cost model, "off" likewise), "reset_timing".
+ * stored; 0 = Q and the column dots; -1, default = cost model, "off" likewise), "diag_sq_mfma" (squared-operand product of
+ * the diagonal parts, lrn_upload_diag: 1 = the 64 x 64 FP64 MFMA tile form, 0 = the rows form, one wave per column group and
+ * eight rows in registers, -1, default = by the number of diagonal rows), "reset_timing".
  * Counters of these options: "op_factored_scaled" (blocks per application through Y), "op_quadform_fused" (blocks per
  * application through the fused kernel), "fac_scaled_y" (products Y = W Vd), "hop_over_budget" (operator choices that found H
  * above the budget), "prec_ts_stored_rows" (rows of ts filled from stored entries in the LAST lrn_prec_setup).

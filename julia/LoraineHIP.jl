@@ -80,6 +80,14 @@ function set_factored!(ctx::Ctx, i::Integer, on::Bool = true)
     check(ctx, ccall((:lrn_set_factored, LIB), Cint, (Ptr{Cvoid}, Cint, Cint), ctx.h, i - 1, on ? 1 : 0), "lrn_set_factored")
 end
 
+# ---- diagonal parts of factored block i (after set_factored!): constraint rows[s] (1-based here) is diag(a[:, s]) + V D V';
+# a is msz x length(rows).  An empty `rows` clears them
+function upload_diag!(ctx::Ctx, i::Integer, rows::Vector{Int64}, a::Matrix{Float64})
+    rows0 = rows .- 1
+    check(ctx, ccall((:lrn_upload_diag, LIB), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float64}),
+        ctx.h, i - 1, length(rows0), rows0, a), "lrn_upload_diag")
+end
+
 # ---- prepare_W (src/prepare_W.jl:28-94) -------------------------------------------------------
 function prepare_W(ctx::Ctx, solver)
     for i in 1:solver.model.nlmi

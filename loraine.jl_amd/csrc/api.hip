@@ -125,6 +125,7 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "hop_max_mb")) { c->opt.hop_max_mb = value < 0.0 ? -1.0 : value; c->hop_version = -1; }
   else if (!strcmp(key, "fac_op_scaled")) { c->opt.fac_op_scaled = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }
   else if (!strcmp(key, "fac_quadform")) { c->opt.fac_quadform = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }
+  else if (!strcmp(key, "diag_sq_mfma")) c->opt.diag_sq_mfma = std::max(-1, std::min(1, (int)value));
   else if (!strcmp(key, "fac_cross_lds")) c->opt.fac_cross_lds = std::max(-1, std::min(1, (int)value));
   else if (!strcmp(key, "jacobi_cross")) c->opt.jacobi_cross = (int)value;
   else if (!strcmp(key, "jacobi_early")) c->opt.jacobi_early = value;
@@ -393,6 +394,11 @@ int64_t lrn_get_count(lrn_ctx* c, const char* key) {
   if (!strcmp(key, "adense_bytes")) {
     int64_t s = 0;
     for (const auto& b : c->lmi) if (b.Adense.p) s += (int64_t)b.Adense.bytes;
+    return s;
+  }
+  if (!strcmp(key, "diag_rows")) {      // diagonal rows of all blocks (lrn_upload_diag): state
+    int64_t s = 0;
+    for (const auto& b : c->lmi) s += b.dg_n;
     return s;
   }
   auto it = c->counts.find(key);

@@ -934,7 +934,18 @@ using namespace lrn;
 // the CG side (mat-vec, H_alpha, PCG) reads the entries of AA: not for factored blocks -- unless option "cg_factored" is set:
 // then the operator runs in factor form (dataops.hip) or through H assembled in mode 1 (hop.hip) and ts of H_alpha comes from
 // the factors.  One GPU only (partial: lrn_matvec_partial; world > 1: any call) -- the factor routes are not sharded
+// ... and not for a block with diagonal parts (lrn_upload_diag), whatever cg_factored says: ts of H_alpha is built from the
+// factors and the stored rows and would silently miss them
+static int no_diag(lrn_ctx* c, const char* what) {
+  for (size_t il = 0; il < c->lmi.size(); ++il)
+    if (c->lmi[il].factored && c->lmi[il].dg_n > 0)
+      return set_error(c, LRN_ERR_STATE, "%s: block %d is factored with diagonal parts (lrn_upload_diag): the CG path does not "
+                                         "hold them, such a model is solved with kit = 0", what, (int)il);
+  return LRN_OK;
+}
+
 static int no_factored(lrn_ctx* c, const char* what, bool partial = false) {
+  LRN_TRY(no_diag(c, what));
   for (size_t il = 0; il < c->lmi.size(); ++il)
     if (c->lmi[il].factored) {
       if (c->opt.cg_factored != 0 && (partial || c->world > 1))
@@ -1000,6 +1011,7 @@ extern "C" int lrn_prec_setup(lrn_ctx* c, int prec, int erank, int aamat, int* i
 
 extern "C" int lrn_prec_apply(lrn_ctx* c, const double* x, double* Mx) {
   if (!c || !x || !Mx) return LRN_ERR_ARG;
+  LRN_TRY(no_diag(c, "lrn_prec_apply"));
   LRN_HIP(c, hipSetDevice(c->device));
   const int n = c->nvar;
   LRN_TRY(copy_in(c, c->v0.p, x, (size_t)n * 8));

@@ -85,6 +85,12 @@ struct LmiBlock {
   // option "fac_op_scaled" (pure factored block): Y = W Vd (msz x nvar khat) of the scaling `Ys_version` (dataops.hip::fac_scaled_y)
   lrn::DBuf Ys;
   long Ys_version = -1;
+  // diagonal parts (lrn_upload_diag, factored blocks only): constraint A_k = diag(a_k) + V_k D_k V_k' for the dg_n constraints
+  // ("diagonal rows") listed there -- factored positions, never stored ones.  Row s: H index dg_h[s], natural constraint
+  // number dg_nat[s], column s of dg_a (msz x dg_n, column-major, +a); dg_of_pos[p] = row of position p or -1 (diagops.hip)
+  int dg_n = 0;
+  lrn::DBuf dg_h, dg_nat, dg_of_pos;   // int32 [dg_n], [dg_n], [nvar]
+  lrn::DBuf dg_a;                      // double [msz * dg_n]
 };
 
 struct lrn_ctx;
@@ -166,6 +172,8 @@ struct LrnOptions {
                                   // composition mat(AA' x) -> W M W -> AA vec(.): 0, cost model (hop.hip::fac_op_scaled_on): -1
   int fac_quadform = -1;          // AA vec(Z) of a factored block inside the CG operator by the fused quadratic form of facops.hip
                                   // (Q = Z Vd never stored): 1, Q and fac_coldot_kernel: 0, cost model: -1
+  int diag_sq_mfma = -1;          // squared-operand product of the diagonal parts (diagops.hip::diag_sq): the MFMA tile form (1), the
+                                  // rows form, one wave per column group (0), by the number of diagonal rows (-1)
 };
 
 struct lrn_ctx {
@@ -222,6 +230,7 @@ struct lrn_ctx {
   lrn::DBuf P, P2, T, slabs, Hd, BG;
   lrn::DBuf m0, m1, m2, cgbuf;   // msz^2 work matrices (mat-vec / rhs), PCG vectors
   lrn::DBuf facY, facM;          // hybrid factored block: Y = W Vd when U is G' Vd (msz x nvar khat); the stored part of mat(AA' x)
+  lrn::DBuf dgP, dgC, dgH, dgT, dgTA;   // diagonal parts (diagops.hip): Ad' (W o W), Ad' (Y o Y) summed over khat, H_DD, T = rows diag(W A_s W), T' Ad
   int T_m = 0;                 // matrix side and block the T workspace was last laid out for
   const void* T_owner = nullptr;
   int T_layout = 0;            // 0: msz^2 per matrix, lower tiles (T_k = W A_k W); 1: packed lower tiles (L' A_k L)

@@ -1082,6 +1082,7 @@ int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_
 static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form, bool fused) {
   if (factor_form && !b.factored) return aa_times_factored(c, b, Z, y);
   if (b.factored) LRN_TRY(aa_times_factored(c, b, Z, y, fused));      // (a hybrid block goes on with its stored rows; a pure one has none)
+  if (b.factored && b.dg_n > 0) LRN_TRY(aa_times_diag(c, b, Z, y));   // (diagonal parts: disjoint from the stored rows, after the factor form)
   if (b.npos_nz > b.nd) c->counts["op_sparse"] += 1;
   if (b.nd > 0) c->counts["op_dense"] += 1;
   if (b.npos_nz > b.nd)
@@ -1127,6 +1128,7 @@ static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M, 
   if (factor_form && !b.factored) return aat_to_mat_factored(c, b, x, M);
   if (!b.factored) return aat_to_mat_stored(c, b, x, M);
   LRN_TRY(aat_to_mat_factored(c, b, x, M));
+  if (b.dg_n > 0) LRN_TRY(aat_to_mat_diag(c, b, x, M));      // (diagonal parts: the diagonal of M only)
   if (!b.hybrid()) return LRN_OK;
   // hybrid: the stored rows through the stored-entry kernels into a matrix of their own, then one elementwise sum -- both
   // terms are exactly symmetric, so the sum is

@@ -272,7 +272,8 @@ static double est_operator_s(const lrn_ctx* c) {
 // costs 0.02 / 1.27 / 0.09 ms per scaling, the gain of one to three applications -- on from msz 256 (the smallest side
 // measured) when the previous scaling saw at least four operator applications (cg_prev_iters, constant within a scaling).
 bool fac_op_scaled_on(const lrn_ctx* c, const LmiBlock& b) {
-  if (!cg_factored_on(c) || !b.factored || b.hybrid()) return false;      // (a hybrid block keeps the composition)
+  if (!cg_factored_on(c) || !b.factored || b.hybrid() || b.dg_n > 0) return false;      // (a hybrid block keeps the composition; with
+                                                                                          // diagonal parts W M W is not -Y diag Y')
   if (c->opt.fac_op_scaled >= 0) return c->opt.fac_op_scaled == 1;
   return b.msz >= 256 && c->cg_prev_iters >= 4;
 }

@@ -174,15 +174,17 @@ static void free_block(LmiBlock& b) {
   b.dense_route = LmiBlock::DENSE_SCALAR;      // (Adense goes below)
   for (DBuf* d : {&b.ent_ptr, &b.ent_r, &b.ent_c, &b.ent_v, &b.Adense, &b.hidx, &b.sigma_d, &b.ipos_d, &b.cq_q, &b.cq_ptr, &b.cq_j, &b.cq_v, &b.pc_ptr, &b.pc_r, &b.pc_t, &b.ent_t, &b.Mv, &b.Zs, &b.b_ptr, &b.b_col,
                   &b.b_val, &b.X, &b.S, &b.W, &b.G, &b.Gi, &b.Si, &b.D, &b.DDsi, &b.Vprev, &b.Cd, &b.Rd, &b.delX, &b.delS, &b.Xn, &b.Sn, &b.RNT,
-                  &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd, &b.v_ptr, &b.v_col, &b.v_val, &b.v_w, &b.Vd, &b.Ys})
+                  &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd, &b.v_ptr, &b.v_col, &b.v_val, &b.v_w, &b.Vd, &b.Ys,
+                  &b.dg_h, &b.dg_nat, &b.dg_of_pos, &b.dg_a})
     release(*d);
+  b.dg_n = 0;
 }
 
 void lrn_free_model(lrn_ctx* c) {
   for (auto& b : c->lmi) free_block(b);
   c->lmi.clear();
   for (DBuf* d : {&c->cl_ptr, &c->cl_row, &c->cl_val, &c->lin_xs, &c->H, &c->L, &c->cholwork,
-                  &c->v0, &c->v1, &c->v2, &c->v3, &c->P, &c->P2, &c->T, &c->slabs, &c->Hd, &c->BG, &c->m0, &c->m1, &c->m2, &c->cgbuf, &c->facY, &c->facM, &c->cl_rown,
+                  &c->v0, &c->v1, &c->v2, &c->v3, &c->P, &c->P2, &c->T, &c->slabs, &c->Hd, &c->BG, &c->m0, &c->m1, &c->m2, &c->cgbuf, &c->facY, &c->facM, &c->dgP, &c->dgC, &c->dgH, &c->dgT, &c->dgTA, &c->cl_rown,
                   &c->hdiag, &c->wchol, &c->lp_r, &c->lp_c, &c->lp_ptr, &c->lp_l, &c->lp_w, &c->cr_ptr, &c->cr_col, &c->cr_val})
     release(*d);
   c->T_m = 0;
@@ -588,6 +590,12 @@ static bool factors_partial(const lrn_ctx* c, const LmiBlock& b, const double* w
   return false;
 }
 
+// the diagonal parts belong to the declaration "factored": they go with it
+static void drop_diag(LmiBlock& b) {
+  for (DBuf* d : {&b.dg_h, &b.dg_nat, &b.dg_of_pos, &b.dg_a}) release(*d);
+  b.dg_n = 0;
+}
+
 static int has_entries_error(lrn_ctx* c, const LmiBlock& b, int ilmi) {
   return set_error(c, LRN_ERR_STATE, "lrn_set_factored: the AA of block %d has entries (%ld): a factored block takes its "
                                      "constraints from the factors alone, or each one from a stored row or from factors, never both", ilmi, b.nent);
@@ -659,6 +667,7 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
   b.v_partial = factors_partial(c, b, wh.data());
   if (b.factored && stored_and_factored(c, b, wh.data()) >= 0) {      // (new factors that overlap the stored rows of a hybrid block)
     b.factored = false;
+    drop_diag(b);
     return has_entries_error(c, b, ilmi);
   }
   if (b.factored) LRN_TRY(lowrank_dense_factors(c, b));      // (new factors of a factored block: its operators read Vd)
@@ -678,6 +687,7 @@ extern "C" int lrn_set_factored(lrn_ctx* c, int ilmi, int on) {
   LmiBlock& b = c->lmi[ilmi];
   if (!on) {
     b.factored = false;
+    drop_diag(b);
     return LRN_OK;
   }
   if (!b.has_V)
@@ -690,5 +700,67 @@ extern "C" int lrn_set_factored(lrn_ctx* c, int ilmi, int on) {
   LRN_TRY(lowrank_dense_factors(c, b));
   b.factored = true;
   LRN_HIP(c, hipStreamSynchronize(c->stream));
+  return LRN_OK;
+}
+
+// Diagonal parts of a factored block: constraint rows[s] (0-based) is diag(a_s) + V D V', a_s = column s of a (msz x nrows).
+// Host or device arrays; nrows = 0 clears.  The rows are factored positions -- a stored constraint carries its diagonal in its
+// entries.  Kept: dg_h (H index per row), dg_nat (constraint per row), dg_of_pos (position -> row or -1), dg_a (diagops.hip)
+extern "C" int lrn_upload_diag(lrn_ctx* c, int ilmi, int64_t nrows, const int64_t* rows, const double* a) {
+  if (!c) return LRN_ERR_ARG;
+  if (ilmi < 0 || ilmi >= c->nlmi) return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: block %d of %d", ilmi, c->nlmi);
+  LRN_HIP(c, hipSetDevice(c->device));
+  LmiBlock& b = c->lmi[ilmi];
+  const int m = b.msz, nvar = c->nvar;
+  if (nrows < 0 || nrows > nvar) return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: %lld rows, the model has %d constraints", (long long)nrows, nvar);
+  if (!b.factored)
+    return set_error(c, LRN_ERR_STATE, "lrn_upload_diag: block %d is not factored (lrn_set_factored): a diagonal part goes with "
+                                       "the factors of a factored block", ilmi);
+  if (nrows == 0) {
+    drop_diag(b);
+    return LRN_OK;
+  }
+  if (!rows || !a) return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: null array");
+  const int ns = (int)nrows;
+  std::vector<int64_t> rw(ns);
+  LRN_HIP(c, hipMemcpy(rw.data(), rows, (size_t)ns * 8, hipMemcpyDefault));
+  std::vector<int> dgh(ns), nat(ns), of_pos(nvar, -1);
+  for (int s = 0; s < ns; ++s) {
+    const int64_t k = rw[s];
+    if (k < 0 || k >= nvar) return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: row %lld out of range (0 .. %d)", (long long)k, nvar - 1);
+    const int pos = b.ipos[(int)k];
+    if (of_pos[pos] >= 0) return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: row %lld is listed twice", (long long)k);
+    if (pos < b.npos_nz)
+      return set_error(c, LRN_ERR_STATE, "lrn_upload_diag: constraint %lld of block %d is stored (it has entries): its diagonal "
+                                         "belongs into the stored matrix", (long long)k, ilmi);
+    of_pos[pos] = s;
+    nat[s] = (int)k;
+    dgh[s] = c->pos_space ? pos : (int)k;
+  }
+  // staged in buffers of their own and swapped in at the end: an allocation or a copy that fails halfway leaves the parts
+  // already uploaded, and their dg_n, as they were
+  DBuf th, tn, tp, ta;
+  auto stage = [&]() -> int {
+    LRN_TRY(ensure(c, th, (size_t)ns * 4));
+    LRN_TRY(ensure(c, tn, (size_t)ns * 4));
+    LRN_TRY(ensure(c, tp, (size_t)nvar * 4));
+    LRN_TRY(ensure(c, ta, (size_t)ns * m * 8));
+    LRN_TRY(copy_in(c, th.p, dgh.data(), (size_t)ns * 4));
+    LRN_TRY(copy_in(c, tn.p, nat.data(), (size_t)ns * 4));
+    LRN_TRY(copy_in(c, tp.p, of_pos.data(), (size_t)nvar * 4));
+    LRN_TRY(copy_in(c, ta.p, a, (size_t)ns * m * 8));
+    LRN_HIP(c, hipStreamSynchronize(c->stream));      // (the host vectors above are read by asynchronous copies)
+    return LRN_OK;
+  };
+  const int rc = stage();
+  if (rc == LRN_OK) {
+    std::swap(b.dg_h, th);
+    std::swap(b.dg_nat, tn);
+    std::swap(b.dg_of_pos, tp);
+    std::swap(b.dg_a, ta);
+  }
+  for (DBuf* d : {&th, &tn, &tp, &ta}) release(*d);      // (the previous buffers, or the unfinished new ones)
+  if (rc != LRN_OK) return rc;
+  b.dg_n = ns;
   return LRN_OK;
 }

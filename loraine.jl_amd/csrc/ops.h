@@ -84,7 +84,12 @@ bool chol_path_applicable(lrn_ctx* c, LmiBlock& b, long* pcap_out);
 // schur_factored.hip: rank-one data (mode -1), rank-k data (mode 1), cross terms of a hybrid factored block
 int assemble_rank1(lrn_ctx* c, LmiBlock& b);
 int assemble_lowrank(lrn_ctx* c, LmiBlock& b);
-int assemble_cross(lrn_ctx* c, LmiBlock& b);
+int factored_y(lrn_ctx* c, LmiBlock& b, const double** Y);      // Y = W Vd (msz x nvar khat) after assemble_lowrank: its U, or one more product
+int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);
+// diagops.hip: diagonal parts of a factored block (lrn_upload_diag), A_k = diag(a_k) + V_k D_k V_k'
+int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y);    // H_DD, the cross terms with the factors (Y) and with the stored rows
+int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // y[nat(s)] -= sum_i a_si Z_ii
+int aat_to_mat_diag(lrn_ctx* c, LmiBlock& b, const double* x, double* M);    // M_ii -= sum_s x[nat(s)] a_si
 void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I (ipstep.hip)
 // n x n helpers (prepw.hip)
 void eye_mat(hipStream_t st, double* V, int n);                            // V = I

@@ -23,7 +23,8 @@
 //   rank-k data (mode 1): U = G' V, H += blocksum(d d' .* (U'U).^2) over khat x khat blocks, again in the
 //        epilogue of one MFMA product (assemble_lowrank).
 // This file: the sparse owners, the linear part, the driver schur_assemble, factorisation and solve.  schur_dense.hip: the dense
-// owners; schur_factored.hip: rank-one / rank-k data and hybrid blocks; schur_plan.h: the launch decisions, host only.
+// owners; schur_factored.hip: rank-one / rank-k data and hybrid blocks; diagops.hip: diagonal parts of factored blocks;
+// schur_plan.h: the launch decisions, host only.
 #include <algorithm>
 
 #include "ops.h"
@@ -246,6 +247,10 @@ int schur_assemble(lrn_ctx* c, int mode) {
     if (b.hybrid() && c->world > 1)
       return set_error(c, LRN_ERR_STATE, "lrn_schur_assemble: mode 1 on a factored block with stored constraints runs on one "
                                          "GPU (the cross terms are not sharded)");
+  for (const auto& b : c->lmi)
+    if (b.factored && b.dg_n > 0 && c->world > 1)
+      return set_error(c, LRN_ERR_STATE, "lrn_schur_assemble: mode 1 on a factored block with diagonal parts (lrn_upload_diag) runs "
+                                         "on one GPU (their terms are not sharded)");
   LRN_HIP(c, hipMemsetAsync(c->H.p, 0, (size_t)n * n * 8, c->stream));
   c->H_partial = false;
   c->H_owned_only = false;
@@ -260,7 +265,15 @@ int schur_assemble(lrn_ctx* c, int mode) {
     } else if (mode == 1 && b.hybrid()) {     // H_SS from the stored entries, then H_FF and the cross terms (see assemble_cross)
       LRN_TRY(assemble_stored(c, b));
       LRN_TRY(assemble_lowrank(c, b));
-      LRN_TRY(assemble_cross(c, b));
+      const double* Y = nullptr;
+      if (n > b.npos_nz) LRN_TRY(factored_y(c, b, &Y));
+      LRN_TRY(assemble_cross(c, b, Y));
+      if (b.dg_n > 0) LRN_TRY(assemble_diag(c, b, Y));
+    } else if (mode == 1 && b.factored && b.dg_n > 0) {     // pure block with diagonal rows (diagops.hip)
+      LRN_TRY(assemble_lowrank(c, b));
+      const double* Y = nullptr;
+      LRN_TRY(factored_y(c, b, &Y));
+      LRN_TRY(assemble_diag(c, b, Y));
     } else if (mode == 1) {
       LRN_TRY(assemble_lowrank(c, b));
     } else {

@@ -231,13 +231,12 @@ __global__ __launch_bounds__(256) void fac_cross_coldot_kernel(const double* __r
   H[h_lower(hidx[s], hj, ldh)] += acc;
 }
 
-int assemble_cross(lrn_ctx* c, LmiBlock& b) {
+// Y = W Vd: what assemble_lowrank left in BG when only W exists, one more product into a workspace of its own otherwise.
+// Formed once per assembly of a block and shared by assemble_cross and diagops.hip::assemble_diag
+int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
   const int n = c->nvar, m = b.msz, kh = b.lr_khat;
   const long R = (long)n * kh;
   if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");
-  const int nf = n - b.npos_nz;
-  if (nf <= 0) return LRN_OK;
-  // Y = W Vd: what assemble_lowrank left in BG when only W exists, one more product into a workspace of its own otherwise
   const double* Y = c->BG.as<double>();
   tic(c);
   if (b.have_G) {
@@ -251,6 +250,15 @@ int assemble_cross(lrn_ctx* c, LmiBlock& b) {
     Y = c->facY.as<double>();
   }
   toc(c, "hybrid_y");
+  *Yout = Y;
+  return LRN_OK;
+}
+
+int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y) {
+  const int n = c->nvar, m = b.msz, kh = b.lr_khat;
+  const long R = (long)n * kh;
+  const int nf = n - b.npos_nz;
+  if (nf <= 0) return LRN_OK;
   tic(c);
   if (b.npos_nz > b.nd) {
     const size_t cap = c->opt.fac_cross_lds == 1 ? 65536 : 32768;      // bytes of one column: forced / by default

@@ -195,6 +195,18 @@ class Device:
         operators AA vec(.) / mat(AA' .) run in factor form, the Schur matrix comes from schur_assemble(1)."""
         self._chk(self.lib.lrn_set_factored(self.h, int(ilmi), 1 if on else 0), "lrn_set_factored")
 
+    def upload_diag(self, ilmi, rows, a):
+        """Diagonal parts of the factored block ilmi (after set_factored): constraint rows[s] (0-based) is
+        diag(a[:, s]) + V diag(d) V' with its factors; a is msz x len(rows).  An empty `rows` clears them."""
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
+        if rows.size == 0:
+            self._chk(self.lib.lrn_upload_diag(self.h, int(ilmi), 0, None, None), "lrn_upload_diag")
+            return
+        a = f64(np.asarray(a, dtype=np.float64).reshape(-1, rows.size))
+        if 0 <= int(ilmi) < len(self.msizes) and a.shape[0] != self.msizes[ilmi]:
+            raise ValueError(f"diagonal parts of {a.shape[0]} entries, block {ilmi} has side {self.msizes[ilmi]}")
+        self._chk(self.lib.lrn_upload_diag(self.h, int(ilmi), int(rows.size), ptr(rows), ptr(a)), "lrn_upload_diag")
+
     def synthetic_dense_model(self, msz, nvar, seed):
         self._chk(self.lib.lrn_synthetic_dense_model(self.h, int(msz), int(nvar), C.c_uint64(seed)),
                   "lrn_synthetic_dense_model")

@@ -47,6 +47,10 @@ class MyModel:
     # Optimizer.load_factored_model(..., cg=True): the CG path (kit = 1) is allowed on this factored model -- the solver sets
     # the library option cg_factored = 1 (operator in factor form or through H of mode 1, ts of H_alpha from the factors)
     factored_cg: bool = False
+    # diagonal parts of factored blocks: diag[i] = {k: a (length m_i)} -- constraint k (0-based) of block i is
+    # diag(a) + V diag(d) V' with its factors in `lowrank` (none for a purely diagonal constraint, e.g. a trace row).  {} for a
+    # block without them and for a materialised block, whose entries hold the diagonal
+    diag: list = field(default_factory=list)
 
 
 def check_factored_kit(model, kit):
@@ -55,6 +59,14 @@ def check_factored_kit(model, kit):
     if getattr(model, "factored", False) and int(kit) != 0 and not getattr(model, "factored_cg", False):
         raise ValueError("a factored model (load_factored_model) needs kit = 0: the CG path reads the constraint "
                          "matrices, which do not exist")
+
+
+def check_diag_kit(model, kit):
+    """kit = 1 against a factored model with diagonal parts, before any device exists: the CG path (also under
+    load_factored_model(..., cg=True)) builds ts of H_alpha from the factors and the stored rows and would miss them."""
+    if int(kit) != 0 and getattr(model, "factored", False) and any(getattr(model, "diag", None) or []):
+        raise ValueError("a factored model with diagonal parts (a constraint given as (V, d, a)) needs kit = 0: the CG path "
+                         "does not hold the diagonal parts")
 
 
 def _rank_one_rows(blockA, n):
@@ -261,24 +273,43 @@ def _stored_matrix(item, m, where):
     return A
 
 
+def diag_fro_sq(V, d, a):
+    """||diag(a) + V diag(d) V'||_F^2 - ||V diag(d) V'||_F^2 = 2 sum_p d_p sum_i a_i v_ip^2 + ||a||^2 (no m x m matrix)."""
+    return float(2.0 * np.sum(d * (a @ (V * V))) + a @ a)
+
+
 def _check_factors(F0, factors, n):
-    """factors[i][k] = (V, d) -> dense (m x r) V and d per constraint, or a symmetric m x m matrix (a stored constraint) -> csc;
-    ValueError otherwise."""
+    """factors[i][k] = (V, d) -> dense (m x r) V and d per constraint, or a symmetric m x m matrix (a stored constraint) -> csc,
+    or (V, d, a) -> (V, d) and the diagonal part a (V may be None: a purely diagonal constraint); ValueError otherwise.
+    -> (items per block, {k: a} per block); an all-zero a is the pair (V, d)."""
     if len(factors) != len(F0):
         raise ValueError(f"factors for {len(factors)} LMI blocks, F0 has {len(F0)}")
-    out = []
+    out, diags = [], []
     for i, blk in enumerate(factors):
         m = F0[i].shape[0]
         if F0[i].shape != (m, m):
             raise ValueError(f"block {i + 1}: F0 is {F0[i].shape}, not square")
         if len(blk) != n:
             raise ValueError(f"block {i + 1}: factors of {len(blk)} constraints, b has {n} entries")
-        facs = []
+        facs, dg = [], {}
         for j, item in enumerate(blk):
             if sp.issparse(item) or isinstance(item, np.ndarray):
                 facs.append(_stored_matrix(item, m, f"block {i + 1}, constraint {j + 1}"))
                 continue
-            V, d = item
+            if len(item) == 3:
+                V, d, a = item
+                a = np.asarray(a.toarray() if sp.issparse(a) else a, dtype=np.float64).ravel()
+                if a.size != m:
+                    raise ValueError(f"block {i + 1}, constraint {j + 1}: the diagonal part has {a.size} entries, the block "
+                                     f"has side {m}")
+                if not np.all(np.isfinite(a)):
+                    raise ValueError(f"block {i + 1}, constraint {j + 1}: the diagonal part has a non-finite entry")
+                if V is None:
+                    V = np.zeros((m, 0))
+                if a.any():
+                    dg[j] = a.copy()
+            else:
+                V, d = item
             V = np.asarray(V.toarray() if sp.issparse(V) else V, dtype=np.float64)
             if V.ndim == 1:
                 V = V.reshape(-1, 1)
@@ -290,7 +321,8 @@ def _check_factors(F0, factors, n):
                                  f"(at most {LOWRANK_MAX})")
             facs.append((V, d))
         out.append(facs)
-    return out
+        diags.append(dg)
+    return out, diags
 
 
 def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, kappa=8, factored_form=-1) -> MyModel:
@@ -302,16 +334,21 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
     qA follow the rule of _prepare_A (stable sort by nnz, descending: the stored constraints take the first positions, the
     factored ones follow in their natural order), `lowrank` pads the stored constraints with weight-0 columns, `stored`
     keeps the matrices.
+    factors[i][k] may also be a triple (V, d, a): A_ik = V diag(d) V' + diag(a) with a of length m_i (V = None and d = [] for a
+    purely diagonal constraint: a trace row is (None, [], ones)).  The diagonal parts of a factored block go to `diag[i]`; a
+    bare 1-D array stays an error, a triple whose a is all zero is the pair (V, d).
     factored_form: 1 = every block factored; -1 = a block whose factors are so small that the sparse path serves it --
     sum_k nnz(V_k V_k') <= kappa * (number of factored constraints), i.e. on average at most `datasparsity` entries per
     constraint, the count below which the reference treats a constraint as sparse -- is materialised (sparse AA built from
-    the factors, stored matrices taken as they are, the existing path) and stays un-factored."""
+    the factors, stored matrices taken as they are, the existing path) and stays un-factored.  A diagonal part counts nnz(a)
+    entries towards that sum; in a materialised block the constraint is the sparse sum, and one with a diagonal part gets
+    weight-0 factor columns in `lowrank` -- its entries carry it whole, as those of a stored matrix do."""
     n = len(b)
     if factored_form not in (-1, 1):
         raise ValueError(f"factored_form = {factored_form} (-1 auto, 1 always factored)")
-    items_all = _check_factors(F0, factors, n)
+    items_all, diags_all = _check_factors(F0, factors, n)
     nlmi = len(F0)
-    A, AA, C, lowrank, fblocks, aa_fro, stored = [], [], [], [], [], [], []
+    A, AA, C, lowrank, fblocks, aa_fro, stored, diag = [], [], [], [], [], [], [], []
     nzA = np.zeros((n, nlmi), dtype=np.int64)
     sigmaA = np.zeros((n, nlmi), dtype=np.int64)
     qA = np.zeros((2, nlmi), dtype=np.int64)
@@ -325,10 +362,14 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
         st = {k: it for k, it in enumerate(items) if sp.issparse(it)}
         none = (np.zeros((m, 0)), np.zeros(0))                 # a stored constraint has no factor column
         facs = [none if k in st else it for k, it in enumerate(items)]
+        dg = diags_all[i]
         lr = pad_factors(facs, n, m)
-        lowrank.append(lr)
         supp = [int(np.count_nonzero(np.any(V != 0.0, axis=1))) for V, _ in facs]
-        small = sum(s * s for s in supp) <= kappa * (n - len(st))
+        small = sum(s * s for s in supp) + sum(int(np.count_nonzero(a)) for a in dg.values()) <= kappa * (n - len(st))
+        fro_dg = sum(diag_fro_sq(*facs[k], a) for k, a in dg.items())       # (what the diagonal parts add to ||.||_F^2)
+        if factored_form == -1 and small and dg:
+            lr = pad_factors([none if k in dg else f for k, f in enumerate(facs)], n, m)
+        lowrank.append(lr)
         if factored_form == -1 and small:
             blk = [sp.csc_matrix(F)]
             for k, ((V, d), s) in enumerate(zip(facs, supp)):
@@ -338,6 +379,8 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
                 rows = np.nonzero(np.any(V != 0.0, axis=1))[0]
                 sub = (V[rows] * d) @ V[rows].T
                 Ak = sp.coo_matrix((sub.ravel(), (np.repeat(rows, s), np.tile(rows, s))), shape=(m, m)).tocsc()
+                if k in dg:
+                    Ak = (Ak + sp.diags(dg[k], format="csc")).tocsc()
                 Ak.eliminate_zeros()
                 blk.append(Ak)
             AAi, _, Ci, nz, sg, q = _prepare_A([blk], 0, kappa, n)
@@ -346,6 +389,7 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
             fblocks.append(False)
             aa_fro.append(float(sp.linalg.norm(AAi[0])))
             stored.append({})
+            diag.append({})
         elif st:
             empty = sp.csc_matrix((m, m))
             AAi, _, _, nz, sg, q = _prepare_A([[empty] + [st.get(k, empty) for k in range(n)]], 0, kappa, n)
@@ -354,23 +398,29 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
             C.append(sp.csc_matrix(-F) if sp.issparse(F) else -F)
             nzA[:, i], sigmaA[:, i], qA[:, i] = nz[:, 0], sg[:, 0], q[:, 0]
             fblocks.append(True)
-            aa_fro.append(float(np.hypot(factors_fro(*lr, n), sp.linalg.norm(AAi[0]))))
+            fro = factors_fro(*lr, n)
+            if dg:
+                fro = float(np.sqrt(max(fro * fro + fro_dg, 0.0)))
+            aa_fro.append(float(np.hypot(fro, sp.linalg.norm(AAi[0]))))
             stored.append(st)
+            diag.append(dg)
         else:
             A.append([F])
             AA.append(sp.csr_matrix((n, m * m)))
             C.append(sp.csc_matrix(-F) if sp.issparse(F) else -F)
             sigmaA[:, i] = np.arange(n)
             fblocks.append(True)
-            aa_fro.append(factors_fro(*lr, n))
+            fro = factors_fro(*lr, n)
+            aa_fro.append(float(np.sqrt(max(fro * fro + fro_dg, 0.0))) if dg else fro)
             stored.append({})
+            diag.append(dg)
     if C_lin is None or C_lin.shape[1] == 0:
         C_lin = sp.csr_matrix((n, 0))
         d_lin = np.zeros(0)
     msizes = np.array([blk[0].shape[0] for blk in A], dtype=np.int64)
     return MyModel(A, AA, [], C, nzA, sigmaA, qA, np.asarray(b, float), float(b_const), np.asarray(d_lin, float),
                    sp.csr_matrix(C_lin), n, msizes, int(C_lin.shape[1]), nlmi, lowrank, "",
-                   any(fblocks), True, fblocks, aa_fro, stored)
+                   any(fblocks), True, fblocks, aa_fro, stored, diag=diag)
 
 
 def _tokens(line):

@@ -12,7 +12,7 @@ calls a JuMP user makes:
 import numpy as np
 
 from . import solvers
-from .model import MyModel, build_factored_model, build_model, check_factored_kit, model_from_sdpa
+from .model import MyModel, build_factored_model, build_model, check_diag_kit, check_factored_kit, model_from_sdpa
 
 # MOI.TerminationStatus values used by the reference (MOI_wrapper.jl:252-265)
 OPTIMIZE_NOT_CALLED = "OPTIMIZE_NOT_CALLED"
@@ -89,6 +89,9 @@ class Optimizer:
         factors[i][k] may instead be a symmetric msz x msz matrix (SciPy sparse or a 2-D array): that constraint is stored
         as a matrix -- a trace row, a few sparse side constraints among thousands of factored ones (a hybrid block; the
         others stay factors, nothing else is materialised).
+        factors[i][k] may also be a triple (V, d, a): A_i,k+1 = V diag(d) V' + diag(a), a of length msz (V = None, d = [] for a
+        purely diagonal constraint -- the trace row tr X = 1 is (None, [], ones(msz))).  No entry list is formed for it; needs
+        kit = 0, also with cg=True (ValueError otherwise).
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
         if not self.resident:
@@ -111,6 +114,7 @@ class Optimizer:
             model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
             model.factored_cg = bool(cg) and model.factored
             check_factored_kit(model, self.options.get("kit", 0))
+            check_diag_kit(model, self.options.get("kit", 0))
         else:
             A, b, b_const, d_lin, C_lin, max_sense, factors = payload
             self.max_sense = max_sense

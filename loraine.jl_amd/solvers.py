@@ -19,7 +19,7 @@ import scipy.linalg as sla
 import scipy.sparse as sp
 
 from .device import Device
-from .model import MyModel, check_factored_kit
+from .model import MyModel, check_diag_kit, check_factored_kit
 
 # src/Solvers.jl:169-185
 DEFAULT_OPTIONS = {
@@ -105,6 +105,7 @@ class MySolver:
             # of AA in H_alpha, the NumPy host loop multiplies by AA)
             # -- unless the model was loaded with cg=True: then kit = 1 runs from the factors (option cg_factored below)
             check_factored_kit(model, self.kit)
+            check_diag_kit(model, self.kit)
             if not self._resident:
                 raise ValueError("a factored model (load_factored_model) needs the resident solver "
                                  "(Optimizer(resident=True)): the NumPy host loop multiplies by AA")
@@ -129,6 +130,10 @@ class MySolver:
                     self.dev.upload_lowrank(i, khat, V, d)                      # [GPU] one-time
                     if getattr(model, "factored", False) and model.factored_blocks[i]:
                         self.dev.set_factored(i)                                # [GPU] the factors are the data
+                        dg = model.diag[i] if getattr(model, "diag", None) else {}
+                        if dg:                                                  # [GPU] ... and the diagonal parts beside them
+                            rows = sorted(dg)
+                            self.dev.upload_diag(i, rows, np.column_stack([dg[k] for k in rows]))
                 self.lowrank = True
                 if getattr(model, "factored", False):
                     # kit = 1 was checked above: the model allows it.  kit = 0 on a device another solve used: the default
