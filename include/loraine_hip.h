@@ -386,6 +386,17 @@ int lrn_hbm_copy_peak(lrn_ctx* ctx, int64_t bytes, double* gbps);
 int lrn_dbg_gemm(lrn_ctx* ctx, int transA, int transB, int M, int N, int K, double alpha,
                  const double* A, int lda, const double* B, int ldb, double beta, double* C,
                  int ldc, int flags, int ksplit);
+/* One function of csrc/products.hip (or symadd of ipstep.hip) on host operands, on the context's stream.
+ * A, Bm: n x n column-major.  kind 0: pgemm_nt(A, Bm, out0, tri, alpha, Ct = out1 or NULL)
+ *        1: pgemm_nt_sym(A, Bm, out0, alpha, tri)
+ *        2: gemm_nt_sym_ns(A, Bm, scratch, a, T = out0, part) ; *scalar = part[0] + ... + part[npart-1], added on the host in index order
+ *        3: gemm_nt_slabs(A, Bm, out0, alpha) + slabs_to_c_and_ct(out0, out1) ; *scalar = number of slabs the product came back in
+ *        4: prod_slabs(A, Bm, work, alpha, tri) + symadd (scale = a, out = out0, dotp = A, grid = min(1024, tile pairs)) ;
+ *           *scalar = sum of part[] in index order
+ * tri: 0 or one of the four triangular-K flags (64, 128, 1024, 2048).  out0 (and out1 where given) are uploaded before the
+ * call, so an element that no kernel writes comes back as the caller left it.  out1: required by kind 3; scalar: by 2, 3, 4. */
+int lrn_dbg_product(lrn_ctx* ctx, int kind, int n, const double* A, const double* Bm, double alpha, double a, int tri,
+                    double* out0, double* out1, double* scalar);
 /* What lrn_dbg_gemm would launch for the same arguments, decided on the host alone (no context, no device): out6 =
  * { kernel, tile side, grid x, grid z, dynamic LDS bytes, split-K slabs }.  kernel: 0 nothing, 1 / 2 register-staged
  * 64 / 128 tile, 3 direct-to-LDS 128 tile, 4 64-tile DMA pipeline, 5 K-segment, 6 / 7 / 8 K-contiguous 128 / 160 / strip. */

@@ -86,6 +86,8 @@ SIGNATURES = {
     "lrn_xcc_probe": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "lrn_dbg_gemm": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
                                C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "lrn_dbg_product": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                  C.c_void_p, C.c_void_p, PD]),
     "lrn_dbg_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                     C.c_int, C.c_int, PI]),
     "lrn_dbg_schur_chol_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, PI, PI64, PI, PI, PI, PD]),
@@ -97,6 +99,7 @@ SIGNATURES = {
 }
 
 GEMM_TRI_LOWER, GEMM_TRI_UPPER, GEMM_OFFDIAG_X2, GEMM_SQUARE, GEMM_KSEG_TRI, GEMM_SMALL_TILE = 1, 2, 4, 8, 16, 32
+GEMM_KFROM_N, GEMM_KFROM_M, GEMM_KTO_N, GEMM_KTO_M, GEMM_C_MIRROR, GEMM_DYN_MASKS = 64, 128, 1024, 2048, 4096, 131072
 
 _lib = None
 

@@ -3,6 +3,7 @@
 
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
+#include "ops.h"
 #include "schur_plan.h"
 
 using namespace lrn;
@@ -522,6 +523,66 @@ int lrn_dbg_gemm(lrn_ctx* c, int transA, int transB, int M, int N, int K, double
   rc = copy_out(c, C, dC.p, c_el * 8);
   release(dA); release(dB); release(dC); release(dS);
   return rc;
+}
+
+int lrn_dbg_product(lrn_ctx* c, int kind, int n, const double* A, const double* Bm, double alpha, double a, int tri, double* out0,
+                    double* out1, double* scalar) {
+  if (!c || kind < 0 || kind > 4 || n < 1 || !A || !Bm || !out0) return LRN_ERR_ARG;
+  if ((kind == 3 && !out1) || (kind >= 2 && !scalar)) return LRN_ERR_ARG;
+  if (tri != 0 && tri != GEMM_KFROM_M && tri != GEMM_KFROM_N && tri != GEMM_KTO_M && tri != GEMM_KTO_N) return LRN_ERR_ARG;
+  LRN_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t nn8 = (size_t)n * n * 8;
+  const long nt = (n + 31) / 32;
+  DBuf dA, dB, d0, d1, dW, dP;
+  LRN_TRY(ensure(c, dA, nn8));
+  LRN_TRY(ensure(c, dB, nn8));
+  LRN_TRY(ensure(c, d0, nn8));
+  LRN_TRY(copy_in(c, dA.p, A, nn8));
+  LRN_TRY(copy_in(c, dB.p, Bm, nn8));
+  // the results start from what the caller put there: an element no kernel writes comes back as it went in
+  LRN_TRY(copy_in(c, d0.p, out0, nn8));
+  if (out1) {
+    LRN_TRY(ensure(c, d1, nn8));
+    LRN_TRY(copy_in(c, d1.p, out1, nn8));
+  }
+  if (kind == 2 || kind == 4) {
+    LRN_TRY(ensure(c, dW, nn8, true));
+    LRN_TRY(ensure(c, dP, (size_t)(nt * nt + 64) * 8, true));
+  }
+  const double *pA = dA.as<double>(), *pB = dB.as<double>();
+  int npart = 0, nslab = 0;
+  int rc = LRN_OK;
+  if (kind == 0) {
+    rc = pgemm_nt(c, st, n, pA, pB, d0.as<double>(), tri, alpha, out1 ? d1.as<double>() : nullptr);
+  } else if (kind == 1) {
+    rc = pgemm_nt_sym(c, st, n, pA, pB, d0.as<double>(), alpha, tri);
+  } else if (kind == 2) {
+    rc = gemm_nt_sym_ns(st, n, pA, pB, dW.as<double>(), a, d0.as<double>(), dP.as<double>(), &npart);
+  } else if (kind == 3) {
+    SlabSrc src;
+    rc = gemm_nt_slabs(st, n, pA, pB, d0.as<double>(), alpha, &src);
+    if (rc == LRN_OK) slabs_to_c_and_ct(st, src, n, d0.as<double>(), d1.as<double>());
+    nslab = src.n;
+  } else {
+    SlabSrc src;
+    rc = prod_slabs(c, st, n, pA, pB, dW.as<double>(), alpha, tri, &src);
+    npart = (int)std::min<long>(1024, nt * nt);
+    if (rc == LRN_OK) symadd(st, (unsigned)npart, src, n, a, d0.as<double>(), pA, dP.as<double>());
+  }
+  if (rc == LRN_OK && hipGetLastError() != hipSuccess) rc = LRN_ERR_HIP;
+  if (rc == LRN_OK) rc = copy_out(c, out0, d0.p, nn8);
+  if (rc == LRN_OK && out1) rc = copy_out(c, out1, d1.p, nn8);
+  if (rc == LRN_OK && kind == 3) *scalar = (double)nslab;
+  if (rc == LRN_OK && (kind == 2 || kind == 4)) {
+    std::vector<double> part((size_t)npart);
+    rc = copy_out(c, part.data(), dP.p, (size_t)npart * 8);
+    double s = 0.0;
+    for (int i = 0; i < npart; ++i) s += part[i];
+    *scalar = s;
+  }
+  release(dA); release(dB); release(d0); release(d1); release(dW); release(dP);
+  return rc == LRN_OK ? rc : set_error(c, rc, "lrn_dbg_product: kind %d failed", kind);
 }
 
 int lrn_dbg_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, double beta, int ldc, int flags, int ksplit,

@@ -159,6 +159,10 @@ __global__ __launch_bounds__(256) void symadd_kernel(SlabSrc T, int n, double sc
   if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
+void symadd(hipStream_t st, unsigned grid, const SlabSrc& T, int n, double scale, double* out, const double* dotp, double* part) {
+  hipLaunchKernelGGL(symadd_kernel, dim3(grid), dim3(256), 0, st, T, n, scale, out, dotp, part);
+}
+
 __device__ __forceinline__ double block_sum_parts(const double* __restrict__ part, int np, double* sh) {
   double s = 0.0;
   for (int e = threadIdx.x; e < np; e += 256) s += part[e];

@@ -91,6 +91,8 @@ int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y);    // H_DD, the cro
 int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // y[nat(s)] -= sum_i a_si Z_ii
 int aat_to_mat_diag(lrn_ctx* c, LmiBlock& b, const double* x, double* M);    // M_ii -= sum_s x[nat(s)] a_si
 void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I (ipstep.hip)
+// out = scale (T + T') from T or its slabs by `grid` workgroups; dotp: part[0 .. grid) = partial sums of <dotp, out> (ipstep.hip)
+void symadd(hipStream_t st, unsigned grid, const SlabSrc& T, int n, double scale, double* out, const double* dotp, double* part);
 // n x n helpers (prepw.hip)
 void eye_mat(hipStream_t st, double* V, int n);                            // V = I
 void mirror_lower(hipStream_t st, double* A, int n);                       // upper triangle <- lower triangle, in place

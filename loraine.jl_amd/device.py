@@ -361,6 +361,19 @@ class Device:
         self._chk(rc, "lrn_dbg_gemm")
         return Cm
 
+    def dbg_product(self, kind, A, Bm, alpha=1.0, a=0.0, tri=0, want_out1=True):
+        """One function of the n x n product layer (lrn_dbg_product); returns (out0, out1, scalar).  The outputs start as
+        NaN, so an element that no kernel wrote comes back as NaN; out1 is None where it was not asked for."""
+        A = f64(A); Bm = f64(Bm)
+        n = A.shape[0]
+        out0 = np.full((n, n), np.nan, order="F")
+        out1 = np.full((n, n), np.nan, order="F") if (want_out1 and kind in (0, 3)) else None
+        s = C.c_double(np.nan)
+        rc = self.lib.lrn_dbg_product(self.h, int(kind), n, ptr(A), ptr(Bm), float(alpha), float(a), int(tri), ptr(out0),
+                                      ptr(out1), C.byref(s))
+        self._chk(rc, "lrn_dbg_product")
+        return out0, out1, s.value
+
     def dbg_mfma_probe(self, A16x4, B4x16):
         A = np.require(A16x4, dtype=np.float64, requirements=["C"])
         B = np.require(B4x16, dtype=np.float64, requirements=["C"])

@@ -33,6 +33,18 @@ def test_header_symbols_are_exported(lib):
     assert sorted(_capi.SIGNATURES) == names
 
 
+def test_gemm_flag_constants_match_the_enum():
+    """The GEMM flags the tests pass through lrn_dbg_gemm (_capi.py) against the enum of csrc/lrn_common.h."""
+    from loraine_jl_amd import _capi
+    txt = open(os.path.join(ROOT, "loraine.jl_amd", "csrc", "lrn_common.h")).read()
+    enum = {k: int(v) for k, v in re.findall(r"^\s*(GEMM_[A-Z0-9_]+)\s*=\s*(\d+)\s*,", txt, flags=re.M)}
+    names = [n for n in dir(_capi) if n.startswith("GEMM_")]
+    assert {"GEMM_TRI_LOWER", "GEMM_KFROM_N", "GEMM_KFROM_M", "GEMM_KTO_N", "GEMM_KTO_M", "GEMM_C_MIRROR",
+            "GEMM_DYN_MASKS"} <= set(names)
+    for n in names:
+        assert getattr(_capi, n) == enum[n], n
+
+
 def test_version_and_device_count(lib):
     assert lib.lrn_version() >= 100
     assert lib.lrn_device_count() >= 0

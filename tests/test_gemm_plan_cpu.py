@@ -103,3 +103,47 @@ def test_gemm_plan_rejects_more_than_64_splits():
     rc, got = _plan((0, 1, 300, 200, 1000, 300, 200, 300, 0, 0, 65))
     assert rc == -1            # LRN_ERR_ARG
     assert got[0] == 0         # nothing planned
+
+
+# ---- the shapes of tests/test_gpu_products.py
+KFROM_N, KFROM_M, KTO_N, KTO_M, C_MIRROR, DYN_MASKS = 64, 128, 1024, 2048, 4096, 131072
+K_RANGE_FLAG_SETS = [KFROM_M, KTO_M, KFROM_N, KTO_N, KFROM_N | TRI_LOWER | C_MIRROR, KTO_N | TRI_LOWER | C_MIRROR,
+                     KFROM_M | TRI_LOWER]
+
+
+@pytest.mark.parametrize("dyn", [0, DYN_MASKS])
+@pytest.mark.parametrize("flags", K_RANGE_FLAG_SETS)
+@pytest.mark.parametrize("n,kernel", [(300, LDS), (385, LDS), (400, LDS), (130, REG128)])
+def test_k_range_products_take_the_128_tile(n, kernel, flags, dyn):
+    """Any K-range flag forces the 128 tile whatever the size: the direct-to-LDS kernel from K = 256 on, below it the
+    register-staged one with its own K-range code -- the GPU file covers both."""
+    rc, got = _plan((0, 1, n, n, n, n, n, n, 0, flags | dyn, 1))
+    assert rc == 0
+    assert got[:2] == (kernel, 128)
+    assert got[5] == 1
+
+
+@pytest.mark.parametrize("flags", [KFROM_M, KTO_M, KFROM_M | DYN_MASKS, KTO_M | DYN_MASKS])
+def test_k_range_rectangular_product_takes_the_128_tile(flags):
+    rc, got = _plan((0, 1, 300, 140, 300, 300, 140, 300, 0, flags, 1))
+    assert rc == 0
+    assert got[:2] == (LDS, 128)
+
+
+# split factor of a square NT product of side n: (lower 64-tiles alone, full product) -- auto_split_factor restated by hand
+SPLIT_FACTORS = {255: (1, 1), 256: (2, 2), 300: (3, 3), 385: (4, 4), 481: (5, 4), 650: (6, 4), 1100: (4, 3), 1300: (2, 1)}
+
+
+@pytest.mark.parametrize("n", sorted(SPLIT_FACTORS))
+def test_split_factors_of_the_product_layer_sizes(n):
+    got = []
+    for flags in (TRI_LOWER, 0):
+        rc, plan = _plan((0, 1, n, n, n, n, n, n, 0.0, flags, 1))
+        assert rc == 0
+        got.append(plan[5])
+    assert tuple(got) == SPLIT_FACTORS[n]
+
+
+def test_split_factors_cover_every_value():
+    assert {v[0] for v in SPLIT_FACTORS.values()} == {1, 2, 3, 4, 5, 6}
+    assert {v[1] for v in SPLIT_FACTORS.values()} == {1, 2, 3, 4}
