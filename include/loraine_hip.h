@@ -77,7 +77,9 @@ int lrn_upload_lowrank(lrn_ctx* ctx, int ilmi, int khat, const int64_t* V_colptr
  * a hybrid block is returned).  on = 0 takes the declaration back.
  * lrn_get_count: "op_factored" / "op_dense" / "op_sparse" count the operator calls by route, "op_dense_tri" /
  * "op_dense_stream" / "op_dense_scalar" the passes over dense constraint data by tier (column tails of symmetric data /
- * 16-byte loads over both triangles / one element per lane; the tier is decided when the model is uploaded); "device_bytes",
+ * 16-byte loads over both triangles / one element per lane; the tier is decided when the model is uploaded);
+ * "op_sparse_pattern" counts the blocks the CG operator took through the pattern-restricted route (once per block and call
+ * of lrn_matvec / lrn_matvec_partial), "op_wmw_pattern" the right-hand sides AA vec(W M W) formed on the pattern; "device_bytes",
  * "device_bytes_peak" (device memory of this context now / at most) and "adense_bytes" (dense constraint slabs) are state. */
 int lrn_set_factored(lrn_ctx* ctx, int ilmi, int on);
 /* Diagonal parts of a factored block (after lrn_set_factored(ilmi, 1)): constraint rows[s] (0-based, as k of

@@ -805,6 +805,7 @@ bool use_sparse_matvec(const lrn_ctx* c, const LmiBlock& b) {
 static int matvec_sparse_block(lrn_ctx* c, LmiBlock& b, const double* x, double* y, int q_lo, int q_hi, bool mirror) {
   const int m = b.msz;
   hipStream_t st = c->stream;
+  c->counts["op_sparse_pattern"] += 1;
   LRN_TRY(ensure(c, c->m1, (size_t)m * m * 8));
   double* N = c->m1.as<double>();
   const bool small = m < 1500;        // W and N sit in L2: one wave per stored entry (see sp_dot_wave_kernel)
@@ -881,6 +882,7 @@ bool wmw_pattern_ok(const lrn_ctx* c, const LmiBlock& b) {
 
 int aa_times_wmw_pattern(lrn_ctx* c, LmiBlock& b, const double* M, double* N, double* y) {
   const int m = b.msz;
+  c->counts["op_wmw_pattern"] += 1;
   LRN_TRY(pgemm_nt(c, c->stream, m, M, b.W.as<double>(), N));                   // N = M W' = M W
   hipLaunchKernelGGL(sp_dot_wave_kernel, dim3((unsigned)((b.ncq + 3) / 4)), dim3(256), 0, c->stream, b.cq_q.as<long>(),
                      b.pc_t.as<int>(), b.ncq, b.W.as<double>(), N, m, 0, m, 1, b.Zs.as<double>());

@@ -312,6 +312,13 @@ class Device:
         self._chk(self.lib.lrn_matvec(self.h, ptr(x), ptr(y)), "lrn_matvec")
         return y
 
+    def matvec_partial(self, x):
+        """This rank's share of the operator under set_shard(rank, world): the ranks' vectors add up to matvec(x)."""
+        x = f64(x)
+        y = np.zeros(self.nvar)
+        self._chk(self.lib.lrn_matvec_partial(self.h, ptr(x), ptr(y)), "lrn_matvec_partial")
+        return y
+
     def prec_setup(self, prec, erank, aamat):
         info = C.c_int(0)
         self._chk(self.lib.lrn_prec_setup(self.h, int(prec), int(erank), int(aamat), C.byref(info)),

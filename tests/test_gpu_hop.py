@@ -45,16 +45,24 @@ def test_operator_by_H_by_pattern_and_by_gemms_agree(dev, case):
         model = _lowrank(300, int(case[7:]), 5)
     m = int(model.msizes[0])
     W, Gm = _scaling(m, rng)
-    dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes)
+    # every constraint stored by its entries (no dense slot: thetaG11's arrow constraint too), or there is no pattern route
+    dev.set_option("dense_threshold", int(np.diff(model.AA[0].tocsr().indptr).max()) + 1)
+    try:
+        dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes)
+    finally:
+        dev.set_option("dense_threshold", -1)
     dev.set_scaling(0, W, Gm)
     xs = [rng.standard_normal(model.n), np.eye(model.n)[:, model.n - 1].copy(), np.ones(model.n)]
     try:
         for x in xs:
             dev.set_option("matvec_h", 1)
             dev.set_option("matvec_sparse", 1)
+            n0 = dev.count("op_sparse_pattern")
             dense = dev.matvec(x)
+            assert dev.count("op_sparse_pattern") == n0
             dev.set_option("matvec_sparse", 2)
             sparse = dev.matvec(x)
+            assert dev.count("op_sparse_pattern") == n0 + 1
             dev.set_option("matvec_h", 2)
             n0 = dev.count("hop_matvec")
             byh = dev.matvec(x)
@@ -264,12 +272,14 @@ def test_right_hand_sides_through_the_pattern_of_the_constraints(dev):
     out = {}
     for forced in (0, 1):
         dev.set_option("wmw_pattern_min", 8 if forced else 1500)
+        dev.reset_timing()                                  # (counters from zero)
         try:
             s, ha = resident.load(model, dict(kit=1, preconditioner=2, erank=3, verb=0, eDIMACS=1e-7, tol_cg_min=1e-10, tol_cg=1e-10), device=dev)
             s.solve(ha)
         finally:
             dev.set_option("wmw_pattern_min", 1500)
         assert s.status == 1
+        assert (dev.count("op_wmw_pattern") > 0) == bool(forced)
         out[forced] = [t["primal_obj"] for t in s.trace]
     assert len(out[0]) == len(out[1])
     for a, b in zip(out[0], out[1]):

@@ -367,21 +367,32 @@ def test_sparse_pattern_matvec_matches_gemm_matvec(dev, case):
     m = int(model.msizes[0])
     Gm = rng.standard_normal((m, m)) / np.sqrt(m) + np.diag(np.exp(rng.uniform(-2, 2, m)))
     W = Gm @ Gm.T
-    dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes)
+    # every constraint stored by its entries (no dense slot: thetaG11's arrow constraint too), or there is no pattern route
+    dev.set_option("dense_threshold", int(np.diff(model.AA[0].tocsr().indptr).max()) + 1)
+    try:
+        dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes)
+    finally:
+        dev.set_option("dense_threshold", -1)
     dev.set_scaling(0, W, Gm)
     x = rng.standard_normal(model.n)
     try:
+        dev.set_option("matvec_h", 1)
         dev.set_option("matvec_sparse", 1)
+        n0 = dev.count("op_sparse_pattern")
         dense = dev.matvec(x)
+        assert dev.count("op_sparse_pattern") == n0            # the two products ...
         dev.set_option("matvec_sparse", 2)
         sparse = dev.matvec(x)
+        assert dev.count("op_sparse_pattern") == n0 + 1        # ... and the pattern route, not the products again
         acc = np.zeros(model.n)
         for r in range(3):
             dev.set_shard(r, 3)
             part = np.zeros(model.n)
             dev._chk(dev.lib.lrn_matvec_partial(dev.h, ptr(x), ptr(part)), "lrn_matvec_partial")
             acc += part
+        assert dev.count("op_sparse_pattern") == n0 + 4
     finally:
+        dev.set_option("matvec_h", 0)
         dev.set_shard(0, 1)
         dev.set_option("matvec_sparse", 0)
     Mx = model.AA[0].T @ x
