@@ -93,7 +93,7 @@ int lrn_set_factored(lrn_ctx* ctx, int ilmi, int on);
  * a_k' diag(W A_s W) for the stored rows of a hybrid block -- dense products with one operand squared entrywise, no entry list
  * (option "diag_sq_mfma"), fixed order, no atomics.  With diagonal rows in any block lrn_matvec, lrn_matvec_partial,
  * lrn_prec_setup, lrn_prec_apply and lrn_pcg return LRN_ERR_STATE also under "cg_factored" = 1 (ts of H_alpha does not hold
- * the diagonal parts), and mode 1 returns LRN_ERR_STATE under world > 1.
+ * the diagonal parts) -- unless option "cg_diag" = 1 is set beside it --, and mode 1 returns LRN_ERR_STATE under world > 1.
  * lrn_get_count: "diag_rows" (state: diagonal rows of all blocks), "op_diag" (operator calls that added a diagonal part),
  * "schur_diag" (assemblies of a block with diagonal rows), "diag_sq_rows" / "diag_sq_mfma" (squared-operand products by form),
  * "diag_stored_cross" (cross terms with stored rows); timing keys under "profile": "diag_dd", "diag_cross", "diag_stored". */
@@ -183,6 +183,11 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * mode 1, ts of H_alpha comes from the factors (P = L' Vd, T = Vd' Um, one transposing pass) and, for the stored constraints
  * of a hybrid block, from their entries on a compact npos_nz x msz buffer.  lrn_matvec_partial and every call under world > 1
  * keep returning LRN_ERR_STATE for a factored block: the factor routes are not sharded and were run on one GPU only),
+ * "cg_diag" (0, default: a factored block with diagonal parts, lrn_upload_diag, is refused by these entry points whatever
+ * "cg_factored" says; 1, together with "cg_factored" = 1: accepted on one GPU -- the operators carry the diagonal parts as they
+ * do for kit = 0, and lrn_prec_setup adds ts[nat(s), a msz + r] -= sum_i a_si Um[i, a] L[i, r] / sqrt(d) for every diagonal row s
+ * to the factor part of ts, one FP64 MFMA tile product; lrn_matvec_partial and world > 1 stay refused; counter
+ * "prec_ts_diag_rows": diagonal rows added in the LAST lrn_prec_setup),
  * "hop_max_mb" (budget of the assembled-matrix operator in MiB: when nvar^2 * 8 bytes exceed it H is not assembled, even under
  * "matvec_h" = 2, and the matrix-free operator runs; -1, default: no limit for a model without a factored block, and for one
  * with a factored block the free device memory minus the mode-1 workspace), "fac_op_scaled" (under "cg_factored", pure

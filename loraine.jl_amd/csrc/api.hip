@@ -123,6 +123,7 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
     c->hop_version = -1;
   }
   else if (!strcmp(key, "cg_factored")) { c->opt.cg_factored = value != 0.0 ? 1 : 0; c->hop_version = -1; }
+  else if (!strcmp(key, "cg_diag")) { c->opt.cg_diag = value != 0.0 ? 1 : 0; c->hop_version = -1; }
   else if (!strcmp(key, "hop_max_mb")) { c->opt.hop_max_mb = value < 0.0 ? -1.0 : value; c->hop_version = -1; }
   else if (!strcmp(key, "fac_op_scaled")) { c->opt.fac_op_scaled = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }
   else if (!strcmp(key, "fac_quadform")) { c->opt.fac_quadform = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }

@@ -406,6 +406,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
   P->has_dense = false;
   c->counts["prec_ts_factored"] = 0;
   c->counts["prec_ts_stored_rows"] = 0;
+  c->counts["prec_ts_diag_rows"] = 0;
   const int n = c->nvar;
   hipStream_t st = c->stream;
   if (kind == 0) return LRN_OK;
@@ -511,6 +512,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     int col0 = 0;
     long ts_factored = 0;      // blocks whose part of ts came from the factors ("prec_ts_factored", of the LAST setup)
     long ts_stored = 0;        // rows of ts filled from the stored entries of hybrid blocks ("prec_ts_stored_rows", ditto)
+    long ts_diag_rows = 0;     // rows of ts that got the term of their diagonal part ("prec_ts_diag_rows", ditto; option "cg_diag")
     for (int il = 0; il < c->nlmi; ++il) {
       LmiBlock& b = c->lmi[il];
       const int m = b.msz, k = erank;
@@ -570,7 +572,9 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
         gp.B = b.Vd.as<double>(); gp.sBk = 1; gp.sBn = m;
         gp.C = c->BG.as<double>(); gp.sCm = 1; gp.sCn = m;
         gp.M = m; gp.N = (int)R; gp.K = m;
+        if (c->opt.profile_ops) tic(c);      // (measurement, tools/cg_diag_times.py: this product beside the diagonal-row kernel)
         LRN_TRY(gemm(st, gp));
+        if (c->opt.profile_ops) toc(c, "prec_ts_p");
         GemmDesc gt;     // T = Vd' Um, R x k
         gt.A = b.Vd.as<double>(); gt.sAm = m; gt.sAk = 1;
         gt.B = Um; gt.sBk = 1; gt.sBn = m;
@@ -610,6 +614,14 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
           }
           ts_stored += np;
         }
+        if (b.factored && b.dg_n > 0) {
+          // diagonal parts (option "cg_diag": lrn_prec_setup refused the block without it): -(L' diag(a_s) u_a)' / sqrt(d_j) added
+          // to the rows fac_ts_kernel wrote the factor part of -- no stored row among them
+          if (c->opt.profile_ops) tic(c);
+          LRN_TRY(ts_diag(c, b, Zf, Um, k, P->d.as<double>(), P->ts.as<double>() + (size_t)col0 * n));
+          if (c->opt.profile_ops) toc(c, "prec_ts_diag");
+          ts_diag_rows += b.dg_n;
+        }
         col0 += k * m;
         continue;
       }
@@ -636,6 +648,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     }
     c->counts["prec_ts_factored"] = ts_factored;
     c->counts["prec_ts_stored_rows"] = ts_stored;
+    c->counts["prec_ts_diag_rows"] = ts_diag_rows;
     if (P->has_LD)      // ts = L_D^-1 t   (the reference: AAAATtau \ t, Solvers.jl:767)
       LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, false, P->ts.as<double>(), ksz, n,
                               P->workD.as<double>() + chol_work_doubles(n)));
@@ -936,16 +949,23 @@ using namespace lrn;
 // the factors.  One GPU only (partial: lrn_matvec_partial; world > 1: any call) -- the factor routes are not sharded
 // ... and not for a block with diagonal parts (lrn_upload_diag), whatever cg_factored says: ts of H_alpha is built from the
 // factors and the stored rows and would silently miss them
-static int no_diag(lrn_ctx* c, const char* what) {
+// ... unless option "cg_diag" is set beside cg_factored: then prec_setup adds the diagonal-row term to ts (diagops.hip::ts_diag);
+// the operators carry the diagonal parts anyway.  One GPU and not lrn_matvec_partial, as for cg_factored
+static int no_diag(lrn_ctx* c, const char* what, bool partial = false) {
   for (size_t il = 0; il < c->lmi.size(); ++il)
-    if (c->lmi[il].factored && c->lmi[il].dg_n > 0)
+    if (c->lmi[il].factored && c->lmi[il].dg_n > 0) {
+      if (c->opt.cg_diag != 0 && c->opt.cg_factored != 0 && (partial || c->world > 1))
+        return set_error(c, LRN_ERR_STATE, "%s: block %d is factored with diagonal parts (lrn_upload_diag): option cg_diag runs on "
+                                           "one GPU (world = %d) and not through lrn_matvec_partial", what, (int)il, c->world);
+      if (cg_diag_on(c)) return LRN_OK;
       return set_error(c, LRN_ERR_STATE, "%s: block %d is factored with diagonal parts (lrn_upload_diag): the CG path does not "
                                          "hold them, such a model is solved with kit = 0", what, (int)il);
+    }
   return LRN_OK;
 }
 
 static int no_factored(lrn_ctx* c, const char* what, bool partial = false) {
-  LRN_TRY(no_diag(c, what));
+  LRN_TRY(no_diag(c, what, partial));
   for (size_t il = 0; il < c->lmi.size(); ++il)
     if (c->lmi[il].factored) {
       if (c->opt.cg_factored != 0 && (partial || c->world > 1))

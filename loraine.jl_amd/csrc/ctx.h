@@ -165,6 +165,9 @@ struct LrnOptions {
                                   // of the H_alpha setup.  Ignored with world > 1
   int cg_factored = 0;            // CG path (lrn_matvec, lrn_prec_setup, lrn_prec_apply, lrn_pcg) on factored blocks: 0 refused (the
                                   // state error of cgops.hip::no_factored), 1 accepted on one GPU -- pure, hybrid and mixed models
+  int cg_diag = 0;                // ... on factored blocks WITH diagonal parts (lrn_upload_diag): 0 refused whatever cg_factored says (the
+                                  // state error of cgops.hip::no_diag), 1 accepted where cg_factored accepts the block -- ts of
+                                  // H_alpha gets the diagonal-row term (diagops.hip::ts_diag); lrn_matvec_partial stays refused
   double hop_max_mb = -1.0;       // budget of the assembled-matrix operator in MiB: H (nvar^2 * 8 bytes) above it is not assembled
                                   // ("hop_over_budget").  -1: none for a model without a factored block; with one, the free device
                                   // memory minus the mode-1 workspace
@@ -298,6 +301,8 @@ bool cg_lowrank_operator(const lrn_ctx* c, const LmiBlock& b);   // matrix-free 
 bool cg_lowrank_ts(const lrn_ctx* c, const LmiBlock& b, int erank);   // ts of H_alpha for this block from the factors?
 // option "cg_factored": the CG path accepts factored blocks (one GPU only)
 inline bool cg_factored_on(const lrn_ctx* c) { return c->opt.cg_factored != 0 && c->world <= 1; }
+// option "cg_diag": ... and factored blocks with diagonal parts among them
+inline bool cg_diag_on(const lrn_ctx* c) { return c->opt.cg_diag != 0 && cg_factored_on(c); }
 bool fac_op_scaled_on(const lrn_ctx* c, const LmiBlock& b);      // hop.hip: operator of this pure factored block through Y = W Vd?
 bool fac_quadform_on(const lrn_ctx* c, const LmiBlock& b);       // hop.hip: AA vec(Z) of this factored block by the fused kernel?
 // facops.hip: out[nat(h)] -= sum_p w[h kh + p] v_c' Z v_c over the kh factor columns c = h kh + p of every constraint

@@ -30,6 +30,9 @@
 //     group lies on kh neighbouring lanes of one accumulator block and is summed by an xor butterfly of log2 kh steps; the
 //     lane with c % kh == 0 writes D[s, c / kh].
 // No atomics, fixed order in both forms: two calls give the same bits.  The forms differ from each other in rounding.
+//
+// The CG path (option "cg_diag"): the operators above carry the diagonal parts; ts of H_alpha gets their
+// term from ts_diag_mfma_kernel at the end of this file, a sibling of the MFMA form with a scaled instead of a squared operand.
 #include <algorithm>
 
 #include "../../include/loraine_hip.h"
@@ -373,6 +376,112 @@ int aat_to_mat_diag(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
                      b.dg_nat.as<int>(), b.dg_n, x, m, c->dgP.as<double>());
   hipLaunchKernelGGL(diag_aat_apply_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, c->dgP.as<double>(), nch, m, M);
   c->counts["op_diag"] += 1;
+  return LRN_OK;
+}
+
+// ---------------------------------------------------------------- ts of H_alpha (option "cg_diag", cgops.hip::prec_setup)
+// The rows of ts that belong to diagonal rows miss  -(L' diag(a_s) u_a)[r] / sqrt(d_j)  after fac_ts_kernel (which holds the
+// factor part, a zero for a purely diagonal constraint).  With L the Cholesky factor of 2 W - Um Um' (lower, upper triangle
+// zeroed, element (i, r) at L[i + r m]) and u_a column a of Um,
+//     ts[nat(s), a m + r] += -(1 / sqrt(d[nat(s)])) sum_{i >= r} Ad[i, s] Um[i, a] L[i, r]
+// is a dense product with both operands K-contiguous (column r of L, column s of Ad) -- the tile of diag_sq_mfma_kernel,
+// written out a second time: with the K step in a shared inline function the compiler orders the address arithmetic of
+// diag_sq_mfma_kernel differently (one instruction more), and that kernel's code is to stay what it is.  The differences:
+//   operands: As[r][k] = L[k0 + k, r0 + r],  Bs[s][k] = Ad[k0 + k, s0 + s] Um[k0 + k, a]  (scaled as it is staged, where diag_sq
+//     squares; one value of Um per thread and K step, its staging column k is fixed); blockIdx.x picks 64 columns r of L,
+//     blockIdx.y 64 diagonal rows s, blockIdx.z the eigenvector a
+//   triangular K range: column r of L is zero above row r, so the tile of columns r0 .. r0 + 63 starts at k0 = r0 & ~15 (r0 is a
+//     multiple of 64: k0 = r0) and a tile with r0 >= m does not exist; inside the first K steps the zeros of L do the masking
+//   transposed store: ts is contiguous along its rows j, so the DIAGONAL ROWS are the B operand -- the sixteen ci lanes of an
+//     accumulator block run over s.  A store instruction writes, per register, 4 (kq) x 16 (ci) elements: sixteen lanes one
+//     run of ts column a m + r at rows nat(s) .. -- 128 contiguous bytes where the diagonal rows are consecutive constraints --
+//     and the four kq groups four neighbouring columns.  No LDS transpose
+//   accumulating epilogue: scaled by -1 / sqrt(d[nat(s)]) and ADDED to what fac_ts_kernel left; diagonal rows are no stored
+//     rows (lrn_upload_diag), every element of ts has one writer, no atomics: two setups give the same bits
+__global__ __launch_bounds__(256) void ts_diag_mfma_kernel(const double* __restrict__ Lf, const double* __restrict__ Ad, int ns,
+                                                           const double* __restrict__ Um, const int* __restrict__ nat,
+                                                           const double* __restrict__ d, int m, int nvar,
+                                                           double* __restrict__ ts) {
+  __shared__ double As[DG_T * DG_LD];
+  __shared__ double Bs[DG_T * DG_LD];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wr = wv >> 1, wc = wv & 1;
+  const int ci = lane & 15, kq = lane >> 4;
+  const int r0 = blockIdx.x * DG_T;
+  const int s0 = blockIdx.y * DG_T;
+  const double* __restrict__ ua = Um + (long)blockIdx.z * m;
+  dg_v4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = dg_v4{0.0, 0.0, 0.0, 0.0};
+  // staging map of both operands: thread (k = t & 15, row = (t >> 4) + 16 pass)
+  const int vk = t & 15, vr = t >> 4;
+  double areg[4], breg[4], ureg;
+  auto fetch = [&](int k0) {
+    const bool kin = k0 + vk < m;
+    ureg = kin ? ua[k0 + vk] : 0.0;
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      const int r = r0 + vr + 16 * ps;
+      const int s = s0 + vr + 16 * ps;
+      areg[ps] = (kin && r < m) ? Lf[(long)(k0 + vk) + (long)r * m] : 0.0;
+      breg[ps] = (kin && s < ns) ? Ad[(long)(k0 + vk) + (long)s * m] : 0.0;
+    }
+  };
+  const int kbeg = r0 & ~(DG_K - 1);         // rows of L above r0 are zero in every column of the tile
+  fetch(kbeg);
+  for (int k0 = kbeg; k0 < m; k0 += DG_K) {
+    __syncthreads();                       // the waves are done with the previous step's tiles
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      As[(vr + 16 * ps) * DG_LD + vk] = areg[ps];
+      Bs[(vr + 16 * ps) * DG_LD + vk] = breg[ps] * ureg;
+    }
+    __syncthreads();
+    if (k0 + DG_K < m) fetch(k0 + DG_K);
+#pragma unroll
+    for (int ks = 0; ks < DG_K / 4; ++ks) {
+      const int k = 4 * ks + kq;
+      const double a0 = As[(32 * wr + ci) * DG_LD + k];
+      const double a1 = As[(32 * wr + 16 + ci) * DG_LD + k];
+      const double b0 = Bs[(32 * wc + ci) * DG_LD + k];
+      const double b1 = Bs[(32 * wc + 16 + ci) * DG_LD + k];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+  }
+  // element (column r0 + 32 wr + 16 ib + kq + 4 q of L, diagonal row s0 + 32 wc + 16 jb + ci)
+#pragma unroll
+  for (int jb = 0; jb < 2; ++jb) {
+    const int s = s0 + 32 * wc + 16 * jb + ci;
+    if (s >= ns) continue;
+    const int j = nat[s];
+    const double sc = -1.0 / sqrt(d[j]);
+    double* __restrict__ out = ts + ((long)blockIdx.z * m) * nvar + j;
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = r0 + 32 * wr + 16 * ib + kq + 4 * q;
+        if (r < m) out[(long)r * nvar] += sc * acc[ib][jb][q];
+      }
+  }
+}
+
+// ts (the block's nvar x erank msz part, column 0 = its first) += the diagonal-row term; L = chol(2 W - Um Um') with a zeroed
+// upper triangle, Um msz x erank, d the nvar scalings of H_alpha.  One form
+int ts_diag(lrn_ctx* c, LmiBlock& b, const double* Lf, const double* Um, int erank, const double* d, double* ts) {
+  const int m = b.msz, ns = b.dg_n;
+  if (ns <= 0 || erank <= 0) return LRN_OK;
+  const long tx = (m + DG_T - 1) / DG_T, ty = (ns + DG_T - 1) / DG_T;
+  if (ty > 65535 || erank > 65535) return set_error(c, LRN_ERR_ARG, "ts_diag: %ld row tiles, erank %d", ty, erank);
+  hipLaunchKernelGGL(ts_diag_mfma_kernel, dim3((unsigned)tx, (unsigned)ty, (unsigned)erank), dim3(256), 0, c->stream, Lf,
+                     b.dg_a.as<double>(), ns, Um, b.dg_nat.as<int>(), d, m, c->nvar, ts);
+  c->counts["ts_diag_mfma"] += 1;
   return LRN_OK;
 }
 

@@ -247,6 +247,10 @@ static double est_operator_block_s(const lrn_ctx* c, const LmiBlock& b, bool fac
     // hybrid block: its stored rows on top, twice (mat(AA' x) and AA vec(.)) -- the sparse tier at the pattern rate, the
     // dense slots as one pass over the slabs each
     if (b.hybrid()) t += 2.0 * ((double)b.nent * 1.43e-12 + (double)b.nd * m * m * 8.0 / 6.0e12) + 20e-6;
+    // diagonal parts (option "cg_diag"): the two passes over Ad, dg_n x msz doubles each, three launches.  Section 16 measured
+    // them inside aa_times / aat_to_mat only (no difference from the pure block within the spread, 4000 rows included): the
+    // rate is the stream rate of the stored rows above, not a new measurement
+    if (b.factored && b.dg_n > 0) t += 2.0 * (double)b.dg_n * m * 8.0 / 6.0e12 + 15e-6;
     return t;
   }
   if (use_sparse_matvec(c, b))
@@ -315,6 +319,16 @@ static double est_assemble_s(const lrn_ctx* c, int mode) {
       // U = G' Vd and the blocked square of U' U on its lower triangle (section 10: 1.28e11 flop in 3.78 ms)
       const double R = n * b.lr_khat;
       t += (2.0 * R * m * m + 0.5 * R * R * m) / 3.4e13;
+      if (b.factored && b.dg_n > 0) {
+        // diagonal parts (assemble_diag), at the rates section 16 MEASURED at msz 2000 / nvar 4000 / khat 2 / 4000 rows -- those
+        // measurements, not new ones: C = Ad' (Y o Y), 2 dg_n m R = 128 GFLOP in 2.8 ms; H_DD = the squared product and the
+        // lower tiles of P Ad, 2 dg_n m^2 + dg_n^2 m = 64 GFLOP in 1.6 ms; Y = W Vd of a pure block at the rate of the hybrid
+        // term below (a hybrid block pays it there); four launches and the scatters
+        const double ns = b.dg_n;
+        t += 2.0 * ns * m * R / (1.28e11 / 2.8e-3) + (2.0 * ns * m * m + ns * ns * m) / (6.4e10 / 1.6e-3) + 40e-6;
+        if (!b.hybrid()) t += 2.0 * R * m * m / 3.4e13;
+        else t += (double)b.nd * 2.0 * m * m * m / 3.4e13 + 2.0 * (double)b.npos_nz * m * ns / 3.4e13;      // t_s of the dense slots, T Ad
+      }
       if (!b.hybrid()) continue;
       // hybrid: Y = W Vd once more when G exists, the cross terms -- nnz(A_s) R multiply-adds per stored constraint at the
       // pair rate below, one product A_s Y per dense slot -- and H_SS over the stored positions by the mode-0 terms
@@ -363,9 +377,22 @@ static double hop_budget_bytes(const lrn_ctx* c) {
   double need = 0.0;
   for (const auto& b : c->lmi) {
     const double mr = (double)b.msz * (double)c->nvar * b.lr_khat * 8.0;
-    need = std::max(need, mr * (b.hybrid() ? (b.nd > 0 ? 3.0 : 2.0) : 1.0));
+    double w = mr * (b.hybrid() ? (b.nd > 0 ? 3.0 : 2.0) : 1.0);
+    if (b.factored && b.dg_n > 0) {
+      // the mode-1 workspace of assemble_diag (option "cg_diag"): Y of a pure block too, P (dg_n x msz), H_DD (dg_n^2), C (dg_n x
+      // nvar), and T, T' Ad of the stored rows
+      const double ns = b.dg_n, nst = b.npos_nz;
+      if (!b.hybrid()) w += mr;
+      w += (ns * b.msz + ns * ns + ns * c->nvar + nst * b.msz + nst * ns) * 8.0;
+    }
+    need = std::max(need, w);
   }
-  const double held = (double)c->H.bytes + (double)c->BG.bytes + (double)c->facY.bytes + (double)c->P.bytes;
+  double held = (double)c->H.bytes + (double)c->BG.bytes + (double)c->facY.bytes + (double)c->P.bytes;
+  for (const auto& b : c->lmi)
+    if (b.factored && b.dg_n > 0) {      // (a model without diagonal rows does not reuse these: its budget stays what it was)
+      held += (double)c->dgP.bytes + (double)c->dgC.bytes + (double)c->dgH.bytes + (double)c->dgT.bytes + (double)c->dgTA.bytes;
+      break;
+    }
   return (double)fr + held - need;
 }
 

@@ -90,6 +90,8 @@ int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);
 int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y);    // H_DD, the cross terms with the factors (Y) and with the stored rows
 int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // y[nat(s)] -= sum_i a_si Z_ii
 int aat_to_mat_diag(lrn_ctx* c, LmiBlock& b, const double* x, double* M);    // M_ii -= sum_s x[nat(s)] a_si
+// ts of H_alpha (option "cg_diag"): ts[nat(s), a m + r] -= sum_i a_si Um[i, a] L[i, r] / sqrt(d[nat(s)]), added to the factor part
+int ts_diag(lrn_ctx* c, LmiBlock& b, const double* Lf, const double* Um, int erank, const double* d, double* ts);
 void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I (ipstep.hip)
 // out = scale (T + T') from T or its slabs by `grid` workgroups; dotp: part[0 .. grid) = partial sums of <dotp, out> (ipstep.hip)
 void symadd(hipStream_t st, unsigned grid, const SlabSrc& T, int n, double scale, double* out, const double* dotp, double* part);

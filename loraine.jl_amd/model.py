@@ -47,6 +47,9 @@ class MyModel:
     # Optimizer.load_factored_model(..., cg=True): the CG path (kit = 1) is allowed on this factored model -- the solver sets
     # the library option cg_factored = 1 (operator in factor form or through H of mode 1, ts of H_alpha from the factors)
     factored_cg: bool = False
+    # Optimizer.load_factored_model(..., cg="diag"): ... also when factored blocks carry diagonal parts (`diag` below) -- the solver
+    # sets the library option cg_diag = 1 beside cg_factored (ts of H_alpha gets the term of the diagonal rows)
+    factored_cg_diag: bool = False
     # diagonal parts of factored blocks: diag[i] = {k: a (length m_i)} -- constraint k (0-based) of block i is
     # diag(a) + V diag(d) V' with its factors in `lowrank` (none for a purely diagonal constraint, e.g. a trace row).  {} for a
     # block without them and for a materialised block, whose entries hold the diagonal
@@ -63,7 +66,10 @@ def check_factored_kit(model, kit):
 
 def check_diag_kit(model, kit):
     """kit = 1 against a factored model with diagonal parts, before any device exists: the CG path (also under
-    load_factored_model(..., cg=True)) builds ts of H_alpha from the factors and the stored rows and would miss them."""
+    load_factored_model(..., cg=True)) builds ts of H_alpha from the factors and the stored rows and would miss them -- unless the
+    model was loaded with cg="diag" (factored_cg_diag): then the library adds their term (option cg_diag)."""
+    if getattr(model, "factored_cg_diag", False):
+        return
     if int(kit) != 0 and getattr(model, "factored", False) and any(getattr(model, "diag", None) or []):
         raise ValueError("a factored model with diagonal parts (a constraint given as (V, d, a)) needs kit = 0: the CG path "
                          "does not hold the diagonal parts")

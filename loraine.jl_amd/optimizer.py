@@ -91,14 +91,18 @@ class Optimizer:
         others stay factors, nothing else is materialised).
         factors[i][k] may also be a triple (V, d, a): A_i,k+1 = V diag(d) V' + diag(a), a of length msz (V = None, d = [] for a
         purely diagonal constraint -- the trace row tr X = 1 is (None, [], ones(msz))).  No entry list is formed for it; needs
-        kit = 0, also with cg=True (ValueError otherwise).
+        kit = 0, also with cg=True (ValueError otherwise).  cg="diag" is cg=True and admits kit = 1 on such a model as well
+        (opt-in: library option cg_diag beside cg_factored -- ts of H_alpha gets the term of the diagonal parts); one GPU only.
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
         if not self.resident:
             raise ValueError("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
                              "multiplies by AA")
+        cg_diag = isinstance(cg, str) and cg == "diag"
+        if isinstance(cg, str) and not cg_diag:
+            raise ValueError(f"load_factored_model: cg is False, True or \"diag\", not {cg!r}")
         self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
-                                      int(factored_form), bool(cg)))
+                                      int(factored_form), cg_diag, bool(cg)))
         return self
 
     def _copy_to(self):
@@ -109,10 +113,11 @@ class Optimizer:
             model = model_from_sdpa(payload, datarank=drank, kappa=kappa)
             self.max_sense = False
         elif kind == "factored":
-            F0, factors, b, b_const, d_lin, C_lin, max_sense, form, cg = payload
+            F0, factors, b, b_const, d_lin, C_lin, max_sense, form, cg_diag, cg = payload
             self.max_sense = max_sense
             model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
             model.factored_cg = bool(cg) and model.factored
+            model.factored_cg_diag = cg_diag and model.factored
             check_factored_kit(model, self.options.get("kit", 0))
             check_diag_kit(model, self.options.get("kit", 0))
         else:

@@ -140,6 +140,11 @@ class MySolver:
                     self.dev.set_option("cg_factored", 1 if self.kit == 1 else 0)
                     if self.kit == 1:
                         self._say(" ---The CG path runs from the factors of the factored blocks (cg_factored = 1)")
+                    # ... with diagonal parts only when the model was loaded with cg="diag" (check_diag_kit above)
+                    cg_diag = self.kit == 1 and bool(getattr(model, "factored_cg_diag", False))
+                    self.dev.set_option("cg_diag", 1 if cg_diag else 0)
+                    if cg_diag:
+                        self._say(" ---The CG path holds the diagonal parts of the factored blocks (cg_diag = 1)")
                 if self.kit == 1:
                     self.dev.set_option("cg_lowrank", -1)
                     self._say(f" ---The CG path uses the rank-{self.datarank} factors of the data (cg_lowrank = -1)")
@@ -544,7 +549,7 @@ class MySolver:
                 rhs_ms=d.timing("rhs"), residual_d_ms=d.timing("residual_d"), stats_ms=d.timing("stats"),
                 hop_assemble=d.count("hop_assemble"), hop_over_budget=d.count("hop_over_budget"),
                 op_factored_scaled=d.count("op_factored_scaled"), op_quadform_fused=d.count("op_quadform_fused"),
-                prec_ts_stored_rows=d.count("prec_ts_stored_rows"), hop_matvec=d.count("hop_matvec"),
+                prec_ts_stored_rows=d.count("prec_ts_stored_rows"), prec_ts_diag_rows=d.count("prec_ts_diag_rows"), hop_matvec=d.count("hop_matvec"),
                 prec_lanczos_steps=d.count("prec_lanczos_steps"), lanczos_plain=d.count("lanczos_plain"),
                 prec_dense_build=d.count("prec_dense_build"),
                 ns_steps=d.count("ns_steps"), lyap_steps=d.count("lyap_steps"), lyap_ms=d.timing("lyap"),
