@@ -197,7 +197,17 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * the matrix-free operator only: 1 = AA vec(Z) of the factor part by the fused quadratic form of facops.hip, Q = Z Vd never
  * stored; 0 = Q and the column dots; -1, default = cost model, "off" likewise), "diag_sq_mfma" (squared-operand product of
  * the diagonal parts, lrn_upload_diag: 1 = the 64 x 64 FP64 MFMA tile form, 0 = the rows form, one wave per column group and
- * eight rows in registers, -1, default = by the number of diagonal rows), "reset_timing".
+ * eight rows in registers, -1, default = by the number of diagonal rows),
+ * "lowrank_ragged" (rank-k assembly, mode 1, of a block whose constraints have MIXED ranks: 0, default = every constraint on
+ * khat columns, the padded route, every route, counter and bit as before; 1 = by rank class -- the constraints are grouped by
+ * the power of two >= their rank (number of weighted factor columns; 1, 2, 4, 8, 16; rank 0: no group), the weighted columns
+ * compacted class by class (16 first) into Vc, msz x Rc, and H_FF comes from U_c = G' Vc (W Vc) and one FP64 MFMA tile launch
+ * over a host-built tile list (raggedops.hip), msz Rc^2 / 2 multiply-adds instead of msz (nvar khat)^2 / 2.  Taken per block
+ * when world == 1 and 0 < Rc < nvar khat; a uniform block, an empty one and a sharded run keep the padded route and count
+ * "ragged_fallback".  The data operators, the cross terms of a hybrid block and the terms of diagonal parts stay on the
+ * padded layout.  Counters: "schur_ragged" (blocks assembled by rank class), "ragged_fallback", and the STATE of the last
+ * block assembled that way (survives reset_timing): "ragged_cols" (Rc), "ragged_classes" (classes present), "ragged_tiles";
+ * timing key "ragged" (U_c and the tile launch, beside "lowrank_u"), "reset_timing".
  * Counters of these options: "op_factored_scaled" (blocks per application through Y), "op_quadform_fused" (blocks per
  * application through the fused kernel), "fac_scaled_y" (products Y = W Vd), "hop_over_budget" (operator choices that found H
  * above the budget), "prec_ts_stored_rows" (rows of ts filled from stored entries in the LAST lrn_prec_setup).

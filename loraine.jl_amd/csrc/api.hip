@@ -118,6 +118,7 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "comm_fail_ensure")) lrn::comm_inject_ensure_failure(c);      // test hook (tests/test_gpu_comm.py)
   else if (!strcmp(key, "pcg_lookahead")) c->opt.pcg_lookahead = std::max(0, std::min(8, (int)value));
   else if (!strcmp(key, "lowrank_form")) c->opt.lowrank_form = std::max(-1, std::min(1, (int)value));
+  else if (!strcmp(key, "lowrank_ragged")) { c->opt.lowrank_ragged = value != 0.0 ? 1 : 0; c->hop_version = -1; }
   else if (!strcmp(key, "cg_lowrank")) {      // (the operator choice is taken again; an H of the other mode is not reused)
     c->opt.cg_lowrank = std::max(-1, std::min(1, (int)value));
     c->hop_version = -1;
@@ -403,6 +404,10 @@ int64_t lrn_get_count(lrn_ctx* c, const char* key) {
     for (const auto& b : c->lmi) s += b.dg_n;
     return s;
   }
+  // the last block assembled by rank class (option "lowrank_ragged"): compacted columns, classes present, tiles launched
+  if (!strcmp(key, "ragged_cols")) return (int64_t)c->rg_last_cols;
+  if (!strcmp(key, "ragged_classes")) return (int64_t)c->rg_last_classes;
+  if (!strcmp(key, "ragged_tiles")) return (int64_t)c->rg_last_tiles;
   auto it = c->counts.find(key);
   return it == c->counts.end() ? 0 : it->second;
 }

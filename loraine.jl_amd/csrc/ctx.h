@@ -76,6 +76,13 @@ struct LmiBlock {
   bool have_Bd = false;     // dense copy of the rank-one factors (rank-one assembly from W)
   lrn::DBuf Vd;             // dense copy of the rank-k factors, msz x (nvar * lr_khat) (dense U product, assembly from W)
   bool have_Vd = false;
+  // rank-class route of the rank-k assembly (option "lowrank_ragged", raggedops.hip, ragged_plan.h): rg_Rc = the compacted
+  // column count, counted at lrn_upload_lowrank; the plan's device copies and the compacted dense factors Vc (msz x rg_Rc) are
+  // built at the first assembly by that route (rg_ready) and dropped by a new upload
+  long rg_Rc = 0, rg_ntiles = 0;
+  int rg_ncls = 0;
+  bool rg_ready = false;
+  lrn::DBuf rg_src, rg_wc, rg_gh, rg_tiles, Vc;   // int64 [rg_Rc], double [rg_Rc], int32 [groups], RaggedTile [rg_ntiles]
   // factored block (lrn_set_factored): the factors ARE the constraint data -- AA vec(.) and mat(AA' .) go through Vd
   // (dataops.hip, "factor form"), the Schur matrix through mode 1 only.  Pure: AA has no entry.  Hybrid: a few constraints
   // are stored instead (rows of AA, positions [0, npos_nz) as everywhere) and have weight-0 factor columns; every constraint
@@ -175,6 +182,8 @@ struct LrnOptions {
                                   // composition mat(AA' x) -> W M W -> AA vec(.): 0, cost model (hop.hip::fac_op_scaled_on): -1
   int fac_quadform = -1;          // AA vec(Z) of a factored block inside the CG operator by the fused quadratic form of facops.hip
                                   // (Q = Z Vd never stored): 1, Q and fac_coldot_kernel: 0, cost model: -1
+  int lowrank_ragged = 0;         // rank-k assembly of a block of mixed ranks by rank class (raggedops.hip): 1, the padded route: 0.  One
+                                  // GPU, and only where the classes are not all khat -- the padded route otherwise ("ragged_fallback")
   int diag_sq_mfma = -1;          // squared-operand product of the diagonal parts (diagops.hip::diag_sq): the MFMA tile form (1), the
                                   // rows form, one wave per column group (0), by the number of diagonal rows (-1)
 };
@@ -232,6 +241,8 @@ struct lrn_ctx {
   // assembly workspaces
   lrn::DBuf P, P2, T, slabs, Hd, BG;
   lrn::DBuf m0, m1, m2, cgbuf;   // msz^2 work matrices (mat-vec / rhs), PCG vectors
+  bool BG_ragged = false;        // the last assemble_lowrank left U_c of the rank-class route in BG (not Y = W Vd of the padded layout)
+  long rg_last_cols = 0, rg_last_classes = 0, rg_last_tiles = 0;   // the last block assembled by rank class (lrn_get_count "ragged_*")
   lrn::DBuf facY, facM;          // hybrid factored block: Y = W Vd when U is G' Vd (msz x nvar khat); the stored part of mat(AA' x)
   lrn::DBuf dgP, dgC, dgH, dgT, dgTA;   // diagonal parts (diagops.hip): Ad' (W o W), Ad' (Y o Y) summed over khat, H_DD, T = rows diag(W A_s W), T' Ad
   int T_m = 0;                 // matrix side and block the T workspace was last laid out for
@@ -288,6 +299,10 @@ int schur_add_diag(lrn_ctx* c, double eps);
 int schur_get(lrn_ctx* c, double* Hout);
 // schur_factored.hip
 int lowrank_dense_factors(lrn_ctx* c, LmiBlock& b);     // b.Vd from the uploaded rank-k factors (once per upload)
+// rank-class route of a block under option "lowrank_ragged": one GPU, some but not all columns survive the compaction
+inline bool lowrank_ragged_on(const lrn_ctx* c, const LmiBlock& b) {
+  return c->opt.lowrank_ragged != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
+}
 // hop.hip: the CG operator through the assembled matrix
 // y = H x; qpart (may be null): receives *nq partial sums of x'y (*nq = 0: not formed, e.g. sharded)
 int hop_apply(lrn_ctx* c, const double* x_dev, double* y_dev, double* qpart = nullptr, int* nq = nullptr);

@@ -318,7 +318,10 @@ static double est_assemble_s(const lrn_ctx* c, int mode) {
     if (mode == 1 && (b.factored || cg_lowrank_covered(b))) {
       // U = G' Vd and the blocked square of U' U on its lower triangle (section 10: 1.28e11 flop in 3.78 ms)
       const double R = n * b.lr_khat;
-      t += (2.0 * R * m * m + 0.5 * R * R * m) / 3.4e13;
+      // option "lowrank_ragged": the two products run on the Rc compacted columns (raggedops.hip); everything below stays
+      // on the padded layout
+      const double Rp = lowrank_ragged_on(c, b) ? (double)b.rg_Rc : R;
+      t += (2.0 * Rp * m * m + 0.5 * Rp * Rp * m) / 3.4e13;
       if (b.factored && b.dg_n > 0) {
         // diagonal parts (assemble_diag), at the rates section 16 MEASURED at msz 2000 / nvar 4000 / khat 2 / 4000 rows -- those
         // measurements, not new ones: C = Ad' (Y o Y), 2 dg_n m R = 128 GFLOP in 2.8 ms; H_DD = the squared product and the

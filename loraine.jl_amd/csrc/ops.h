@@ -86,6 +86,8 @@ int assemble_rank1(lrn_ctx* c, LmiBlock& b);
 int assemble_lowrank(lrn_ctx* c, LmiBlock& b);
 int factored_y(lrn_ctx* c, LmiBlock& b, const double** Y);      // Y = W Vd (msz x nvar khat) after assemble_lowrank: its U, or one more product
 int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);
+// raggedops.hip: H_FF of a block of mixed ranks by rank class (option "lowrank_ragged"; assemble_lowrank decides)
+int assemble_ragged(lrn_ctx* c, LmiBlock& b);
 // diagops.hip: diagonal parts of a factored block (lrn_upload_diag), A_k = diag(a_k) + V_k D_k V_k'
 int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y);    // H_DD, the cross terms with the factors (Y) and with the stored rows
 int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // y[nat(s)] -= sum_i a_si Z_ii

@@ -21,10 +21,11 @@
 //   rank-one data (mode -1): BG = B G (sparse x dense), H += (BG BG').^2 with the square
 //        fused in the MFMA GEMM epilogue (makeBBBB.jl:7-14).
 //   rank-k data (mode 1): U = G' V, H += blocksum(d d' .* (U'U).^2) over khat x khat blocks, again in the
-//        epilogue of one MFMA product (assemble_lowrank).
+//        epilogue of one MFMA product (assemble_lowrank).  Option "lowrank_ragged": a block of mixed ranks by rank class, on
+//        the compacted columns (raggedops.hip).
 // This file: the sparse owners, the linear part, the driver schur_assemble, factorisation and solve.  schur_dense.hip: the dense
-// owners; schur_factored.hip: rank-one / rank-k data and hybrid blocks; diagops.hip: diagonal parts of factored blocks;
-// schur_plan.h: the launch decisions, host only.
+// owners; schur_factored.hip: rank-one / rank-k data and hybrid blocks; raggedops.hip: rank-k data by rank class; diagops.hip:
+// diagonal parts of factored blocks; schur_plan.h, ragged_plan.h: the launch decisions, host only.
 #include <algorithm>
 
 #include "ops.h"

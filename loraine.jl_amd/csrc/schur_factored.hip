@@ -104,6 +104,13 @@ int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
   if (fromW && !b.have_W) return set_error(c, LRN_ERR_STATE, "rank-k mode needs G or W (lrn_prepare_w / lrn_set_scaling)");
   const int kh = b.lr_khat;
   const long R = (long)n * kh;
+  // option "lowrank_ragged": a block of mixed ranks by rank class (raggedops.hip) -- on one GPU and where the compaction drops
+  // columns; a uniform block, an empty one and a sharded run keep the padded route below, bit for bit
+  if (c->opt.lowrank_ragged) {
+    if (lowrank_ragged_on(c, b)) return assemble_ragged(c, b);
+    c->counts["ragged_fallback"] += 1;
+  }
+  c->BG_ragged = false;
   const double* M = fromW ? b.W.as<double>() : b.G.as<double>();
   // U by one dense product or by a gather over the stored factor entries: the gather reads nnz * msz words of G / W, the
   // product does 2 R msz^2 flop -- the gather wins below a density of about 2 %
@@ -231,7 +238,8 @@ __global__ __launch_bounds__(256) void fac_cross_coldot_kernel(const double* __r
   H[h_lower(hidx[s], hj, ldh)] += acc;
 }
 
-// Y = W Vd: what assemble_lowrank left in BG when only W exists, one more product into a workspace of its own otherwise.
+// Y = W Vd: what the padded route of assemble_lowrank left in BG when only W exists, one more product into a workspace of its
+// own otherwise.
 // Formed once per assembly of a block and shared by assemble_cross and diagops.hip::assemble_diag
 int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
   const int n = c->nvar, m = b.msz, kh = b.lr_khat;
@@ -239,7 +247,7 @@ int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
   if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");
   const double* Y = c->BG.as<double>();
   tic(c);
-  if (b.have_G) {
+  if (b.have_G || c->BG_ragged) {      // (after the rank-class route BG holds U_c in the compacted layout)
     LRN_TRY(ensure(c, c->facY, (size_t)m * R * 8));
     GemmDesc g;
     g.A = b.W.as<double>(); g.sAm = 1; g.sAk = m;

@@ -54,6 +54,41 @@ class MyModel:
     # diag(a) + V diag(d) V' with its factors in `lowrank` (none for a purely diagonal constraint, e.g. a trace row).  {} for a
     # block without them and for a materialised block, whose entries hold the diagonal
     diag: list = field(default_factory=list)
+    # Optimizer.load_factored_model(..., ragged=True): mode 1 assembles a block of mixed ranks by rank class (ragged_plan below) --
+    # the solver sets the library option lowrank_ragged = 1
+    ragged: bool = False
+
+
+RAGGED_CLASSES = (16, 8, 4, 2, 1)     # layout order of the rank classes
+RAGGED_TILE = 64                      # tile side of the rank-class kernel: every class size divides it
+
+
+def ragged_plan(ranks):
+    """The rank-class plan of one block (library option lowrank_ragged; csrc/ragged_plan.h is the same function of the factor
+    weights).  ranks[h] = number of weighted factor columns of the constraint with H index h.  Class of a constraint = the
+    smallest of 1, 2, 4, 8, 16 that is >= its rank; rank 0 has no group.  Classes are laid out 16, 8, 4, 2, 1, the groups of a
+    class in increasing H index, each on `class` compacted columns.  Tiles: 64 x 64, anchored at the segment starts; for every
+    class pair (A, B), A at or before B, all tiles of seg_A x seg_B when A != B and those with tile row >= tile column when
+    A == B.  -> dict(classes = class per constraint (0: none), seg = {class: (seg0, seg1)}, Rc, ncls = classes present, gh =
+    H index per group, tiles = tile count)."""
+    ranks = [int(r) for r in ranks]
+    if any(r < 0 or r > LOWRANK_MAX for r in ranks):
+        raise ValueError(f"ragged_plan: ranks must lie in 0 .. {LOWRANK_MAX}")
+    classes = [0 if r == 0 else padded_rank(r) for r in ranks]
+    seg, gh, col = {}, [], 0
+    for c in RAGGED_CLASSES:
+        members = [h for h, ch in enumerate(classes) if ch == c]
+        seg[c] = (col, col + c * len(members))
+        col += c * len(members)
+        gh += members
+    nt = {c: -(-(s1 - s0) // RAGGED_TILE) for c, (s0, s1) in seg.items()}
+    tiles = 0
+    for i, a in enumerate(RAGGED_CLASSES):
+        tiles += nt[a] * (nt[a] + 1) // 2
+        for b in RAGGED_CLASSES[i + 1:]:
+            tiles += nt[a] * nt[b]
+    return dict(classes=classes, seg=seg, Rc=col, ncls=sum(1 for c in RAGGED_CLASSES if seg[c][1] > seg[c][0]), gh=gh,
+                tiles=tiles)
 
 
 def check_factored_kit(model, kit):

@@ -79,7 +79,7 @@ class Optimizer:
         return self
 
     def load_factored_model(self, F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factored_form=-1,
-                            cg=False):
+                            cg=False, ragged=False):
         """The same problem given by its factors alone: F0[i] the constant matrix of block i (the A[i][0] of load_model),
         factors[i][k] = (V, d) with A_i,k+1 = V diag(d) V' (V msz x r, r <= 16, d = +-1, dense or sparse).  No A_ik, no
         row of AA and no dense constraint slab is ever formed, on the host or on the device; implies datarank = the
@@ -93,6 +93,9 @@ class Optimizer:
         purely diagonal constraint -- the trace row tr X = 1 is (None, [], ones(msz))).  No entry list is formed for it; needs
         kit = 0, also with cg=True (ValueError otherwise).  cg="diag" is cg=True and admits kit = 1 on such a model as well
         (opt-in: library option cg_diag beside cg_factored -- ts of H_alpha gets the term of the diagonal parts); one GPU only.
+        ragged=True (opt-in): the Schur assembly groups the constraints of a factored block by rank class instead of padding all
+        of them to the largest rank (library option lowrank_ragged) -- for blocks of mixed ranks, a few constraints of rank 9
+        beside thousands of rank 1; a block of uniform rank and a sharded run keep the padded route.
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
         if not self.resident:
@@ -102,7 +105,7 @@ class Optimizer:
         if isinstance(cg, str) and not cg_diag:
             raise ValueError(f"load_factored_model: cg is False, True or \"diag\", not {cg!r}")
         self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
-                                      int(factored_form), cg_diag, bool(cg)))
+                                      int(factored_form), bool(ragged), cg_diag, bool(cg)))
         return self
 
     def _copy_to(self):
@@ -113,11 +116,12 @@ class Optimizer:
             model = model_from_sdpa(payload, datarank=drank, kappa=kappa)
             self.max_sense = False
         elif kind == "factored":
-            F0, factors, b, b_const, d_lin, C_lin, max_sense, form, cg_diag, cg = payload
+            F0, factors, b, b_const, d_lin, C_lin, max_sense, form, ragged, cg_diag, cg = payload
             self.max_sense = max_sense
             model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
             model.factored_cg = bool(cg) and model.factored
             model.factored_cg_diag = cg_diag and model.factored
+            model.ragged = bool(ragged) and model.factored
             check_factored_kit(model, self.options.get("kit", 0))
             check_diag_kit(model, self.options.get("kit", 0))
         else:

@@ -145,6 +145,11 @@ class MySolver:
                     self.dev.set_option("cg_diag", 1 if cg_diag else 0)
                     if cg_diag:
                         self._say(" ---The CG path holds the diagonal parts of the factored blocks (cg_diag = 1)")
+                    # load_factored_model(..., ragged=True): blocks of mixed ranks are assembled by rank class
+                    ragged = bool(getattr(model, "ragged", False))
+                    self.dev.set_option("lowrank_ragged", 1 if ragged else 0)
+                    if ragged:
+                        self._say(" ---The Schur assembly groups the factored constraints by rank class (lowrank_ragged = 1)")
                 if self.kit == 1:
                     self.dev.set_option("cg_lowrank", -1)
                     self._say(f" ---The CG path uses the rank-{self.datarank} factors of the data (cg_lowrank = -1)")
