@@ -207,7 +207,20 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * "ragged_fallback".  The data operators, the cross terms of a hybrid block and the terms of diagonal parts stay on the
  * padded layout.  Counters: "schur_ragged" (blocks assembled by rank class), "ragged_fallback", and the STATE of the last
  * block assembled that way (survives reset_timing): "ragged_cols" (Rc), "ragged_classes" (classes present), "ragged_tiles";
- * timing key "ragged" (U_c and the tile launch, beside "lowrank_u"), "reset_timing".
+ * timing key "ragged" (U_c and the tile launch, beside "lowrank_u"),
+ * "ragged_ops" (the factor form of AA vec(.) and mat(AA' .) of such a block: 0, default = on the nvar khat padded columns, every
+ * route, counter, error text and bit as before; any other value = 1 = on the Rc compacted columns of "lowrank_ragged" -- Q = Z Vc
+ * and sums by group, or the fused quadratic form on (Vc, Rc) under "fac_quadform"; mat(AA' x) = -sum_c s_c f_c f_c' by one FP64
+ * MFMA launch over the lower 64 x 64 tiles and K-chunks with F = Vc, or Yc = W Vc under "fac_op_scaled" (raggedops.hip).
+ * Independent of "lowrank_ragged", the same condition per block: world == 1 and 0 < Rc < nvar khat; otherwise the padded code
+ * runs bit for bit and "ragged_ops_fallback" counts.  The first call by either route builds the plan and Vc.  Every caller of
+ * the factor form gets it: the resident entry points, lrn_matvec / lrn_pcg under "cg_factored", the covered blocks of
+ * "cg_lowrank"; lrn_matvec_partial and world > 1 stay as they are.  Counters: "op_ragged" (operator calls by this route;
+ * "op_factored" counts as well), "ragged_ops_fallback", and the STATE "ragged_ops_chunks" (K-chunks of the last launch; survives
+ * reset_timing); timing keys stay "aa_times" / "aat_to_mat"),
+ * "ragged_ops_split" (K-chunks of that launch: 0, default = auto, 1 .. 16 forced, clamped to the K-steps ceil(Rc / 16) of the
+ * block; chunk s covers the steps [s nsteps / ks, (s + 1) nsteps / ks) and the chunks are added in the order 0 .. ks - 1),
+ * "reset_timing".
  * Counters of these options: "op_factored_scaled" (blocks per application through Y), "op_quadform_fused" (blocks per
  * application through the fused kernel), "fac_scaled_y" (products Y = W Vd), "hop_over_budget" (operator choices that found H
  * above the budget), "prec_ts_stored_rows" (rows of ts filled from stored entries in the LAST lrn_prec_setup).

@@ -119,6 +119,8 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "pcg_lookahead")) c->opt.pcg_lookahead = std::max(0, std::min(8, (int)value));
   else if (!strcmp(key, "lowrank_form")) c->opt.lowrank_form = std::max(-1, std::min(1, (int)value));
   else if (!strcmp(key, "lowrank_ragged")) { c->opt.lowrank_ragged = value != 0.0 ? 1 : 0; c->hop_version = -1; }
+  else if (!strcmp(key, "ragged_ops")) { c->opt.ragged_ops = value != 0.0 ? 1 : 0; c->hop_version = -1; }
+  else if (!strcmp(key, "ragged_ops_split")) c->opt.ragged_ops_split = std::max(0, std::min(16, (int)value));
   else if (!strcmp(key, "cg_lowrank")) {      // (the operator choice is taken again; an H of the other mode is not reused)
     c->opt.cg_lowrank = std::max(-1, std::min(1, (int)value));
     c->hop_version = -1;
@@ -408,6 +410,7 @@ int64_t lrn_get_count(lrn_ctx* c, const char* key) {
   if (!strcmp(key, "ragged_cols")) return (int64_t)c->rg_last_cols;
   if (!strcmp(key, "ragged_classes")) return (int64_t)c->rg_last_classes;
   if (!strcmp(key, "ragged_tiles")) return (int64_t)c->rg_last_tiles;
+  if (!strcmp(key, "ragged_ops_chunks")) return (int64_t)c->rg_last_chunks;      // (option "ragged_ops": K-chunks of the last syrk launch)
   auto it = c->counts.find(key);
   return it == c->counts.end() ? 0 : it->second;
 }

@@ -83,6 +83,14 @@ struct LmiBlock {
   int rg_ncls = 0;
   bool rg_ready = false;
   lrn::DBuf rg_src, rg_wc, rg_gh, rg_tiles, Vc;   // int64 [rg_Rc], double [rg_Rc], int32 [groups], RaggedTile [rg_ntiles]
+  // option "ragged_ops" (the data operators on the compacted columns, raggedops.hip): column -> group, the segment starts and
+  // first groups of the five classes (rg_grp0[5] = the number of groups), and Yc = W Vc (msz x rg_Rc) of the scaling
+  // `Yc_version` for option "fac_op_scaled" -- all built with the plan, on the first call of either route
+  lrn::DBuf rg_cg;                                // int32 [rg_Rc]
+  long rg_seg0[5] = {0, 0, 0, 0, 0};
+  int rg_grp0[6] = {0, 0, 0, 0, 0, 0};
+  lrn::DBuf Yc;
+  long Yc_version = -1;
   // factored block (lrn_set_factored): the factors ARE the constraint data -- AA vec(.) and mat(AA' .) go through Vd
   // (dataops.hip, "factor form"), the Schur matrix through mode 1 only.  Pure: AA has no entry.  Hybrid: a few constraints
   // are stored instead (rows of AA, positions [0, npos_nz) as everywhere) and have weight-0 factor columns; every constraint
@@ -184,6 +192,10 @@ struct LrnOptions {
                                   // (Q = Z Vd never stored): 1, Q and fac_coldot_kernel: 0, cost model: -1
   int lowrank_ragged = 0;         // rank-k assembly of a block of mixed ranks by rank class (raggedops.hip): 1, the padded route: 0.  One
                                   // GPU, and only where the classes are not all khat -- the padded route otherwise ("ragged_fallback")
+  int ragged_ops = 0;             // AA vec(.) and mat(AA' .) of a block of mixed ranks in factor form on the compacted columns of the
+                                  // rank classes (raggedops.hip): 1, on the padded layout: 0.  Independent of lowrank_ragged; the
+                                  // same conditions, the padded code otherwise ("ragged_ops_fallback")
+  int ragged_ops_split = 0;       // K-chunks of ragged_syrk_kernel: 0 auto, 1 .. 16 forced (clamped to the K-steps of the block)
   int diag_sq_mfma = -1;          // squared-operand product of the diagonal parts (diagops.hip::diag_sq): the MFMA tile form (1), the
                                   // rows form, one wave per column group (0), by the number of diagonal rows (-1)
 };
@@ -243,6 +255,7 @@ struct lrn_ctx {
   lrn::DBuf m0, m1, m2, cgbuf;   // msz^2 work matrices (mat-vec / rhs), PCG vectors
   bool BG_ragged = false;        // the last assemble_lowrank left U_c of the rank-class route in BG (not Y = W Vd of the padded layout)
   long rg_last_cols = 0, rg_last_classes = 0, rg_last_tiles = 0;   // the last block assembled by rank class (lrn_get_count "ragged_*")
+  long rg_last_chunks = 0;       // K-chunks of the last ragged_syrk_kernel launch (lrn_get_count "ragged_ops_chunks")
   lrn::DBuf facY, facM;          // hybrid factored block: Y = W Vd when U is G' Vd (msz x nvar khat); the stored part of mat(AA' x)
   lrn::DBuf dgP, dgC, dgH, dgT, dgTA;   // diagonal parts (diagops.hip): Ad' (W o W), Ad' (Y o Y) summed over khat, H_DD, T = rows diag(W A_s W), T' Ad
   int T_m = 0;                 // matrix side and block the T workspace was last laid out for
@@ -303,6 +316,10 @@ int lowrank_dense_factors(lrn_ctx* c, LmiBlock& b);     // b.Vd from the uploade
 inline bool lowrank_ragged_on(const lrn_ctx* c, const LmiBlock& b) {
   return c->opt.lowrank_ragged != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
 }
+// the data operators of a block on the compacted columns under option "ragged_ops": the same condition
+inline bool ragged_ops_on(const lrn_ctx* c, const LmiBlock& b) {
+  return c->opt.ragged_ops != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
+}
 // hop.hip: the CG operator through the assembled matrix
 // y = H x; qpart (may be null): receives *nq partial sums of x'y (*nq = 0: not formed, e.g. sharded)
 int hop_apply(lrn_ctx* c, const double* x_dev, double* y_dev, double* qpart = nullptr, int* nq = nullptr);
@@ -323,6 +340,8 @@ bool fac_quadform_on(const lrn_ctx* c, const LmiBlock& b);       // hop.hip: AA 
 // facops.hip: out[nat(h)] -= sum_p w[h kh + p] v_c' Z v_c over the kh factor columns c = h kh + p of every constraint
 int fac_quadform(lrn_ctx* c, const double* Z, const double* Vd, const double* w, int m, int kh, int nvar, const int* sigma,
                  double* out);
+// the first half alone on any column layout V (msz x R): *part = nstrip x R partial sums of <(Z V)(:, c), V(:, c)> by row strips
+int fac_quadform_parts(lrn_ctx* c, const double* Z, const double* V, int m, long R, double** part, int* nstrip);
 }  // namespace lrn
 
 #define LRN_HIP(c, expr)                                                                   \

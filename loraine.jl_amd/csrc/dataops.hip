@@ -963,6 +963,15 @@ static int fac_workspace(lrn_ctx* c, LmiBlock& b, double** ws) {
 static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused = false) {
   const int m = b.msz, kh = b.lr_khat;
   const long R = (long)c->nvar * kh;
+  // option "ragged_ops": a block of mixed ranks on the compacted columns of its rank classes (raggedops.hip), under the
+  // conditions of the rank-class assembly; a uniform block, an empty one and a sharded run keep the padded code below
+  if (c->opt.ragged_ops) {
+    if (ragged_ops_on(c, b)) {
+      if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
+      return aa_times_ragged(c, b, Z, y, fused);
+    }
+    c->counts["ragged_ops_fallback"] += 1;
+  }
   if (fused) {
     if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
     LRN_TRY(fac_quadform(c, Z, b.Vd.as<double>(), b.v_w.as<double>(), m, kh, c->nvar,
@@ -988,6 +997,18 @@ static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y
 static int aat_to_mat_factored(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const double* F = nullptr) {
   const int m = b.msz, kh = b.lr_khat;
   const long R = (long)c->nvar * kh;
+  if (c->opt.ragged_ops) {      // (as in aa_times_factored; F is then Yc = W Vc of fac_scaled_y, or null)
+    if (ragged_ops_on(c, b)) {
+      if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
+      if (F && F != b.Yc.as<double>()) return set_error(c, LRN_ERR_STATE, "ragged_ops: scaled factors in the padded layout");
+      int ks = 1;
+      LRN_TRY(aat_to_mat_ragged(c, b, x, M, F, &ks));
+      if (ks == 1)
+        hipLaunchKernelGGL(mirror_lower_tiled_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(32, 8), 0, c->stream, M, m);
+      return LRN_OK;
+    }
+    c->counts["ragged_ops_fallback"] += 1;
+  }
   double* Vs = nullptr;
   LRN_TRY(fac_workspace(c, b, &Vs));
   if (!F) F = b.Vd.as<double>();
@@ -1180,6 +1201,14 @@ static int aat_to_mat_stored(lrn_ctx* c, LmiBlock& b, const double* x, double* M
 //     W mat(AA' x) W = -W Vd diag(w o x) Vd' W = -Y diag(w o x) Y',
 // the scaled copy, lower-triangle product and mirror of aat_to_mat_factored on Y instead of Vd -- no W M W product
 static int fac_scaled_y(lrn_ctx* c, LmiBlock& b) {
+  if (ragged_ops_on(c, b)) {      // option "ragged_ops": Yc = W Vc (msz x Rc) instead, cached the same way (raggedops.hip)
+    if (b.Yc_version == c->scal_version && b.Yc.p) return LRN_OK;
+    if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
+    OpTimer t(c, "fac_scaled_y");
+    LRN_TRY(ragged_scaled_y(c, b));
+    c->counts["fac_scaled_y"] += 1;
+    return t.done(LRN_OK);
+  }
   if (b.Ys_version == c->scal_version && b.Ys.p) return LRN_OK;
   if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
   OpTimer t(c, "fac_scaled_y");
@@ -1213,7 +1242,7 @@ int matvec_dev(lrn_ctx* c, const double* x, double* y) {
       double* N = c->m0.as<double>();
       {
         OpTimer t(c, "aat_to_mat");
-        LRN_TRY(t.done(aat_to_mat_factored(c, b, x, N, b.Ys.as<double>())));
+        LRN_TRY(t.done(aat_to_mat_factored(c, b, x, N, ragged_ops_on(c, b) ? b.Yc.as<double>() : b.Ys.as<double>())));
       }
       LRN_TRY(aa_times(c, b, N, y, false, fused));
       c->counts["op_factored_scaled"] += 1;

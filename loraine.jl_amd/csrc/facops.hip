@@ -129,6 +129,19 @@ __global__ __launch_bounds__(256) void fac_quadform_reduce_kernel(const double* 
   out[sigma ? sigma[h] : h] -= s;
 }
 
+// fac_quadform_kernel alone, on any column layout (the compacted columns of option "ragged_ops": raggedops.hip reduces the
+// partial sums by group)
+int fac_quadform_parts(lrn_ctx* c, const double* Z, const double* V, int m, long R, double** part, int* nstrip_out) {
+  const int nstrip = (m + FQ_T - 1) / FQ_T;
+  const long ntile = (R + FQ_T - 1) / FQ_T;
+  if (ntile > 2147483647L || nstrip > 65535) return set_error(c, LRN_ERR_ARG, "fac_quadform: %ld x %d tiles", ntile, nstrip);
+  LRN_TRY(ensure(c, c->slabs, (size_t)nstrip * (size_t)R * 8));
+  *part = c->slabs.as<double>();
+  *nstrip_out = nstrip;
+  hipLaunchKernelGGL(fac_quadform_kernel, dim3((unsigned)ntile, (unsigned)nstrip), dim3(256), 0, c->stream, Z, V, m, R, *part);
+  return LRN_OK;
+}
+
 int fac_quadform(lrn_ctx* c, const double* Z, const double* Vd, const double* w, int m, int kh, int nvar, const int* sigma,
                  double* out) {
   const long R = (long)nvar * kh;

@@ -241,7 +241,8 @@ static bool cg_lowrank_on(const lrn_ctx* c) { return c->opt.cg_lowrank != 0 && c
 static double est_operator_block_s(const lrn_ctx* c, const LmiBlock& b, bool factors) {
   const double m = b.msz;
   if (factors) {      // Q = Z Vd (2 m^2 R flop) and the lower triangle of Vs Vd' (m^2 R), the two products of wmw; as many launches
-    const double R = (double)c->nvar * b.lr_khat;       // as the entry route (section 11: 1.35 + 0.89 ms for 9.6e10 flop)
+    // as the entry route (section 11: 1.35 + 0.89 ms for 9.6e10 flop).  Option "ragged_ops": both run on the Rc compacted columns
+    const double R = ragged_ops_on(c, b) ? (double)b.rg_Rc : (double)c->nvar * b.lr_khat;
     double t = 3.0 * m * m * R / 4.0e13 + 40e-6;
     if (!(b.factored && fac_op_scaled_on(c, b))) t += 4.0 * m * m * m / 5.0e13;      // (Y = W Vd: no W M W product)
     // hybrid block: its stored rows on top, twice (mat(AA' x) and AA vec(.)) -- the sparse tier at the pattern rate, the

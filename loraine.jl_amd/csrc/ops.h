@@ -88,6 +88,14 @@ int factored_y(lrn_ctx* c, LmiBlock& b, const double** Y);      // Y = W Vd (msz
 int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);
 // raggedops.hip: H_FF of a block of mixed ranks by rank class (option "lowrank_ragged"; assemble_lowrank decides)
 int assemble_ragged(lrn_ctx* c, LmiBlock& b);
+// ... and the two data operators in factor form on the same compacted columns (option "ragged_ops"; aa_times_factored and
+// aat_to_mat_factored of dataops.hip decide).  ragged_setup: the plan of the block and Vc, once per upload, whichever route
+// comes first; ragged_scaled_y: Yc = W Vc of the current scaling (option "fac_op_scaled")
+int ragged_setup(lrn_ctx* c, LmiBlock& b);
+int ragged_scaled_y(lrn_ctx* c, LmiBlock& b);
+int aa_times_ragged(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused);            // y[nat] -= sum_c wc <(Z Vc)_c, Vc_c> by group
+// M = -F diag(wc o x) F', F = Vc (null) or Yc; *ks = 1: lower tiles only, the caller mirrors them
+int aat_to_mat_ragged(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const double* F, int* ks);
 // diagops.hip: diagonal parts of a factored block (lrn_upload_diag), A_k = diag(a_k) + V_k D_k V_k'
 int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y);    // H_DD, the cross terms with the factors (Y) and with the stored rows
 int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // y[nat(s)] -= sum_i a_si Z_ii

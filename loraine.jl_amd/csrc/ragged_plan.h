@@ -1,6 +1,7 @@
 // Host-side plan of the rank-class route of the rank-k Schur assembly (option "lowrank_ragged", raggedops.hip): the constraints
 // of a block grouped by rank class, the compacted column layout and the tile list of the one launch.  Pure functions of the
-// factor weights -- no context, no HIP runtime call -- in the style of schur_plan.h.  Python specification: model.ragged_plan.
+// factor weights -- no context, no HIP runtime call -- in the style of schur_plan.h.  Python specification: model.ragged_plan;
+// the column -> group map and the K-chunks of the data operators (option "ragged_ops"): model.ragged_columns, ragged_chunks.
 //
 // Rank r_j of constraint j = its factor columns of non-zero weight; class c_j = the smallest of {1, 2, 4, 8, 16} >= r_j.  A
 // constraint of rank 0 (a stored row of a hybrid block, a purely diagonal row, an empty constraint) has no group.  Classes are
@@ -32,6 +33,7 @@ struct RaggedPlan {
   long seg0[RG_NCLS] = {0, 0, 0, 0, 0}, seg1[RG_NCLS] = {0, 0, 0, 0, 0};      // columns of class ci: [seg0, seg1)
   int grp0[RG_NCLS] = {0, 0, 0, 0, 0};                  // first group of class ci
   std::vector<int> gh;                                  // group -> H index
+  std::vector<int> cg;                                  // compacted column -> group (option "ragged_ops": the data operators)
   std::vector<long> src;                                // compacted column -> padded column h khat + p, -1 for padding
   std::vector<double> wc;                               // weight of the compacted column (0 in the padding)
   std::vector<RaggedTile> tiles;
@@ -53,6 +55,30 @@ inline long ragged_cols(const double* w, int nvar, int khat) {
     if (r > 0) Rc += ragged_class_size(ragged_class_of(r));
   }
   return Rc;
+}
+
+// ---- the data operators on the compacted columns (option "ragged_ops", raggedops.hip)
+// K-chunks of the column range [0, Rc) walked in steps of RG_KSTEP columns: nsteps = ceil(Rc / 16), ks clamped to
+// [1, min(16, nsteps)], chunk s = the steps [s nsteps / ks, (s + 1) nsteps / ks) -- uneven where ks does not divide nsteps,
+// the last step a tail where 16 does not divide Rc.  Every step belongs to exactly one chunk.
+static constexpr int RG_KSTEP = 16;
+static constexpr int RG_MAX_CHUNKS = 16;
+#if defined(__HIPCC__)
+#define RG_HD __host__ __device__
+#else
+#define RG_HD
+#endif
+RG_HD inline long ragged_steps(long Rc) { return (Rc + RG_KSTEP - 1) / RG_KSTEP; }
+inline int ragged_clamp_chunks(long Rc, int ks) {
+  const long ns = ragged_steps(Rc), hi = ns < RG_MAX_CHUNKS ? ns : RG_MAX_CHUNKS;
+  return ks < 1 || hi < 1 ? 1 : (int)(ks > hi ? hi : ks);
+}
+// columns [*c0, *c1) of chunk s of ks (ks already clamped)
+RG_HD inline void ragged_chunk_cols(long Rc, int ks, int s, long* c0, long* c1) {
+  const long ns = ragged_steps(Rc);
+  const long s0 = (long)s * ns / ks, s1 = (long)(s + 1) * ns / ks;
+  *c0 = s0 * RG_KSTEP;
+  *c1 = s1 * RG_KSTEP < Rc ? s1 * RG_KSTEP : Rc;
 }
 
 // tiles of the layout: for every class pair (A, B), A at or before B, the 64 x 64 tiles of seg_A x seg_B anchored at the
@@ -92,10 +118,12 @@ inline RaggedPlan plan_ragged(const double* w, int nvar, int khat, bool with_til
   p.gh.reserve(grp);
   p.src.assign(p.Rc, -1);
   p.wc.assign(p.Rc, 0.0);
+  p.cg.assign(p.Rc, 0);
   for (int ci = 0; ci < RG_NCLS; ++ci) {
     long at = p.seg0[ci];
     for (long h = 0; h < nvar; ++h) {
       if (cls[h] != ci) continue;
+      for (int q = 0; q < ragged_class_size(ci); ++q) p.cg[at + q] = (int)p.gh.size();
       p.gh.push_back((int)h);
       long k = at;
       for (int q = 0; q < khat; ++q)

@@ -1,4 +1,5 @@
-// Rank-class route of the rank-k Schur assembly (option "lowrank_ragged", schur_factored.hip::assemble_lowrank).
+// Rank-class route of the rank-k Schur assembly (option "lowrank_ragged", schur_factored.hip::assemble_lowrank), and below it
+// the two data operators in factor form on the same compacted columns (option "ragged_ops", dataops.hip).
 //
 // The padded route pads every constraint of a block to khat columns, khat from the LARGEST rank, and pays msz R^2 multiply-adds
 // for H_FF = blocksum(d d' o (U' V)^2), R = nvar khat.  Here the constraints are grouped by rank class (ragged_plan.h): class c_j
@@ -134,8 +135,9 @@ __global__ __launch_bounds__(256) void ragged_blocksum_kernel(const double* __re
     }
 }
 
-// the plan of the block and its device copies, Vc among them: once per lrn_upload_lowrank (b.rg_ready)
-static int ragged_setup(lrn_ctx* c, LmiBlock& b) {
+// the plan of the block and its device copies, Vc among them: once per lrn_upload_lowrank (b.rg_ready), by the first assembly
+// or the first data operator that takes a rank-class route
+int ragged_setup(lrn_ctx* c, LmiBlock& b) {
   if (b.rg_ready) return LRN_OK;
   const int n = c->nvar, m = b.msz, kh = b.lr_khat;
   const long R = (long)n * kh;
@@ -152,6 +154,10 @@ static int ragged_setup(lrn_ctx* c, LmiBlock& b) {
   LRN_TRY(copy_in(c, b.rg_wc.p, p.wc.data(), (size_t)p.Rc * 8));
   LRN_TRY(copy_in(c, b.rg_gh.p, p.gh.data(), p.gh.size() * 4));
   LRN_TRY(copy_in(c, b.rg_tiles.p, p.tiles.data(), p.tiles.size() * sizeof(RaggedTile)));
+  LRN_TRY(ensure(c, b.rg_cg, (size_t)p.Rc * 4));
+  LRN_TRY(copy_in(c, b.rg_cg.p, p.cg.data(), (size_t)p.Rc * 4));
+  for (int ci = 0; ci < RG_NCLS; ++ci) { b.rg_seg0[ci] = p.seg0[ci]; b.rg_grp0[ci] = p.grp0[ci]; }
+  b.rg_grp0[RG_NCLS] = (int)p.gh.size();
   LRN_TRY(ensure(c, b.Vc, (size_t)m * p.Rc * 8));
   LRN_HIP(c, hipMemsetAsync(b.Vc.p, 0, (size_t)m * p.Rc * 8, c->stream));
   hipLaunchKernelGGL(ragged_dense_kernel, dim3((unsigned)p.Rc), dim3(64), 0, c->stream, b.v_ptr.as<long>(), b.v_col.as<int>(),
@@ -193,6 +199,304 @@ int assemble_ragged(lrn_ctx* c, LmiBlock& b) {
   c->rg_last_cols = Rc;
   c->rg_last_classes = b.rg_ncls;
   c->rg_last_tiles = b.rg_ntiles;
+  return LRN_OK;
+}
+
+// ================================================================ the data operators on the compacted columns
+// Option "ragged_ops" (dataops.hip::aa_times_factored, aat_to_mat_factored decide): the factor form of AA vec(Z) and mat(AA' x)
+// of a block of mixed ranks on Vc (msz x Rc) instead of Vd (msz x nvar khat), with the plan the assembly above uses.
+//     (AA vec(Z))_j = -sum_{c in group of j} wc_c v_c' Z v_c     Q = Z Vc by the product every route uses (or the fused quadratic
+//                                                               form of facops.hip on (Vc, Rc)), then sums by GROUP through gh
+//     mat(AA' x)    = -sum_c s_c f_c f_c',  s_c = wc_c x[nat(gh[cg[c]])],  F = Vc or Yc = W Vc (option "fac_op_scaled")
+// A constraint of rank 0 has no group and receives nothing.  Every sum has a fixed order and one writer: no atomics.
+//
+// ragged_syrk_kernel: 256 threads, grid = lower tiles x K-chunks.  Workgroup (t, s): the 64 x 64 tile (ti, tj), ti >= tj, of M
+// over the columns of chunk s (ragged_plan.h::ragged_chunk_cols), in steps of 16 columns, the tail zero-filled.  Both panels
+// are staged as [k][i], coalesced along the rows of F:
+//   Ps[k][i] = s_c F[i0 + i, c]   Qs[k][j] = F[j0 + j, c]   c = chunk start + k0 + k      16 x 64 doubles each, row stride 80
+// 2 x 10 240 = 20 480 bytes of LDS.  s_c is computed while staging (thread (i = t & 63, k = t >> 6 + 4 pass): k, hence c and
+// s_c, are wave-uniform) -- no scaled copy of the factors is written or read back.  The global loads of the next step are
+// issued before the MFMAs of the current one.  Wave w owns the 32 x 32 block (w >> 1, w & 1) as 2 x 2 accumulators of
+// v_mfma_f64_16x16x4_f64 with the j side as the A operand and the i side as the B operand: D[row = j][col = i], so the 16
+// lanes of a quarter hold 16 consecutive i of one column j of M -- 128-byte stores.  Both fragment reads are the A read of
+// fac_quadform_kernel's Zs (rows k, k + 1, sixteen consecutive i, row stride 80): conflict-free by the derivation there --
+// derived, not measured.  The tile goes to slab s of c->slabs (ks > 1) or straight to M (ks = 1; the part of a diagonal tile
+// above the diagonal is written too and overwritten by the mirror).
+// ragged_syrk_reduce_kernel: adds the slabs in the order 0 .. ks - 1 for i >= j and writes M[i, j] and M[j, i] from the one
+// sum, by 32 x 32 tile pairs through LDS as mirror_lower_tiled_kernel does: M is exactly symmetric, two calls give equal bits.
+struct RaggedSegs { long seg0[RG_NCLS]; int grp0[RG_NCLS + 1]; };
+
+// first column and class size of group g (g < grp0[RG_NCLS])
+__device__ __forceinline__ long ragged_group_col(const RaggedSegs& sg, int g, int* cj) {
+  int ci = 0;
+  while (ci < RG_NCLS - 1 && g >= sg.grp0[ci + 1]) ++ci;
+  *cj = 16 >> ci;
+  return sg.seg0[ci] + (long)(g - sg.grp0[ci]) * (16 >> ci);
+}
+
+// out[nat(gh[g])] -= sum_{p < c_j} wc[col] <Q(:, col), Vc(:, col)>, col = first column of group g + p: one wave per group,
+// the rows by the four accumulators and the one shuffle tree of fac_coldot_kernel
+__global__ __launch_bounds__(256) void ragged_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Vc,
+                                                            const double* __restrict__ wc, int m, RaggedSegs sg,
+                                                            const int* __restrict__ gh, const int* __restrict__ sigma,
+                                                            double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= sg.grp0[RG_NCLS]) return;
+  int cj;
+  const long c0 = ragged_group_col(sg, g, &cj);
+  double s = 0.0;
+  for (int p = 0; p < cj; ++p) {
+    const long col = c0 + p;
+    const double wp = wc[col];
+    if (wp == 0.0) continue;                       // padding column (wave-uniform)
+    const double* __restrict__ q = Q + col * m;
+    const double* __restrict__ v = Vc + col * m;
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+    int r = lane;
+    for (; r + 192 < m; r += 256) {
+      t0 += q[r] * v[r];
+      t1 += q[r + 64] * v[r + 64];
+      t2 += q[r + 128] * v[r + 128];
+      t3 += q[r + 192] * v[r + 192];
+    }
+    for (; r < m; r += 64) t0 += q[r] * v[r];
+    s += wp * ((t0 + t1) + (t2 + t3));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if (lane != 0) return;
+  const int h = gh[g];
+  out[sigma ? sigma[h] : h] -= s;
+}
+
+// the same sums from the partial sums of fac_quadform_kernel on (Vc, Rc): strips in order, then the columns of the group
+// (one thread per group; fixed order)
+__global__ __launch_bounds__(256) void ragged_quadform_reduce_kernel(const double* __restrict__ part, int nstrip, long Rc,
+                                                                     const double* __restrict__ wc, RaggedSegs sg,
+                                                                     const int* __restrict__ gh, const int* __restrict__ sigma,
+                                                                     double* __restrict__ out) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= sg.grp0[RG_NCLS]) return;
+  int cj;
+  const long c0 = ragged_group_col(sg, g, &cj);
+  double s = 0.0;
+  for (int p = 0; p < cj; ++p) {
+    const long col = c0 + p;
+    const double wp = wc[col];
+    if (wp == 0.0) continue;                       // padding column
+    double q = 0.0;
+    for (int st = 0; st < nstrip; ++st) q += part[(long)st * Rc + col];
+    s += wp * q;
+  }
+  const int h = gh[g];
+  out[sigma ? sigma[h] : h] -= s;
+}
+
+static constexpr int RS_LD = 80;       // row stride of Ps / Qs (doubles)
+
+__global__ __launch_bounds__(256) void ragged_syrk_kernel(const double* __restrict__ F, int m, long Rc,
+                                                          const double* __restrict__ wc, const int* __restrict__ cg,
+                                                          const int* __restrict__ gh, const int* __restrict__ sigma,
+                                                          const double* __restrict__ x, int ks, double* __restrict__ out,
+                                                          long slab_stride) {
+  __shared__ double Ps[RG_KSTEP * RS_LD];
+  __shared__ double Qs[RG_KSTEP * RS_LD];
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wr = w >> 1, wn = w & 1;
+  const int ci = lane & 15, kq = lane >> 4;
+  // lower tile (ti, tj) of the workgroup: blockIdx.x = ti (ti + 1) / 2 + tj
+  const long tl = blockIdx.x;
+  long ti = (long)((sqrt(8.0 * (double)tl + 1.0) - 1.0) * 0.5);
+  while (ti * (ti + 1) / 2 > tl) --ti;
+  while ((ti + 1) * (ti + 2) / 2 <= tl) ++ti;
+  const int tj = (int)(tl - ti * (ti + 1) / 2);
+  const int i0 = (int)ti * RG_TILE, j0 = tj * RG_TILE;
+  long cb, ce;
+  ragged_chunk_cols(Rc, ks, blockIdx.y, &cb, &ce);
+  rg_v4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = rg_v4{0.0, 0.0, 0.0, 0.0};
+  // staging map of both panels: thread (row = t & 63, k = t >> 6 + 4 pass)
+  const int zi = t & 63, zk = t >> 6;
+  const bool iok = i0 + zi < m, jok = j0 + zi < m;
+  double preg[4], qreg[4];
+  auto fetch = [&](long k0) {
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      const long col = cb + k0 + zk + 4 * ps;
+      double sc = 0.0, fi = 0.0, fj = 0.0;
+      if (col < ce) {
+        const int h = gh[cg[col]];
+        sc = -(wc[col] * x[sigma ? sigma[h] : h]);
+        if (iok) fi = F[(long)(i0 + zi) + col * m];
+        if (jok) fj = F[(long)(j0 + zi) + col * m];
+      }
+      preg[ps] = sc * fi;
+      qreg[ps] = fj;
+    }
+  };
+  fetch(0);
+  for (long k0 = 0; cb + k0 < ce; k0 += RG_KSTEP) {
+    __syncthreads();                       // the waves are done with the previous step's panels
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      Ps[(zk + 4 * ps) * RS_LD + zi] = preg[ps];
+      Qs[(zk + 4 * ps) * RS_LD + zi] = qreg[ps];
+    }
+    __syncthreads();
+    if (cb + k0 + RG_KSTEP < ce) fetch(k0 + RG_KSTEP);
+#pragma unroll
+    for (int kk = 0; kk < RG_KSTEP / 4; ++kk) {
+      const int k = 4 * kk + kq;
+      const double a0 = Qs[k * RS_LD + 32 * wn + ci];
+      const double a1 = Qs[k * RS_LD + 32 * wn + 16 + ci];
+      const double b0 = Ps[k * RS_LD + 32 * wr + ci];
+      const double b1 = Ps[k * RS_LD + 32 * wr + 16 + ci];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+  }
+  // acc[jb][ib][r] = M[i0 + 32 wr + 16 ib + ci, j0 + 32 wn + 16 jb + kq + 4 r]
+  double* __restrict__ C = out + (long)blockIdx.y * slab_stride;
+#pragma unroll
+  for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib) {
+      const int i = i0 + 32 * wr + 16 * ib + ci;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = j0 + 32 * wn + 16 * jb + kq + 4 * r;
+        if (i < m && j < m) C[(long)i + (long)j * m] = acc[jb][ib][r];
+      }
+    }
+}
+
+__global__ void ragged_syrk_reduce_kernel(const double* __restrict__ slabs, long stride, int ks, double* __restrict__ M, int n) {
+  __shared__ double tile[32][33];
+  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;      // source tile rows bx.., columns by.. (on or below the diagonal)
+  if (bx < by) return;
+  for (int r = threadIdx.y; r < 32; r += 8) {
+    const int i = bx + threadIdx.x, j = by + r;
+    double v = 0.0;
+    if (i < n && j < n && i >= j) {
+      const long e = (long)i + (long)j * n;
+      for (int s = 0; s < ks; ++s) v += slabs[(long)s * stride + e];
+      M[e] = v;
+    }
+    tile[r][threadIdx.x] = v;
+  }
+  __syncthreads();
+  for (int r = threadIdx.y; r < 32; r += 8) {
+    const int i = by + threadIdx.x, j = bx + r;              // destination (i, j) = transposed position
+    if (i < n && j < n && i < j) M[(long)i + (long)j * n] = tile[threadIdx.x][r];
+  }
+}
+
+static RaggedSegs ragged_segs(const LmiBlock& b) {
+  RaggedSegs sg;
+  for (int ci = 0; ci < RG_NCLS; ++ci) sg.seg0[ci] = b.rg_seg0[ci];
+  for (int ci = 0; ci <= RG_NCLS; ++ci) sg.grp0[ci] = b.rg_grp0[ci];
+  return sg;
+}
+
+// Yc = W Vc (msz x Rc) of the current scaling: what fac_scaled_y is on the padded layout
+int ragged_scaled_y(lrn_ctx* c, LmiBlock& b) {
+  LRN_TRY(ragged_setup(c, b));
+  if (b.Yc_version == c->scal_version && b.Yc.p) return LRN_OK;
+  const int m = b.msz;
+  LRN_TRY(ensure(c, b.Yc, (size_t)m * b.rg_Rc * 8));
+  GemmDesc g;
+  g.A = b.W.as<double>(); g.sAm = 1; g.sAk = m;
+  g.B = b.Vc.as<double>(); g.sBk = 1; g.sBn = m;
+  g.C = b.Yc.as<double>(); g.sCm = 1; g.sCn = m;
+  g.M = m; g.N = (int)b.rg_Rc; g.K = m;
+  LRN_TRY(gemm(c->stream, g));
+  b.Yc_version = c->scal_version;
+  return LRN_OK;
+}
+
+// y += the factor part of AA vec(Z).  The caller has checked the factors and the route (ragged_ops_on)
+int aa_times_ragged(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused) {
+  const int m = b.msz;
+  LRN_TRY(ragged_setup(c, b));
+  const long Rc = b.rg_Rc;
+  const RaggedSegs sg = ragged_segs(b);
+  const int ngrp = sg.grp0[RG_NCLS];
+  const int* sigma = c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr;
+  if (fused) {
+    double* part = nullptr;
+    int nstrip = 0;
+    LRN_TRY(fac_quadform_parts(c, Z, b.Vc.as<double>(), m, Rc, &part, &nstrip));
+    hipLaunchKernelGGL(ragged_quadform_reduce_kernel, dim3((ngrp + 255) / 256), dim3(256), 0, c->stream, part, nstrip, Rc,
+                       b.rg_wc.as<double>(), sg, b.rg_gh.as<int>(), sigma, y);
+    c->counts["op_quadform_fused"] += 1;
+  } else {
+    LRN_TRY(ensure(c, c->BG, (size_t)m * Rc * 8));
+    double* Q = c->BG.as<double>();
+    GemmDesc g;     // Q = Z Vc, msz x Rc
+    g.A = Z; g.sAm = 1; g.sAk = m;
+    g.B = b.Vc.as<double>(); g.sBk = 1; g.sBn = m;
+    g.C = Q; g.sCm = 1; g.sCn = m;
+    g.M = m; g.N = (int)Rc; g.K = m;
+    LRN_TRY(gemm(c->stream, g));
+    hipLaunchKernelGGL(ragged_coldot_kernel, dim3((ngrp + 3) / 4), dim3(256), 0, c->stream, Q, b.Vc.as<double>(),
+                       b.rg_wc.as<double>(), m, sg, b.rg_gh.as<int>(), sigma, y);
+  }
+  c->counts["op_factored"] += 1;
+  c->counts["op_ragged"] += 1;
+  return LRN_OK;
+}
+
+// K-chunks of the syrk when the option leaves them open: the smallest ks for which tiles x ks fills the chip FOUR times over at
+// the kernel's compiled occupancy (workgroups per CU x CUs, asked of the runtime once), a chunk kept to at least 16 K-steps
+// (256 columns).  The first rule -- fill the chip once, ks = 2 at msz 2000 -- had no measurement behind it; the sweep of
+// tools/ragged_ops_times.py at msz 2000 / nvar 4000 found ks = 8 the fastest or within 4 % of it at
+// Rc = 4015, 6000 and 42 372, which is this rule there.  One matrix side only: a starting point elsewhere
+static int ragged_auto_chunks(long tiles, long Rc) {
+  static long slots = 0;
+  if (slots == 0) {
+    int dev = 0, cus = 0, per = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ragged_syrk_kernel, 256, 0) != hipSuccess || cus <= 0 || per <= 0)
+      slots = 256;
+    else
+      slots = (long)cus * per;
+  }
+  const long want = (4 * slots + tiles - 1) / tiles, cap = ragged_steps(Rc) / 16;
+  return (int)std::max<long>(1, std::min(want, cap));
+}
+
+// M = -sum_c s_c f_c f_c', F = Vc (null) or Yc.  *ks_out = 1: the lower tiles are in M and the caller mirrors them
+// (mirror_lower_tiled_kernel of dataops.hip); > 1: M is complete
+int aat_to_mat_ragged(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const double* F, int* ks_out) {
+  const int m = b.msz;
+  LRN_TRY(ragged_setup(c, b));
+  const long Rc = b.rg_Rc, mm = (long)m * m;
+  if (!F) F = b.Vc.as<double>();
+  const long tm = (m + RG_TILE - 1) / RG_TILE, tiles = tm * (tm + 1) / 2;
+  if (tiles > 2147483647L) return set_error(c, LRN_ERR_ARG, "ragged_ops: %ld tiles", tiles);
+  const int ks = ragged_clamp_chunks(Rc, c->opt.ragged_ops_split > 0 ? c->opt.ragged_ops_split : ragged_auto_chunks(tiles, Rc));
+  double* out = M;
+  if (ks > 1) {
+    LRN_TRY(ensure(c, c->slabs, (size_t)ks * mm * 8));
+    out = c->slabs.as<double>();
+  }
+  hipLaunchKernelGGL(ragged_syrk_kernel, dim3((unsigned)tiles, (unsigned)ks), dim3(256), 0, c->stream, F, m, Rc,
+                     b.rg_wc.as<double>(), b.rg_cg.as<int>(), b.rg_gh.as<int>(),
+                     c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, x, ks, out, mm);
+  if (ks > 1)
+    hipLaunchKernelGGL(ragged_syrk_reduce_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(32, 8), 0, c->stream,
+                       c->slabs.as<double>(), mm, ks, M, m);
+  *ks_out = ks;
+  c->rg_last_chunks = ks;
+  c->counts["op_factored"] += 1;
+  c->counts["op_ragged"] += 1;
   return LRN_OK;
 }
 

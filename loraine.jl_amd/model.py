@@ -55,7 +55,8 @@ class MyModel:
     # block without them and for a materialised block, whose entries hold the diagonal
     diag: list = field(default_factory=list)
     # Optimizer.load_factored_model(..., ragged=True): mode 1 assembles a block of mixed ranks by rank class (ragged_plan below) --
-    # the solver sets the library option lowrank_ragged = 1
+    # the solver sets the library option lowrank_ragged = 1.  ragged="ops": the data operators of such a block run on the
+    # compacted columns as well (ragged_columns below) -- library option ragged_ops = 1 beside it
     ragged: bool = False
 
 
@@ -89,6 +90,40 @@ def ragged_plan(ranks):
             tiles += nt[a] * nt[b]
     return dict(classes=classes, seg=seg, Rc=col, ncls=sum(1 for c in RAGGED_CLASSES if seg[c][1] > seg[c][0]), gh=gh,
                 tiles=tiles)
+
+
+RAGGED_KSTEP = 16                     # K step of the operator kernels on the compacted columns
+RAGGED_MAX_CHUNKS = 16
+
+
+def ragged_chunks(Rc, ks):
+    """The K-chunks of the column range [0, Rc) (csrc/ragged_plan.h::ragged_chunk_cols): nsteps = ceil(Rc / 16), ks clamped to
+    [1, min(16, nsteps)], chunk s = the steps [s nsteps / ks, (s + 1) nsteps / ks) -- uneven where ks does not divide nsteps,
+    the last step a tail.  -> (clamped ks, [(first column, end column)] per chunk)."""
+    Rc, ks = int(Rc), int(ks)
+    nsteps = -(-Rc // RAGGED_KSTEP)
+    ks = max(1, min(ks, RAGGED_MAX_CHUNKS, nsteps))
+    return ks, [(s * nsteps // ks * RAGGED_KSTEP, min((s + 1) * nsteps // ks * RAGGED_KSTEP, Rc)) for s in range(ks)]
+
+
+def ragged_columns(ranks, ks=1):
+    """The compacted column layout the data operators walk under the library option ragged_ops (csrc/ragged_plan.h: cg, the
+    weight pattern and the chunks; ragged_plan above keeps what it returns).  -> dict(Rc, gh = H index per group, start = first
+    column per group, size = class size per group, cg = group per compacted column, wc = per compacted column the index p of
+    the weighted factor column of its constraint it holds (the p-th weighted one, in their original order) or -1 for padding,
+    ks = clamped chunk count, chunks = [(first column, end column)])."""
+    p = ragged_plan(ranks)
+    start, size, cg, wc = [], [], [], []
+    for c in RAGGED_CLASSES:
+        s0, s1 = p["seg"][c]
+        for g in range((s1 - s0) // c):
+            h = p["gh"][len(start)]
+            cg += [len(start)] * c
+            wc += [q if q < int(ranks[h]) else -1 for q in range(c)]
+            start.append(s0 + g * c)
+            size.append(c)
+    ks, chunks = ragged_chunks(p["Rc"], ks)
+    return dict(Rc=p["Rc"], gh=p["gh"], start=start, size=size, cg=cg, wc=wc, ks=ks, chunks=chunks)
 
 
 def check_factored_kit(model, kit):

@@ -96,6 +96,8 @@ class Optimizer:
         ragged=True (opt-in): the Schur assembly groups the constraints of a factored block by rank class instead of padding all
         of them to the largest rank (library option lowrank_ragged) -- for blocks of mixed ranks, a few constraints of rank 9
         beside thousands of rank 1; a block of uniform rank and a sharded run keep the padded route.
+        ragged="ops" is ragged=True and moves the two data operators of such a block, AA vec(.) and mat(AA' .), to the same
+        compacted columns (library option ragged_ops beside lowrank_ragged).
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
         if not self.resident:
@@ -104,8 +106,10 @@ class Optimizer:
         cg_diag = isinstance(cg, str) and cg == "diag"
         if isinstance(cg, str) and not cg_diag:
             raise ValueError(f"load_factored_model: cg is False, True or \"diag\", not {cg!r}")
+        if isinstance(ragged, str) and ragged != "ops":
+            raise ValueError(f"load_factored_model: ragged is False, True or \"ops\", not {ragged!r}")
         self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
-                                      int(factored_form), bool(ragged), cg_diag, bool(cg)))
+                                      int(factored_form), "ops" if ragged == "ops" else bool(ragged), cg_diag, bool(cg)))
         return self
 
     def _copy_to(self):
@@ -121,7 +125,7 @@ class Optimizer:
             model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
             model.factored_cg = bool(cg) and model.factored
             model.factored_cg_diag = cg_diag and model.factored
-            model.ragged = bool(ragged) and model.factored
+            model.ragged = ragged if model.factored else False      # (False, True or "ops")
             check_factored_kit(model, self.options.get("kit", 0))
             check_diag_kit(model, self.options.get("kit", 0))
         else:

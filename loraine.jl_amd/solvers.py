@@ -146,9 +146,15 @@ class MySolver:
                     if cg_diag:
                         self._say(" ---The CG path holds the diagonal parts of the factored blocks (cg_diag = 1)")
                     # load_factored_model(..., ragged=True): blocks of mixed ranks are assembled by rank class
-                    ragged = bool(getattr(model, "ragged", False))
+                    # ... ragged="ops": and their two data operators run on the same compacted columns
+                    rg = getattr(model, "ragged", False)
+                    ragged, ops = bool(rg), isinstance(rg, str) and rg == "ops"
                     self.dev.set_option("lowrank_ragged", 1 if ragged else 0)
-                    if ragged:
+                    self.dev.set_option("ragged_ops", 1 if ops else 0)
+                    if ops:
+                        self._say(" ---The Schur assembly and the data operators group the factored constraints by rank class "
+                                  "(lowrank_ragged = 1, ragged_ops = 1)")
+                    elif ragged:
                         self._say(" ---The Schur assembly groups the factored constraints by rank class (lowrank_ragged = 1)")
                 if self.kit == 1:
                     self.dev.set_option("cg_lowrank", -1)
