@@ -205,7 +205,7 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * over a host-built tile list (raggedops.hip), msz Rc^2 / 2 multiply-adds instead of msz (nvar khat)^2 / 2.  Taken per block
  * when world == 1 and 0 < Rc < nvar khat; a uniform block, an empty one and a sharded run keep the padded route and count
  * "ragged_fallback".  The data operators, the cross terms of a hybrid block and the terms of diagonal parts stay on the
- * padded layout.  Counters: "schur_ragged" (blocks assembled by rank class), "ragged_fallback", and the STATE of the last
+ * padded layout (options "ragged_ops", "ragged_cross" below move them).  Counters: "schur_ragged" (blocks assembled by rank class), "ragged_fallback", and the STATE of the last
  * block assembled that way (survives reset_timing): "ragged_cols" (Rc), "ragged_classes" (classes present), "ragged_tiles";
  * timing key "ragged" (U_c and the tile launch, beside "lowrank_u"),
  * "ragged_ops" (the factor form of AA vec(.) and mat(AA' .) of such a block: 0, default = on the nvar khat padded columns, every
@@ -220,6 +220,17 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * reset_timing); timing keys stay "aa_times" / "aat_to_mat"),
  * "ragged_ops_split" (K-chunks of that launch: 0, default = auto, 1 .. 16 forced, clamped to the K-steps ceil(Rc / 16) of the
  * block; chunk s covers the steps [s nsteps / ks, (s + 1) nsteps / ks) and the chunks are added in the order 0 .. ks - 1),
+ * "ragged_cross" (Y = W V and its consumers in mode 1 of such a block, the cross terms of the stored constraints of a hybrid
+ * block and of the diagonal parts: 0, default = on the nvar khat padded columns, every route, counter, error text and bit as
+ * before; any other value = 1 = on the Rc compacted columns -- Yc = W Vc once per scaling, or the product the rank-class
+ * assembly left when only W exists ("ragged_y_reused"), the cross terms summed by group, C = Ad' (Yc o Yc) class by class.
+ * Independent of the options above, the same condition per block; otherwise the padded code runs bit for bit and
+ * "ragged_cross_fallback" counts.  Counter "schur_cross_ragged", per block and assembly; timing keys stay "hybrid_y",
+ * "hybrid_cross", "diag_cross"),
+ * "ragged_ts" (ts of H_alpha, lrn_prec_setup(1, ..), of such a block on the factor route: 0, default = P = L' Vd and T = Vd' Um
+ * on the padded columns; any other value = 1 = on the compacted ones, every element of the block's part of ts written once.
+ * The same condition per block; otherwise the padded code bit for bit and "ragged_ts_fallback" counts.  Counter
+ * "prec_ts_ragged", blocks of the last setup, "prec_ts_factored" counts them too; timing key "prec_ts_p" stays),
  * "reset_timing".
  * Counters of these options: "op_factored_scaled" (blocks per application through Y), "op_quadform_fused" (blocks per
  * application through the fused kernel), "fac_scaled_y" (products Y = W Vd), "hop_over_budget" (operator choices that found H

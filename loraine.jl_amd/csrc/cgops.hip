@@ -407,6 +407,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
   c->counts["prec_ts_factored"] = 0;
   c->counts["prec_ts_stored_rows"] = 0;
   c->counts["prec_ts_diag_rows"] = 0;
+  c->counts["prec_ts_ragged"] = 0;
   const int n = c->nvar;
   hipStream_t st = c->stream;
   if (kind == 0) return LRN_OK;
@@ -513,6 +514,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     long ts_factored = 0;      // blocks whose part of ts came from the factors ("prec_ts_factored", of the LAST setup)
     long ts_stored = 0;        // rows of ts filled from the stored entries of hybrid blocks ("prec_ts_stored_rows", ditto)
     long ts_diag_rows = 0;     // rows of ts that got the term of their diagonal part ("prec_ts_diag_rows", ditto; option "cg_diag")
+    long ts_ragged = 0;        // blocks among ts_factored whose part came from the compacted columns ("prec_ts_ragged", ditto; option "ragged_ts")
     for (int il = 0; il < c->nlmi; ++il) {
       LmiBlock& b = c->lmi[il];
       const int m = b.msz, k = erank;
@@ -562,29 +564,40 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       // a factored block (option "cg_factored") has no choice to make: there are no entries to take ts from
       if (b.factored || cg_lowrank_ts(c, b, k)) {
         // from the rank-k factors: P = L' Vd and T = Vd' Um, then fac_ts_kernel (the whole nvar x k m block, every element once)
+        // option "ragged_ts": a block of mixed ranks from Pc = L' Vc and Tc = Vc' Um on its Rc compacted columns, then
+        // ragged_ts_kernel (raggedops.hip); a uniform block keeps the padded columns and fac_ts_kernel, bit for bit
+        const bool rts = ragged_ts_on(c, b);
+        if (c->opt.ragged_ts && !rts) c->counts["ragged_ts_fallback"] += 1;
         const int kh = b.lr_khat;
-        const long R = (long)n * kh;
-        LRN_TRY(lowrank_dense_factors(c, b));
+        const long R = rts ? b.rg_Rc : (long)n * kh;
+        if (rts) LRN_TRY(ragged_setup(c, b));
+        else LRN_TRY(lowrank_dense_factors(c, b));
+        const double* Vf = rts ? b.Vc.as<double>() : b.Vd.as<double>();
         LRN_TRY(ensure(c, c->BG, (size_t)m * R * 8));
         LRN_TRY(ensure(c, P->Tf, (size_t)R * k * 8));
         GemmDesc gp;     // P = L' Vd, m x R (the upper triangle of Zf is zero: tril2_kernel)
         gp.A = Zf; gp.sAm = m; gp.sAk = 1;
-        gp.B = b.Vd.as<double>(); gp.sBk = 1; gp.sBn = m;
+        gp.B = Vf; gp.sBk = 1; gp.sBn = m;
         gp.C = c->BG.as<double>(); gp.sCm = 1; gp.sCn = m;
         gp.M = m; gp.N = (int)R; gp.K = m;
         if (c->opt.profile_ops) tic(c);      // (measurement, tools/cg_diag_times.py: this product beside the diagonal-row kernel)
         LRN_TRY(gemm(st, gp));
         if (c->opt.profile_ops) toc(c, "prec_ts_p");
         GemmDesc gt;     // T = Vd' Um, R x k
-        gt.A = b.Vd.as<double>(); gt.sAm = m; gt.sAk = 1;
+        gt.A = Vf; gt.sAm = m; gt.sAk = 1;
         gt.B = Um; gt.sBk = 1; gt.sBn = m;
         gt.C = P->Tf.as<double>(); gt.sCm = 1; gt.sCn = R;
         gt.M = (int)R; gt.N = k; gt.K = m;
         LRN_TRY(gemm(st, gt));
-        hipLaunchKernelGGL(fac_ts_kernel, dim3((n + FTS_TILE - 1) / FTS_TILE, (m + FTS_TILE - 1) / FTS_TILE, k), dim3(256), 0, st,
-                           c->BG.as<double>(), P->Tf.as<double>(), b.v_w.as<double>(),
-                           c->pos_space ? b.ipos_d.as<int>() : (const int*)nullptr, P->d.as<double>(), m, kh, R, n,
-                           P->ts.as<double>() + (size_t)col0 * n);
+        if (rts) {
+          LRN_TRY(ragged_ts(c, b, c->BG.as<double>(), P->Tf.as<double>(), P->d.as<double>(), k,
+                            P->ts.as<double>() + (size_t)col0 * n));
+          ++ts_ragged;
+        } else
+          hipLaunchKernelGGL(fac_ts_kernel, dim3((n + FTS_TILE - 1) / FTS_TILE, (m + FTS_TILE - 1) / FTS_TILE, k), dim3(256), 0, st,
+                             c->BG.as<double>(), P->Tf.as<double>(), b.v_w.as<double>(),
+                             c->pos_space ? b.ipos_d.as<int>() : (const int*)nullptr, P->d.as<double>(), m, kh, R, n,
+                             P->ts.as<double>() + (size_t)col0 * n);
         ++ts_factored;
         if (b.hybrid()) {
           // the stored constraints have weight-0 columns: their rows came out as zeros.  (D^-1/2 A_s u_a)' Z for these npos_nz
@@ -649,6 +662,7 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
     c->counts["prec_ts_factored"] = ts_factored;
     c->counts["prec_ts_stored_rows"] = ts_stored;
     c->counts["prec_ts_diag_rows"] = ts_diag_rows;
+    c->counts["prec_ts_ragged"] = ts_ragged;
     if (P->has_LD)      // ts = L_D^-1 t   (the reference: AAAATtau \ t, Solvers.jl:767)
       LRN_TRY(trsm_left_lower(st, P->LD.as<double>(), n, n, false, P->ts.as<double>(), ksz, n,
                               P->workD.as<double>() + chol_work_doubles(n)));

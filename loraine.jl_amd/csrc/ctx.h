@@ -91,6 +91,9 @@ struct LmiBlock {
   int rg_grp0[6] = {0, 0, 0, 0, 0, 0};
   lrn::DBuf Yc;
   long Yc_version = -1;
+  // options "ragged_cross" / "ragged_ts" (cross terms of the assembly, ts of H_alpha on the compacted columns): H index -> group,
+  // -1 for a constraint of rank 0 -- the inverse of rg_gh, built with the plan
+  lrn::DBuf rg_hg;                                // int32 [nvar]
   // factored block (lrn_set_factored): the factors ARE the constraint data -- AA vec(.) and mat(AA' .) go through Vd
   // (dataops.hip, "factor form"), the Schur matrix through mode 1 only.  Pure: AA has no entry.  Hybrid: a few constraints
   // are stored instead (rows of AA, positions [0, npos_nz) as everywhere) and have weight-0 factor columns; every constraint
@@ -195,6 +198,11 @@ struct LrnOptions {
   int ragged_ops = 0;             // AA vec(.) and mat(AA' .) of a block of mixed ranks in factor form on the compacted columns of the
                                   // rank classes (raggedops.hip): 1, on the padded layout: 0.  Independent of lowrank_ragged; the
                                   // same conditions, the padded code otherwise ("ragged_ops_fallback")
+  int ragged_cross = 0;           // Y = W V and its consumers in the mode-1 assembly of a block of mixed ranks -- the cross terms of a hybrid
+                                  // block and of the diagonal parts -- on the compacted columns (Yc = W Vc): 1, on the padded layout: 0.
+                                  // Independent of the two above; the same conditions, the padded code otherwise ("ragged_cross_fallback")
+  int ragged_ts = 0;              // ts of H_alpha of a block that takes the factor route, P = L' V and T = V' Um, on the compacted columns:
+                                  // 1, on the padded layout: 0.  The same conditions, the padded code otherwise ("ragged_ts_fallback")
   int ragged_ops_split = 0;       // K-chunks of ragged_syrk_kernel: 0 auto, 1 .. 16 forced (clamped to the K-steps of the block)
   int diag_sq_mfma = -1;          // squared-operand product of the diagonal parts (diagops.hip::diag_sq): the MFMA tile form (1), the
                                   // rows form, one wave per column group (0), by the number of diagonal rows (-1)
@@ -319,6 +327,15 @@ inline bool lowrank_ragged_on(const lrn_ctx* c, const LmiBlock& b) {
 // the data operators of a block on the compacted columns under option "ragged_ops": the same condition
 inline bool ragged_ops_on(const lrn_ctx* c, const LmiBlock& b) {
   return c->opt.ragged_ops != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
+}
+// Y and the cross terms of the mode-1 assembly (option "ragged_cross"), ts of H_alpha (option "ragged_ts"): the same condition.
+// Every path they serve refuses world > 1 before it gets here (hybrid blocks, diagonal parts, lrn_prec_setup on factored
+// blocks): the world clause cannot be false today and is kept so that the four conditions read alike
+inline bool ragged_cross_on(const lrn_ctx* c, const LmiBlock& b) {
+  return c->opt.ragged_cross != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
+}
+inline bool ragged_ts_on(const lrn_ctx* c, const LmiBlock& b) {
+  return c->opt.ragged_ts != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
 }
 // hop.hip: the CG operator through the assembled matrix
 // y = H x; qpart (may be null): receives *nq partial sums of x'y (*nq = 0: not formed, e.g. sharded)

@@ -29,6 +29,8 @@
 //     Epilogue: the accumulator element of column c is multiplied by w[c]; kh (a power of two <= 16) divides 16, so a column
 //     group lies on kh neighbouring lanes of one accumulator block and is summed by an xor butterfly of log2 kh steps; the
 //     lane with c % kh == 0 writes D[s, c / kh].
+//   Option "ragged_cross" (DESIGN section 20): C from Yc = W Vc, one launch of either form per rank class, the store going
+//     through a group -> H index map (hmap) -- the one change to both kernels, a null map being the code as it was.
 // No atomics, fixed order in both forms: two calls give the same bits.  The forms differ from each other in rounding.
 //
 // The CG path (option "cg_diag"): the operators above carry the diagonal parts; ts of H_alpha gets their
@@ -38,6 +40,7 @@
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
 #include "ops.h"
+#include "ragged_plan.h"
 
 namespace lrn {
 
@@ -52,7 +55,7 @@ static constexpr int DG_MFMA_MIN = 16; // auto: the MFMA form from this many dia
 
 __global__ __launch_bounds__(256) void diag_sq_rows_kernel(const double* __restrict__ Ad, int ns, const double* __restrict__ B,
                                                            long ldb, int m, int ng, int kh, const double* __restrict__ w,
-                                                           double* __restrict__ D, long ldd) {
+                                                           double* __restrict__ D, long ldd, const int* __restrict__ hmap) {
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= ng) return;                             // (whole wave)
@@ -83,13 +86,13 @@ __global__ __launch_bounds__(256) void diag_sq_rows_kernel(const double* __restr
     double v = acc[t];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0 && s0 + t < ns) D[(long)(s0 + t) * ldd + g] = v;
+    if (lane == 0 && s0 + t < ns) D[(long)(s0 + t) * ldd + (hmap ? hmap[g] : g)] = v;
   }
 }
 
 __global__ __launch_bounds__(256) void diag_sq_mfma_kernel(const double* __restrict__ Ad, int ns, const double* __restrict__ B,
                                                            long ldb, int m, long nc, int kh, const double* __restrict__ w,
-                                                           double* __restrict__ D, long ldd) {
+                                                           double* __restrict__ D, long ldd, const int* __restrict__ hmap) {
   __shared__ double As[DG_T * DG_LD];
   __shared__ double Bs[DG_T * DG_LD];
   const int t = threadIdx.x, lane = t & 63;
@@ -151,14 +154,16 @@ __global__ __launch_bounds__(256) void diag_sq_mfma_kernel(const double* __restr
         double v = acc[ib][jb][r] * wcol;
         for (int off = 1; off < kh; off <<= 1) v += __shfl_xor(v, off, 64);      // (kh is uniform: every lane takes part)
         const int s = s0 + 32 * wr + 16 * ib + kq + 4 * r;
-        if ((ci & (kh - 1)) == 0 && s < ns && cc < nc) D[(long)s * ldd + cc / kh] = v;
+        if ((ci & (kh - 1)) == 0 && s < ns && cc < nc) D[(long)s * ldd + (hmap ? (long)hmap[cc / kh] : cc / kh)] = v;
       }
   }
 }
 
-// D[s * ldd + g] = sum_{p < kh} w[g kh + p] sum_i Ad[i + s m] B[i + (g kh + p) ldb]^2   (w null: weights 1); s < ns, g < ng
+// D[s * ldd + g] = sum_{p < kh} w[g kh + p] sum_i Ad[i + s m] B[i + (g kh + p) ldb]^2   (w null: weights 1); s < ns, g < ng.
+// hmap (option "ragged_cross": the groups of one rank class, B and w starting at its segment): the sum of group g goes to
+// D[s * ldd + hmap[g]] instead -- the store alone differs; null is the code above
 static int diag_sq(lrn_ctx* c, const double* Ad, int ns, const double* B, long ldb, int m, int ng, int kh, const double* w,
-                   double* D, long ldd) {
+                   double* D, long ldd, const int* hmap = nullptr) {
   if (ns <= 0 || ng <= 0 || m <= 0 || kh <= 0) return LRN_OK;
   const bool mfma = c->opt.diag_sq_mfma == 1 || (c->opt.diag_sq_mfma < 0 && ns >= DG_MFMA_MIN);
   const long nc = (long)ng * kh;
@@ -168,13 +173,13 @@ static int diag_sq(lrn_ctx* c, const double* Ad, int ns, const double* B, long l
     const long tx = (nc + DG_T - 1) / DG_T, ty = (ns + DG_T - 1) / DG_T;
     if (tx > 2147483647L || ty > 65535) return set_error(c, LRN_ERR_ARG, "diag_sq: %ld x %ld tiles", tx, ty);
     hipLaunchKernelGGL(diag_sq_mfma_kernel, dim3((unsigned)tx, (unsigned)ty), dim3(256), 0, c->stream, Ad, ns, B, ldb, m, nc,
-                       kh, w, D, ldd);
+                       kh, w, D, ldd, hmap);
     c->counts["diag_sq_mfma"] += 1;
   } else {
     const long ty = (ns + DG_ROWS - 1) / DG_ROWS;
     if (ty > 65535) return set_error(c, LRN_ERR_ARG, "diag_sq: %ld row groups (rows form)", ty);
     hipLaunchKernelGGL(diag_sq_rows_kernel, dim3((unsigned)((ng + 3) / 4), (unsigned)ty), dim3(256), 0, c->stream, Ad, ns, B,
-                       ldb, m, ng, kh, w, D, ldd);
+                       ldb, m, ng, kh, w, D, ldd, hmap);
     c->counts["diag_sq_rows"] += 1;
   }
   return LRN_OK;
@@ -273,7 +278,20 @@ int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y) {
   // C = Ad' (Y o Y), weighted by d and summed over khat: dg_n x nvar by H index (row s contiguous), then C + C'
   tic(c);
   LRN_TRY(ensure(c, c->dgC, (size_t)ns * n * 8));
-  LRN_TRY(diag_sq(c, Ad, ns, Y, m, m, n, kh, b.v_w.as<double>(), c->dgC.as<double>(), n));
+  if (ragged_cross_on(c, b)) {
+    // option "ragged_cross": Y is Yc = W Vc (factored_y).  Inside one class segment the group size is uniform, so either form
+    // runs per class on B = Yc + seg0 msz, w = wc + seg0 and stores through the class's part of gh; a constraint of rank 0 has
+    // no writer: C is zeroed first
+    LRN_TRY(ragged_setup(c, b));
+    LRN_HIP(c, hipMemsetAsync(c->dgC.p, 0, (size_t)ns * n * 8, c->stream));
+    for (int ci = 0; ci < RG_NCLS; ++ci) {
+      const int ngc = b.rg_grp0[ci + 1] - b.rg_grp0[ci];
+      if (ngc <= 0) continue;
+      LRN_TRY(diag_sq(c, Ad, ns, Y + b.rg_seg0[ci] * m, m, m, ngc, ragged_class_size(ci), b.rg_wc.as<double>() + b.rg_seg0[ci],
+                      c->dgC.as<double>(), n, b.rg_gh.as<int>() + b.rg_grp0[ci]));
+    }
+  } else
+    LRN_TRY(diag_sq(c, Ad, ns, Y, m, m, n, kh, b.v_w.as<double>(), c->dgC.as<double>(), n));
   hipLaunchKernelGGL(diag_cross_scatter_kernel, dim3((n - b.npos_nz + 255) / 256, gy), dim3(256), 0, c->stream,
                      c->dgC.as<double>(), ns, dgh, b.dg_of_pos.as<int>(), b.hidx.as<int>(), b.npos_nz, n, H, n);
   toc(c, "diag_cross");

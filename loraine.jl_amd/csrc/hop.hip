@@ -298,7 +298,7 @@ bool fac_quadform_on(const lrn_ctx* c, const LmiBlock& b) {
 static double est_ts_s(const lrn_ctx* c, const LmiBlock& b, int erank, bool factors) {
   const double m = b.msz, n = c->nvar, k = erank;
   if (factors) {
-    const double R = n * b.lr_khat;
+    const double R = ragged_ts_on(c, b) ? (double)b.rg_Rc : n * b.lr_khat;      // option "ragged_ts": on the Rc compacted columns
     return 2.0 * m * m * R / 4.0e13 + 2.0 * m * R * k / 1.0e13 + k * (m * R + m * n) * 8.0 / 3.0e12 + 20e-6;      // three launches in all
   }
   return k * ((double)b.nd * m * m * 8.0 / 1.0e12 + (double)(b.nent) * 2.0e-10 + n * m * 8.0 / 3.0e12 + 2.0 * n * m * m / 4.0e13 + 25e-6);
@@ -322,6 +322,8 @@ static double est_assemble_s(const lrn_ctx* c, int mode) {
       // option "lowrank_ragged": the two products run on the Rc compacted columns (raggedops.hip); everything below stays
       // on the padded layout
       const double Rp = lowrank_ragged_on(c, b) ? (double)b.rg_Rc : R;
+      // option "ragged_cross": Y, the cross terms of a hybrid block and C of the diagonal parts on the compacted columns too
+      const double Rx = ragged_cross_on(c, b) ? (double)b.rg_Rc : R;
       t += (2.0 * Rp * m * m + 0.5 * Rp * Rp * m) / 3.4e13;
       if (b.factored && b.dg_n > 0) {
         // diagonal parts (assemble_diag), at the rates section 16 MEASURED at msz 2000 / nvar 4000 / khat 2 / 4000 rows -- those
@@ -329,14 +331,14 @@ static double est_assemble_s(const lrn_ctx* c, int mode) {
         // lower tiles of P Ad, 2 dg_n m^2 + dg_n^2 m = 64 GFLOP in 1.6 ms; Y = W Vd of a pure block at the rate of the hybrid
         // term below (a hybrid block pays it there); four launches and the scatters
         const double ns = b.dg_n;
-        t += 2.0 * ns * m * R / (1.28e11 / 2.8e-3) + (2.0 * ns * m * m + ns * ns * m) / (6.4e10 / 1.6e-3) + 40e-6;
-        if (!b.hybrid()) t += 2.0 * R * m * m / 3.4e13;
+        t += 2.0 * ns * m * Rx / (1.28e11 / 2.8e-3) + (2.0 * ns * m * m + ns * ns * m) / (6.4e10 / 1.6e-3) + 40e-6;
+        if (!b.hybrid()) t += 2.0 * Rx * m * m / 3.4e13;
         else t += (double)b.nd * 2.0 * m * m * m / 3.4e13 + 2.0 * (double)b.npos_nz * m * ns / 3.4e13;      // t_s of the dense slots, T Ad
       }
       if (!b.hybrid()) continue;
       // hybrid: Y = W Vd once more when G exists, the cross terms -- nnz(A_s) R multiply-adds per stored constraint at the
       // pair rate below, one product A_s Y per dense slot -- and H_SS over the stored positions by the mode-0 terms
-      t += 2.0 * R * m * m / 3.4e13 + (double)b.nent * R * 4.0e-12 + nd * 2.0 * R * m * m / 3.4e13;
+      t += 2.0 * Rx * m * m / 3.4e13 + (double)b.nent * Rx * 4.0e-12 + nd * 2.0 * Rx * m * m / 3.4e13;
     }
     if (b.nd > 0) t += (4.0 / 3.0 * nd * m * m * m + 0.5 * nd * nd * m * m + nd * (n - nd) * m * m * 0.5) / 6.0e13;
     double s1 = 0.0, s2 = 0.0;       // sum over sparse pairs of nnz_i nnz_j = ((sum nnz)^2 + sum nnz^2) / 2

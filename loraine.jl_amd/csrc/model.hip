@@ -176,7 +176,7 @@ static void free_block(LmiBlock& b) {
   for (DBuf* d : {&b.ent_ptr, &b.ent_r, &b.ent_c, &b.ent_v, &b.Adense, &b.hidx, &b.sigma_d, &b.ipos_d, &b.cq_q, &b.cq_ptr, &b.cq_j, &b.cq_v, &b.pc_ptr, &b.pc_r, &b.pc_t, &b.ent_t, &b.Mv, &b.Zs, &b.b_ptr, &b.b_col,
                   &b.b_val, &b.X, &b.S, &b.W, &b.G, &b.Gi, &b.Si, &b.D, &b.DDsi, &b.Vprev, &b.Cd, &b.Rd, &b.delX, &b.delS, &b.Xn, &b.Sn, &b.RNT,
                   &b.t0, &b.t1, &b.t2, &b.LXf, &b.LXt, &b.LSf, &b.Yh, &b.Zh, &b.Ki, &b.Bs, &b.TX, &b.Qm, &b.lyap, &b.Bd, &b.v_ptr, &b.v_col, &b.v_val, &b.v_w, &b.Vd, &b.Ys,
-                  &b.rg_src, &b.rg_wc, &b.rg_gh, &b.rg_tiles, &b.rg_cg, &b.Vc, &b.Yc, &b.dg_h, &b.dg_nat, &b.dg_of_pos, &b.dg_a})
+                  &b.rg_src, &b.rg_wc, &b.rg_gh, &b.rg_hg, &b.rg_tiles, &b.rg_cg, &b.Vc, &b.Yc, &b.dg_h, &b.dg_nat, &b.dg_of_pos, &b.dg_a})
     release(*d);
   b.dg_n = 0;
   b.rg_ready = false;
@@ -665,7 +665,7 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
   release(b.Vd);                 // (the dense copy is rebuilt from these factors on first use)
   b.have_Vd = false;
   b.Ys_version = -1;             // (and Y = W Vd of option "fac_op_scaled" with it)
-  for (DBuf* rg : {&b.rg_src, &b.rg_wc, &b.rg_gh, &b.rg_tiles, &b.rg_cg, &b.Vc, &b.Yc}) release(*rg);      // (and the rank-class plan, option
+  for (DBuf* rg : {&b.rg_src, &b.rg_wc, &b.rg_gh, &b.rg_hg, &b.rg_tiles, &b.rg_cg, &b.Vc, &b.Yc}) release(*rg);      // (and the rank-class plan, option
   b.rg_ready = false;                                                                      // "lowrank_ragged": rebuilt on first use)
   b.Yc_version = -1;
   b.rg_Rc = ragged_cols(wh.data(), nvar, khat);

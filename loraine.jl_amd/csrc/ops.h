@@ -84,7 +84,7 @@ bool chol_path_applicable(lrn_ctx* c, LmiBlock& b, long* pcap_out);
 // schur_factored.hip: rank-one data (mode -1), rank-k data (mode 1), cross terms of a hybrid factored block
 int assemble_rank1(lrn_ctx* c, LmiBlock& b);
 int assemble_lowrank(lrn_ctx* c, LmiBlock& b);
-int factored_y(lrn_ctx* c, LmiBlock& b, const double** Y);      // Y = W Vd (msz x nvar khat) after assemble_lowrank: its U, or one more product
+int factored_y(lrn_ctx* c, LmiBlock& b, const double** Y);      // Y = W Vd (msz x nvar khat) after assemble_lowrank: its U, or one more product; Yc = W Vc (msz x Rc) under ragged_cross_on
 int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);
 // raggedops.hip: H_FF of a block of mixed ranks by rank class (option "lowrank_ragged"; assemble_lowrank decides)
 int assemble_ragged(lrn_ctx* c, LmiBlock& b);
@@ -96,6 +96,11 @@ int ragged_scaled_y(lrn_ctx* c, LmiBlock& b);
 int aa_times_ragged(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused);            // y[nat] -= sum_c wc <(Z Vc)_c, Vc_c> by group
 // M = -F diag(wc o x) F', F = Vc (null) or Yc; *ks = 1: lower tiles only, the caller mirrors them
 int aat_to_mat_ragged(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const double* F, int* ks);
+// ... the cross terms of a hybrid block on Yc = W Vc, by group (option "ragged_cross"; factored_y hands Yc out, assemble_cross
+// and assemble_diag follow it) and ts of H_alpha from Pc = L' Vc (msz x Rc) and Tc = Vc' Um (Rc x erank) (option "ragged_ts";
+// prec_setup decides): every element of the block's nvar x erank msz part of ts written once
+int assemble_cross_ragged(lrn_ctx* c, LmiBlock& b, const double* Yc);
+int ragged_ts(lrn_ctx* c, LmiBlock& b, const double* Pc, const double* Tc, const double* d, int erank, double* ts);
 // diagops.hip: diagonal parts of a factored block (lrn_upload_diag), A_k = diag(a_k) + V_k D_k V_k'
 int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y);    // H_DD, the cross terms with the factors (Y) and with the stored rows
 int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // y[nat(s)] -= sum_i a_si Z_ii

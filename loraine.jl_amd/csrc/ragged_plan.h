@@ -1,7 +1,8 @@
 // Host-side plan of the rank-class route of the rank-k Schur assembly (option "lowrank_ragged", raggedops.hip): the constraints
 // of a block grouped by rank class, the compacted column layout and the tile list of the one launch.  Pure functions of the
 // factor weights -- no context, no HIP runtime call -- in the style of schur_plan.h.  Python specification: model.ragged_plan;
-// the column -> group map and the K-chunks of the data operators (option "ragged_ops"): model.ragged_columns, ragged_chunks.
+// the column -> group map and the K-chunks of the data operators (option "ragged_ops"): model.ragged_columns, ragged_chunks;
+// the H index -> group map of the cross terms and of ts of H_alpha (options "ragged_cross", "ragged_ts"): ragged_columns' hg.
 //
 // Rank r_j of constraint j = its factor columns of non-zero weight; class c_j = the smallest of {1, 2, 4, 8, 16} >= r_j.  A
 // constraint of rank 0 (a stored row of a hybrid block, a purely diagonal row, an empty constraint) has no group.  Classes are
@@ -33,6 +34,7 @@ struct RaggedPlan {
   long seg0[RG_NCLS] = {0, 0, 0, 0, 0}, seg1[RG_NCLS] = {0, 0, 0, 0, 0};      // columns of class ci: [seg0, seg1)
   int grp0[RG_NCLS] = {0, 0, 0, 0, 0};                  // first group of class ci
   std::vector<int> gh;                                  // group -> H index
+  std::vector<int> hg;                                  // H index -> group, -1 for a constraint of rank 0 (the inverse of gh)
   std::vector<int> cg;                                  // compacted column -> group (option "ragged_ops": the data operators)
   std::vector<long> src;                                // compacted column -> padded column h khat + p, -1 for padding
   std::vector<double> wc;                               // weight of the compacted column (0 in the padding)
@@ -116,6 +118,7 @@ inline RaggedPlan plan_ragged(const double* w, int nvar, int khat, bool with_til
   }
   p.Rc = col;
   p.gh.reserve(grp);
+  p.hg.assign(nvar, -1);
   p.src.assign(p.Rc, -1);
   p.wc.assign(p.Rc, 0.0);
   p.cg.assign(p.Rc, 0);
@@ -124,6 +127,7 @@ inline RaggedPlan plan_ragged(const double* w, int nvar, int khat, bool with_til
     for (long h = 0; h < nvar; ++h) {
       if (cls[h] != ci) continue;
       for (int q = 0; q < ragged_class_size(ci); ++q) p.cg[at + q] = (int)p.gh.size();
+      p.hg[h] = (int)p.gh.size();
       p.gh.push_back((int)h);
       long k = at;
       for (int q = 0; q < khat; ++q)

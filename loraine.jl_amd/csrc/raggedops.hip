@@ -1,5 +1,6 @@
 // Rank-class route of the rank-k Schur assembly (option "lowrank_ragged", schur_factored.hip::assemble_lowrank), and below it
-// the two data operators in factor form on the same compacted columns (option "ragged_ops", dataops.hip).
+// the two data operators in factor form on the same compacted columns (option "ragged_ops", dataops.hip), the cross terms of a
+// hybrid block (option "ragged_cross") and ts of H_alpha (option "ragged_ts", cgops.hip) at the end of the file.
 //
 // The padded route pads every constraint of a block to khat columns, khat from the LARGEST rank, and pays msz R^2 multiply-adds
 // for H_FF = blocksum(d d' o (U' V)^2), R = nvar khat.  Here the constraints are grouped by rank class (ragged_plan.h): class c_j
@@ -156,6 +157,8 @@ int ragged_setup(lrn_ctx* c, LmiBlock& b) {
   LRN_TRY(copy_in(c, b.rg_tiles.p, p.tiles.data(), p.tiles.size() * sizeof(RaggedTile)));
   LRN_TRY(ensure(c, b.rg_cg, (size_t)p.Rc * 4));
   LRN_TRY(copy_in(c, b.rg_cg.p, p.cg.data(), (size_t)p.Rc * 4));
+  LRN_TRY(ensure(c, b.rg_hg, (size_t)n * 4));
+  LRN_TRY(copy_in(c, b.rg_hg.p, p.hg.data(), (size_t)n * 4));
   for (int ci = 0; ci < RG_NCLS; ++ci) { b.rg_seg0[ci] = p.seg0[ci]; b.rg_grp0[ci] = p.grp0[ci]; }
   b.rg_grp0[RG_NCLS] = (int)p.gh.size();
   LRN_TRY(ensure(c, b.Vc, (size_t)m * p.Rc * 8));
@@ -194,7 +197,8 @@ int assemble_ragged(lrn_ctx* c, LmiBlock& b) {
                        fromW ? b.Vc.as<double>() : U, m, b.rg_tiles.as<RaggedTile>(), b.rg_wc.as<double>(), b.rg_gh.as<int>(),
                        c->H.as<double>(), n);
   toc(c, "ragged");
-  c->BG_ragged = true;     // (BG holds U_c, not Y = W Vd: factored_y forms its own product)
+  c->BG_ragged = true;     // (BG holds U_c, not Y = W Vd: factored_y forms its own product -- or, under "ragged_cross" with W
+                           // only, hands out this U_c = W Vc as Yc)
   c->counts["schur_ragged"] += 1;
   c->rg_last_cols = Rc;
   c->rg_last_classes = b.rg_ncls;
@@ -497,6 +501,204 @@ int aat_to_mat_ragged(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const
   c->rg_last_chunks = ks;
   c->counts["op_factored"] += 1;
   c->counts["op_ragged"] += 1;
+  return LRN_OK;
+}
+
+// ================================================================ cross terms of a hybrid block on the compacted columns
+// Option "ragged_cross" (schur_factored.hip::factored_y, assemble_cross decide): H_sj = sum_c wc_c y_c' A_s y_c over the columns
+// c of the GROUP of the factored constraint j, y_c the columns of Yc = W Vc (msz x Rc).  A constraint of rank 0 has no group and
+// receives nothing (the padded kernel adds + 0 to its entries).
+//
+// ragged_cross_kernel: fac_cross_kernel of schur_factored.hip with grid.x over the groups instead of the factored positions --
+// hj = gh[g], the columns group start .. + class size, weight-0 padding skipped (uniform over the workgroup).  Everything else
+// is that kernel's: workgroup (g, y) takes the 32 sparse-tier stored positions s_lo + 32 y .., wave v the positions + 4 t + v,
+// t < 8, in eight register sums; a column of Yc is staged in LDS (msz x 8 bytes, dynamic) or read from global memory by the
+// same code; lanes stride the entry list of A_s, one shuffle tree in a fixed order, the sum weighted and added over the
+// columns in order; lane 0 adds the eight sums to H, one writer per entry, no atomics.  LDS accesses: the staging writes are
+// ds_write_b64 of consecutive doubles (lane l -> dwords 2 l, 2 l + 1 of a 256-dword run: conflict-free); the gather reads
+// ycol[r], ycol[cc] follow the entry list of A_s, their banks are data-dependent -- an entry list sorted by column reads one
+// address for cc (a broadcast) and scattered rows for r, anything from free to a multi-way conflict.  Derived, not measured.
+template <bool LDS>
+__global__ __launch_bounds__(256) void ragged_cross_kernel(const long* __restrict__ ptr, const int* __restrict__ er,
+                                                           const int* __restrict__ ec, const double* __restrict__ ev,
+                                                           const double* __restrict__ Yc, const double* __restrict__ wc, int m,
+                                                           RaggedSegs sg, int s_lo, int s_hi, const int* __restrict__ gh,
+                                                           const int* __restrict__ hidx, double* __restrict__ H, int ldh) {
+  extern __shared__ double rg_ycol[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x;
+  if (g >= sg.grp0[RG_NCLS]) return;             // (whole workgroup)
+  int cj;
+  const long c0 = ragged_group_col(sg, g, &cj);
+  const int hj = gh[g];
+  const int sb = s_lo + blockIdx.y * 32 + wave;
+  double acc[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) acc[t] = 0.0;
+  for (int p = 0; p < cj; ++p) {
+    const long col = c0 + p;
+    const double wp = wc[col];
+    if (wp == 0.0) continue;                     // padding column (uniform over the workgroup)
+    const double* __restrict__ yg = Yc + col * m;
+    if (LDS) {
+      __syncthreads();                           // the waves are done with the previous column
+      for (int r = threadIdx.x; r < m; r += 256) rg_ycol[r] = yg[r];
+      __syncthreads();
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int sp = sb + 4 * t;                 // wave-uniform
+      if (sp >= s_hi) continue;
+      double q = 0.0;
+      for (long e = ptr[sp] + lane; e < ptr[sp + 1]; e += 64) {
+        const int r = er[e], cc = ec[e];
+        q += ev[e] * (LDS ? rg_ycol[r] * rg_ycol[cc] : yg[r] * yg[cc]);
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
+      acc[t] += wp * q;
+    }
+  }
+  if (lane != 0) return;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const int sp = sb + 4 * t;
+    if (sp >= s_hi) continue;
+    H[h_lower(hidx[sp], hj, ldh)] += acc[t];
+  }
+}
+
+// dense slot s: Q = A_s Yc is one product (msz x Rc), H_sj = sum_c wc_c <Q(:, c), Yc(:, c)> one wave per group (the sums of
+// fac_cross_coldot_kernel), written once.  No LDS
+__global__ __launch_bounds__(256) void ragged_cross_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Yc,
+                                                                  const double* __restrict__ wc, int m, RaggedSegs sg, int s,
+                                                                  const int* __restrict__ gh, const int* __restrict__ hidx,
+                                                                  double* __restrict__ H, int ldh) {
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= sg.grp0[RG_NCLS]) return;             // (whole wave)
+  int cj;
+  const long c0 = ragged_group_col(sg, g, &cj);
+  double acc = 0.0;
+  for (int p = 0; p < cj; ++p) {
+    const long col = c0 + p;
+    const double wp = wc[col];
+    if (wp == 0.0) continue;
+    const double* __restrict__ q = Q + col * m;
+    const double* __restrict__ y = Yc + col * m;
+    double t = 0.0;
+    for (int r = lane; r < m; r += 64) t += q[r] * y[r];
+    acc += wp * t;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if (lane != 0) return;
+  H[h_lower(hidx[s], gh[g], ldh)] += acc;
+}
+
+// the caller (assemble_cross) has checked the route (ragged_cross_on) and that factored positions exist; Yc from factored_y
+int assemble_cross_ragged(lrn_ctx* c, LmiBlock& b, const double* Yc) {
+  const int n = c->nvar, m = b.msz;
+  if (!Yc) return set_error(c, LRN_ERR_STATE, "ragged_cross: Yc = W Vc was not formed");
+  LRN_TRY(ragged_setup(c, b));
+  const long Rc = b.rg_Rc;
+  const RaggedSegs sg = ragged_segs(b);
+  const int ngrp = sg.grp0[RG_NCLS];
+  if (ngrp <= 0) return LRN_OK;
+  tic(c);
+  if (b.npos_nz > b.nd) {
+    const size_t cap = c->opt.fac_cross_lds == 1 ? 65536 : 32768;      // the rule of assemble_cross
+    const bool lds = c->opt.fac_cross_lds != 0 && (size_t)m * 8 <= cap;
+    const dim3 grid((unsigned)ngrp, (unsigned)((b.npos_nz - b.nd + 31) / 32));
+#define LRN_RCROSS_LAUNCH(L, SH)                                                                                          \
+  hipLaunchKernelGGL(ragged_cross_kernel<L>, grid, dim3(256), SH, c->stream, b.ent_ptr.as<long>(), b.ent_r.as<int>(),    \
+                     b.ent_c.as<int>(), b.ent_v.as<double>(), Yc, b.rg_wc.as<double>(), m, sg, b.nd, b.npos_nz,           \
+                     b.rg_gh.as<int>(), b.hidx.as<int>(), c->H.as<double>(), n)
+    if (lds) LRN_RCROSS_LAUNCH(true, (size_t)m * 8);
+    else LRN_RCROSS_LAUNCH(false, 0);
+#undef LRN_RCROSS_LAUNCH
+    c->counts[lds ? "hybrid_cross_lds" : "hybrid_cross_global"] += 1;
+  }
+  if (b.nd > 0) {
+    LRN_TRY(ensure(c, c->P, (size_t)m * Rc * 8));
+    double* Q = c->P.as<double>();
+    for (int s = 0; s < b.nd; ++s) {
+      GemmDesc g;     // Q = A_s Yc
+      g.A = b.Adense.as<double>() + (long)s * m * m; g.sAm = 1; g.sAk = m;
+      g.B = Yc; g.sBk = 1; g.sBn = m;
+      g.C = Q; g.sCm = 1; g.sCn = m;
+      g.M = m; g.N = (int)Rc; g.K = m;
+      LRN_TRY(gemm(c->stream, g));
+      hipLaunchKernelGGL(ragged_cross_coldot_kernel, dim3((ngrp + 3) / 4), dim3(256), 0, c->stream, Q, Yc, b.rg_wc.as<double>(),
+                         m, sg, s, b.rg_gh.as<int>(), b.hidx.as<int>(), c->H.as<double>(), n);
+    }
+    c->counts["hybrid_cross_dense"] += 1;
+  }
+  toc(c, "hybrid_cross");
+  return LRN_OK;
+}
+
+// ================================================================ ts of H_alpha on the compacted columns
+// Option "ragged_ts" (cgops.hip::prec_setup decides): with Pc = L' Vc (msz x Rc) and Tc = Vc' Um (Rc x erank),
+//     ts[j, col0 + a m + r] = -(1 / sqrt(d_j)) sum_{c in group of j} wc_c Tc[c, a] Pc[r, c]
+// -- the sum fac_ts_kernel of cgops.hip forms over the khat padded columns of constraint j, over the class-size columns of its
+// group instead, in the same order (the weighted columns keep their order in a group), padding skipped.
+//
+// ragged_ts_kernel keeps that kernel's tiling: workgroup tile = 64 natural rows j x 64 rows r of Pc, eigenvector = blockIdx.z;
+// wave w takes the constraints j0 + w, j0 + w + 4, ..: h = ipos ? ipos[j] : j, g = hg[h], the columns group start .. + class
+// size; its 64 lanes read 64 consecutive doubles of each column of Pc (512 B per load) with the coefficient wc_c Tc[c, a] as a
+// wave-uniform scalar.  hg[h] < 0 (rank 0: a stored row, a purely diagonal row) stores 0, as do rows j >= nvar and r >= msz of
+// a partial tile.  The sums go to row jl of an LDS tile of 64 x 65 doubles (33 280 bytes): ds_write_b64, lane l at dwords
+// 130 jl + 2 l -- 64 consecutive doubles, conflict-free.  After the barrier lane l of wave w reads tile[l][rr], rr = w, w + 4, ..:
+// dword address 130 l + 2 rr, bank (2 l + 2 rr) mod 64 -- the 32 lanes of a half take the 32 even banks and their odd
+// neighbours once each: conflict-free, where a row stride of 64 doubles would put all of them on one bank pair.  Derived from
+// the bank rule as for fac_ts_kernel, not measured.  The wave then writes 64 consecutive rows j of one column of ts.  Every
+// element of the block's part of ts is written exactly once: no memset, no atomics, two setups give the same bits.
+static constexpr int RTS_TILE = 64;
+__global__ __launch_bounds__(256) void ragged_ts_kernel(const double* __restrict__ Pm, const double* __restrict__ T,
+                                                        const double* __restrict__ wc, RaggedSegs sg, const int* __restrict__ hg,
+                                                        const int* __restrict__ ipos, const double* __restrict__ d, int m, long Rc,
+                                                        int nvar, double* __restrict__ ts) {
+  __shared__ double tile[RTS_TILE][RTS_TILE + 1];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int j0 = blockIdx.x * RTS_TILE, r0 = blockIdx.y * RTS_TILE, a = blockIdx.z;
+  const double* __restrict__ Ta = T + (long)a * Rc;
+  const int r = r0 + lane;
+  for (int jl = wv; jl < RTS_TILE; jl += 4) {
+    const int j = j0 + jl;
+    double s = 0.0;
+    if (j < nvar) {                                  // (wave-uniform)
+      const int g = hg[ipos ? ipos[j] : j];
+      if (g >= 0) {                                  // (rank 0: no group, the row stays zero)
+        int cj;
+        const long c0 = ragged_group_col(sg, g, &cj);
+        for (int p = 0; p < cj; ++p) {
+          const double wp = wc[c0 + p];
+          if (wp == 0.0) continue;                   // padding column
+          const double cf = wp * Ta[c0 + p];
+          if (r < m) s += cf * Pm[(c0 + p) * m + r];
+        }
+      }
+    }
+    tile[jl][lane] = s;
+  }
+  __syncthreads();
+  const int j = j0 + lane;
+  if (j >= nvar) return;
+  const double sc = -1.0 / sqrt(d[j]);
+  double* __restrict__ out = ts + (long)a * m * nvar + j;
+  for (int rr = wv; rr < RTS_TILE && r0 + rr < m; rr += 4) out[(long)(r0 + rr) * nvar] = sc * tile[lane][rr];
+}
+
+int ragged_ts(lrn_ctx* c, LmiBlock& b, const double* Pc, const double* Tc, const double* d, int erank, double* ts) {
+  const int n = c->nvar, m = b.msz;
+  LRN_TRY(ragged_setup(c, b));
+  const long tx = (n + RTS_TILE - 1) / RTS_TILE, ty = (m + RTS_TILE - 1) / RTS_TILE;
+  if (ty > 65535 || erank > 65535) return set_error(c, LRN_ERR_ARG, "ragged_ts: %ld row tiles, erank %d", ty, erank);
+  hipLaunchKernelGGL(ragged_ts_kernel, dim3((unsigned)tx, (unsigned)ty, (unsigned)erank), dim3(256), 0, c->stream, Pc, Tc,
+                     b.rg_wc.as<double>(), ragged_segs(b), b.rg_hg.as<int>(),
+                     c->pos_space ? b.ipos_d.as<int>() : (const int*)nullptr, d, m, b.rg_Rc, n, ts);
   return LRN_OK;
 }
 

@@ -245,6 +245,26 @@ int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
   const int n = c->nvar, m = b.msz, kh = b.lr_khat;
   const long R = (long)n * kh;
   if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");
+  // option "ragged_cross": Yc = W Vc (msz x Rc) instead -- what the rank-class route left in BG when only W exists, the product
+  // ragged_scaled_y caches per scaling otherwise (shared with the operator under "fac_op_scaled").  assemble_cross and
+  // assemble_diag ask the same condition and read the compacted layout
+  if (c->opt.ragged_cross) {
+    if (ragged_cross_on(c, b)) {
+      LRN_TRY(ragged_setup(c, b));
+      tic(c);
+      if (c->BG_ragged && !b.have_G) {
+        *Yout = c->BG.as<double>();
+        c->counts["ragged_y_reused"] += 1;
+      } else {
+        LRN_TRY(ragged_scaled_y(c, b));
+        *Yout = b.Yc.as<double>();
+      }
+      toc(c, "hybrid_y");
+      c->counts["schur_cross_ragged"] += 1;
+      return LRN_OK;
+    }
+    c->counts["ragged_cross_fallback"] += 1;
+  }
   const double* Y = c->BG.as<double>();
   tic(c);
   if (b.have_G || c->BG_ragged) {      // (after the rank-class route BG holds U_c in the compacted layout)
@@ -267,6 +287,7 @@ int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y) {
   const long R = (long)n * kh;
   const int nf = n - b.npos_nz;
   if (nf <= 0) return LRN_OK;
+  if (ragged_cross_on(c, b)) return assemble_cross_ragged(c, b, Y);      // (Y is Yc then: factored_y)
   tic(c);
   if (b.npos_nz > b.nd) {
     const size_t cap = c->opt.fac_cross_lds == 1 ? 65536 : 32768;      // bytes of one column: forced / by default

@@ -56,7 +56,8 @@ class MyModel:
     diag: list = field(default_factory=list)
     # Optimizer.load_factored_model(..., ragged=True): mode 1 assembles a block of mixed ranks by rank class (ragged_plan below) --
     # the solver sets the library option lowrank_ragged = 1.  ragged="ops": the data operators of such a block run on the
-    # compacted columns as well (ragged_columns below) -- library option ragged_ops = 1 beside it
+    # compacted columns as well (ragged_columns below) -- library option ragged_ops = 1 beside it.  ragged="all": so do the cross
+    # terms of the assembly (stored rows, diagonal parts) and ts of H_alpha -- ragged_cross = 1 and ragged_ts = 1 beside the two
     ragged: bool = False
 
 
@@ -111,7 +112,8 @@ def ragged_columns(ranks, ks=1):
     weight pattern and the chunks; ragged_plan above keeps what it returns).  -> dict(Rc, gh = H index per group, start = first
     column per group, size = class size per group, cg = group per compacted column, wc = per compacted column the index p of
     the weighted factor column of its constraint it holds (the p-th weighted one, in their original order) or -1 for padding,
-    ks = clamped chunk count, chunks = [(first column, end column)])."""
+    ks = clamped chunk count, chunks = [(first column, end column)], hg = group per H index, -1 for a constraint of rank 0 --
+    the inverse of gh that the cross terms and ts of H_alpha walk under the library options ragged_cross and ragged_ts)."""
     p = ragged_plan(ranks)
     start, size, cg, wc = [], [], [], []
     for c in RAGGED_CLASSES:
@@ -123,7 +125,10 @@ def ragged_columns(ranks, ks=1):
             start.append(s0 + g * c)
             size.append(c)
     ks, chunks = ragged_chunks(p["Rc"], ks)
-    return dict(Rc=p["Rc"], gh=p["gh"], start=start, size=size, cg=cg, wc=wc, ks=ks, chunks=chunks)
+    hg = [-1] * len(p["classes"])
+    for g, h in enumerate(p["gh"]):
+        hg[h] = g
+    return dict(Rc=p["Rc"], gh=p["gh"], start=start, size=size, cg=cg, wc=wc, ks=ks, chunks=chunks, hg=hg)
 
 
 def check_factored_kit(model, kit):

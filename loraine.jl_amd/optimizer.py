@@ -98,6 +98,8 @@ class Optimizer:
         beside thousands of rank 1; a block of uniform rank and a sharded run keep the padded route.
         ragged="ops" is ragged=True and moves the two data operators of such a block, AA vec(.) and mat(AA' .), to the same
         compacted columns (library option ragged_ops beside lowrank_ragged).
+        ragged="all" is ragged="ops" and moves what else walked the padded columns there too: Y = W V with the cross terms of
+        stored constraints and diagonal parts in the assembly, and ts of H_alpha (library options ragged_cross and ragged_ts).
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
         if not self.resident:
@@ -106,10 +108,10 @@ class Optimizer:
         cg_diag = isinstance(cg, str) and cg == "diag"
         if isinstance(cg, str) and not cg_diag:
             raise ValueError(f"load_factored_model: cg is False, True or \"diag\", not {cg!r}")
-        if isinstance(ragged, str) and ragged != "ops":
-            raise ValueError(f"load_factored_model: ragged is False, True or \"ops\", not {ragged!r}")
+        if isinstance(ragged, str) and ragged not in ("ops", "all"):
+            raise ValueError(f"load_factored_model: ragged is False, True, \"ops\" or \"all\", not {ragged!r}")
         self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
-                                      int(factored_form), "ops" if ragged == "ops" else bool(ragged), cg_diag, bool(cg)))
+                                      int(factored_form), ragged if isinstance(ragged, str) else bool(ragged), cg_diag, bool(cg)))
         return self
 
     def _copy_to(self):
@@ -125,7 +127,7 @@ class Optimizer:
             model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
             model.factored_cg = bool(cg) and model.factored
             model.factored_cg_diag = cg_diag and model.factored
-            model.ragged = ragged if model.factored else False      # (False, True or "ops")
+            model.ragged = ragged if model.factored else False      # (False, True, "ops" or "all")
             check_factored_kit(model, self.options.get("kit", 0))
             check_diag_kit(model, self.options.get("kit", 0))
         else:

@@ -147,11 +147,18 @@ class MySolver:
                         self._say(" ---The CG path holds the diagonal parts of the factored blocks (cg_diag = 1)")
                     # load_factored_model(..., ragged=True): blocks of mixed ranks are assembled by rank class
                     # ... ragged="ops": and their two data operators run on the same compacted columns
+                    # ... ragged="all": and the cross terms of the assembly and ts of H_alpha
                     rg = getattr(model, "ragged", False)
-                    ragged, ops = bool(rg), isinstance(rg, str) and rg == "ops"
+                    rest = isinstance(rg, str) and rg == "all"
+                    ragged, ops = bool(rg), rest or (isinstance(rg, str) and rg == "ops")
                     self.dev.set_option("lowrank_ragged", 1 if ragged else 0)
                     self.dev.set_option("ragged_ops", 1 if ops else 0)
-                    if ops:
+                    self.dev.set_option("ragged_cross", 1 if rest else 0)
+                    self.dev.set_option("ragged_ts", 1 if rest else 0)
+                    if rest:
+                        self._say(" ---The Schur assembly with its cross terms, the data operators and H_alpha group the factored "
+                                  "constraints by rank class (lowrank_ragged = 1, ragged_ops = 1, ragged_cross = 1, ragged_ts = 1)")
+                    elif ops:
                         self._say(" ---The Schur assembly and the data operators group the factored constraints by rank class "
                                   "(lowrank_ragged = 1, ragged_ops = 1)")
                     elif ragged:
