@@ -53,6 +53,10 @@ int lrn_upload_model(lrn_ctx* ctx, int nlmi, int nvar, const int64_t* msizes,
                      const double* Clin_nzval);
 /* Rank-k constraint data of block ilmi (datarank >= 1; reference docs/src/low-rank_data.md): A_k = V_k diag(d_k) V_k'
  * with d in {+1, -1}, every constraint padded to khat columns (khat = 1, 2, 4, 8 or 16; padding columns empty, weight 0).
+ * khat = 32 or 64 (a WIDE block, constraints of rank 17 .. 64) is accepted under lrn_set_option "lowrank_wide" = 1 and
+ * refused with LRN_ERR_ARG otherwise, as any other value is: mode 1 assembles such a block by rank class whatever
+ * "lowrank_ragged" says (one GPU: LRN_ERR_ARG from lrn_schur_assemble when world > 1; lrn_get_count "schur_wide"), and it
+ * carries no diagonal parts (lrn_upload_diag on it, and this call with a wide khat on a block that holds them: LRN_ERR_ARG).
  * V: (nvar * khat) x msz CSC, 1-based, row k * khat + p = column p of V_k (the orientation of B above); d: nvar * khat
  * weights in the same order.  Call after lrn_upload_model / lrn_synthetic_dense_model; lrn_schur_assemble(mode 1) uses
  * them.  AA stays what every other entry point reads (unless the block is declared factored, below).  If some constraint
@@ -208,6 +212,10 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * padded layout (options "ragged_ops", "ragged_cross" below move them).  Counters: "schur_ragged" (blocks assembled by rank class), "ragged_fallback", and the STATE of the last
  * block assembled that way (survives reset_timing): "ragged_cols" (Rc), "ragged_classes" (classes present), "ragged_tiles";
  * timing key "ragged" (U_c and the tile launch, beside "lowrank_u"),
+ * "lowrank_wide" (0, default = lrn_upload_lowrank takes khat up to 16; 1 = khat 32 and 64 as well.  A block uploaded so is
+ * wide: the classes 64 and 32 lead the layout, mode 1 takes the rank-class route for it unconditionally, also when Rc = nvar
+ * khat; "ragged_ops", "ragged_cross", "ragged_ts" keep their condition and move its other routes from the padded layout at
+ * khat 32 / 64 to the compacted columns; counter "schur_wide" = assemblies of a wide block),
  * "ragged_ops" (the factor form of AA vec(.) and mat(AA' .) of such a block: 0, default = on the nvar khat padded columns, every
  * route, counter, error text and bit as before; any other value = 1 = on the Rc compacted columns of "lowrank_ragged" -- Q = Z Vc
  * and sums by group, or the fused quadratic form on (Vc, Rc) under "fac_quadform"; mat(AA' x) = -sum_c s_c f_c f_c' by one FP64

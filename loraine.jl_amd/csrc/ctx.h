@@ -84,11 +84,11 @@ struct LmiBlock {
   bool rg_ready = false;
   lrn::DBuf rg_src, rg_wc, rg_gh, rg_tiles, Vc;   // int64 [rg_Rc], double [rg_Rc], int32 [groups], RaggedTile [rg_ntiles]
   // option "ragged_ops" (the data operators on the compacted columns, raggedops.hip): column -> group, the segment starts and
-  // first groups of the five classes (rg_grp0[5] = the number of groups), and Yc = W Vc (msz x rg_Rc) of the scaling
-  // `Yc_version` for option "fac_op_scaled" -- all built with the plan, on the first call of either route
+  // first groups of the seven classes 64 .. 1 of ragged_plan.h (rg_grp0[7] = the number of groups), and Yc = W Vc (msz x rg_Rc)
+  // of the scaling `Yc_version` for option "fac_op_scaled" -- all built with the plan, on the first call of either route
   lrn::DBuf rg_cg;                                // int32 [rg_Rc]
-  long rg_seg0[5] = {0, 0, 0, 0, 0};
-  int rg_grp0[6] = {0, 0, 0, 0, 0, 0};
+  long rg_seg0[7] = {};
+  int rg_grp0[8] = {};
   lrn::DBuf Yc;
   long Yc_version = -1;
   // options "ragged_cross" / "ragged_ts" (cross terms of the assembly, ts of H_alpha on the compacted columns): H index -> group,
@@ -195,6 +195,8 @@ struct LrnOptions {
                                   // (Q = Z Vd never stored): 1, Q and fac_coldot_kernel: 0, cost model: -1
   int lowrank_ragged = 0;         // rank-k assembly of a block of mixed ranks by rank class (raggedops.hip): 1, the padded route: 0.  One
                                   // GPU, and only where the classes are not all khat -- the padded route otherwise ("ragged_fallback")
+  int lowrank_wide = 0;           // lrn_upload_lowrank accepts khat 32 and 64 (factored constraints of rank 17 .. 64): 1, refuses them: 0.
+                                  // A block uploaded so is assembled by rank class whatever lowrank_ragged says (raggedops.hip)
   int ragged_ops = 0;             // AA vec(.) and mat(AA' .) of a block of mixed ranks in factor form on the compacted columns of the
                                   // rank classes (raggedops.hip): 1, on the padded layout: 0.  Independent of lowrank_ragged; the
                                   // same conditions, the padded code otherwise ("ragged_ops_fallback")
@@ -320,9 +322,14 @@ int schur_add_diag(lrn_ctx* c, double eps);
 int schur_get(lrn_ctx* c, double* Hout);
 // schur_factored.hip
 int lowrank_dense_factors(lrn_ctx* c, LmiBlock& b);     // b.Vd from the uploaded rank-k factors (once per upload)
-// rank-class route of a block under option "lowrank_ragged": one GPU, some but not all columns survive the compaction
+// a wide block: factors padded to 32 or 64 columns (lrn_upload_lowrank under option "lowrank_wide")
+inline bool lowrank_wide(const LmiBlock& b) { return b.lr_khat > 16; }
+// rank-class route of a block under option "lowrank_ragged": one GPU, some but not all columns survive the compaction.  A wide
+// block takes it whatever the option says and also when every column survives (a uniform rank-32 block): the padded product
+// sums blocks of at most 16 x 16 and must never see it
 inline bool lowrank_ragged_on(const lrn_ctx* c, const LmiBlock& b) {
-  return c->opt.lowrank_ragged != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
+  if (c->world > 1 || b.rg_Rc <= 0) return false;
+  return lowrank_wide(b) || (c->opt.lowrank_ragged != 0 && b.rg_Rc < (long)c->nvar * b.lr_khat);
 }
 // the data operators of a block on the compacted columns under option "ragged_ops": the same condition
 inline bool ragged_ops_on(const lrn_ctx* c, const LmiBlock& b) {

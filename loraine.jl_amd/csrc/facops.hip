@@ -6,7 +6,7 @@
 // the regime of kit = 1 (msz in the low hundreds, nvar in the tens of thousands).  Here Q never leaves the registers.
 //
 // fac_quadform_kernel: 256 threads, workgroup tile = 64 rows of Z (strip blockIdx.y) x 64 factor columns (blockIdx.x).  khat
-// is a power of two <= 16, so a column tile holds whole constraints.  K = m is walked in steps of 16: the workgroup stages
+// is a power of two <= 64 (32 and 64: a wide block), so a column tile holds whole constraints.  K = m is walked in steps of 16: the workgroup stages
 //   Zs[k][i] = Z[i0 + i, k0 + k]   16 x 64 doubles, row stride 80   (Z is symmetric: read down its columns, coalesced)
 //   Vs[c][k] = Vd[k0 + k, c0 + c]  64 x 16 doubles, row stride 18
 // 10 240 + 9 216 bytes, and 1 024 bytes for the sums of the two wave rows: 20 480 bytes of LDS, eight workgroups per CU of

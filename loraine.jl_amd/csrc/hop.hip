@@ -319,8 +319,8 @@ static double est_assemble_s(const lrn_ctx* c, int mode) {
     if (mode == 1 && (b.factored || cg_lowrank_covered(b))) {
       // U = G' Vd and the blocked square of U' U on its lower triangle (section 10: 1.28e11 flop in 3.78 ms)
       const double R = n * b.lr_khat;
-      // option "lowrank_ragged": the two products run on the Rc compacted columns (raggedops.hip); everything below stays
-      // on the padded layout
+      // option "lowrank_ragged", and every wide block (khat 32 / 64): the two products run on the Rc compacted columns
+      // (raggedops.hip); everything below stays on the padded layout
       const double Rp = lowrank_ragged_on(c, b) ? (double)b.rg_Rc : R;
       // option "ragged_cross": Y, the cross terms of a hybrid block and C of the diagonal parts on the compacted columns too
       const double Rx = ragged_cross_on(c, b) ? (double)b.rg_Rc : R;

@@ -612,11 +612,17 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
                                   const double* V_nzval, const double* d) {
   if (!c) return LRN_ERR_ARG;
   if (ilmi < 0 || ilmi >= c->nlmi) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: block %d of %d", ilmi, c->nlmi);
-  if (khat != 1 && khat != 2 && khat != 4 && khat != 8 && khat != 16)
-    return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: khat = %d (1, 2, 4, 8 or 16)", khat);
+  const bool wide = khat == 32 || khat == 64;      // (a wide block: option "lowrank_wide")
+  if (khat != 1 && khat != 2 && khat != 4 && khat != 8 && khat != 16 && !(wide && c->opt.lowrank_wide)) {
+    if (!c->opt.lowrank_wide) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: khat = %d (1, 2, 4, 8 or 16)", khat);
+    return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: khat = %d (1, 2, 4, 8, 16, or 32 or 64 under option lowrank_wide)", khat);
+  }
   if (!V_colptr || !d) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: null factor array");
   LRN_HIP(c, hipSetDevice(c->device));
   LmiBlock& b = c->lmi[ilmi];
+  if (wide && b.dg_n > 0)
+    return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: khat = %d on block %d, which holds diagonal parts (lrn_upload_diag): a "
+                                     "wide block carries none -- store such a constraint as a matrix", khat, ilmi);
   const int m = b.msz, nvar = c->nvar;
   const long R = (long)nvar * khat;
   if ((double)R * m >= 9.0e18 / 8.0 || R > 0x7fffffffL) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: too many factor columns");
@@ -728,6 +734,9 @@ extern "C" int lrn_upload_diag(lrn_ctx* c, int ilmi, int64_t nrows, const int64_
     drop_diag(b);
     return LRN_OK;
   }
+  if (lowrank_wide(b))
+    return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: block %d is wide (khat = %d > 16): a wide block carries no diagonal part "
+                                     "-- store such a constraint as a matrix", ilmi, b.lr_khat);
   if (!rows || !a) return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: null array");
   const int ns = (int)nrows;
   std::vector<int64_t> rw(ns);

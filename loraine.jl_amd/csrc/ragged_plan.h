@@ -4,18 +4,25 @@
 // the column -> group map and the K-chunks of the data operators (option "ragged_ops"): model.ragged_columns, ragged_chunks;
 // the H index -> group map of the cross terms and of ts of H_alpha (options "ragged_cross", "ragged_ts"): ragged_columns' hg.
 //
-// Rank r_j of constraint j = its factor columns of non-zero weight; class c_j = the smallest of {1, 2, 4, 8, 16} >= r_j.  A
-// constraint of rank 0 (a stored row of a hybrid block, a purely diagonal row, an empty constraint) has no group.  Classes are
-// laid out in descending order (16, 8, 4, 2, 1), the groups of a class in increasing H index; group g holds the weighted
-// columns of its constraint in their original order, then weight-0 padding up to c_j columns.
+// Rank r_j of constraint j = its factor columns of non-zero weight; class c_j = the smallest of {1, 2, 4, 8, 16, 32, 64} >= r_j
+// (32 and 64 occur in a wide block only, khat > 16 under option "lowrank_wide").  A constraint of rank 0 (a stored row of a
+// hybrid block, a purely diagonal row, an empty constraint) has no group.  Classes are laid out in descending order (64, 32,
+// 16, 8, 4, 2, 1), the groups of a class in increasing H index; group g holds the weighted columns of its constraint in their
+// original order, then weight-0 padding up to c_j columns.  An empty class has an empty segment and no tile: a block without
+// ranks above 16 has the columns, the group order and the tile list it had with five classes.
 #pragma once
 #include <vector>
 
 namespace lrn {
 
-static constexpr int RG_NCLS = 5;                       // classes 16, 8, 4, 2, 1 in layout order
+#if defined(__HIPCC__)
+#define RG_HD __host__ __device__
+#else
+#define RG_HD
+#endif
+static constexpr int RG_NCLS = 7;                       // classes 64, 32, 16, 8, 4, 2, 1 in layout order
 static constexpr int RG_TILE = 64;                      // tile side of ragged_blocksum_kernel: every class size divides it
-inline int ragged_class_size(int ci) { return 16 >> ci; }
+RG_HD inline int ragged_class_size(int ci) { return 64 >> ci; }
 
 // One workgroup of ragged_blocksum_kernel: rows [r0, r1) x columns [c0, c1) of T = U_c' B_c (at most 64 x 64; r1, c1 = the tile
 // end or the segment end), whose ka x kb blocks belong to the groups gi0 + (row - r0) / ka and gj0 + (col - c0) / kb.
@@ -31,8 +38,8 @@ struct RaggedTile {
 struct RaggedPlan {
   long Rc = 0;                                          // compacted columns, sum of c_j
   int ncls = 0;                                         // classes present
-  long seg0[RG_NCLS] = {0, 0, 0, 0, 0}, seg1[RG_NCLS] = {0, 0, 0, 0, 0};      // columns of class ci: [seg0, seg1)
-  int grp0[RG_NCLS] = {0, 0, 0, 0, 0};                  // first group of class ci
+  long seg0[RG_NCLS] = {}, seg1[RG_NCLS] = {};          // columns of class ci: [seg0, seg1)
+  int grp0[RG_NCLS] = {};                               // first group of class ci
   std::vector<int> gh;                                  // group -> H index
   std::vector<int> hg;                                  // H index -> group, -1 for a constraint of rank 0 (the inverse of gh)
   std::vector<int> cg;                                  // compacted column -> group (option "ragged_ops": the data operators)
@@ -41,7 +48,7 @@ struct RaggedPlan {
   std::vector<RaggedTile> tiles;
 };
 
-// class index (0: 16 .. 4: 1) of a rank 1 .. 16
+// class index (0: 64 .. 6: 1) of a rank 1 .. 64
 inline int ragged_class_of(int r) {
   int ci = RG_NCLS - 1;
   while (ragged_class_size(ci) < r) --ci;
@@ -65,11 +72,6 @@ inline long ragged_cols(const double* w, int nvar, int khat) {
 // the last step a tail where 16 does not divide Rc.  Every step belongs to exactly one chunk.
 static constexpr int RG_KSTEP = 16;
 static constexpr int RG_MAX_CHUNKS = 16;
-#if defined(__HIPCC__)
-#define RG_HD __host__ __device__
-#else
-#define RG_HD
-#endif
 RG_HD inline long ragged_steps(long Rc) { return (Rc + RG_KSTEP - 1) / RG_KSTEP; }
 inline int ragged_clamp_chunks(long Rc, int ks) {
   const long ns = ragged_steps(Rc), hi = ns < RG_MAX_CHUNKS ? ns : RG_MAX_CHUNKS;
@@ -98,7 +100,7 @@ inline long ragged_tile_count(const long* seg0, const long* seg1) {
 inline RaggedPlan plan_ragged(const double* w, int nvar, int khat, bool with_tiles = true) {
   RaggedPlan p;
   std::vector<int> cls(nvar, -1);
-  long cnt[RG_NCLS] = {0, 0, 0, 0, 0};
+  long cnt[RG_NCLS] = {};
   for (long h = 0; h < nvar; ++h) {
     int r = 0;
     for (int q = 0; q < khat; ++q) r += w[h * khat + q] != 0.0;

@@ -28,6 +28,10 @@
 // model share H.  Rows and columns beyond the segment end carry zero operands and weight 0 and take part in the shuffles, which
 // the whole wave executes.  In a diagonal tile of a class with itself the blocks with gi < gj are skipped: every unordered pair
 // of constraints has exactly one writer, no atomics -- two assemblies give the same bits.
+// A wide block (khat 32 or 64, option "lowrank_wide") adds the classes 64 and 32 in front of the layout and always takes this
+// route.  A tile with ka or kb above 16 leaves the K loop for ragged_wide_epilogue below (a branch uniform over the workgroup):
+// a class-32 block is one wave's 32 x 32 sub-tile, a class-64 block the whole tile.  A tile with ka, kb <= 16 runs the epilogue
+// above, unchanged.
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
 #include "ops.h"
@@ -47,6 +51,106 @@ __global__ void ragged_dense_kernel(const long* __restrict__ ptr, const int* __r
   const long s = src[h];
   if (s < 0) return;
   for (long f = ptr[s] + threadIdx.x; f < ptr[s + 1]; f += blockDim.x) Vc[(long)col[f] + h * msz] = val[f];
+}
+
+// ---- epilogue of a tile of a wide block (ka or kb in {32, 64}; the other side any class size).  A class-32 block is the 32 x 32
+// sub-tile of one wave, a class-64 block the whole tile.  Order of the sum, fixed:
+//   1. inside each 16 x 16 accumulator the register / lane butterfly of the narrow epilogue with the sizes capped at 16;
+//   2. across the wave's two accumulators in a direction of size >= 32, index 0 + index 1 -- the rows first, then the columns;
+//   3. for size 64 across the two waves in that direction through LDS, wave 0 + wave 1 -- again the rows first.
+// Step 3 reuses the staging buffer As after a barrier: wave w writes the sums of its (32 / min(ka, 32)) x (32 / min(kb, 32)) <= 32
+// blocks to red[32 w + slot] (one lane per block), and after a second barrier the lanes of the wave that is first in every
+// 64-direction read their own and the partner sums and add to H.  Both barriers sit in a branch on ka, kb alone and no lane has
+// left before them: all 256 threads reach them.  LDS banks of the exchange: the writing lanes of one ds_write_b64 hold
+// consecutive slots, i.e. consecutive doubles -- at most 16 of them, distinct bank pairs -- and the reads are the same
+// addresses offset by a multiple of 32 doubles, one pass each: conflict-free (derived from the bank rule, not measured).
+// One writer per entry of H, no atomics.
+__device__ __forceinline__ void ragged_wide_epilogue(const RaggedTile& tl, const rg_v4 (&acc)[2][2], const double* __restrict__ wc,
+                                                     const int* __restrict__ gh, double* __restrict__ H, int ldh,
+                                                     double* __restrict__ red, int w, int lane) {
+  const int ka = tl.ka, kb = tl.kb;
+  const int wr = w >> 1, wn = w & 1;
+  const int ci = lane & 15, kq = lane >> 4;
+  const int ka16 = ka < 16 ? ka : 16, kb16 = kb < 16 ? kb : 16;
+  const int rstep = ka16 > 4 ? ka16 / 4 : 1;         // registers per block inside an accumulator
+  double v[2][2][4];
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb) {
+      const int rb = tl.r0 + 32 * wr + 16 * ib;
+      const int col = tl.c0 + 32 * wn + 16 * jb + ci;
+      const double wcol = col < tl.c1 ? wc[col] : 0.0;
+      double s[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rb + kq + 4 * r;
+        const double a = acc[ib][jb][r];
+        s[r] = a * a * (row < tl.r1 ? wc[row] : 0.0) * wcol;
+      }
+      if (ka16 >= 8) { s[0] += s[1]; s[2] += s[3]; }
+      if (ka16 >= 16) s[0] += s[2];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double x = s[r];
+        if (r % rstep == 0) {                        // (uniform: the whole wave executes the shuffles)
+          for (int o = 1; o < kb16; o <<= 1) x += __shfl_xor(x, o, 64);
+          if (ka16 >= 2) x += __shfl_xor(x, 16, 64);
+          if (ka16 >= 4) x += __shfl_xor(x, 32, 64);
+        }
+        v[ib][jb][r] = x;
+      }
+    }
+  if (ka >= 32) {
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[0][jb][r] += v[1][jb][r];
+  }
+  if (kb >= 32) {
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[ib][0][r] += v[ib][1][r];
+  }
+  const int kaw = ka < 32 ? ka : 32, kbw = kb < 32 ? kb : 32;      // extent of a block inside the wave's 32 x 32
+  const int ncw = 32 / kbw;
+  const bool x64 = ka == 64 || kb == 64;             // (uniform over the workgroup)
+  if (x64) {
+    __syncthreads();                                 // every wave is done with the last K step's As
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+      for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int rw = 16 * ib + kq + 4 * r, cw = 16 * jb + ci;
+          if (rw % kaw == 0 && cw % kbw == 0) red[32 * w + (rw / kaw) * ncw + cw / kbw] = v[ib][jb][r];
+        }
+    __syncthreads();
+  }
+  if ((ka == 64 && wr) || (kb == 64 && wn)) return;  // (whole waves, after the barriers: the partner wave adds)
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rw = 16 * ib + kq + 4 * r, cw = 16 * jb + ci;
+        if (rw % kaw || cw % kbw) continue;
+        const int row = tl.r0 + 32 * wr + rw, col = tl.c0 + 32 * wn + cw;
+        if (row >= tl.r1 || col >= tl.c1) continue;
+        const int gi = tl.gi0 + (row - tl.r0) / ka, gj = tl.gj0 + (col - tl.c0) / kb;
+        if (tl.diag && gi < gj) continue;
+        double x = v[ib][jb][r];
+        if (x64) {
+          const int slot = (rw / kaw) * ncw + cw / kbw;
+          if (ka == 64 && kb == 64) x = (red[slot] + red[64 + slot]) + (red[32 + slot] + red[96 + slot]);
+          else if (ka == 64) x = red[32 * w + slot] + red[32 * (w + 2) + slot];
+          else x = red[32 * w + slot] + red[32 * (w + 1) + slot];
+        }
+        H[h_lower(gh[gi], gh[gj], ldh)] += x;
+      }
 }
 
 __global__ __launch_bounds__(256) void ragged_blocksum_kernel(const double* __restrict__ A, const double* __restrict__ B, int m,
@@ -100,8 +204,12 @@ __global__ __launch_bounds__(256) void ragged_blocksum_kernel(const double* __re
       acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
     }
   }
-  // ---- epilogue: ka x kb blocks inside the 16 x 16 accumulator blocks (ka, kb | 16; uniform over the workgroup)
   const int ka = tl.ka, kb = tl.kb;
+  if (ka > 16 || kb > 16) {                          // a tile of a wide block (uniform over the workgroup): see below
+    ragged_wide_epilogue(tl, acc, wc, gh, H, ldh, As, w, lane);
+    return;
+  }
+  // ---- epilogue: ka x kb blocks inside the 16 x 16 accumulator blocks (ka, kb | 16; uniform over the workgroup)
   const int kqr = ka < 4 ? ka : 4;                   // rows of a block among the lane quarters
   const int rstep = ka > 4 ? ka / 4 : 1;             // registers per block
 #pragma unroll
@@ -173,7 +281,7 @@ int ragged_setup(lrn_ctx* c, LmiBlock& b) {
 }
 
 // H_FF of one block by rank class.  The caller (assemble_lowrank) has checked the factors, the scaling and the route
-// conditions: one GPU, 0 < Rc < R
+// conditions: one GPU, 0 < Rc < R -- or a wide block with 0 < Rc <= R
 int assemble_ragged(lrn_ctx* c, LmiBlock& b) {
   const int n = c->nvar, m = b.msz;
   const bool fromW = !b.have_G;
@@ -234,8 +342,8 @@ struct RaggedSegs { long seg0[RG_NCLS]; int grp0[RG_NCLS + 1]; };
 __device__ __forceinline__ long ragged_group_col(const RaggedSegs& sg, int g, int* cj) {
   int ci = 0;
   while (ci < RG_NCLS - 1 && g >= sg.grp0[ci + 1]) ++ci;
-  *cj = 16 >> ci;
-  return sg.seg0[ci] + (long)(g - sg.grp0[ci]) * (16 >> ci);
+  *cj = ragged_class_size(ci);
+  return sg.seg0[ci] + (long)(g - sg.grp0[ci]) * ragged_class_size(ci);
 }
 
 // out[nat(gh[g])] -= sum_{p < c_j} wc[col] <Q(:, col), Vc(:, col)>, col = first column of group g + p: one wave per group,

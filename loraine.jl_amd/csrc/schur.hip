@@ -252,6 +252,10 @@ int schur_assemble(lrn_ctx* c, int mode) {
     if (b.factored && b.dg_n > 0 && c->world > 1)
       return set_error(c, LRN_ERR_STATE, "lrn_schur_assemble: mode 1 on a factored block with diagonal parts (lrn_upload_diag) runs "
                                          "on one GPU (their terms are not sharded)");
+  for (const auto& b : c->lmi)
+    if (mode == 1 && b.has_V && lowrank_wide(b) && c->world > 1)
+      return set_error(c, LRN_ERR_ARG, "lrn_schur_assemble: mode 1 on a wide block (khat = %d > 16, option lowrank_wide) runs on one "
+                                       "GPU (the rank-class route is not sharded)", b.lr_khat);
   LRN_HIP(c, hipMemsetAsync(c->H.p, 0, (size_t)n * n * 8, c->stream));
   c->H_partial = false;
   c->H_owned_only = false;

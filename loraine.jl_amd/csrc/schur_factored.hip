@@ -106,6 +106,19 @@ int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
   const long R = (long)n * kh;
   // option "lowrank_ragged": a block of mixed ranks by rank class (raggedops.hip) -- on one GPU and where the compaction drops
   // columns; a uniform block, an empty one and a sharded run keep the padded route below, bit for bit
+  // a wide block (khat 32 or 64, option "lowrank_wide") takes that route whatever the option says, a uniform one too: the
+  // blocked epilogue of the padded product below sums blocks of at most 16 x 16
+  if (lowrank_wide(b)) {
+    if (c->world > 1)
+      return set_error(c, LRN_ERR_ARG, "rank-k mode on a wide block (khat = %d > 16) runs on one GPU (the rank-class route is not "
+                                       "sharded)", kh);
+    c->counts["schur_wide"] += 1;
+    if (b.rg_Rc <= 0) {      // (no weighted column: nothing to add; BG holds no Y = W Vd -- factored_y forms its own product)
+      c->BG_ragged = true;
+      return LRN_OK;
+    }
+    return assemble_ragged(c, b);
+  }
   if (c->opt.lowrank_ragged) {
     if (lowrank_ragged_on(c, b)) return assemble_ragged(c, b);
     c->counts["ragged_fallback"] += 1;

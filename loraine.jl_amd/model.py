@@ -60,36 +60,53 @@ class MyModel:
     # terms of the assembly (stored rows, diagonal parts) and ts of H_alpha -- ragged_cross = 1 and ragged_ts = 1 beside the two
     ragged: bool = False
 
+    @property
+    def wide(self):
+        """Optimizer.load_factored_model(..., wide=True): some block holds a constraint of rank 17 .. 64 (its khat is 32 or 64) --
+        the solver sets the library option lowrank_wide = 1 before it uploads the factors; such a block is always assembled by
+        rank class.  Read off `lowrank`: no field of its own."""
+        return any(lr[2] > LOWRANK_MAX for lr in self.lowrank)
+
 
 RAGGED_CLASSES = (16, 8, 4, 2, 1)     # layout order of the rank classes
+RAGGED_CLASSES_WIDE = (64, 32) + RAGGED_CLASSES      # ... of a wide block (load_factored_model(..., wide=True): ranks up to 64)
 RAGGED_TILE = 64                      # tile side of the rank-class kernel: every class size divides it
 
 
-def ragged_plan(ranks):
+def _ragged_classes(max_rank, who):
+    if max_rank not in (LOWRANK_MAX, LOWRANK_MAX_WIDE):
+        raise ValueError(f"{who}: max_rank is {LOWRANK_MAX} or {LOWRANK_MAX_WIDE}, not {max_rank!r}")
+    return RAGGED_CLASSES if max_rank == LOWRANK_MAX else RAGGED_CLASSES_WIDE
+
+
+def ragged_plan(ranks, max_rank=16):
     """The rank-class plan of one block (library option lowrank_ragged; csrc/ragged_plan.h is the same function of the factor
     weights).  ranks[h] = number of weighted factor columns of the constraint with H index h.  Class of a constraint = the
     smallest of 1, 2, 4, 8, 16 that is >= its rank; rank 0 has no group.  Classes are laid out 16, 8, 4, 2, 1, the groups of a
     class in increasing H index, each on `class` compacted columns.  Tiles: 64 x 64, anchored at the segment starts; for every
     class pair (A, B), A at or before B, all tiles of seg_A x seg_B when A != B and those with tile row >= tile column when
     A == B.  -> dict(classes = class per constraint (0: none), seg = {class: (seg0, seg1)}, Rc, ncls = classes present, gh =
-    H index per group, tiles = tile count)."""
+    H index per group, tiles = tile count).
+    max_rank=64 (a wide block): ranks up to 64, the classes 64 and 32 laid out in front of the five, the same tile rule; seg
+    then has the seven keys.  An empty class has an empty segment and no tile."""
     ranks = [int(r) for r in ranks]
-    if any(r < 0 or r > LOWRANK_MAX for r in ranks):
-        raise ValueError(f"ragged_plan: ranks must lie in 0 .. {LOWRANK_MAX}")
+    layout = _ragged_classes(max_rank, "ragged_plan")
+    if any(r < 0 or r > max_rank for r in ranks):
+        raise ValueError(f"ragged_plan: ranks must lie in 0 .. {max_rank}")
     classes = [0 if r == 0 else padded_rank(r) for r in ranks]
     seg, gh, col = {}, [], 0
-    for c in RAGGED_CLASSES:
+    for c in layout:
         members = [h for h, ch in enumerate(classes) if ch == c]
         seg[c] = (col, col + c * len(members))
         col += c * len(members)
         gh += members
     nt = {c: -(-(s1 - s0) // RAGGED_TILE) for c, (s0, s1) in seg.items()}
     tiles = 0
-    for i, a in enumerate(RAGGED_CLASSES):
+    for i, a in enumerate(layout):
         tiles += nt[a] * (nt[a] + 1) // 2
-        for b in RAGGED_CLASSES[i + 1:]:
+        for b in layout[i + 1:]:
             tiles += nt[a] * nt[b]
-    return dict(classes=classes, seg=seg, Rc=col, ncls=sum(1 for c in RAGGED_CLASSES if seg[c][1] > seg[c][0]), gh=gh,
+    return dict(classes=classes, seg=seg, Rc=col, ncls=sum(1 for c in layout if seg[c][1] > seg[c][0]), gh=gh,
                 tiles=tiles)
 
 
@@ -107,16 +124,17 @@ def ragged_chunks(Rc, ks):
     return ks, [(s * nsteps // ks * RAGGED_KSTEP, min((s + 1) * nsteps // ks * RAGGED_KSTEP, Rc)) for s in range(ks)]
 
 
-def ragged_columns(ranks, ks=1):
+def ragged_columns(ranks, ks=1, max_rank=16):
     """The compacted column layout the data operators walk under the library option ragged_ops (csrc/ragged_plan.h: cg, the
     weight pattern and the chunks; ragged_plan above keeps what it returns).  -> dict(Rc, gh = H index per group, start = first
     column per group, size = class size per group, cg = group per compacted column, wc = per compacted column the index p of
     the weighted factor column of its constraint it holds (the p-th weighted one, in their original order) or -1 for padding,
     ks = clamped chunk count, chunks = [(first column, end column)], hg = group per H index, -1 for a constraint of rank 0 --
-    the inverse of gh that the cross terms and ts of H_alpha walk under the library options ragged_cross and ragged_ts)."""
-    p = ragged_plan(ranks)
+    the inverse of gh that the cross terms and ts of H_alpha walk under the library options ragged_cross and ragged_ts).
+    max_rank=64: the layout of a wide block, as in ragged_plan."""
+    p = ragged_plan(ranks, max_rank)
     start, size, cg, wc = [], [], [], []
-    for c in RAGGED_CLASSES:
+    for c in _ragged_classes(max_rank, "ragged_columns"):
         s0, s1 = p["seg"][c]
         for g in range((s1 - s0) // c):
             h = p["gh"][len(start)]
@@ -173,6 +191,7 @@ def _rank_one_rows(blockA, n):
 
 LOWRANK_TOL = 5.0e-6          # ||A_k - V_k D_k V_k'||_F, the limit prep_B applies to the rank-one form (src/model.jl:189)
 LOWRANK_MAX = 16              # largest padded rank of the rank-k assembly
+LOWRANK_MAX_WIDE = 64         # ... of a wide factored block (build_factored_model(..., max_rank=64), library option lowrank_wide)
 
 
 def padded_rank(r):
@@ -359,10 +378,11 @@ def diag_fro_sq(V, d, a):
     return float(2.0 * np.sum(d * (a @ (V * V))) + a @ a)
 
 
-def _check_factors(F0, factors, n):
+def _check_factors(F0, factors, n, max_rank=LOWRANK_MAX):
     """factors[i][k] = (V, d) -> dense (m x r) V and d per constraint, or a symmetric m x m matrix (a stored constraint) -> csc,
     or (V, d, a) -> (V, d) and the diagonal part a (V may be None: a purely diagonal constraint); ValueError otherwise.
-    -> (items per block, {k: a} per block); an all-zero a is the pair (V, d)."""
+    -> (items per block, {k: a} per block); an all-zero a is the pair (V, d).  max_rank: the most factor columns of one
+    constraint; a block that holds a constraint of more than 16 (a wide block) carries no diagonal part."""
     if len(factors) != len(F0):
         raise ValueError(f"factors for {len(factors)} LMI blocks, F0 has {len(F0)}")
     out, diags = [], []
@@ -397,19 +417,27 @@ def _check_factors(F0, factors, n):
             d = np.asarray(d, dtype=np.float64).ravel()
             if V.ndim != 2 or V.shape[0] != m:
                 raise ValueError(f"block {i + 1}, constraint {j + 1}: V is {V.shape}, the block has side {m}")
-            if d.size != V.shape[1] or V.shape[1] > LOWRANK_MAX:
+            if d.size != V.shape[1] or V.shape[1] > max_rank:
                 raise ValueError(f"block {i + 1}, constraint {j + 1}: {V.shape[1]} factor columns, {d.size} weights "
-                                 f"(at most {LOWRANK_MAX})")
+                                 f"(at most {max_rank})")
             facs.append((V, d))
+        wide = [j for j, f in enumerate(facs) if not sp.issparse(f) and f[0].shape[1] > LOWRANK_MAX]
+        if wide and dg:
+            raise ValueError(f"block {i + 1}: constraint {wide[0] + 1} has {facs[wide[0]][0].shape[1]} factor columns (more than "
+                             f"{LOWRANK_MAX}) and constraint {min(dg) + 1} a diagonal part (V, d, a): a block with ranks above "
+                             f"{LOWRANK_MAX} carries no diagonal part -- store that row as a sparse matrix instead")
         out.append(facs)
         diags.append(dg)
     return out, diags
 
 
-def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, kappa=8, factored_form=-1) -> MyModel:
+def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, kappa=8, factored_form=-1,
+                         max_rank=LOWRANK_MAX) -> MyModel:
     """A model given by F_0 (per block), b, optional linear rows and the factors alone: A_ik = V diag(d) V' with
-    factors[i][k] = (V (m_i x r, r <= 16, dense or sparse), d (+-1)).  No A_ik is formed for a factored block: its AA is
+    factors[i][k] = (V (m_i x r, r <= max_rank, dense or sparse), d (+-1)).  No A_ik is formed for a factored block: its AA is
     an n x m^2 matrix without entries (nzA = 0, identity sigmaA) and `lowrank` carries the data.
+    max_rank: 16, or 64 for wide blocks (Optimizer.load_factored_model(..., wide=True)) -- a block with a constraint of rank
+    above 16 is padded to khat 32 or 64 and carries no diagonal part (V, d, a); `wide` of the model says that one exists.
     factors[i][k] may instead be a symmetric m_i x m_i matrix (SciPy sparse or a 2-D array): constraint k of block i is
     STORED.  A block with both kinds is hybrid: its AA holds the rows -vec(A) of the stored constraints only, nzA / sigmaA /
     qA follow the rule of _prepare_A (stable sort by nnz, descending: the stored constraints take the first positions, the
@@ -427,7 +455,9 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
     n = len(b)
     if factored_form not in (-1, 1):
         raise ValueError(f"factored_form = {factored_form} (-1 auto, 1 always factored)")
-    items_all, diags_all = _check_factors(F0, factors, n)
+    if max_rank not in (LOWRANK_MAX, LOWRANK_MAX_WIDE):
+        raise ValueError(f"max_rank = {max_rank!r} ({LOWRANK_MAX}, or {LOWRANK_MAX_WIDE} for wide blocks)")
+    items_all, diags_all = _check_factors(F0, factors, n, max_rank)
     nlmi = len(F0)
     A, AA, C, lowrank, fblocks, aa_fro, stored, diag = [], [], [], [], [], [], [], []
     nzA = np.zeros((n, nlmi), dtype=np.int64)

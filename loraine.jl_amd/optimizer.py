@@ -79,10 +79,10 @@ class Optimizer:
         return self
 
     def load_factored_model(self, F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factored_form=-1,
-                            cg=False, ragged=False):
+                            cg=False, ragged=False, wide=False):
         """The same problem given by its factors alone: F0[i] the constant matrix of block i (the A[i][0] of load_model),
-        factors[i][k] = (V, d) with A_i,k+1 = V diag(d) V' (V msz x r, r <= 16, d = +-1, dense or sparse).  No A_ik, no
-        row of AA and no dense constraint slab is ever formed, on the host or on the device; implies datarank = the
+        factors[i][k] = (V, d) with A_i,k+1 = V diag(d) V' (V msz x r, r <= 16 -- r <= 64 with wide=True --, d = +-1, dense or
+        sparse).  No A_ik, no row of AA and no dense constraint slab is ever formed, on the host or on the device; implies datarank = the
         largest rank (at least 1) and needs kit = 0 and the resident solver (ValueError otherwise).
         cg=True admits kit = 1 as well (opt-in): the CG operator runs from the factors or through H assembled from them, ts of
         H_alpha comes from the factors (library option cg_factored); one GPU only.
@@ -100,8 +100,15 @@ class Optimizer:
         compacted columns (library option ragged_ops beside lowrank_ragged).
         ragged="all" is ragged="ops" and moves what else walked the padded columns there too: Y = W V with the cross terms of
         stored constraints and diagonal parts in the assembly, and ts of H_alpha (library options ragged_cross and ragged_ts).
+        wide=True (opt-in): a constraint may carry up to 64 weighted factor columns -- factor-model covariances with 20 to 60
+        factors -- instead of going in as a stored matrix (library option lowrank_wide).  A block that holds a constraint of
+        rank above 16 is padded to 32 or 64 columns and is always assembled by rank class, whatever `ragged` says; it carries no
+        diagonal part (V, d, a) (ValueError: store that row as a sparse matrix instead); one GPU only.  Combines freely with
+        ragged= and cg=.
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
+        if not isinstance(wide, bool):
+            raise ValueError(f"load_factored_model: wide is False or True, not {wide!r}")
         if not self.resident:
             raise ValueError("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
                              "multiplies by AA")
@@ -111,7 +118,8 @@ class Optimizer:
         if isinstance(ragged, str) and ragged not in ("ops", "all"):
             raise ValueError(f"load_factored_model: ragged is False, True, \"ops\" or \"all\", not {ragged!r}")
         self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
-                                      int(factored_form), ragged if isinstance(ragged, str) else bool(ragged), cg_diag, bool(cg)))
+                                      int(factored_form), ragged if isinstance(ragged, str) else bool(ragged), wide, cg_diag,
+                                      bool(cg)))
         return self
 
     def _copy_to(self):
@@ -122,9 +130,10 @@ class Optimizer:
             model = model_from_sdpa(payload, datarank=drank, kappa=kappa)
             self.max_sense = False
         elif kind == "factored":
-            F0, factors, b, b_const, d_lin, C_lin, max_sense, form, ragged, cg_diag, cg = payload
+            F0, factors, b, b_const, d_lin, C_lin, max_sense, form, ragged, wide, cg_diag, cg = payload
             self.max_sense = max_sense
-            model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form)
+            model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form,
+                                         max_rank=64 if wide else 16)
             model.factored_cg = bool(cg) and model.factored
             model.factored_cg_diag = cg_diag and model.factored
             model.ragged = ragged if model.factored else False      # (False, True, "ops" or "all")

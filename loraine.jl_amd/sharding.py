@@ -233,6 +233,9 @@ class DistributedHotPath:
         if int(world) > 1 and solver.kit == 1 and getattr(solver.model, "factored", False):
             raise ValueError("a factored model under kit = 1 (load_factored_model(..., cg=True)) runs on one GPU: the factor "
                              "routes of the CG path are not sharded")
+        if int(world) > 1 and getattr(solver.model, "wide", False):
+            raise ValueError("a model with factored constraints of rank above 16 (load_factored_model(..., wide=True)) runs on one "
+                             "GPU: the rank-class route of the Schur assembly is not sharded")
         solver.dist = self
         # the C library shards Schur columns in sigma-position space, which exists for one LMI block;
         # multi-block problems assemble replicated (every rank the whole matrix, no exchange)

@@ -126,6 +126,12 @@ class MySolver:
         self.lowrank = False
         if self.datarank >= 1 and model.nlmi > 0:
             if model.lowrank:
+                # load_factored_model(..., wide=True): constraints of rank 17 .. 64, khat 32 or 64 (0 on a device another solve used)
+                wide = bool(getattr(model, "wide", False))
+                self.dev.set_option("lowrank_wide", 1 if wide else 0)
+                if wide:
+                    self._say(" ---Factored constraints carry up to 64 factor columns; their blocks are assembled by rank class "
+                              "(lowrank_wide = 1)")
                 for i, (V, d, khat) in enumerate(model.lowrank):
                     self.dev.upload_lowrank(i, khat, V, d)                      # [GPU] one-time
                     if getattr(model, "factored", False) and model.factored_blocks[i]:
