@@ -464,6 +464,8 @@ int lrn_dbg_mfma_probe(lrn_ctx* ctx, const double* A16x4, const double* B4x16, d
 int lrn_dbg_potrf(lrn_ctx* ctx, int n, double* A, int* info);
 int lrn_dbg_potrs(lrn_ctx* ctx, int n, const double* A, const double* b, double* x, int* info);
 int lrn_dbg_trsm(lrn_ctx* ctx, int n, int nrhs, int trans, const double* A, double* B, int* info);
+/* One-sided Jacobi SVD of A (n x n, column-major): U_sigma = A V, sigma = its column norms (unsorted).  V may be NULL: the
+ * rotations are then not accumulated, as in every call the solver itself makes; U_sigma, sigma and sweeps are the same. */
 int lrn_dbg_svd_jacobi(lrn_ctx* ctx, int n, const double* A, double* U_sigma, double* V,
                        double* sigma, int* sweeps);
 

@@ -7,7 +7,8 @@
 // of the condition number, and every round of the round-robin ordering is n/2 independent
 // column pairs -> one workgroup per pair.
 //   * n <= 96: one workgroup keeps A and V in LDS and runs all sweeps in one launch.
-//   * larger n: one launch per round (n-1 rounds per sweep), columns streamed from L2/MALL.
+//   * larger n: 16- or 32-column blocks, three launches per round of block pairs (Gram, rotate, apply), columns
+//     streamed from L2/MALL.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -37,49 +38,10 @@ __device__ __forceinline__ double block_sum256(double v, double* sh) {
   return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-// one workgroup per column pair of this round
-__global__ __launch_bounds__(256) void jacobi_round_kernel(double* __restrict__ A, double* __restrict__ V,
-                                                          int n, int np, int round, double tol,
-                                                          int* __restrict__ nrot) {
-  __shared__ double sh[4];
-  int p, q;
-  rr_pair(np, round, blockIdx.x, &p, &q);
-  if (q >= n) return;            // padded player
-  double* ap = A + (long)p * n;
-  double* aq = A + (long)q * n;
-  double al = 0.0, be = 0.0, ga = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    double x = ap[i], y = aq[i];
-    al += x * x; be += y * y; ga += x * y;
-  }
-  al = block_sum256(al, sh);
-  be = block_sum256(be, sh);
-  ga = block_sum256(ga, sh);
-  if (!(fabs(ga) > tol * sqrt(al * be))) return;     // also skips zero / NaN columns
-  double zeta = (be - al) / (2.0 * ga);
-  double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-  double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    double x = ap[i], y = aq[i];
-    ap[i] = c * x - s * y;
-    aq[i] = s * x + c * y;
-  }
-  if (V) {
-    double* vp = V + (long)p * n;
-    double* vq = V + (long)q * n;
-    for (int i = threadIdx.x; i < n; i += 256) {
-      double x = vp[i], y = vq[i];
-      vp[i] = c * x - s * y;
-      vq[i] = s * x + c * y;
-    }
-  }
-  if (threadIdx.x == 0) atomicAdd(nrot, 1);
-}
-
 // whole SVD in one workgroup, n <= JAC_SMALL
 __global__ __launch_bounds__(256) void jacobi_small_kernel(double* __restrict__ A, double* __restrict__ V,
                                                           int n, double tol, int max_sweeps,
-                                                          int* __restrict__ sweeps_out, int v_init) {
+                                                          int* __restrict__ sweeps_out) {
   extern __shared__ double smem[];
   double* a = smem;                 // n x n, column stride n+1
   double* v = smem + (size_t)n * (n + 1);
@@ -89,7 +51,7 @@ __global__ __launch_bounds__(256) void jacobi_small_kernel(double* __restrict__ 
   for (int e = t; e < n * n; e += 256) {
     int i = e % n, j = e / n;
     a[i + j * ld] = A[e];
-    if (V) v[i + j * ld] = v_init ? V[e] : ((i == j) ? 1.0 : 0.0);
+    if (V) v[i + j * ld] = (i == j) ? 1.0 : 0.0;
   }
   __syncthreads();
   const int np = (n + 1) & ~1;
@@ -632,7 +594,7 @@ __global__ __launch_bounds__(256) void colnorm_kernel(const double* __restrict__
   if (threadIdx.x == 0) sig[blockIdx.x] = sqrt(s);
 }
 
-int jacobi_svd(lrn_ctx* c, double* A, double* V, double* sigma, int n, int* sweeps_out, bool v_init) {
+int jacobi_svd(lrn_ctx* c, double* A, double* V, double* sigma, int n, int* sweeps_out) {
   hipStream_t st = c->stream;
   const double tol = 2.220446049250313e-16 * sqrt((double)(n > 4 ? n : 4));
   // early stop (option "jacobi_early", default 3e-8; 0 = always run the confirming sweep): see the sweep loop
@@ -645,11 +607,11 @@ int jacobi_svd(lrn_ctx* c, double* A, double* V, double* sigma, int n, int* swee
   if (n <= JAC_SMALL) {
     size_t sh = (size_t)2 * n * (n + 1) * 8;
     hipFuncSetAttribute((const void*)jacobi_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    hipLaunchKernelGGL(jacobi_small_kernel, dim3(1), dim3(256), sh, st, A, V, n, tol, max_sweeps, cnt, v_init ? 1 : 0);
+    hipLaunchKernelGGL(jacobi_small_kernel, dim3(1), dim3(256), sh, st, A, V, n, tol, max_sweeps, cnt);
     LRN_HIP(c, hipMemcpyAsync(&sweeps, cnt, 4, hipMemcpyDeviceToHost, st));
     LRN_HIP(c, hipStreamSynchronize(st));
   } else {
-    if (V && !v_init) hipLaunchKernelGGL(set_identity_kernel, dim3(1024), dim3(256), 0, st, V, n);
+    if (V) hipLaunchKernelGGL(set_identity_kernel, dim3(1024), dim3(256), 0, st, V, n);
     const bool wide = c->opt.jacobi_block == 32 || (c->opt.jacobi_block == 0 && n >= 5000);
     const int jb = wide ? JB2 : JB;
     const int gsz = wide ? 2560 : 768, rsz = wide ? 4096 : 1024;

@@ -167,7 +167,7 @@ int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info) {
   }
   toc(c, "prepw_gemm");
   tic(c);
-  LRN_TRY(jacobi_svd(c, CC, nullptr, b.D.as<double>(), n, &sweeps, false));
+  LRN_TRY(jacobi_svd(c, CC, nullptr, b.D.as<double>(), n, &sweeps));
   hipLaunchKernelGGL(scale_cols_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, CC, b.D.as<double>(), n, 2, V);
   c->counts["svd_sweeps"] = sweeps;
   toc(c, "prepw_svd");
@@ -634,19 +634,19 @@ extern "C" int lrn_prepare_w(lrn_ctx* c, int il, const double* X, const double* 
 
 extern "C" int lrn_dbg_svd_jacobi(lrn_ctx* c, int n, const double* A, double* U_sigma, double* V, double* sigma,
                                   int* sweeps) {
-  if (!c || n <= 0 || !A || !U_sigma || !V || !sigma) return LRN_ERR_ARG;
+  if (!c || n <= 0 || !A || !U_sigma || !sigma) return LRN_ERR_ARG;
   LRN_HIP(c, hipSetDevice(c->device));
   DBuf dA, dV, dS;
   size_t mm = (size_t)n * n * 8;
   LRN_TRY(ensure(c, dA, mm));
-  LRN_TRY(ensure(c, dV, mm));
+  if (V) LRN_TRY(ensure(c, dV, mm));          // V == NULL: no accumulation, as every production caller
   LRN_TRY(ensure(c, dS, (size_t)n * 8));
   LRN_TRY(copy_in(c, dA.p, A, mm));
   int sw = 0;
-  LRN_TRY(jacobi_svd(c, dA.as<double>(), dV.as<double>(), dS.as<double>(), n, &sw));
+  LRN_TRY(jacobi_svd(c, dA.as<double>(), V ? dV.as<double>() : nullptr, dS.as<double>(), n, &sw));
   if (sweeps) *sweeps = sw;
   LRN_TRY(copy_out(c, U_sigma, dA.p, mm));
-  LRN_TRY(copy_out(c, V, dV.p, mm));
+  if (V) LRN_TRY(copy_out(c, V, dV.p, mm));
   int rc = copy_out(c, sigma, dS.p, (size_t)n * 8);
   release(dA); release(dV); release(dS);
   return rc;

@@ -408,13 +408,15 @@ class Device:
                   "lrn_dbg_trsm")
         return B, info.value
 
-    def dbg_svd_jacobi(self, A):
+    def dbg_svd_jacobi(self, A, vectors=True):
+        """vectors=False: V == NULL, no accumulation of the rotations (what the solver's own calls do); V comes back None"""
         A = f64(A)
         n = A.shape[0]
-        U = np.zeros((n, n), order="F"); V = np.zeros((n, n), order="F"); s = np.zeros(n)
+        U = np.zeros((n, n), order="F"); s = np.zeros(n)
+        V = np.zeros((n, n), order="F") if vectors else None
         sw = C.c_int(0)
-        self._chk(self.lib.lrn_dbg_svd_jacobi(self.h, n, ptr(A), ptr(U), ptr(V), ptr(s), C.byref(sw)),
-                  "lrn_dbg_svd_jacobi")
+        self._chk(self.lib.lrn_dbg_svd_jacobi(self.h, n, ptr(A), ptr(U), ptr(V) if vectors else None, ptr(s),
+                                              C.byref(sw)), "lrn_dbg_svd_jacobi")
         return U, s, V, sw.value
 
     # ------------------------------------------------------------------ device-resident iterate
