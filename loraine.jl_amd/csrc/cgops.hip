@@ -18,6 +18,7 @@
 #include "ctx.h"
 #include "jacobi.h"
 #include "ops.h"
+#include "fac_cols.h"
 
 namespace lrn {
 
@@ -312,7 +313,7 @@ __global__ __launch_bounds__(256) void au_dense_kernel(const double* __restrict_
   }
 }
 
-// ts[sigma[p], col] = C[p, col] for the np stored positions of a hybrid factored block: the rows fac_ts_kernel left at zero
+// ts[sigma[p], col] = C[p, col] for the np stored positions of a hybrid factored block: the rows fac_ts_kernel (facops.hip) left at zero
 // (weight-0 factor columns) get their values from the entries, each element written once
 __global__ void ts_store_rows_kernel(const double* __restrict__ C, int np, int m, const int* __restrict__ sigma, int nvar,
                                      double* __restrict__ ts) {
@@ -320,52 +321,6 @@ __global__ void ts_store_rows_kernel(const double* __restrict__ C, int np, int m
   if (e >= (long)np * m) return;
   const int p = (int)(e % np), r = (int)(e / np);
   ts[(long)sigma[p] + (long)r * nvar] = C[e];
-}
-
-// ts of H_alpha from the rank-k factors of a covered block (option "cg_lowrank").  With A_j = sum_p w_hp v_hp v_hp' (h the H
-// index of constraint j, the one the factor columns are stored in), L the Cholesky factor of 2 W - Um Um' and u_a column a
-// of Um, the entry route forms  ts[j, a m + r] = -(L' A_j u_a)[r] / sqrt(d_j)  by one pass over every A_j per eigenvector.
-// Here  P = L' Vd  (m x R, one MFMA product for ALL eigenvectors) and  T = Vd' Um  (R x erank) come first, and
-//     ts[j, col0 + a m + r] = -(1 / sqrt(d_j)) sum_p w[h kh + p] T[h kh + p, a] P[r, h kh + p]
-// is what this kernel does: a weighted sum of the kh columns of P of each constraint, in the order p = 0 .. kh - 1 (no
-// atomics: two setups give the same bits), written TRANSPOSED -- P is contiguous along r, ts along j.
-// Workgroup tile: 64 constraints (natural rows j0 .. j0 + 63 of ts) x 64 rows r of P, eigenvector a = blockIdx.z.  Wave w
-// takes the constraints j0 + w, j0 + w + 4, ..: its 64 lanes read 64 consecutive doubles of each column of P (512 B per
-// load, coalesced whatever the order of h = ipos[j]) with the coefficient w T as a wave-uniform scalar, and store the sums
-// as row jl of an LDS tile of 64 x 65 doubles (33 280 bytes; ds_write_b64 of consecutive addresses).  After the barrier lane
-// l of wave w reads tile[l][rr], rr = w, w + 4, .. -- a stride of 65 doubles = 130 banks, 2 l mod 64 over a 32-lane half:
-// conflict-free, where 64 would be a 32-way conflict -- and the wave writes 64 consecutive rows j of one column of ts.
-static constexpr int FTS_TILE = 64;
-__global__ __launch_bounds__(256) void fac_ts_kernel(const double* __restrict__ Pm, const double* __restrict__ T,
-                                                     const double* __restrict__ w, const int* __restrict__ ipos,
-                                                     const double* __restrict__ d, int m, int kh, long R, int nvar,
-                                                     double* __restrict__ ts) {
-  __shared__ double tile[FTS_TILE][FTS_TILE + 1];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j0 = blockIdx.x * FTS_TILE, r0 = blockIdx.y * FTS_TILE, a = blockIdx.z;
-  const double* __restrict__ Ta = T + (long)a * R;
-  const int r = r0 + lane;
-  for (int jl = wv; jl < FTS_TILE; jl += 4) {
-    const int j = j0 + jl;
-    double s = 0.0;
-    if (j < nvar) {                                  // (wave-uniform)
-      const long c0 = (long)(ipos ? ipos[j] : j) * kh;
-      for (int p = 0; p < kh; ++p) {
-        const double wp = w[c0 + p];
-        if (wp == 0.0) continue;                     // padding column
-        const double cf = wp * Ta[c0 + p];
-        if (r < m) s += cf * Pm[(c0 + p) * m + r];
-      }
-    }
-    tile[jl][lane] = s;
-  }
-  __syncthreads();
-  const int j = j0 + lane;
-  if (j >= nvar) return;
-  const double sc = -1.0 / sqrt(d[j]);
-  double* __restrict__ out = ts + (long)a * m * nvar + j;
-  for (int rr = wv; rr < FTS_TILE && r0 + rr < m; rr += 4) out[(long)(r0 + rr) * nvar] = sc * tile[lane][rr];
 }
 
 // Cd[i, l] = C_lin[i, l] * sqrt(xs_l)   (dense nvar x nlin image of the linear block)
@@ -563,41 +518,28 @@ int prec_setup(lrn_ctx* c, int kind, int erank, int aamat, int* info) {
       hipLaunchKernelGGL(tril2_kernel, dim3(nb((long)m * m)), dim3(256), 0, st, Zf, m);
       // a factored block (option "cg_factored") has no choice to make: there are no entries to take ts from
       if (b.factored || cg_lowrank_ts(c, b, k)) {
-        // from the rank-k factors: P = L' Vd and T = Vd' Um, then fac_ts_kernel (the whole nvar x k m block, every element once)
-        // option "ragged_ts": a block of mixed ranks from Pc = L' Vc and Tc = Vc' Um on its Rc compacted columns, then
-        // ragged_ts_kernel (raggedops.hip); a uniform block keeps the padded columns and fac_ts_kernel, bit for bit
+        // from the rank-k factors: P = L' V and T = V' Um, then fac_ts of facops.hip (the whole nvar x k m block, every element
+        // once).  V = Vd, or under option "ragged_ts" the Rc compacted columns Vc of a block of mixed ranks; a uniform block keeps
+        // the padded columns, bit for bit
         const bool rts = ragged_ts_on(c, b);
         if (c->opt.ragged_ts && !rts) c->counts["ragged_ts_fallback"] += 1;
-        const int kh = b.lr_khat;
-        const long R = rts ? b.rg_Rc : (long)n * kh;
         if (rts) LRN_TRY(ragged_setup(c, b));
         else LRN_TRY(lowrank_dense_factors(c, b));
-        const double* Vf = rts ? b.Vc.as<double>() : b.Vd.as<double>();
+        const FacCols v = fac_cols(c, b, rts);
+        const long R = v.R;
         LRN_TRY(ensure(c, c->BG, (size_t)m * R * 8));
         LRN_TRY(ensure(c, P->Tf, (size_t)R * k * 8));
-        GemmDesc gp;     // P = L' Vd, m x R (the upper triangle of Zf is zero: tril2_kernel)
-        gp.A = Zf; gp.sAm = m; gp.sAk = 1;
-        gp.B = Vf; gp.sBk = 1; gp.sBn = m;
-        gp.C = c->BG.as<double>(); gp.sCm = 1; gp.sCn = m;
-        gp.M = m; gp.N = (int)R; gp.K = m;
         if (c->opt.profile_ops) tic(c);      // (measurement, tools/cg_diag_times.py: this product beside the diagonal-row kernel)
-        LRN_TRY(gemm(st, gp));
+        LRN_TRY(cols_product(c, Zf, true, v.V, R, m, c->BG.as<double>()));      // P = L' V, m x R (the upper triangle of Zf is zero: tril2_kernel)
         if (c->opt.profile_ops) toc(c, "prec_ts_p");
-        GemmDesc gt;     // T = Vd' Um, R x k
-        gt.A = Vf; gt.sAm = m; gt.sAk = 1;
+        GemmDesc gt;     // T = V' Um, R x k
+        gt.A = v.V; gt.sAm = m; gt.sAk = 1;
         gt.B = Um; gt.sBk = 1; gt.sBn = m;
         gt.C = P->Tf.as<double>(); gt.sCm = 1; gt.sCn = R;
         gt.M = (int)R; gt.N = k; gt.K = m;
         LRN_TRY(gemm(st, gt));
-        if (rts) {
-          LRN_TRY(ragged_ts(c, b, c->BG.as<double>(), P->Tf.as<double>(), P->d.as<double>(), k,
-                            P->ts.as<double>() + (size_t)col0 * n));
-          ++ts_ragged;
-        } else
-          hipLaunchKernelGGL(fac_ts_kernel, dim3((n + FTS_TILE - 1) / FTS_TILE, (m + FTS_TILE - 1) / FTS_TILE, k), dim3(256), 0, st,
-                             c->BG.as<double>(), P->Tf.as<double>(), b.v_w.as<double>(),
-                             c->pos_space ? b.ipos_d.as<int>() : (const int*)nullptr, P->d.as<double>(), m, kh, R, n,
-                             P->ts.as<double>() + (size_t)col0 * n);
+        LRN_TRY(fac_ts(c, b, v, c->BG.as<double>(), P->Tf.as<double>(), P->d.as<double>(), k, P->ts.as<double>() + (size_t)col0 * n));
+        if (rts) ++ts_ragged;
         ++ts_factored;
         if (b.hybrid()) {
           // the stored constraints have weight-0 columns: their rows came out as zeros.  (D^-1/2 A_s u_a)' Z for these npos_nz

@@ -83,7 +83,7 @@ struct LmiBlock {
   int rg_ncls = 0;
   bool rg_ready = false;
   lrn::DBuf rg_src, rg_wc, rg_gh, rg_tiles, Vc;   // int64 [rg_Rc], double [rg_Rc], int32 [groups], RaggedTile [rg_ntiles]
-  // option "ragged_ops" (the data operators on the compacted columns, raggedops.hip): column -> group, the segment starts and
+  // option "ragged_ops" (the data operators on the compacted columns, fac_cols.h, raggedops.hip): column -> group, the segment starts and
   // first groups of the seven classes 64 .. 1 of ragged_plan.h (rg_grp0[7] = the number of groups), and Yc = W Vc (msz x rg_Rc)
   // of the scaling `Yc_version` for option "fac_op_scaled" -- all built with the plan, on the first call of either route
   lrn::DBuf rg_cg;                                // int32 [rg_Rc]
@@ -100,7 +100,7 @@ struct LmiBlock {
   // is exactly one of the two.  The stored-entry kernels serve the stored part, schur_factored.hip::assemble_cross the mixed terms
   bool factored = false;
   bool hybrid() const { return factored && npos_nz > 0; }
-  // option "fac_op_scaled" (pure factored block): Y = W Vd (msz x nvar khat) of the scaling `Ys_version` (dataops.hip::fac_scaled_y)
+  // option "fac_op_scaled" (pure factored block): Y = W Vd (msz x nvar khat) of the scaling `Ys_version` (schur_factored.hip::fac_scaled_y)
   lrn::DBuf Ys;
   long Ys_version = -1;
   // diagonal parts (lrn_upload_diag, factored blocks only): constraint A_k = diag(a_k) + V_k D_k V_k' for the dg_n constraints
@@ -198,7 +198,7 @@ struct LrnOptions {
   int lowrank_wide = 0;           // lrn_upload_lowrank accepts khat 32 and 64 (factored constraints of rank 17 .. 64): 1, refuses them: 0.
                                   // A block uploaded so is assembled by rank class whatever lowrank_ragged says (raggedops.hip)
   int ragged_ops = 0;             // AA vec(.) and mat(AA' .) of a block of mixed ranks in factor form on the compacted columns of the
-                                  // rank classes (raggedops.hip): 1, on the padded layout: 0.  Independent of lowrank_ragged; the
+                                  // rank classes (fac_cols.h, raggedops.hip): 1, on the padded layout: 0.  Independent of lowrank_ragged; the
                                   // same conditions, the padded code otherwise ("ragged_ops_fallback")
   int ragged_cross = 0;           // Y = W V and its consumers in the mode-1 assembly of a block of mixed ranks -- the cross terms of a hybrid
                                   // block and of the diagonal parts -- on the compacted columns (Yc = W Vc): 1, on the padded layout: 0.
@@ -331,19 +331,16 @@ inline bool lowrank_ragged_on(const lrn_ctx* c, const LmiBlock& b) {
   if (c->world > 1 || b.rg_Rc <= 0) return false;
   return lowrank_wide(b) || (c->opt.lowrank_ragged != 0 && b.rg_Rc < (long)c->nvar * b.lr_khat);
 }
-// the data operators of a block on the compacted columns under option "ragged_ops": the same condition
-inline bool ragged_ops_on(const lrn_ctx* c, const LmiBlock& b) {
-  return c->opt.ragged_ops != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
+// the compacted columns of a block can stand in for the padded ones: one GPU, some but not all columns survive the compaction
+inline bool ragged_cols_usable(const lrn_ctx* c, const LmiBlock& b) {
+  return c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
 }
-// Y and the cross terms of the mode-1 assembly (option "ragged_cross"), ts of H_alpha (option "ragged_ts"): the same condition.
-// Every path they serve refuses world > 1 before it gets here (hybrid blocks, diagonal parts, lrn_prec_setup on factored
-// blocks): the world clause cannot be false today and is kept so that the four conditions read alike
-inline bool ragged_cross_on(const lrn_ctx* c, const LmiBlock& b) {
-  return c->opt.ragged_cross != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
-}
-inline bool ragged_ts_on(const lrn_ctx* c, const LmiBlock& b) {
-  return c->opt.ragged_ts != 0 && c->world <= 1 && b.rg_Rc > 0 && b.rg_Rc < (long)c->nvar * b.lr_khat;
-}
+// ... for the data operators (option "ragged_ops"), Y and the cross terms of the mode-1 assembly (option "ragged_cross"), ts of
+// H_alpha (option "ragged_ts").  Every path the last two serve refuses world > 1 before it gets here (hybrid blocks, diagonal
+// parts, lrn_prec_setup on factored blocks)
+inline bool ragged_ops_on(const lrn_ctx* c, const LmiBlock& b) { return c->opt.ragged_ops != 0 && ragged_cols_usable(c, b); }
+inline bool ragged_cross_on(const lrn_ctx* c, const LmiBlock& b) { return c->opt.ragged_cross != 0 && ragged_cols_usable(c, b); }
+inline bool ragged_ts_on(const lrn_ctx* c, const LmiBlock& b) { return c->opt.ragged_ts != 0 && ragged_cols_usable(c, b); }
 // hop.hip: the CG operator through the assembled matrix
 // y = H x; qpart (may be null): receives *nq partial sums of x'y (*nq = 0: not formed, e.g. sharded)
 int hop_apply(lrn_ctx* c, const double* x_dev, double* y_dev, double* qpart = nullptr, int* nq = nullptr);
@@ -361,11 +358,10 @@ inline bool cg_factored_on(const lrn_ctx* c) { return c->opt.cg_factored != 0 &&
 inline bool cg_diag_on(const lrn_ctx* c) { return c->opt.cg_diag != 0 && cg_factored_on(c); }
 bool fac_op_scaled_on(const lrn_ctx* c, const LmiBlock& b);      // hop.hip: operator of this pure factored block through Y = W Vd?
 bool fac_quadform_on(const lrn_ctx* c, const LmiBlock& b);       // hop.hip: AA vec(Z) of this factored block by the fused kernel?
-// facops.hip: out[nat(h)] -= sum_p w[h kh + p] v_c' Z v_c over the kh factor columns c = h kh + p of every constraint
-int fac_quadform(lrn_ctx* c, const double* Z, const double* Vd, const double* w, int m, int kh, int nvar, const int* sigma,
-                 double* out);
-// the first half alone on any column layout V (msz x R): *part = nstrip x R partial sums of <(Z V)(:, c), V(:, c)> by row strips
-int fac_quadform_parts(lrn_ctx* c, const double* Z, const double* V, int m, long R, double** part, int* nstrip);
+// facops.hip: out[nat(h)] -= sum_c w_c v_c' Z v_c over the factor columns c of every constraint, on the columns of the view
+// (fac_cols.h), Q = Z V never stored
+struct FacCols;
+int fac_quadform(lrn_ctx* c, const LmiBlock& b, const FacCols& v, const double* Z, const int* sigma, double* out);
 }  // namespace lrn
 
 #define LRN_HIP(c, expr)                                                                   \

@@ -13,6 +13,7 @@
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
 #include "ops.h"
+#include "fac_cols.h"
 
 namespace lrn {
 
@@ -910,20 +911,24 @@ int ensure_m(lrn_ctx* c, int m) {
 // A hybrid block adds the rows of its few stored constraints through the stored-entry kernels (aa_times_impl,
 // aat_to_mat_impl); their factor columns have weight 0 and contribute nothing here.
 
-// out[nat(h)] -= sum_p w[h kh + p] <Q(:, h kh + p), Vd(:, h kh + p)>   (sigma: H index -> constraint, null = identity)
-__global__ __launch_bounds__(256) void fac_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Vd,
-                                                         const double* __restrict__ w, int m, int kh, int nvar,
+// out[nat(h)] -= sum_p w[col] <Q(:, col), V(:, col)> over the columns col of unit u of the layout (fac_cols.h), h its H index
+// (sigma: H index -> constraint, null = identity): one wave per unit
+template <class Cols>
+__global__ __launch_bounds__(256) void fac_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ V,
+                                                         const double* __restrict__ w, int m, Cols lay,
                                                          const int* __restrict__ sigma, double* __restrict__ out) {
   const int lane = threadIdx.x & 63;
-  const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (h >= nvar) return;
+  const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+  typename Cols::Span span;
+  int cnt;
+  if (!lay.unit(u, &span, &cnt)) return;
   double s = 0.0;
-  for (int p = 0; p < kh; ++p) {
-    const long col = (long)h * kh + p;
+  for (int p = 0; p < cnt; ++p) {
+    const long col = lay.col(span, p);
     const double wp = w[col];
     if (wp == 0.0) continue;                       // padding column (wave-uniform)
     const double* __restrict__ q = Q + col * m;
-    const double* __restrict__ v = Vd + col * m;
+    const double* __restrict__ v = V + col * m;
     double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
     int r = lane;
     for (; r + 192 < m; r += 256) {
@@ -937,7 +942,9 @@ __global__ __launch_bounds__(256) void fac_coldot_kernel(const double* __restric
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) out[sigma ? sigma[h] : h] -= s;
+  if (lane != 0) return;
+  const int h = lay.unit_h(u, span);
+  out[sigma ? sigma[h] : h] -= s;
 }
 
 // Vs(:, c) = -w[c] x[nat(c / kh)] Vd(:, c)   (one workgroup per factor column)
@@ -959,37 +966,31 @@ static int fac_workspace(lrn_ctx* c, LmiBlock& b, double** ws) {
   return LRN_OK;
 }
 
-// y += AA vec(Z), Z symmetric.  fused (option "fac_quadform", the CG operator only): facops.hip, Q never stored
+// y += AA vec(Z), Z symmetric: Q = Z V by the product every route uses, then the column dots -- or, fused (option
+// "fac_quadform", the CG operator only), the quadratic form of facops.hip, Q never stored.  V is Vd, or under option
+// "ragged_ops" the compacted columns Vc of a block of mixed ranks (the conditions of the rank-class assembly; a uniform block,
+// an empty one and a sharded run keep the padded columns)
 static int aa_times_factored(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused = false) {
-  const int m = b.msz, kh = b.lr_khat;
-  const long R = (long)c->nvar * kh;
-  // option "ragged_ops": a block of mixed ranks on the compacted columns of its rank classes (raggedops.hip), under the
-  // conditions of the rank-class assembly; a uniform block, an empty one and a sharded run keep the padded code below
-  if (c->opt.ragged_ops) {
-    if (ragged_ops_on(c, b)) {
-      if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
-      return aa_times_ragged(c, b, Z, y, fused);
-    }
-    c->counts["ragged_ops_fallback"] += 1;
-  }
+  const int m = b.msz;
+  const bool rg = ragged_ops_on(c, b);
+  if (c->opt.ragged_ops && !rg) c->counts["ragged_ops_fallback"] += 1;
+  if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
+  if (rg) LRN_TRY(ragged_setup(c, b));
+  const FacCols v = fac_cols(c, b, rg);
+  const int* sigma = c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr;
   if (fused) {
-    if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
-    LRN_TRY(fac_quadform(c, Z, b.Vd.as<double>(), b.v_w.as<double>(), m, kh, c->nvar,
-                         c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, y));
-    c->counts["op_factored"] += 1;
-    return LRN_OK;
+    LRN_TRY(fac_quadform(c, b, v, Z, sigma, y));
+  } else {
+    LRN_TRY(ensure(c, c->BG, (size_t)m * v.R * 8));
+    double* Q = c->BG.as<double>();
+    LRN_TRY(cols_product(c, Z, false, v.V, v.R, m, Q));
+    with_layout(c, b, v, [&](auto lay) {
+      hipLaunchKernelGGL(fac_coldot_kernel<decltype(lay)>, dim3((v.nunit + 3) / 4), dim3(256), 0, c->stream, Q, v.V, v.w, m, lay,
+                         sigma, y);
+    });
   }
-  double* Q = nullptr;
-  LRN_TRY(fac_workspace(c, b, &Q));
-  GemmDesc g;     // Q = Z Vd, msz x R
-  g.A = Z; g.sAm = 1; g.sAk = m;
-  g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
-  g.C = Q; g.sCm = 1; g.sCn = m;
-  g.M = m; g.N = (int)R; g.K = m;
-  LRN_TRY(gemm(c->stream, g));
-  hipLaunchKernelGGL(fac_coldot_kernel, dim3((c->nvar + 3) / 4), dim3(256), 0, c->stream, Q, b.Vd.as<double>(),
-                     b.v_w.as<double>(), m, kh, c->nvar, c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr, y);
   c->counts["op_factored"] += 1;
+  if (rg) c->counts["op_ragged"] += 1;
   return LRN_OK;
 }
 
@@ -1200,28 +1201,14 @@ static int aat_to_mat_stored(lrn_ctx* c, LmiBlock& b, const double* x, double* M
 // Y = W Vd of a pure factored block (option "fac_op_scaled"), once per NT scaling: with it
 //     W mat(AA' x) W = -W Vd diag(w o x) Vd' W = -Y diag(w o x) Y',
 // the scaled copy, lower-triangle product and mirror of aat_to_mat_factored on Y instead of Vd -- no W M W product
-static int fac_scaled_y(lrn_ctx* c, LmiBlock& b) {
-  if (ragged_ops_on(c, b)) {      // option "ragged_ops": Yc = W Vc (msz x Rc) instead, cached the same way (raggedops.hip)
-    if (b.Yc_version == c->scal_version && b.Yc.p) return LRN_OK;
-    if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
-    OpTimer t(c, "fac_scaled_y");
-    LRN_TRY(ragged_scaled_y(c, b));
-    c->counts["fac_scaled_y"] += 1;
-    return t.done(LRN_OK);
-  }
-  if (b.Ys_version == c->scal_version && b.Ys.p) return LRN_OK;
+// Option "ragged_ops": Yc = W Vc (msz x Rc) instead.  fac_scaled_y (schur_factored.hip) forms and caches either; this is its
+// timed and counted call from the operator -- nothing is counted while the cached product is current
+static int fac_scaled_y_op(lrn_ctx* c, LmiBlock& b) {
+  const bool rg = ragged_ops_on(c, b);
+  if ((rg ? b.Yc_version : b.Ys_version) == c->scal_version && (rg ? b.Yc.p : b.Ys.p)) return LRN_OK;
   if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
   OpTimer t(c, "fac_scaled_y");
-  const int m = b.msz;
-  const long R = (long)c->nvar * b.lr_khat;
-  LRN_TRY(ensure(c, b.Ys, (size_t)m * R * 8));
-  GemmDesc g;
-  g.A = b.W.as<double>(); g.sAm = 1; g.sAk = m;
-  g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
-  g.C = b.Ys.as<double>(); g.sCm = 1; g.sCn = m;
-  g.M = m; g.N = (int)R; g.K = m;
-  LRN_TRY(gemm(c->stream, g));
-  b.Ys_version = c->scal_version;
+  LRN_TRY(fac_scaled_y(c, b, rg));
   c->counts["fac_scaled_y"] += 1;
   return t.done(LRN_OK);
 }
@@ -1237,7 +1224,7 @@ int matvec_dev(lrn_ctx* c, const double* x, double* y) {
     // quadratic form for the factor part of AA vec(.) (a hybrid block's stored rows still go through aa_times_kernel)
     const bool fused = b.factored && fac_quadform_on(c, b);
     if (b.factored && fac_op_scaled_on(c, b)) {
-      LRN_TRY(fac_scaled_y(c, b));
+      LRN_TRY(fac_scaled_y_op(c, b));
       LRN_TRY(ensure_m(c, m));
       double* N = c->m0.as<double>();
       {

@@ -232,7 +232,7 @@ int hop_apply(lrn_ctx* c, const double* x, double* y, double* qpart, int* nq) {
 //
 // Option "cg_lowrank" (0 never, 1 always, -1 by the terms below): a COVERED block (cg_lowrank_covered: not factored, factors
 // for every constraint that has entries) can serve each piece of the CG path from its rank-k factors instead of its
-// entries -- the assembly of H in mode 1, the matrix-free operator in factor form, ts of H_alpha (cgops.hip::fac_ts_kernel).
+// entries -- the assembly of H in mode 1, the matrix-free operator in factor form, ts of H_alpha (facops.hip::fac_ts_kernel).
 // The three terms est_assemble_s(., 1), est_operator_block_s(., ., true) and est_ts_s(., ., ., true) carry rates measured at
 // msz 2000 / nvar 4000 / rank 2 (DESIGN.md sections 10, 11, 14).  With world > 1 the option is ignored and the entry routes
 // run: the factor routes are not sharded, and no multi-GPU machine was there to test anything else.

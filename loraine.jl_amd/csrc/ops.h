@@ -84,23 +84,24 @@ bool chol_path_applicable(lrn_ctx* c, LmiBlock& b, long* pcap_out);
 // schur_factored.hip: rank-one data (mode -1), rank-k data (mode 1), cross terms of a hybrid factored block
 int assemble_rank1(lrn_ctx* c, LmiBlock& b);
 int assemble_lowrank(lrn_ctx* c, LmiBlock& b);
+// C = op(A) V into msz x R columns (op = transpose where transA): the product of every route that multiplies dense factor columns
+int cols_product(lrn_ctx* c, const double* A, bool transA, const double* V, long R, int m, double* C);
+// Y = W V of the current scaling, cached per scaling: Ys = W Vd (msz x nvar khat), or Yc = W Vc (msz x Rc) where compact
+int fac_scaled_y(lrn_ctx* c, LmiBlock& b, bool compact);
 int factored_y(lrn_ctx* c, LmiBlock& b, const double** Y);      // Y = W Vd (msz x nvar khat) after assemble_lowrank: its U, or one more product; Yc = W Vc (msz x Rc) under ragged_cross_on
-int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);
+int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);   // cross terms of a hybrid block from that Y, in its layout
+// facops.hip: ts of H_alpha from P = L' V (msz x R) and T = V' Um (R x erank) on the columns of the view (fac_cols.h; prec_setup
+// decides, option "ragged_ts"): every element of the block's nvar x erank msz part of ts written once
+struct FacCols;
+int fac_ts(lrn_ctx* c, const LmiBlock& b, const FacCols& v, const double* P, const double* T, const double* d, int erank,
+           double* ts);
 // raggedops.hip: H_FF of a block of mixed ranks by rank class (option "lowrank_ragged"; assemble_lowrank decides)
 int assemble_ragged(lrn_ctx* c, LmiBlock& b);
-// ... and the two data operators in factor form on the same compacted columns (option "ragged_ops"; aa_times_factored and
-// aat_to_mat_factored of dataops.hip decide).  ragged_setup: the plan of the block and Vc, once per upload, whichever route
-// comes first; ragged_scaled_y: Yc = W Vc of the current scaling (option "fac_op_scaled")
+// ... and mat(AA' x) in factor form on the same compacted columns (option "ragged_ops"; aat_to_mat_factored of dataops.hip
+// decides).  ragged_setup: the plan of the block and Vc, once per upload, whichever route on the compacted columns comes first
 int ragged_setup(lrn_ctx* c, LmiBlock& b);
-int ragged_scaled_y(lrn_ctx* c, LmiBlock& b);
-int aa_times_ragged(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused);            // y[nat] -= sum_c wc <(Z Vc)_c, Vc_c> by group
 // M = -F diag(wc o x) F', F = Vc (null) or Yc; *ks = 1: lower tiles only, the caller mirrors them
 int aat_to_mat_ragged(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const double* F, int* ks);
-// ... the cross terms of a hybrid block on Yc = W Vc, by group (option "ragged_cross"; factored_y hands Yc out, assemble_cross
-// and assemble_diag follow it) and ts of H_alpha from Pc = L' Vc (msz x Rc) and Tc = Vc' Um (Rc x erank) (option "ragged_ts";
-// prec_setup decides): every element of the block's nvar x erank msz part of ts written once
-int assemble_cross_ragged(lrn_ctx* c, LmiBlock& b, const double* Yc);
-int ragged_ts(lrn_ctx* c, LmiBlock& b, const double* Pc, const double* Tc, const double* d, int erank, double* ts);
 // diagops.hip: diagonal parts of a factored block (lrn_upload_diag), A_k = diag(a_k) + V_k D_k V_k'
 int assemble_diag(lrn_ctx* c, LmiBlock& b, const double* Y);    // H_DD, the cross terms with the factors (Y) and with the stored rows
 int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // y[nat(s)] -= sum_i a_si Z_ii

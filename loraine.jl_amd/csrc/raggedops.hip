@@ -1,6 +1,7 @@
 // Rank-class route of the rank-k Schur assembly (option "lowrank_ragged", schur_factored.hip::assemble_lowrank), and below it
-// the two data operators in factor form on the same compacted columns (option "ragged_ops", dataops.hip), the cross terms of a
-// hybrid block (option "ragged_cross") and ts of H_alpha (option "ragged_ts", cgops.hip) at the end of the file.
+// mat(AA' x) in factor form on the same compacted columns (option "ragged_ops", dataops.hip).  What else runs on the compacted
+// columns -- AA vec(Z), the cross terms of a hybrid block, ts of H_alpha -- is the padded code on another column layout
+// (fac_cols.h) and lives beside it.
 //
 // The padded route pads every constraint of a block to khat columns, khat from the LARGEST rank, and pays msz R^2 multiply-adds
 // for H_FF = blocksum(d d' o (U' V)^2), R = nvar khat.  Here the constraints are grouped by rank class (ragged_plan.h): class c_j
@@ -290,15 +291,7 @@ int assemble_ragged(lrn_ctx* c, LmiBlock& b) {
   LRN_TRY(ensure(c, c->BG, (size_t)m * Rc * 8));
   double* U = c->BG.as<double>();
   tic(c);
-  {
-    GemmDesc g;     // U_c = G' Vc (or W Vc), msz x Rc
-    g.A = fromW ? b.W.as<double>() : b.G.as<double>();
-    if (fromW) { g.sAm = 1; g.sAk = m; } else { g.sAm = m; g.sAk = 1; }
-    g.B = b.Vc.as<double>(); g.sBk = 1; g.sBn = m;
-    g.C = U; g.sCm = 1; g.sCn = m;
-    g.M = m; g.N = (int)Rc; g.K = m;
-    LRN_TRY(gemm(c->stream, g));
-  }
+  LRN_TRY(cols_product(c, fromW ? b.W.as<double>() : b.G.as<double>(), !fromW, b.Vc.as<double>(), Rc, m, U));      // U_c = G' Vc (or W Vc)
   toc(c, "lowrank_u");     // (U_c alone; "ragged" below: U_c and the tile launch, from the same start)
   if (b.rg_ntiles > 0)
     hipLaunchKernelGGL(ragged_blocksum_kernel, dim3((unsigned)b.rg_ntiles), dim3(256), 0, c->stream, U,
@@ -314,13 +307,13 @@ int assemble_ragged(lrn_ctx* c, LmiBlock& b) {
   return LRN_OK;
 }
 
-// ================================================================ the data operators on the compacted columns
-// Option "ragged_ops" (dataops.hip::aa_times_factored, aat_to_mat_factored decide): the factor form of AA vec(Z) and mat(AA' x)
-// of a block of mixed ranks on Vc (msz x Rc) instead of Vd (msz x nvar khat), with the plan the assembly above uses.
-//     (AA vec(Z))_j = -sum_{c in group of j} wc_c v_c' Z v_c     Q = Z Vc by the product every route uses (or the fused quadratic
-//                                                               form of facops.hip on (Vc, Rc)), then sums by GROUP through gh
+// ================================================================ mat(AA' x) on the compacted columns
+// Option "ragged_ops" (dataops.hip::aat_to_mat_factored decides): the factor form of mat(AA' x) of a block of mixed ranks on Vc
+// (msz x Rc) instead of Vd (msz x nvar khat), with the plan the assembly above uses.
 //     mat(AA' x)    = -sum_c s_c f_c f_c',  s_c = wc_c x[nat(gh[cg[c]])],  F = Vc or Yc = W Vc (option "fac_op_scaled")
-// A constraint of rank 0 has no group and receives nothing.  Every sum has a fixed order and one writer: no atomics.
+// The padded code scales a copy of the factors and runs a lower-triangle product: a different route, which is why this operator
+// has a kernel of its own here while AA vec(Z) is dataops.hip::aa_times_factored on either layout.  A constraint of rank 0 has
+// no group and contributes nothing.  Every sum has a fixed order and one writer: no atomics.
 //
 // ragged_syrk_kernel: 256 threads, grid = lower tiles x K-chunks.  Workgroup (t, s): the 64 x 64 tile (ti, tj), ti >= tj, of M
 // over the columns of chunk s (ragged_plan.h::ragged_chunk_cols), in steps of 16 columns, the tail zero-filled.  Both panels
@@ -336,75 +329,6 @@ int assemble_ragged(lrn_ctx* c, LmiBlock& b) {
 // above the diagonal is written too and overwritten by the mirror).
 // ragged_syrk_reduce_kernel: adds the slabs in the order 0 .. ks - 1 for i >= j and writes M[i, j] and M[j, i] from the one
 // sum, by 32 x 32 tile pairs through LDS as mirror_lower_tiled_kernel does: M is exactly symmetric, two calls give equal bits.
-struct RaggedSegs { long seg0[RG_NCLS]; int grp0[RG_NCLS + 1]; };
-
-// first column and class size of group g (g < grp0[RG_NCLS])
-__device__ __forceinline__ long ragged_group_col(const RaggedSegs& sg, int g, int* cj) {
-  int ci = 0;
-  while (ci < RG_NCLS - 1 && g >= sg.grp0[ci + 1]) ++ci;
-  *cj = ragged_class_size(ci);
-  return sg.seg0[ci] + (long)(g - sg.grp0[ci]) * ragged_class_size(ci);
-}
-
-// out[nat(gh[g])] -= sum_{p < c_j} wc[col] <Q(:, col), Vc(:, col)>, col = first column of group g + p: one wave per group,
-// the rows by the four accumulators and the one shuffle tree of fac_coldot_kernel
-__global__ __launch_bounds__(256) void ragged_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Vc,
-                                                            const double* __restrict__ wc, int m, RaggedSegs sg,
-                                                            const int* __restrict__ gh, const int* __restrict__ sigma,
-                                                            double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= sg.grp0[RG_NCLS]) return;
-  int cj;
-  const long c0 = ragged_group_col(sg, g, &cj);
-  double s = 0.0;
-  for (int p = 0; p < cj; ++p) {
-    const long col = c0 + p;
-    const double wp = wc[col];
-    if (wp == 0.0) continue;                       // padding column (wave-uniform)
-    const double* __restrict__ q = Q + col * m;
-    const double* __restrict__ v = Vc + col * m;
-    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-    int r = lane;
-    for (; r + 192 < m; r += 256) {
-      t0 += q[r] * v[r];
-      t1 += q[r + 64] * v[r + 64];
-      t2 += q[r + 128] * v[r + 128];
-      t3 += q[r + 192] * v[r + 192];
-    }
-    for (; r < m; r += 64) t0 += q[r] * v[r];
-    s += wp * ((t0 + t1) + (t2 + t3));
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane != 0) return;
-  const int h = gh[g];
-  out[sigma ? sigma[h] : h] -= s;
-}
-
-// the same sums from the partial sums of fac_quadform_kernel on (Vc, Rc): strips in order, then the columns of the group
-// (one thread per group; fixed order)
-__global__ __launch_bounds__(256) void ragged_quadform_reduce_kernel(const double* __restrict__ part, int nstrip, long Rc,
-                                                                     const double* __restrict__ wc, RaggedSegs sg,
-                                                                     const int* __restrict__ gh, const int* __restrict__ sigma,
-                                                                     double* __restrict__ out) {
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= sg.grp0[RG_NCLS]) return;
-  int cj;
-  const long c0 = ragged_group_col(sg, g, &cj);
-  double s = 0.0;
-  for (int p = 0; p < cj; ++p) {
-    const long col = c0 + p;
-    const double wp = wc[col];
-    if (wp == 0.0) continue;                       // padding column
-    double q = 0.0;
-    for (int st = 0; st < nstrip; ++st) q += part[(long)st * Rc + col];
-    s += wp * q;
-  }
-  const int h = gh[g];
-  out[sigma ? sigma[h] : h] -= s;
-}
-
 static constexpr int RS_LD = 80;       // row stride of Ps / Qs (doubles)
 
 __global__ __launch_bounds__(256) void ragged_syrk_kernel(const double* __restrict__ F, int m, long Rc,
@@ -510,61 +434,6 @@ __global__ void ragged_syrk_reduce_kernel(const double* __restrict__ slabs, long
   }
 }
 
-static RaggedSegs ragged_segs(const LmiBlock& b) {
-  RaggedSegs sg;
-  for (int ci = 0; ci < RG_NCLS; ++ci) sg.seg0[ci] = b.rg_seg0[ci];
-  for (int ci = 0; ci <= RG_NCLS; ++ci) sg.grp0[ci] = b.rg_grp0[ci];
-  return sg;
-}
-
-// Yc = W Vc (msz x Rc) of the current scaling: what fac_scaled_y is on the padded layout
-int ragged_scaled_y(lrn_ctx* c, LmiBlock& b) {
-  LRN_TRY(ragged_setup(c, b));
-  if (b.Yc_version == c->scal_version && b.Yc.p) return LRN_OK;
-  const int m = b.msz;
-  LRN_TRY(ensure(c, b.Yc, (size_t)m * b.rg_Rc * 8));
-  GemmDesc g;
-  g.A = b.W.as<double>(); g.sAm = 1; g.sAk = m;
-  g.B = b.Vc.as<double>(); g.sBk = 1; g.sBn = m;
-  g.C = b.Yc.as<double>(); g.sCm = 1; g.sCn = m;
-  g.M = m; g.N = (int)b.rg_Rc; g.K = m;
-  LRN_TRY(gemm(c->stream, g));
-  b.Yc_version = c->scal_version;
-  return LRN_OK;
-}
-
-// y += the factor part of AA vec(Z).  The caller has checked the factors and the route (ragged_ops_on)
-int aa_times_ragged(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool fused) {
-  const int m = b.msz;
-  LRN_TRY(ragged_setup(c, b));
-  const long Rc = b.rg_Rc;
-  const RaggedSegs sg = ragged_segs(b);
-  const int ngrp = sg.grp0[RG_NCLS];
-  const int* sigma = c->pos_space ? b.sigma_d.as<int>() : (const int*)nullptr;
-  if (fused) {
-    double* part = nullptr;
-    int nstrip = 0;
-    LRN_TRY(fac_quadform_parts(c, Z, b.Vc.as<double>(), m, Rc, &part, &nstrip));
-    hipLaunchKernelGGL(ragged_quadform_reduce_kernel, dim3((ngrp + 255) / 256), dim3(256), 0, c->stream, part, nstrip, Rc,
-                       b.rg_wc.as<double>(), sg, b.rg_gh.as<int>(), sigma, y);
-    c->counts["op_quadform_fused"] += 1;
-  } else {
-    LRN_TRY(ensure(c, c->BG, (size_t)m * Rc * 8));
-    double* Q = c->BG.as<double>();
-    GemmDesc g;     // Q = Z Vc, msz x Rc
-    g.A = Z; g.sAm = 1; g.sAk = m;
-    g.B = b.Vc.as<double>(); g.sBk = 1; g.sBn = m;
-    g.C = Q; g.sCm = 1; g.sCn = m;
-    g.M = m; g.N = (int)Rc; g.K = m;
-    LRN_TRY(gemm(c->stream, g));
-    hipLaunchKernelGGL(ragged_coldot_kernel, dim3((ngrp + 3) / 4), dim3(256), 0, c->stream, Q, b.Vc.as<double>(),
-                       b.rg_wc.as<double>(), m, sg, b.rg_gh.as<int>(), sigma, y);
-  }
-  c->counts["op_factored"] += 1;
-  c->counts["op_ragged"] += 1;
-  return LRN_OK;
-}
-
 // K-chunks of the syrk when the option leaves them open: the smallest ks for which tiles x ks fills the chip FOUR times over at
 // the kernel's compiled occupancy (workgroups per CU x CUs, asked of the runtime once), a chunk kept to at least 16 K-steps
 // (256 columns).  The first rule -- fill the chip once, ks = 2 at msz 2000 -- had no measurement behind it; the sweep of
@@ -609,204 +478,6 @@ int aat_to_mat_ragged(lrn_ctx* c, LmiBlock& b, const double* x, double* M, const
   c->rg_last_chunks = ks;
   c->counts["op_factored"] += 1;
   c->counts["op_ragged"] += 1;
-  return LRN_OK;
-}
-
-// ================================================================ cross terms of a hybrid block on the compacted columns
-// Option "ragged_cross" (schur_factored.hip::factored_y, assemble_cross decide): H_sj = sum_c wc_c y_c' A_s y_c over the columns
-// c of the GROUP of the factored constraint j, y_c the columns of Yc = W Vc (msz x Rc).  A constraint of rank 0 has no group and
-// receives nothing (the padded kernel adds + 0 to its entries).
-//
-// ragged_cross_kernel: fac_cross_kernel of schur_factored.hip with grid.x over the groups instead of the factored positions --
-// hj = gh[g], the columns group start .. + class size, weight-0 padding skipped (uniform over the workgroup).  Everything else
-// is that kernel's: workgroup (g, y) takes the 32 sparse-tier stored positions s_lo + 32 y .., wave v the positions + 4 t + v,
-// t < 8, in eight register sums; a column of Yc is staged in LDS (msz x 8 bytes, dynamic) or read from global memory by the
-// same code; lanes stride the entry list of A_s, one shuffle tree in a fixed order, the sum weighted and added over the
-// columns in order; lane 0 adds the eight sums to H, one writer per entry, no atomics.  LDS accesses: the staging writes are
-// ds_write_b64 of consecutive doubles (lane l -> dwords 2 l, 2 l + 1 of a 256-dword run: conflict-free); the gather reads
-// ycol[r], ycol[cc] follow the entry list of A_s, their banks are data-dependent -- an entry list sorted by column reads one
-// address for cc (a broadcast) and scattered rows for r, anything from free to a multi-way conflict.  Derived, not measured.
-template <bool LDS>
-__global__ __launch_bounds__(256) void ragged_cross_kernel(const long* __restrict__ ptr, const int* __restrict__ er,
-                                                           const int* __restrict__ ec, const double* __restrict__ ev,
-                                                           const double* __restrict__ Yc, const double* __restrict__ wc, int m,
-                                                           RaggedSegs sg, int s_lo, int s_hi, const int* __restrict__ gh,
-                                                           const int* __restrict__ hidx, double* __restrict__ H, int ldh) {
-  extern __shared__ double rg_ycol[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = blockIdx.x;
-  if (g >= sg.grp0[RG_NCLS]) return;             // (whole workgroup)
-  int cj;
-  const long c0 = ragged_group_col(sg, g, &cj);
-  const int hj = gh[g];
-  const int sb = s_lo + blockIdx.y * 32 + wave;
-  double acc[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) acc[t] = 0.0;
-  for (int p = 0; p < cj; ++p) {
-    const long col = c0 + p;
-    const double wp = wc[col];
-    if (wp == 0.0) continue;                     // padding column (uniform over the workgroup)
-    const double* __restrict__ yg = Yc + col * m;
-    if (LDS) {
-      __syncthreads();                           // the waves are done with the previous column
-      for (int r = threadIdx.x; r < m; r += 256) rg_ycol[r] = yg[r];
-      __syncthreads();
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int sp = sb + 4 * t;                 // wave-uniform
-      if (sp >= s_hi) continue;
-      double q = 0.0;
-      for (long e = ptr[sp] + lane; e < ptr[sp + 1]; e += 64) {
-        const int r = er[e], cc = ec[e];
-        q += ev[e] * (LDS ? rg_ycol[r] * rg_ycol[cc] : yg[r] * yg[cc]);
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
-      acc[t] += wp * q;
-    }
-  }
-  if (lane != 0) return;
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int sp = sb + 4 * t;
-    if (sp >= s_hi) continue;
-    H[h_lower(hidx[sp], hj, ldh)] += acc[t];
-  }
-}
-
-// dense slot s: Q = A_s Yc is one product (msz x Rc), H_sj = sum_c wc_c <Q(:, c), Yc(:, c)> one wave per group (the sums of
-// fac_cross_coldot_kernel), written once.  No LDS
-__global__ __launch_bounds__(256) void ragged_cross_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Yc,
-                                                                  const double* __restrict__ wc, int m, RaggedSegs sg, int s,
-                                                                  const int* __restrict__ gh, const int* __restrict__ hidx,
-                                                                  double* __restrict__ H, int ldh) {
-  const int lane = threadIdx.x & 63;
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= sg.grp0[RG_NCLS]) return;             // (whole wave)
-  int cj;
-  const long c0 = ragged_group_col(sg, g, &cj);
-  double acc = 0.0;
-  for (int p = 0; p < cj; ++p) {
-    const long col = c0 + p;
-    const double wp = wc[col];
-    if (wp == 0.0) continue;
-    const double* __restrict__ q = Q + col * m;
-    const double* __restrict__ y = Yc + col * m;
-    double t = 0.0;
-    for (int r = lane; r < m; r += 64) t += q[r] * y[r];
-    acc += wp * t;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if (lane != 0) return;
-  H[h_lower(hidx[s], gh[g], ldh)] += acc;
-}
-
-// the caller (assemble_cross) has checked the route (ragged_cross_on) and that factored positions exist; Yc from factored_y
-int assemble_cross_ragged(lrn_ctx* c, LmiBlock& b, const double* Yc) {
-  const int n = c->nvar, m = b.msz;
-  if (!Yc) return set_error(c, LRN_ERR_STATE, "ragged_cross: Yc = W Vc was not formed");
-  LRN_TRY(ragged_setup(c, b));
-  const long Rc = b.rg_Rc;
-  const RaggedSegs sg = ragged_segs(b);
-  const int ngrp = sg.grp0[RG_NCLS];
-  if (ngrp <= 0) return LRN_OK;
-  tic(c);
-  if (b.npos_nz > b.nd) {
-    const size_t cap = c->opt.fac_cross_lds == 1 ? 65536 : 32768;      // the rule of assemble_cross
-    const bool lds = c->opt.fac_cross_lds != 0 && (size_t)m * 8 <= cap;
-    const dim3 grid((unsigned)ngrp, (unsigned)((b.npos_nz - b.nd + 31) / 32));
-#define LRN_RCROSS_LAUNCH(L, SH)                                                                                          \
-  hipLaunchKernelGGL(ragged_cross_kernel<L>, grid, dim3(256), SH, c->stream, b.ent_ptr.as<long>(), b.ent_r.as<int>(),    \
-                     b.ent_c.as<int>(), b.ent_v.as<double>(), Yc, b.rg_wc.as<double>(), m, sg, b.nd, b.npos_nz,           \
-                     b.rg_gh.as<int>(), b.hidx.as<int>(), c->H.as<double>(), n)
-    if (lds) LRN_RCROSS_LAUNCH(true, (size_t)m * 8);
-    else LRN_RCROSS_LAUNCH(false, 0);
-#undef LRN_RCROSS_LAUNCH
-    c->counts[lds ? "hybrid_cross_lds" : "hybrid_cross_global"] += 1;
-  }
-  if (b.nd > 0) {
-    LRN_TRY(ensure(c, c->P, (size_t)m * Rc * 8));
-    double* Q = c->P.as<double>();
-    for (int s = 0; s < b.nd; ++s) {
-      GemmDesc g;     // Q = A_s Yc
-      g.A = b.Adense.as<double>() + (long)s * m * m; g.sAm = 1; g.sAk = m;
-      g.B = Yc; g.sBk = 1; g.sBn = m;
-      g.C = Q; g.sCm = 1; g.sCn = m;
-      g.M = m; g.N = (int)Rc; g.K = m;
-      LRN_TRY(gemm(c->stream, g));
-      hipLaunchKernelGGL(ragged_cross_coldot_kernel, dim3((ngrp + 3) / 4), dim3(256), 0, c->stream, Q, Yc, b.rg_wc.as<double>(),
-                         m, sg, s, b.rg_gh.as<int>(), b.hidx.as<int>(), c->H.as<double>(), n);
-    }
-    c->counts["hybrid_cross_dense"] += 1;
-  }
-  toc(c, "hybrid_cross");
-  return LRN_OK;
-}
-
-// ================================================================ ts of H_alpha on the compacted columns
-// Option "ragged_ts" (cgops.hip::prec_setup decides): with Pc = L' Vc (msz x Rc) and Tc = Vc' Um (Rc x erank),
-//     ts[j, col0 + a m + r] = -(1 / sqrt(d_j)) sum_{c in group of j} wc_c Tc[c, a] Pc[r, c]
-// -- the sum fac_ts_kernel of cgops.hip forms over the khat padded columns of constraint j, over the class-size columns of its
-// group instead, in the same order (the weighted columns keep their order in a group), padding skipped.
-//
-// ragged_ts_kernel keeps that kernel's tiling: workgroup tile = 64 natural rows j x 64 rows r of Pc, eigenvector = blockIdx.z;
-// wave w takes the constraints j0 + w, j0 + w + 4, ..: h = ipos ? ipos[j] : j, g = hg[h], the columns group start .. + class
-// size; its 64 lanes read 64 consecutive doubles of each column of Pc (512 B per load) with the coefficient wc_c Tc[c, a] as a
-// wave-uniform scalar.  hg[h] < 0 (rank 0: a stored row, a purely diagonal row) stores 0, as do rows j >= nvar and r >= msz of
-// a partial tile.  The sums go to row jl of an LDS tile of 64 x 65 doubles (33 280 bytes): ds_write_b64, lane l at dwords
-// 130 jl + 2 l -- 64 consecutive doubles, conflict-free.  After the barrier lane l of wave w reads tile[l][rr], rr = w, w + 4, ..:
-// dword address 130 l + 2 rr, bank (2 l + 2 rr) mod 64 -- the 32 lanes of a half take the 32 even banks and their odd
-// neighbours once each: conflict-free, where a row stride of 64 doubles would put all of them on one bank pair.  Derived from
-// the bank rule as for fac_ts_kernel, not measured.  The wave then writes 64 consecutive rows j of one column of ts.  Every
-// element of the block's part of ts is written exactly once: no memset, no atomics, two setups give the same bits.
-static constexpr int RTS_TILE = 64;
-__global__ __launch_bounds__(256) void ragged_ts_kernel(const double* __restrict__ Pm, const double* __restrict__ T,
-                                                        const double* __restrict__ wc, RaggedSegs sg, const int* __restrict__ hg,
-                                                        const int* __restrict__ ipos, const double* __restrict__ d, int m, long Rc,
-                                                        int nvar, double* __restrict__ ts) {
-  __shared__ double tile[RTS_TILE][RTS_TILE + 1];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j0 = blockIdx.x * RTS_TILE, r0 = blockIdx.y * RTS_TILE, a = blockIdx.z;
-  const double* __restrict__ Ta = T + (long)a * Rc;
-  const int r = r0 + lane;
-  for (int jl = wv; jl < RTS_TILE; jl += 4) {
-    const int j = j0 + jl;
-    double s = 0.0;
-    if (j < nvar) {                                  // (wave-uniform)
-      const int g = hg[ipos ? ipos[j] : j];
-      if (g >= 0) {                                  // (rank 0: no group, the row stays zero)
-        int cj;
-        const long c0 = ragged_group_col(sg, g, &cj);
-        for (int p = 0; p < cj; ++p) {
-          const double wp = wc[c0 + p];
-          if (wp == 0.0) continue;                   // padding column
-          const double cf = wp * Ta[c0 + p];
-          if (r < m) s += cf * Pm[(c0 + p) * m + r];
-        }
-      }
-    }
-    tile[jl][lane] = s;
-  }
-  __syncthreads();
-  const int j = j0 + lane;
-  if (j >= nvar) return;
-  const double sc = -1.0 / sqrt(d[j]);
-  double* __restrict__ out = ts + (long)a * m * nvar + j;
-  for (int rr = wv; rr < RTS_TILE && r0 + rr < m; rr += 4) out[(long)(r0 + rr) * nvar] = sc * tile[lane][rr];
-}
-
-int ragged_ts(lrn_ctx* c, LmiBlock& b, const double* Pc, const double* Tc, const double* d, int erank, double* ts) {
-  const int n = c->nvar, m = b.msz;
-  LRN_TRY(ragged_setup(c, b));
-  const long tx = (n + RTS_TILE - 1) / RTS_TILE, ty = (m + RTS_TILE - 1) / RTS_TILE;
-  if (ty > 65535 || erank > 65535) return set_error(c, LRN_ERR_ARG, "ragged_ts: %ld row tiles, erank %d", ty, erank);
-  hipLaunchKernelGGL(ragged_ts_kernel, dim3((unsigned)tx, (unsigned)ty, (unsigned)erank), dim3(256), 0, c->stream, Pc, Tc,
-                     b.rg_wc.as<double>(), ragged_segs(b), b.rg_hg.as<int>(),
-                     c->pos_space ? b.ipos_d.as<int>() : (const int*)nullptr, d, m, b.rg_Rc, n, ts);
   return LRN_OK;
 }
 

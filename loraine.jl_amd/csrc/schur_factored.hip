@@ -1,6 +1,7 @@
 // Schur-complement assembly from factors: rank-one data (mode -1), rank-k data (mode 1) and the cross terms of a hybrid
 // factored block.  Overview: schur.hip.
 #include "ops.h"
+#include "fac_cols.h"
 #include "schur_plan.h"
 
 namespace lrn {
@@ -133,13 +134,7 @@ int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
   double* U = c->BG.as<double>();
   tic(c);
   if (dense) {
-    GemmDesc g;     // U = G' Vd (or W Vd), msz x R
-    g.A = M;
-    if (fromW) { g.sAm = 1; g.sAk = m; } else { g.sAm = m; g.sAk = 1; }
-    g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
-    g.C = U; g.sCm = 1; g.sCn = m;
-    g.M = m; g.N = (int)R; g.K = m;
-    LRN_TRY(gemm(c->stream, g));
+    LRN_TRY(cols_product(c, M, !fromW, b.Vd.as<double>(), R, m, U));      // U = G' Vd (or W Vd), msz x R
   } else {
     hipLaunchKernelGGL(lowrank_gather_kernel, dim3((unsigned)R), dim3(256), 0, c->stream, b.v_ptr.as<long>(),
                        b.v_col.as<int>(), b.v_val.as<double>(), M, m, fromW ? 1 : 0, U);
@@ -164,35 +159,55 @@ int assemble_lowrank(lrn_ctx* c, LmiBlock& b) {
   return LRN_OK;
 }
 
+// C = op(A) V into msz x R columns, op(A) = A' where transA: the one product of every route that multiplies the dense factors
+// (or columns laid out like them) from the left -- U = G' V, Y = W V, Q = Z V, Q = A_s Y, P = L' V
+int cols_product(lrn_ctx* c, const double* A, bool transA, const double* V, long R, int m, double* C) {
+  GemmDesc g;
+  g.A = A;
+  if (transA) { g.sAm = m; g.sAk = 1; } else { g.sAm = 1; g.sAk = m; }
+  g.B = V; g.sBk = 1; g.sBn = m;
+  g.C = C; g.sCm = 1; g.sCn = m;
+  g.M = m; g.N = (int)R; g.K = m;
+  return gemm(c->stream, g);
+}
+
 // ---- hybrid factored block: a few constraints S are stored (positions [0, npos_nz)), the others F are factors.  H has three
 // parts: H_FF by assemble_lowrank (the stored positions have weight-0 columns and receive + 0), H_SS by assemble_stored
-// over the stored positions, and the cross terms, with Y = W Vd (msz x R, column hidx[j] khat + p):
-//     H_sj = tr(A_s W A_j W) = sum_p d_jp y_jp' A_s y_jp            (A_s from ent_v = +A, d from v_w = +d: the signs agree)
-// a sparse quadratic form per column of Y, nnz(A_s) R multiply-adds per stored constraint.
+// over the stored positions, and the cross terms, with Y = W V:
+//     H_sj = tr(A_s W A_j W) = sum_p d_jp y_jp' A_s y_jp            (A_s from ent_v = +A, d from the weights = +d: the signs agree)
+// over the columns p of the factored constraint j, a sparse quadratic form per column of Y, nnz(A_s) R multiply-adds per stored
+// constraint.  Y is W Vd (msz x nvar khat) or, under option "ragged_cross", Yc = W Vc (msz x Rc) of a block of mixed ranks: the
+// kernels are templates on the column layout (fac_cols.h), a unit the factored position p_f + x or the group x.  A constraint of
+// rank 0 has no group and receives nothing (on the padded layout + 0).
 //
-// fac_cross_kernel: workgroup (x, y) owns the factored position j = p_f + x and the 32 sparse-tier stored positions
-// s0 + 32 y ..; wave v takes the stored positions s0 + 32 y + 4 t + v, t < 8, and keeps their sums in registers.  The khat
-// columns of Y of position j are staged in LDS one at a time (LDS: msz * 8 bytes, up to 32 KiB -- five workgroups per CU) or,
-// for longer columns, gathered from global memory by the same code; lanes stride the entry list of A_s, one shuffle tree
-// adds in a fixed order, the sum is weighted by d_jp and added over p in order.  Each workgroup writes its 32 entries of the
-// lower triangle of H exactly once, += because the blocks of a model share H.  No atomics: two assemblies give the same bits.
-template <bool LDS>
+// fac_cross_kernel: workgroup (x, y) owns unit x and the 32 sparse-tier stored positions s0 + 32 y ..; wave v takes the stored
+// positions s0 + 32 y + 4 t + v, t < 8, and keeps their sums in registers.  The columns of Y of the unit are staged in LDS one at
+// a time (LDS: msz * 8 bytes, dynamic, up to 32 KiB -- five workgroups per CU) or, for longer columns, gathered from global
+// memory by the same code; lanes stride the entry list of A_s, one shuffle tree adds in a fixed order, the sum is weighted by
+// d_jp and added over p in order, weight-0 padding skipped (uniform over the workgroup).  Each workgroup writes its 32 entries of
+// the lower triangle of H exactly once, += because the blocks of a model share H.  No atomics: two assemblies give the same bits.
+// LDS accesses: the staging writes are ds_write_b64 of consecutive doubles (lane l -> dwords 2 l, 2 l + 1 of a 256-dword run:
+// conflict-free); the gather reads ycol[r], ycol[cc] follow the entry list of A_s, their banks are data-dependent -- an entry
+// list sorted by column reads one address for cc (a broadcast) and scattered rows for r, anything from free to a multi-way
+// conflict.  Derived, not measured.
+template <class Cols, bool LDS>
 __global__ __launch_bounds__(256) void fac_cross_kernel(const long* __restrict__ ptr, const int* __restrict__ er,
                                                         const int* __restrict__ ec, const double* __restrict__ ev,
-                                                        const double* __restrict__ Y, const double* __restrict__ w, int m, int kh,
-                                                        int s_lo, int s_hi, int p_f, int p_end,
-                                                        const int* __restrict__ hidx, double* __restrict__ H, int ldh) {
+                                                        const double* __restrict__ Y, const double* __restrict__ w, int m,
+                                                        Cols lay, int s_lo, int s_hi, const int* __restrict__ hidx,
+                                                        double* __restrict__ H, int ldh) {
   extern __shared__ double ycol[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j = p_f + blockIdx.x;
-  if (j >= p_end) return;                        // (whole workgroup)
-  const int hj = hidx[j];
+  typename Cols::Span span;
+  int cnt;
+  if (!lay.pos_unit(blockIdx.x, hidx, &span, &cnt)) return;      // (whole workgroup)
+  const int hj = lay.unit_h(blockIdx.x, span);
   const int sb = s_lo + blockIdx.y * 32 + wave;
   double acc[8];
 #pragma unroll
   for (int t = 0; t < 8; ++t) acc[t] = 0.0;
-  for (int p = 0; p < kh; ++p) {
-    const long col = (long)hj * kh + p;
+  for (int p = 0; p < cnt; ++p) {
+    const long col = lay.col(span, p);
     const double wp = w[col];
     if (wp == 0.0) continue;                     // padding column (uniform over the workgroup)
     const double* __restrict__ yg = Y + col * m;
@@ -224,19 +239,20 @@ __global__ __launch_bounds__(256) void fac_cross_kernel(const long* __restrict__
   }
 }
 
-// stored constraint in dense slot s: Q = A_s Y is one product, H_sj = sum_p d_jp <Q(:, jp), Y(:, jp)> one wave per factored
-// position j (the column dot of dataops.hip::fac_coldot_kernel), written once
+// stored constraint in dense slot s: Q = A_s Y is one product, H_sj = sum_p d_jp <Q(:, jp), Y(:, jp)> one wave per unit (the
+// column dot of dataops.hip::fac_coldot_kernel with one accumulator), written once.  No LDS
+template <class Cols>
 __global__ __launch_bounds__(256) void fac_cross_coldot_kernel(const double* __restrict__ Q, const double* __restrict__ Y,
-                                                               const double* __restrict__ w, int m, int kh, int s, int p_f,
-                                                               int p_end, const int* __restrict__ hidx, double* __restrict__ H,
-                                                               int ldh) {
+                                                               const double* __restrict__ w, int m, Cols lay, int s,
+                                                               const int* __restrict__ hidx, double* __restrict__ H, int ldh) {
   const int lane = threadIdx.x & 63;
-  const int j = p_f + blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (j >= p_end) return;
-  const int hj = hidx[j];
+  const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+  typename Cols::Span span;
+  int cnt;
+  if (!lay.pos_unit(u, hidx, &span, &cnt)) return;       // (whole wave)
   double acc = 0.0;
-  for (int p = 0; p < kh; ++p) {
-    const long col = (long)hj * kh + p;
+  for (int p = 0; p < cnt; ++p) {
+    const long col = lay.col(span, p);
     const double wp = w[col];
     if (wp == 0.0) continue;
     const double* __restrict__ q = Q + col * m;
@@ -248,7 +264,21 @@ __global__ __launch_bounds__(256) void fac_cross_coldot_kernel(const double* __r
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
   if (lane != 0) return;
-  H[h_lower(hidx[s], hj, ldh)] += acc;
+  H[h_lower(hidx[s], lay.unit_h(u, span), ldh)] += acc;
+}
+
+// Y = W V of the current NT scaling, cached in the block until the scaling changes: Ys = W Vd (msz x nvar khat) or, compact,
+// Yc = W Vc (msz x Rc).  Shared by the operator under option "fac_op_scaled" (dataops.hip) and, Yc, by factored_y below
+int fac_scaled_y(lrn_ctx* c, LmiBlock& b, bool compact) {
+  if (compact) LRN_TRY(ragged_setup(c, b));
+  DBuf& Y = compact ? b.Yc : b.Ys;
+  long& version = compact ? b.Yc_version : b.Ys_version;
+  if (version == c->scal_version && Y.p) return LRN_OK;
+  const FacCols v = fac_cols(c, b, compact);
+  LRN_TRY(ensure(c, Y, (size_t)b.msz * v.R * 8));
+  LRN_TRY(cols_product(c, b.W.as<double>(), false, v.V, v.R, b.msz, Y.as<double>()));
+  version = c->scal_version;
+  return LRN_OK;
 }
 
 // Y = W Vd: what the padded route of assemble_lowrank left in BG when only W exists, one more product into a workspace of its
@@ -259,7 +289,7 @@ int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
   const long R = (long)n * kh;
   if (!b.have_W) return set_error(c, LRN_ERR_STATE, "W not set (call lrn_prepare_w or lrn_set_scaling)");
   // option "ragged_cross": Yc = W Vc (msz x Rc) instead -- what the rank-class route left in BG when only W exists, the product
-  // ragged_scaled_y caches per scaling otherwise (shared with the operator under "fac_op_scaled").  assemble_cross and
+  // fac_scaled_y caches per scaling otherwise (shared with the operator under "fac_op_scaled").  assemble_cross and
   // assemble_diag ask the same condition and read the compacted layout
   if (c->opt.ragged_cross) {
     if (ragged_cross_on(c, b)) {
@@ -269,7 +299,7 @@ int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
         *Yout = c->BG.as<double>();
         c->counts["ragged_y_reused"] += 1;
       } else {
-        LRN_TRY(ragged_scaled_y(c, b));
+        LRN_TRY(fac_scaled_y(c, b, true));
         *Yout = b.Yc.as<double>();
       }
       toc(c, "hybrid_y");
@@ -282,12 +312,7 @@ int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
   tic(c);
   if (b.have_G || c->BG_ragged) {      // (after the rank-class route BG holds U_c in the compacted layout)
     LRN_TRY(ensure(c, c->facY, (size_t)m * R * 8));
-    GemmDesc g;
-    g.A = b.W.as<double>(); g.sAm = 1; g.sAk = m;
-    g.B = b.Vd.as<double>(); g.sBk = 1; g.sBn = m;
-    g.C = c->facY.as<double>(); g.sCm = 1; g.sCn = m;
-    g.M = m; g.N = (int)R; g.K = m;
-    LRN_TRY(gemm(c->stream, g));
+    LRN_TRY(cols_product(c, b.W.as<double>(), false, b.Vd.as<double>(), R, m, c->facY.as<double>()));
     Y = c->facY.as<double>();
   }
   toc(c, "hybrid_y");
@@ -295,38 +320,39 @@ int factored_y(lrn_ctx* c, LmiBlock& b, const double** Yout) {
   return LRN_OK;
 }
 
+// the cross terms of a hybrid block from Y of factored_y, in the layout factored_y chose (ragged_cross_on)
 int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y) {
-  const int n = c->nvar, m = b.msz, kh = b.lr_khat;
-  const long R = (long)n * kh;
-  const int nf = n - b.npos_nz;
-  if (nf <= 0) return LRN_OK;
-  if (ragged_cross_on(c, b)) return assemble_cross_ragged(c, b, Y);      // (Y is Yc then: factored_y)
+  const int n = c->nvar, m = b.msz;
+  if (n - b.npos_nz <= 0) return LRN_OK;
+  const bool rg = ragged_cross_on(c, b);
+  if (rg) {
+    if (!Y) return set_error(c, LRN_ERR_STATE, "ragged_cross: Yc = W Vc was not formed");
+    LRN_TRY(ragged_setup(c, b));
+  }
+  const FacCols v = fac_cols(c, b, rg);
+  if (v.npos <= 0) return LRN_OK;
   tic(c);
   if (b.npos_nz > b.nd) {
     const size_t cap = c->opt.fac_cross_lds == 1 ? 65536 : 32768;      // bytes of one column: forced / by default
     const bool lds = c->opt.fac_cross_lds != 0 && (size_t)m * 8 <= cap;
-    const dim3 grid((unsigned)nf, (unsigned)((b.npos_nz - b.nd + 31) / 32));
-#define LRN_CROSS_LAUNCH(L, SH)                                                                                        \
-  hipLaunchKernelGGL(fac_cross_kernel<L>, grid, dim3(256), SH, c->stream, b.ent_ptr.as<long>(), b.ent_r.as<int>(),    \
-                     b.ent_c.as<int>(), b.ent_v.as<double>(), Y, b.v_w.as<double>(), m, kh, b.nd, b.npos_nz, b.npos_nz, n, \
-                     b.hidx.as<int>(), c->H.as<double>(), n)
-    if (lds) LRN_CROSS_LAUNCH(true, (size_t)m * 8);
-    else LRN_CROSS_LAUNCH(false, 0);
-#undef LRN_CROSS_LAUNCH
+    const dim3 grid((unsigned)v.npos, (unsigned)((b.npos_nz - b.nd + 31) / 32));
+    with_layout(c, b, v, [&](auto lay) {
+      using Cols = decltype(lay);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(lds ? fac_cross_kernel<Cols, true> : fac_cross_kernel<Cols, false>), grid, dim3(256),
+                         lds ? (size_t)m * 8 : 0, c->stream, b.ent_ptr.as<long>(), b.ent_r.as<int>(), b.ent_c.as<int>(),
+                         b.ent_v.as<double>(), Y, v.w, m, lay, b.nd, b.npos_nz, b.hidx.as<int>(), c->H.as<double>(), n);
+    });
     c->counts[lds ? "hybrid_cross_lds" : "hybrid_cross_global"] += 1;
   }
   if (b.nd > 0) {
-    LRN_TRY(ensure(c, c->P, (size_t)m * R * 8));
+    LRN_TRY(ensure(c, c->P, (size_t)m * v.R * 8));
     double* Q = c->P.as<double>();
     for (int s = 0; s < b.nd; ++s) {
-      GemmDesc g;     // Q = A_s Y
-      g.A = b.Adense.as<double>() + (long)s * m * m; g.sAm = 1; g.sAk = m;
-      g.B = Y; g.sBk = 1; g.sBn = m;
-      g.C = Q; g.sCm = 1; g.sCn = m;
-      g.M = m; g.N = (int)R; g.K = m;
-      LRN_TRY(gemm(c->stream, g));
-      hipLaunchKernelGGL(fac_cross_coldot_kernel, dim3((nf + 3) / 4), dim3(256), 0, c->stream, Q, Y, b.v_w.as<double>(), m, kh,
-                         s, b.npos_nz, n, b.hidx.as<int>(), c->H.as<double>(), n);
+      LRN_TRY(cols_product(c, b.Adense.as<double>() + (long)s * m * m, false, Y, v.R, m, Q));      // Q = A_s Y
+      with_layout(c, b, v, [&](auto lay) {
+        hipLaunchKernelGGL(fac_cross_coldot_kernel<decltype(lay)>, dim3((v.npos + 3) / 4), dim3(256), 0, c->stream, Q, Y, v.w, m,
+                           lay, s, b.hidx.as<int>(), c->H.as<double>(), n);
+      });
     }
     c->counts["hybrid_cross_dense"] += 1;
   }

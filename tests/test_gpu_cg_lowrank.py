@@ -1,5 +1,5 @@
 """GPU: the CG path from the rank-k factors of the data (option cg_lowrank; csrc/hop.hip: H of the assembled-matrix operator
-in mode 1, csrc/dataops.hip: the matrix-free operator in factor form, csrc/cgops.hip: ts of H_alpha by fac_ts_kernel)
+in mode 1, csrc/dataops.hip: the matrix-free operator in factor form, csrc/cgops.hip, csrc/facops.hip: ts of H_alpha by fac_ts_kernel)
 against the extended-precision reference of oracle/cg_reference.py.
 
 The inputs are those of tests/cg_lowrank_cases.py (constraints built from their factors; L1 one block in position space,
