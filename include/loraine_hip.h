@@ -56,7 +56,8 @@ int lrn_upload_model(lrn_ctx* ctx, int nlmi, int nvar, const int64_t* msizes,
  * khat = 32 or 64 (a WIDE block, constraints of rank 17 .. 64) is accepted under lrn_set_option "lowrank_wide" = 1 and
  * refused with LRN_ERR_ARG otherwise, as any other value is: mode 1 assembles such a block by rank class whatever
  * "lowrank_ragged" says (one GPU: LRN_ERR_ARG from lrn_schur_assemble when world > 1; lrn_get_count "schur_wide"), and it
- * carries no diagonal parts (lrn_upload_diag on it, and this call with a wide khat on a block that holds them: LRN_ERR_ARG).
+ * carries no diagonal parts (lrn_upload_diag on it, and this call with a wide khat on a block that holds them: LRN_ERR_ARG)
+ * unless lrn_set_option "wide_diag" = 1 admits them.
  * V: (nvar * khat) x msz CSC, 1-based, row k * khat + p = column p of V_k (the orientation of B above); d: nvar * khat
  * weights in the same order.  Call after lrn_upload_model / lrn_synthetic_dense_model; lrn_schur_assemble(mode 1) uses
  * them.  AA stays what every other entry point reads (unless the block is declared factored, below).  If some constraint
@@ -216,6 +217,13 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * wide: the classes 64 and 32 lead the layout, mode 1 takes the rank-class route for it unconditionally, also when Rc = nvar
  * khat; "ragged_ops", "ragged_cross", "ragged_ts" keep their condition and move its other routes from the padded layout at
  * khat 32 / 64 to the compacted columns; counter "schur_wide" = assemblies of a wide block),
+ * "wide_diag" (0, default = a wide block carries no diagonal parts: lrn_upload_diag on it, a wide lrn_upload_lowrank on a block
+ * that holds diagonal rows, and the MFMA form of the squared-operand product at khat 32 / 64 return LRN_ERR_ARG, texts
+ * unchanged; 1 = the three accept -- a factor-model constraint B S B' + diag(psi) with 17 .. 64 factors goes in as factors
+ * and a diagonal row, the rows of a re-uploaded block stay as under a narrow re-upload, and C = Ad' (Y o Y) sums column groups
+ * of 32 and 64 in a fixed order, no atomics (diagops.hip; per class under "ragged_cross").  The CG path takes such a block
+ * where "cg_factored" and "cg_diag" take a narrow one.  One GPU, not through lrn_matvec_partial, stored constraints carry
+ * their diagonal in their entries: those refusals stay.  Resets the operator choice, as "lowrank_wide" does),
  * "ragged_ops" (the factor form of AA vec(.) and mat(AA' .) of such a block: 0, default = on the nvar khat padded columns, every
  * route, counter, error text and bit as before; any other value = 1 = on the Rc compacted columns of "lowrank_ragged" -- Q = Z Vc
  * and sums by group, or the fused quadratic form on (Vc, Rc) under "fac_quadform"; mat(AA' x) = -sum_c s_c f_c f_c' by one FP64

@@ -67,7 +67,8 @@ end
 
 # ---- rank-k factors of block i (datarank = k >= 1, docs/src/low-rank_data.md): A_j = V_j diag(d_j) V_j', every
 # constraint padded to khat in (1, 2, 4, 8, 16) columns -- 32 and 64 as well under the library option "lowrank_wide" = 1 (lrn_set_option): a
-# wide block, assembled by rank class on one GPU, without diagonal parts; V is (n * khat) x msz, row (j - 1) * khat + p = column p of V_j
+# wide block, assembled by rank class on one GPU, without diagonal parts unless the library option "wide_diag" = 1 admits them
+# (upload_diag! on a wide block, factors plus diag(a) of rank 17 .. 64); V is (n * khat) x msz, row (j - 1) * khat + p = column p of V_j
 function upload_lowrank!(ctx::Ctx, i::Integer, khat::Integer, V::SparseMatrixCSC{Float64, Int64}, d::Vector{Float64})
     check(ctx, ccall((:lrn_upload_lowrank, LIB), Cint,
         (Ptr{Cvoid}, Cint, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),

@@ -120,6 +120,7 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "lowrank_form")) c->opt.lowrank_form = std::max(-1, std::min(1, (int)value));
   else if (!strcmp(key, "lowrank_ragged")) { c->opt.lowrank_ragged = value != 0.0 ? 1 : 0; c->hop_version = -1; }
   else if (!strcmp(key, "lowrank_wide")) { c->opt.lowrank_wide = value != 0.0 ? 1 : 0; c->hop_version = -1; }
+  else if (!strcmp(key, "wide_diag")) { c->opt.wide_diag = value != 0.0 ? 1 : 0; c->hop_version = -1; }
   else if (!strcmp(key, "ragged_ops")) { c->opt.ragged_ops = value != 0.0 ? 1 : 0; c->hop_version = -1; }
   else if (!strcmp(key, "ragged_cross")) { c->opt.ragged_cross = value != 0.0 ? 1 : 0; c->hop_version = -1; }
   else if (!strcmp(key, "ragged_ts")) c->opt.ragged_ts = value != 0.0 ? 1 : 0;

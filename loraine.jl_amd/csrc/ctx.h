@@ -197,6 +197,9 @@ struct LrnOptions {
                                   // GPU, and only where the classes are not all khat -- the padded route otherwise ("ragged_fallback")
   int lowrank_wide = 0;           // lrn_upload_lowrank accepts khat 32 and 64 (factored constraints of rank 17 .. 64): 1, refuses them: 0.
                                   // A block uploaded so is assembled by rank class whatever lowrank_ragged says (raggedops.hip)
+  int wide_diag = 0;              // diagonal parts on a wide block (khat 32 / 64): 1 = lrn_upload_diag accepts a wide block, a wide
+                                  // lrn_upload_lowrank a block that holds diagonal rows, diag_sq groups of 32 and 64 in its MFMA form
+                                  // (diagops.hip::diag_sq_wide_mfma_kernel); 0 = the three refuse, as before the option existed
   int ragged_ops = 0;             // AA vec(.) and mat(AA' .) of a block of mixed ranks in factor form on the compacted columns of the
                                   // rank classes (fac_cols.h, raggedops.hip): 1, on the padded layout: 0.  Independent of lowrank_ragged; the
                                   // same conditions, the padded code otherwise ("ragged_ops_fallback")

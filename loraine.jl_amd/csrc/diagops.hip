@@ -28,7 +28,8 @@
 //     lanes (one row each), two-way conflicted under a wider grouping (rows start at 0, 4, 8, 12 mod 32) -- not measured.
 //     Epilogue: the accumulator element of column c is multiplied by w[c]; kh (a power of two <= 16) divides 16, so a column
 //     group lies on kh neighbouring lanes of one accumulator block and is summed by an xor butterfly of log2 kh steps; the
-//     lane with c % kh == 0 writes D[s, c / kh].
+//     lane with c % kh == 0 writes D[s, c / kh].  kh = 32 and 64 (a wide block, option "wide_diag"): diag_sq_wide_mfma_kernel,
+//     the same tile and K loop with an epilogue that goes on across the wave's two accumulators and, for 64, across two waves.
 //   Option "ragged_cross" (DESIGN section 20): C from Yc = W Vc, one launch of either form per rank class, the store going
 //     through a group -> H index map (hmap) -- the one change to both kernels, a null map being the code as it was.
 // No atomics, fixed order in both forms: two calls give the same bits.  The forms differ from each other in rounding.
@@ -51,7 +52,9 @@ static constexpr int DG_K = 16;        // K step
 static constexpr int DG_LD = 18;       // row stride of As, Bs (doubles)
 static constexpr int DG_ROWS = 8;      // rows per wave of the rows form
 static constexpr int DG_MFMA_MIN = 16; // auto: the MFMA form from this many diagonal rows on (measured at msz 2000 / nvar 4000 / khat 2: the rows
-                                       // form is 1.8 x faster at 1 row, the MFMA form 1.3 x at 16, 3 x at 64, 13 x at 4000; 2 .. 15 rows not measured)
+                                       // form is 1.8 x faster at 1 row, the MFMA form 1.3 x at 16, 3 x at 64, 13 x at 4000; 2 .. 15 rows not measured).
+                                       // At kh 32 / 64 (option "wide_diag") the MFMA form measured faster at every row count: 1.4 x at 1 row,
+                                       // 6 x at 16, 19 x at 64, 16 x at 4000 -- the rule was not re-tuned for them
 
 __global__ __launch_bounds__(256) void diag_sq_rows_kernel(const double* __restrict__ Ad, int ns, const double* __restrict__ B,
                                                            long ldb, int m, int ng, int kh, const double* __restrict__ w,
@@ -159,6 +162,126 @@ __global__ __launch_bounds__(256) void diag_sq_mfma_kernel(const double* __restr
   }
 }
 
+// ---- the MFMA form for column groups of 32 and 64 (a wide block with diagonal parts, option "wide_diag").
+// A second kernel, not a template parameter of the one above: that kernel's code is to stay what it is (see the comment above
+// ts_diag_mfma_kernel), and a second body keeps its source untouched.  Tile, staging and K loop are the ones above, written out
+// again.  Geometry: the tile covers the columns c0 .. c0 + 63 with c0 % 64 == 0 and wave (wr, wc) holds the columns
+// 32 wc + 16 jb + ci, so a group of 32 is exactly one wave's columns and a group of 64 the columns of the waves wc = 0 and
+// wc = 1 of one wr.  Order of the sum, fixed -- the rule of raggedops.hip::ragged_wide_epilogue:
+//   1. the accumulator element of column cc is multiplied by w[cc]; a column beyond nc has weight 0 (its operand is zero too);
+//   2. inside each accumulator block the xor butterfly over the 16 ci lanes (offsets 1, 2, 4, 8);
+//   3. across the wave's two accumulators, jb = 0 + jb = 1;
+//   4. kh = 64: across the two waves of the row through LDS, wc = 0 + wc = 1.  The exchange reuses As after a barrier: the
+//      lanes ci == 0 of a wave wc = 1 write their eight row sums to red[32 wr + 16 ib + kq + 4 r], and after a second barrier
+//      the same lanes of the wave wc = 0 read them.  Both barriers sit in a branch on kh alone, a kernel argument, and no
+//      lane has left before them: all 256 threads reach them.  LDS banks of the exchange: one ds_write_b64 has four active
+//      lanes (kq = 0 .. 3, ci = 0) on four consecutive doubles, the reads are the same addresses: distinct bank pairs, no
+//      conflict (derived from the bank rule, not measured);
+//   5. one writer per element: the lane ci == 0 (of the wave wc == 0 for kh = 64) stores D[s ldd + (hmap ? hmap[g] : g)] for
+//      s < ns and g < nc / kh.  A half-full last tile of a class-32 segment: the wave wc = 1 holds group nc / 32, no store.
+// No atomics: two runs give the same bits.  The compiler's report (registers, LDS, occupancy): DESIGN section 23.
+__global__ __launch_bounds__(256) void diag_sq_wide_mfma_kernel(const double* __restrict__ Ad, int ns, const double* __restrict__ B,
+                                                                long ldb, int m, long nc, int kh, const double* __restrict__ w,
+                                                                double* __restrict__ D, long ldd, const int* __restrict__ hmap) {
+  __shared__ double As[DG_T * DG_LD];
+  __shared__ double Bs[DG_T * DG_LD];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wr = wv >> 1, wc = wv & 1;
+  const int ci = lane & 15, kq = lane >> 4;
+  const long c0 = (long)blockIdx.x * DG_T;
+  const int s0 = blockIdx.y * DG_T;
+  dg_v4 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = dg_v4{0.0, 0.0, 0.0, 0.0};
+  // staging map of both operands: thread (k = t & 15, row = (t >> 4) + 16 pass)
+  const int vk = t & 15, vr = t >> 4;
+  double areg[4], breg[4];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      const int s = s0 + vr + 16 * ps;
+      const long cc = c0 + vr + 16 * ps;
+      const bool kin = k0 + vk < m;
+      areg[ps] = (kin && s < ns) ? Ad[(long)(k0 + vk) + (long)s * m] : 0.0;
+      breg[ps] = (kin && cc < nc) ? B[(long)(k0 + vk) + cc * ldb] : 0.0;
+    }
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < m; k0 += DG_K) {
+    __syncthreads();                       // the waves are done with the previous step's tiles
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+      As[(vr + 16 * ps) * DG_LD + vk] = areg[ps];
+      Bs[(vr + 16 * ps) * DG_LD + vk] = breg[ps] * breg[ps];
+    }
+    __syncthreads();
+    if (k0 + DG_K < m) fetch(k0 + DG_K);
+#pragma unroll
+    for (int ks = 0; ks < DG_K / 4; ++ks) {
+      const int k = 4 * ks + kq;
+      const double a0 = As[(32 * wr + ci) * DG_LD + k];
+      const double a1 = As[(32 * wr + 16 + ci) * DG_LD + k];
+      const double b0 = Bs[(32 * wc + ci) * DG_LD + k];
+      const double b1 = Bs[(32 * wc + 16 + ci) * DG_LD + k];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+  }
+  // element (row s0 + 32 wr + 16 ib + kq + 4 r, column c0 + 32 wc + 16 jb + ci): steps 1 to 3, v[ib][r] = the wave's 32 columns
+  double v[2][4];
+  {
+    const long cc0 = c0 + 32 * wc + ci, cc1 = cc0 + 16;
+    const double w0 = cc0 < nc ? (w ? w[cc0] : 1.0) : 0.0;
+    const double w1 = cc1 < nc ? (w ? w[cc1] : 1.0) : 0.0;
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double x0 = acc[ib][0][r] * w0, x1 = acc[ib][1][r] * w1;
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {     // (every lane takes part)
+          x0 += __shfl_xor(x0, off, 64);
+          x1 += __shfl_xor(x1, off, 64);
+        }
+        v[ib][r] = x0 + x1;
+      }
+  }
+  const bool x64 = kh == 64;                         // (a kernel argument: uniform over the grid)
+  if (x64) {
+    double* __restrict__ red = As;                   // 64 of its 1152 doubles
+    __syncthreads();                                 // every wave is done with the last K step's As
+    if (wc == 1 && ci == 0) {
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[32 * wr + 16 * ib + kq + 4 * r] = v[ib][r];
+    }
+    __syncthreads();
+    if (wc == 0 && ci == 0) {
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[ib][r] += red[32 * wr + 16 * ib + kq + 4 * r];
+    }
+  }
+  if (ci != 0 || (x64 && wc != 0)) return;           // (after the barriers)
+  const long g = x64 ? c0 / 64 : (c0 + 32 * wc) / 32;
+  if (g >= nc / kh) return;
+  const long gd = hmap ? (long)hmap[g] : g;
+#pragma unroll
+  for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int s = s0 + 32 * wr + 16 * ib + kq + 4 * r;
+      if (s < ns) D[(long)s * ldd + gd] = v[ib][r];
+    }
+}
+
 // D[s * ldd + g] = sum_{p < kh} w[g kh + p] sum_i Ad[i + s m] B[i + (g kh + p) ldb]^2   (w null: weights 1); s < ns, g < ng.
 // hmap (option "ragged_cross": the groups of one rank class, B and w starting at its segment): the sum of group g goes to
 // D[s * ldd + hmap[g]] instead -- the store alone differs; null is the code above
@@ -169,11 +292,20 @@ static int diag_sq(lrn_ctx* c, const double* Ad, int ns, const double* B, long l
   const long nc = (long)ng * kh;
   if (mfma) {
     // (the butterfly of the epilogue needs a column group on kh neighbouring lanes of one accumulator block)
-    if (kh > 16 || (kh & (kh - 1))) return set_error(c, LRN_ERR_ARG, "diag_sq: the MFMA form needs khat in 1, 2, 4, 8, 16, not %d", kh);
+    // (option "wide_diag": groups of 32 and 64, a wave's columns or the tile's, go to the kernel with the wide epilogue)
+    const bool wide = (kh == 32 || kh == 64) && c->opt.wide_diag;
+    if (!wide && (kh > 16 || (kh & (kh - 1)))) {
+      if (!c->opt.wide_diag) return set_error(c, LRN_ERR_ARG, "diag_sq: the MFMA form needs khat in 1, 2, 4, 8, 16, not %d", kh);
+      return set_error(c, LRN_ERR_ARG, "diag_sq: the MFMA form needs khat in 1, 2, 4, 8, 16, or 32 or 64 under option wide_diag, not %d", kh);
+    }
     const long tx = (nc + DG_T - 1) / DG_T, ty = (ns + DG_T - 1) / DG_T;
     if (tx > 2147483647L || ty > 65535) return set_error(c, LRN_ERR_ARG, "diag_sq: %ld x %ld tiles", tx, ty);
-    hipLaunchKernelGGL(diag_sq_mfma_kernel, dim3((unsigned)tx, (unsigned)ty), dim3(256), 0, c->stream, Ad, ns, B, ldb, m, nc,
-                       kh, w, D, ldd, hmap);
+    if (wide)
+      hipLaunchKernelGGL(diag_sq_wide_mfma_kernel, dim3((unsigned)tx, (unsigned)ty), dim3(256), 0, c->stream, Ad, ns, B, ldb, m,
+                         nc, kh, w, D, ldd, hmap);
+    else
+      hipLaunchKernelGGL(diag_sq_mfma_kernel, dim3((unsigned)tx, (unsigned)ty), dim3(256), 0, c->stream, Ad, ns, B, ldb, m, nc,
+                         kh, w, D, ldd, hmap);
     c->counts["diag_sq_mfma"] += 1;
   } else {
     const long ty = (ns + DG_ROWS - 1) / DG_ROWS;

@@ -620,7 +620,7 @@ extern "C" int lrn_upload_lowrank(lrn_ctx* c, int ilmi, int khat, const int64_t*
   if (!V_colptr || !d) return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: null factor array");
   LRN_HIP(c, hipSetDevice(c->device));
   LmiBlock& b = c->lmi[ilmi];
-  if (wide && b.dg_n > 0)
+  if (wide && b.dg_n > 0 && !c->opt.wide_diag)      // (option "wide_diag": the rows stay, as under a narrow re-upload)
     return set_error(c, LRN_ERR_ARG, "lrn_upload_lowrank: khat = %d on block %d, which holds diagonal parts (lrn_upload_diag): a "
                                      "wide block carries none -- store such a constraint as a matrix", khat, ilmi);
   const int m = b.msz, nvar = c->nvar;
@@ -734,7 +734,7 @@ extern "C" int lrn_upload_diag(lrn_ctx* c, int ilmi, int64_t nrows, const int64_
     drop_diag(b);
     return LRN_OK;
   }
-  if (lowrank_wide(b))
+  if (lowrank_wide(b) && !c->opt.wide_diag)      // (option "wide_diag": accepted, diagops.hip sums groups of 32 and 64)
     return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: block %d is wide (khat = %d > 16): a wide block carries no diagonal part "
                                      "-- store such a constraint as a matrix", ilmi, b.lr_khat);
   if (!rows || !a) return set_error(c, LRN_ERR_ARG, "lrn_upload_diag: null array");

@@ -67,6 +67,13 @@ class MyModel:
         rank class.  Read off `lowrank`: no field of its own."""
         return any(lr[2] > LOWRANK_MAX for lr in self.lowrank)
 
+    @property
+    def wide_diag(self):
+        """Optimizer.load_factored_model(..., wide="diag"): some wide block (khat 32 or 64) carries diagonal parts -- the solver
+        sets the library option wide_diag = 1 before it uploads them.  Read off `lowrank` and `diag` of the same block: no field
+        of its own."""
+        return any(lr[2] > LOWRANK_MAX and bool(dg) for lr, dg in zip(self.lowrank, self.diag))
+
 
 RAGGED_CLASSES = (16, 8, 4, 2, 1)     # layout order of the rank classes
 RAGGED_CLASSES_WIDE = (64, 32) + RAGGED_CLASSES      # ... of a wide block (load_factored_model(..., wide=True): ranks up to 64)
@@ -378,11 +385,11 @@ def diag_fro_sq(V, d, a):
     return float(2.0 * np.sum(d * (a @ (V * V))) + a @ a)
 
 
-def _check_factors(F0, factors, n, max_rank=LOWRANK_MAX):
+def _check_factors(F0, factors, n, max_rank=LOWRANK_MAX, wide_diag=False):
     """factors[i][k] = (V, d) -> dense (m x r) V and d per constraint, or a symmetric m x m matrix (a stored constraint) -> csc,
     or (V, d, a) -> (V, d) and the diagonal part a (V may be None: a purely diagonal constraint); ValueError otherwise.
     -> (items per block, {k: a} per block); an all-zero a is the pair (V, d).  max_rank: the most factor columns of one
-    constraint; a block that holds a constraint of more than 16 (a wide block) carries no diagonal part."""
+    constraint; a block that holds a constraint of more than 16 (a wide block) carries no diagonal part unless wide_diag."""
     if len(factors) != len(F0):
         raise ValueError(f"factors for {len(factors)} LMI blocks, F0 has {len(F0)}")
     out, diags = [], []
@@ -422,7 +429,7 @@ def _check_factors(F0, factors, n, max_rank=LOWRANK_MAX):
                                  f"(at most {max_rank})")
             facs.append((V, d))
         wide = [j for j, f in enumerate(facs) if not sp.issparse(f) and f[0].shape[1] > LOWRANK_MAX]
-        if wide and dg:
+        if wide and dg and not wide_diag:
             raise ValueError(f"block {i + 1}: constraint {wide[0] + 1} has {facs[wide[0]][0].shape[1]} factor columns (more than "
                              f"{LOWRANK_MAX}) and constraint {min(dg) + 1} a diagonal part (V, d, a): a block with ranks above "
                              f"{LOWRANK_MAX} carries no diagonal part -- store that row as a sparse matrix instead")
@@ -432,12 +439,15 @@ def _check_factors(F0, factors, n, max_rank=LOWRANK_MAX):
 
 
 def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, kappa=8, factored_form=-1,
-                         max_rank=LOWRANK_MAX) -> MyModel:
+                         max_rank=LOWRANK_MAX, wide_diag=False) -> MyModel:
     """A model given by F_0 (per block), b, optional linear rows and the factors alone: A_ik = V diag(d) V' with
     factors[i][k] = (V (m_i x r, r <= max_rank, dense or sparse), d (+-1)).  No A_ik is formed for a factored block: its AA is
     an n x m^2 matrix without entries (nzA = 0, identity sigmaA) and `lowrank` carries the data.
     max_rank: 16, or 64 for wide blocks (Optimizer.load_factored_model(..., wide=True)) -- a block with a constraint of rank
     above 16 is padded to khat 32 or 64 and carries no diagonal part (V, d, a); `wide` of the model says that one exists.
+    wide_diag=True (with max_rank=64; Optimizer.load_factored_model(..., wide="diag")): a wide block may hold (V, d, a) items --
+    a factor-model covariance B S B' + diag(psi) with 17 .. 64 factors; `diag[i]` is filled as for a narrow block, `wide_diag` of
+    the model says that such a block exists (library option wide_diag).
     factors[i][k] may instead be a symmetric m_i x m_i matrix (SciPy sparse or a 2-D array): constraint k of block i is
     STORED.  A block with both kinds is hybrid: its AA holds the rows -vec(A) of the stored constraints only, nzA / sigmaA /
     qA follow the rule of _prepare_A (stable sort by nnz, descending: the stored constraints take the first positions, the
@@ -457,7 +467,11 @@ def build_factored_model(F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, ka
         raise ValueError(f"factored_form = {factored_form} (-1 auto, 1 always factored)")
     if max_rank not in (LOWRANK_MAX, LOWRANK_MAX_WIDE):
         raise ValueError(f"max_rank = {max_rank!r} ({LOWRANK_MAX}, or {LOWRANK_MAX_WIDE} for wide blocks)")
-    items_all, diags_all = _check_factors(F0, factors, n, max_rank)
+    if wide_diag not in (False, True):
+        raise ValueError(f"wide_diag is False or True, not {wide_diag!r}")
+    if wide_diag and max_rank != LOWRANK_MAX_WIDE:
+        raise ValueError(f"wide_diag = True needs max_rank = {LOWRANK_MAX_WIDE} (diagonal parts on wide blocks), not {max_rank!r}")
+    items_all, diags_all = _check_factors(F0, factors, n, max_rank, bool(wide_diag))
     nlmi = len(F0)
     A, AA, C, lowrank, fblocks, aa_fro, stored, diag = [], [], [], [], [], [], [], []
     nzA = np.zeros((n, nlmi), dtype=np.int64)

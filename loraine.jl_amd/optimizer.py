@@ -105,10 +105,13 @@ class Optimizer:
         rank above 16 is padded to 32 or 64 columns and is always assembled by rank class, whatever `ragged` says; it carries no
         diagonal part (V, d, a) (ValueError: store that row as a sparse matrix instead); one GPU only.  Combines freely with
         ragged= and cg=.
+        wide="diag" (opt-in) is wide=True and lifts that refusal: a wide block may hold (V, d, a) items, so B S B' + diag(psi)
+        with 17 .. 64 factors and a trace row (None, [], ones) beside it go in as factors and diagonal rows (library option
+        wide_diag beside lowrank_wide).  Combines with ragged= and cg= as wide=True does; kit = 1 on such a model needs cg="diag".
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
         times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
-        if not isinstance(wide, bool):
-            raise ValueError(f"load_factored_model: wide is False or True, not {wide!r}")
+        if not isinstance(wide, bool) and not (isinstance(wide, str) and wide == "diag"):
+            raise ValueError(f"load_factored_model: wide is False or True (or \"diag\"), not {wide!r}")
         if not self.resident:
             raise ValueError("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
                              "multiplies by AA")
@@ -133,7 +136,7 @@ class Optimizer:
             F0, factors, b, b_const, d_lin, C_lin, max_sense, form, ragged, wide, cg_diag, cg = payload
             self.max_sense = max_sense
             model = build_factored_model(F0, factors, b, b_const, d_lin, C_lin, kappa=kappa, factored_form=form,
-                                         max_rank=64 if wide else 16)
+                                         max_rank=64 if wide else 16, wide_diag=wide == "diag")      # (wide: False, True or "diag")
             model.factored_cg = bool(cg) and model.factored
             model.factored_cg_diag = cg_diag and model.factored
             model.ragged = ragged if model.factored else False      # (False, True, "ops" or "all")

@@ -132,10 +132,19 @@ class MySolver:
                 if wide:
                     self._say(" ---Factored constraints carry up to 64 factor columns; their blocks are assembled by rank class "
                               "(lowrank_wide = 1)")
+                wide_diag = None
                 for i, (V, d, khat) in enumerate(model.lowrank):
                     self.dev.upload_lowrank(i, khat, V, d)                      # [GPU] one-time
                     if getattr(model, "factored", False) and model.factored_blocks[i]:
                         self.dev.set_factored(i)                                # [GPU] the factors are the data
+                        if wide_diag is None:
+                            # load_factored_model(..., wide="diag"): diagonal parts on a wide block.  Set where it is first needed,
+                            # before any upload_diag, in both states (0 on a device another solve used); upload_model has
+                            # cleared the diagonal rows of a used block, so no wide upload_lowrank above met any
+                            wide_diag = bool(getattr(model, "wide_diag", False))
+                            self.dev.set_option("wide_diag", 1 if wide_diag else 0)
+                            if wide_diag:
+                                self._say(" ---Wide factored blocks carry diagonal parts (wide_diag = 1)")
                         dg = model.diag[i] if getattr(model, "diag", None) else {}
                         if dg:                                                  # [GPU] ... and the diagonal parts beside them
                             rows = sorted(dg)
