@@ -4,14 +4,12 @@
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
 #include "ops.h"
+#include "prec.h"
 #include "schur_plan.h"
 
 using namespace lrn;
 
 void lrn_free_model(lrn_ctx* c);
-namespace lrn {
-void prec_free(lrn_ctx* c);
-}
 
 extern "C" {
 
@@ -522,14 +520,10 @@ int lrn_dbg_gemm(lrn_ctx* c, int transA, int transB, int M, int N, int K, double
     rc = gemm(c->stream, g);
     static const int reps = getenv("LRN_DBG_GEMM_REPS") ? atoi(getenv("LRN_DBG_GEMM_REPS")) : 0;   // (measurement: time the product)
     if (reps > 0 && rc == LRN_OK && beta == 0.0) {
-      hipEvent_t e0, e1;
-      (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-      (void)hipEventRecord(e0, c->stream);
+      PhaseTimer timer(c, true);
       for (int i = 0; i < reps; ++i) (void)gemm(c->stream, g);
-      (void)hipEventRecord(e1, c->stream); (void)hipEventSynchronize(e1);
-      float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
+      const float ms = timer.elapsed_ms();
       fprintf(stderr, "[dbg_gemm] M %d N %d K %d flags %d: %.2f us per product (%d back to back)\n", M, N, K, flags, ms * 1e3 / reps, reps);
-      (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
   }
   if (rc != LRN_OK) return set_error(c, rc, "gemm launch failed");

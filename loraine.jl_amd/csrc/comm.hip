@@ -183,8 +183,7 @@ int comm_schur_exchange(lrn_ctx* c, int rc_local, bool gather_blocks) {
     c->H_owned_only = true;
     return LRN_OK;
   }
-  hipEvent_t a0, a1;
-  if (c->profile) { (void)hipEventCreate(&a0); (void)hipEventCreate(&a1); (void)hipEventRecord(a0, c->stream); }
+  PhaseTimer timer(c, c->profile);
   if (c->H_partial) {
     // partial sums of the whole matrix: only the lower triangle is authoritative -> n (n + 1) / 2 doubles
     hipLaunchKernelGGL(pack_lower_kernel, dim3(n), dim3(256), 0, c->stream, c->H.as<double>(), n, m->pack.as<double>());
@@ -196,12 +195,7 @@ int comm_schur_exchange(lrn_ctx* c, int rc_local, bool gather_blocks) {
     LRN_TRY(comm_allgather(c, m->pack.as<double>(), m->gathered.as<double>(), per));
     LRN_TRY(lrn_schur_import_all(c, m->gathered.as<double>()));
   }
-  if (c->profile) {
-    (void)hipEventRecord(a1, c->stream); (void)hipEventSynchronize(a1);
-    float ms = 0; (void)hipEventElapsedTime(&ms, a0, a1);
-    c->timing["exchange"] += ms; c->counts["exchange"] += 1;
-    (void)hipEventDestroy(a0); (void)hipEventDestroy(a1);
-  }
+  timer.stop("exchange");
   LRN_HIP(c, hipGetLastError());
   return LRN_OK;
 }

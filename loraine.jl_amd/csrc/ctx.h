@@ -365,6 +365,39 @@ bool fac_quadform_on(const lrn_ctx* c, const LmiBlock& b);       // hop.hip: AA 
 // (fac_cols.h), Q = Z V never stored
 struct FacCols;
 int fac_quadform(lrn_ctx* c, const LmiBlock& b, const FacCols& v, const double* Z, const int* sigma, double* out);
+
+// HIP-event timer of one phase on the context's stream (nothing unless enabled: c->profile for the outer phases, option
+// "profile_ops" for a single data operator): elapsed_ms() is the time since the construction, stop() adds it to timing[key]
+// and counts the phase; the events go with the scope, on an error return too
+struct PhaseTimer {
+  lrn_ctx* c;
+  hipEvent_t a0 = nullptr, a1 = nullptr;
+  PhaseTimer(lrn_ctx* ctx, bool enabled) : c(ctx) {
+    if (!enabled) return;
+    if (hipEventCreate(&a0) != hipSuccess) a0 = nullptr;
+    if (hipEventCreate(&a1) != hipSuccess) a1 = nullptr;
+    if (on()) (void)hipEventRecord(a0, c->stream);
+  }
+  PhaseTimer(const PhaseTimer&) = delete;
+  bool on() const { return a0 && a1; }
+  float elapsed_ms() {
+    float ms = 0;
+    if (!on()) return ms;
+    (void)hipEventRecord(a1, c->stream);
+    (void)hipEventSynchronize(a1);
+    (void)hipEventElapsedTime(&ms, a0, a1);
+    return ms;
+  }
+  void stop(const char* key) {
+    if (!on()) return;
+    c->timing[key] += elapsed_ms();
+    c->counts[key] += 1;
+  }
+  ~PhaseTimer() {
+    if (a0) (void)hipEventDestroy(a0);
+    if (a1) (void)hipEventDestroy(a1);
+  }
+};
 }  // namespace lrn
 
 #define LRN_HIP(c, expr)                                                                   \

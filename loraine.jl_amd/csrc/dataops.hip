@@ -5,8 +5,8 @@
 // in all their forms: sparse constraints (one wavefront per constraint / per stored column of AA, a deterministic gather,
 // no atomics), dense constraints (three tiers, see dense_route), the pattern-restricted form when mat(AA' x) is sparse,
 // the factor form of factored blocks, and the passes split over the ranks of a multi-GPU run.  The two msz^3 products
-// of W M W run on the FP64 MFMA GEMM (wmw).  All vectors live in natural constraint order.  OpTimer (option
-// "profile_ops") times each operator by itself.  The CG recurrence and the preconditioners that call MyA: cgops.hip.
+// of W M W run on the FP64 MFMA GEMM (wmw).  All vectors live in natural constraint order.  Option "profile_ops"
+// times each operator by itself (PhaseTimer, ctx.h).  The CG recurrence that calls MyA: cgops.hip; its preconditioners: prec.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -1057,30 +1057,11 @@ static int aat_to_mat_factored(lrn_ctx* c, LmiBlock& b, const double* x, double*
 }
 
 // option "profile_ops": one data operator between two events of its own (the phases of the resident loop -- "rhs",
-// "residual_d", "find_step" -- contain other products as well)
-struct OpTimer {
-  lrn_ctx* c;
-  const char* key;
-  hipEvent_t a = nullptr, b = nullptr;
-  OpTimer(lrn_ctx* c_, const char* key_) : c(c_), key(key_) {
-    if (!c->opt.profile_ops) return;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = nullptr; return; }
-    (void)hipEventRecord(a, c->stream);
-  }
-  int done(int rc) {
-    if (a) {
-      (void)hipEventRecord(b, c->stream);
-      (void)hipEventSynchronize(b);
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, a, b);
-      c->timing[key] += ms;
-      c->counts[key] += 1;
-      (void)hipEventDestroy(a);
-      (void)hipEventDestroy(b);
-    }
-    return rc;
-  }
-};
+// "residual_d", "find_step" -- contain other products as well), counted whatever it returns
+static int op_timed(PhaseTimer& t, const char* key, int rc) {
+  t.stop(key);
+  return rc;
+}
 
 static int aa_times_impl(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form = false, bool fused = false);
 static int aa_times2_impl(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);
@@ -1090,16 +1071,16 @@ static int aat_to_mat_impl(lrn_ctx* c, LmiBlock& b, const double* x, double* M, 
 // every other caller keeps the entries of such a block
 // fused (option "fac_quadform", matvec_dev only): the factor part of a factored block by the fused quadratic form
 int aa_times(lrn_ctx* c, LmiBlock& b, const double* Z, double* y, bool factor_form, bool fused) {
-  OpTimer t(c, "aa_times");
-  return t.done(aa_times_impl(c, b, Z, y, factor_form, fused));
+  PhaseTimer t(c, c->opt.profile_ops);
+  return op_timed(t, "aa_times", aa_times_impl(c, b, Z, y, factor_form, fused));
 }
 int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2) {
-  OpTimer t(c, "aa_times2");
-  return t.done(aa_times2_impl(c, b, Z1, y1, Z2, y2));
+  PhaseTimer t(c, c->opt.profile_ops);
+  return op_timed(t, "aa_times2", aa_times2_impl(c, b, Z1, y1, Z2, y2));
 }
 int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_form) {
-  OpTimer t(c, "aat_to_mat");
-  return t.done(aat_to_mat_impl(c, b, x, M, factor_form));
+  PhaseTimer t(c, c->opt.profile_ops);
+  return op_timed(t, "aat_to_mat", aat_to_mat_impl(c, b, x, M, factor_form));
 }
 
 // y += AA vec(Z)
@@ -1207,10 +1188,11 @@ static int fac_scaled_y_op(lrn_ctx* c, LmiBlock& b) {
   const bool rg = ragged_ops_on(c, b);
   if ((rg ? b.Yc_version : b.Ys_version) == c->scal_version && (rg ? b.Yc.p : b.Ys.p)) return LRN_OK;
   if (!b.have_Vd || !b.has_V) return set_error(c, LRN_ERR_STATE, "factored block without factors (lrn_upload_lowrank)");
-  OpTimer t(c, "fac_scaled_y");
+  PhaseTimer t(c, c->opt.profile_ops);
   LRN_TRY(fac_scaled_y(c, b, rg));
   c->counts["fac_scaled_y"] += 1;
-  return t.done(LRN_OK);
+  t.stop("fac_scaled_y");
+  return LRN_OK;
 }
 
 int matvec_dev(lrn_ctx* c, const double* x, double* y) {
@@ -1228,8 +1210,8 @@ int matvec_dev(lrn_ctx* c, const double* x, double* y) {
       LRN_TRY(ensure_m(c, m));
       double* N = c->m0.as<double>();
       {
-        OpTimer t(c, "aat_to_mat");
-        LRN_TRY(t.done(aat_to_mat_factored(c, b, x, N, ragged_ops_on(c, b) ? b.Yc.as<double>() : b.Ys.as<double>())));
+        PhaseTimer t(c, c->opt.profile_ops);
+        LRN_TRY(op_timed(t, "aat_to_mat", aat_to_mat_factored(c, b, x, N, ragged_ops_on(c, b) ? b.Yc.as<double>() : b.Ys.as<double>())));
       }
       LRN_TRY(aa_times(c, b, N, y, false, fused));
       c->counts["op_factored_scaled"] += 1;

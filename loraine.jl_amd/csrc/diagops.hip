@@ -529,7 +529,7 @@ int aat_to_mat_diag(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
   return LRN_OK;
 }
 
-// ---------------------------------------------------------------- ts of H_alpha (option "cg_diag", cgops.hip::prec_setup)
+// ---------------------------------------------------------------- ts of H_alpha (option "cg_diag", prec.hip::prec_setup)
 // The rows of ts that belong to diagonal rows miss  -(L' diag(a_s) u_a)[r] / sqrt(d_j)  after fac_ts_kernel (which holds the
 // factor part, a zero for a purely diagonal constraint).  With L the Cholesky factor of 2 W - Um Um' (lower, upper triangle
 // zeroed, element (i, r) at L[i + r m]) and u_a column a of Um,

@@ -165,7 +165,7 @@ int fac_quadform(lrn_ctx* c, const LmiBlock& b, const FacCols& v, const double* 
 // ts of H_alpha of a block that takes the factor route (a factored block; a covered one under option "cg_lowrank").  With A_j
 // = sum_p w_p v_p v_p' over the columns p of constraint j, L the Cholesky factor of 2 W - Um Um' and u_a column a of Um, the
 // entry route forms  ts[j, a m + r] = -(L' A_j u_a)[r] / sqrt(d_j)  by one pass over every A_j per eigenvector.  Here
-// P = L' V  (m x R, one MFMA product for ALL eigenvectors) and  T = V' Um  (R x erank) come first (cgops.hip::prec_setup), and
+// P = L' V  (m x R, one MFMA product for ALL eigenvectors) and  T = V' Um  (R x erank) come first (prec.hip::prec_setup), and
 //     ts[j, col0 + a m + r] = -(1 / sqrt(d_j)) sum_p w[p] T[p, a] P[r, p]
 // is what this kernel does: a weighted sum of the columns of P of each constraint, in their order, padding skipped (no atomics:
 // two setups give the same bits), written TRANSPOSED -- P is contiguous along r, ts along j.  V is Vd or, under option

@@ -406,20 +406,14 @@ extern "C" int lrn_ip_add_diag(lrn_ctx* c, int il, int which, double eps) {
 extern "C" int lrn_ip_prepare_w(lrn_ctx* c, int il, int* info) {
   BLK(il);
   if (!info) return LRN_ERR_ARG;
-  hipEvent_t a0, a1;
-  if (c->profile) { (void)hipEventCreate(&a0); (void)hipEventCreate(&a1); (void)hipEventRecord(a0, c->stream); }
+  PhaseTimer timer(c, c->profile);
   bool conv = false;
   if (c->opt.nt_mode == 1 && b.msz > 1) LRN_TRY(prepare_w_ns(c, b, info, &conv));
   if (!conv && *info == 0) {
     b.nt_free = false;
     LRN_TRY(prepare_w_block(c, b, info));
   }
-  if (c->profile) {
-    (void)hipEventRecord(a1, c->stream); (void)hipEventSynchronize(a1);
-    float ms = 0; (void)hipEventElapsedTime(&ms, a0, a1);
-    c->timing["prepare_w"] += ms; c->counts["prepare_w"] += 1;
-    (void)hipEventDestroy(a0); (void)hipEventDestroy(a1);
-  }
+  timer.stop("prepare_w");
   return LRN_OK;
 }
 
@@ -537,8 +531,7 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
   if (!c || !dely || !alpha || !beta) return LRN_ERR_ARG;
   LRN_HIP(c, hipSetDevice(c->device));
   LRN_TRY(copy_in(c, c->v0.p, dely, (size_t)c->nvar * 8));
-  hipEvent_t a0, a1;
-  if (c->profile) { (void)hipEventCreate(&a0); (void)hipEventCreate(&a1); (void)hipEventRecord(a0, c->stream); }
+  PhaseTimer timer(c, c->profile);
   for (int il = 0; il < c->nlmi; ++il) {
     LmiBlock& b = c->lmi[il];
     LRN_TRY(ensure_resident(c, b));
@@ -612,12 +605,7 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
     alpha[il] = lamX > -1e-6 ? 0.99 : std::min(1.0, -tau / lamX);
     beta[il] = lamS > -1e-6 ? 0.99 : std::min(1.0, -tau / lamS);
   }
-  if (c->profile) {
-    (void)hipEventRecord(a1, c->stream); (void)hipEventSynchronize(a1);
-    float ms = 0; (void)hipEventElapsedTime(&ms, a0, a1);
-    c->timing["find_step"] += ms; c->counts["find_step"] += 1;
-    (void)hipEventDestroy(a0); (void)hipEventDestroy(a1);
-  }
+  timer.stop("find_step");
   return LRN_OK;
 }
 

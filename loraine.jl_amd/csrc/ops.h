@@ -90,7 +90,7 @@ int cols_product(lrn_ctx* c, const double* A, bool transA, const double* V, long
 int fac_scaled_y(lrn_ctx* c, LmiBlock& b, bool compact);
 int factored_y(lrn_ctx* c, LmiBlock& b, const double** Y);      // Y = W Vd (msz x nvar khat) after assemble_lowrank: its U, or one more product; Yc = W Vc (msz x Rc) under ragged_cross_on
 int assemble_cross(lrn_ctx* c, LmiBlock& b, const double* Y);   // cross terms of a hybrid block from that Y, in its layout
-// facops.hip: ts of H_alpha from P = L' V (msz x R) and T = V' Um (R x erank) on the columns of the view (fac_cols.h; prec_setup
+// facops.hip: ts of H_alpha from P = L' V (msz x R) and T = V' Um (R x erank) on the columns of the view (fac_cols.h; prec.hip::prec_setup
 // decides, option "ragged_ts"): every element of the block's nvar x erank msz part of ts written once
 struct FacCols;
 int fac_ts(lrn_ctx* c, const LmiBlock& b, const FacCols& v, const double* P, const double* T, const double* d, int erank,

@@ -613,15 +613,9 @@ extern "C" int lrn_prepare_w(lrn_ctx* c, int il, const double* X, const double* 
   const size_t mm = (size_t)b.msz * b.msz * 8, mv = (size_t)b.msz * 8;
   LRN_TRY(copy_in(c, b.X.p, X, mm));
   LRN_TRY(copy_in(c, b.S.p, S, mm));
-  hipEvent_t a0, a1;
-  if (c->profile) { (void)hipEventCreate(&a0); (void)hipEventCreate(&a1); (void)hipEventRecord(a0, c->stream); }
+  PhaseTimer timer(c, c->profile);
   LRN_TRY(prepare_w_block(c, b, info));
-  if (c->profile) {
-    (void)hipEventRecord(a1, c->stream); (void)hipEventSynchronize(a1);
-    float ms = 0; (void)hipEventElapsedTime(&ms, a0, a1);
-    c->timing["prepare_w"] += ms; c->counts["prepare_w"] += 1;
-    (void)hipEventDestroy(a0); (void)hipEventDestroy(a1);
-  }
+  timer.stop("prepare_w");
   if (*info != 0) return LRN_OK;
   if (D) LRN_TRY(copy_out(c, D, b.D.p, mv));
   if (G) LRN_TRY(copy_out(c, G, b.G.p, mm));

@@ -148,32 +148,6 @@ __global__ void scatter_vec_kernel(const double* __restrict__ src, const int* __
 
 // ------------------------------------------------------------------ host drivers
 
-// HIP-event timer of one outer phase on the context's stream (nothing unless c->profile): stop() adds the time since the
-// construction to timing[key] and counts the phase; the events go with the scope, on an error return too
-struct PhaseTimer {
-  lrn_ctx* c;
-  hipEvent_t a0 = nullptr, a1 = nullptr;
-  explicit PhaseTimer(lrn_ctx* ctx) : c(ctx) {
-    if (!c->profile) return;
-    (void)hipEventCreate(&a0);
-    (void)hipEventCreate(&a1);
-    (void)hipEventRecord(a0, c->stream);
-  }
-  void stop(const char* key) {
-    if (!a0) return;
-    (void)hipEventRecord(a1, c->stream);
-    (void)hipEventSynchronize(a1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, a0, a1);
-    c->timing[key] += ms;
-    c->counts[key] += 1;
-  }
-  ~PhaseTimer() {
-    if (a0) (void)hipEventDestroy(a0);
-    if (a1) (void)hipEventDestroy(a1);
-  }
-};
-
 // lrn_schur_plan: 1 = the next assembly of this rank would take the Cholesky path (partial sums, all-reduce),
 // 0 = Schur column blocks (all-gather) -- from this rank's own view
 int schur_plan(lrn_ctx* c, int mode) {
@@ -239,7 +213,7 @@ int schur_assemble(lrn_ctx* c, int mode) {
   if (n <= 0) return set_error(c, LRN_ERR_STATE, "no model uploaded");
   if (c->world > 1 && !c->pos_space)
     return set_error(c, LRN_ERR_STATE, "Schur column sharding needs a single LMI block (sigma-position space)");
-  PhaseTimer timer(c);
+  PhaseTimer timer(c, c->profile);
   for (const auto& b : c->lmi)
     if (b.factored && mode != 1)
       return set_error(c, LRN_ERR_STATE, "lrn_schur_assemble: mode %d on a factored block (lrn_set_factored): its constraints "
@@ -331,7 +305,7 @@ int schur_factor(lrn_ctx* c, int* info) {
   size_t bytes = (size_t)n * n * 8;
   LRN_TRY(ensure(c, c->L, bytes));
   LRN_TRY(ensure(c, c->cholwork, chol_work_doubles(n) * 8));
-  PhaseTimer timer(c);
+  PhaseTimer timer(c, c->profile);
   // H is positive semidefinite by construction; late in a solve its smallest eigenvalues sink below the
   // rounding level of the assembly (tru9: lambda_min = -1e-3 at |H| = 4e12).  Pivots at that level are
   // boosted instead of failing the factorisation.  If more than max(8, n/64) pivots are affected the
@@ -366,7 +340,7 @@ int schur_solve(lrn_ctx* c, const double* h, double* dely) {
   if (!c->have_L) return set_error(c, LRN_ERR_STATE, "no factor (call lrn_schur_factor)");
   const int n = c->nvar;
   LRN_TRY(copy_in(c, c->v0.p, h, (size_t)n * 8));
-  PhaseTimer timer(c);
+  PhaseTimer timer(c, c->profile);
   const int* sig = c->pos_space ? c->lmi[0].sigma_d.as<int>() : nullptr;
   const unsigned nvb = (unsigned)((n + 255) / 256);
   // position space: hs[p] = h[sigma[p]]

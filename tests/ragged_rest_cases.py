@@ -1,5 +1,5 @@
 """Seeded cases of what else runs on the compacted columns of a mixed-rank factored block (library options ragged_cross and
-ragged_ts; csrc/fac_cols.h, csrc/schur_factored.hip, csrc/facops.hip, csrc/diagops.hip, csrc/cgops.hip): the cross terms of the mode-1 assembly with stored
+ragged_ts; csrc/fac_cols.h, csrc/schur_factored.hip, csrc/facops.hip, csrc/diagops.hip, csrc/prec.hip): the cross terms of the mode-1 assembly with stored
 constraints and diagonal parts, and ts of H_alpha.  Shared by tests/test_ragged_rest_cpu.py and tests/test_gpu_ragged_rest.py;
 everything is cached and left unchanged, nothing is committed as a fixture.
 

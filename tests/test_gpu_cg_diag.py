@@ -1,5 +1,5 @@
 """GPU: the CG path on factored blocks with diagonal parts, A_k = diag(a_k) + V_k D_k V_k' (library option cg_diag beside
-cg_factored; csrc/cgops.hip: the guard no_diag and the call in prec_setup, csrc/diagops.hip: ts_diag_mfma_kernel, csrc/hop.hip:
+cg_factored; csrc/cgops.hip: the guard no_diag, csrc/prec.hip: the call in prec_setup, csrc/diagops.hip: ts_diag_mfma_kernel, csrc/hop.hip:
 the mode-1 terms of the cost model and the budget) against the extended-precision reference of oracle/cg_reference.py.
 
 The inputs are those of tests/cg_diag_cases.py (D1, D1a, D1h, D2, D3: the models of tests/cg_lowrank_cases.py with diagonal

@@ -1,4 +1,4 @@
-"""GPU: the CG path on factored and hybrid models (library option cg_factored; csrc/cgops.hip: the guard and the stored rows of
+"""GPU: the CG path on factored and hybrid models (library option cg_factored; csrc/cgops.hip: the guard, csrc/prec.hip: the stored rows of
 ts, csrc/hop.hip: H in mode 1 and its memory budget, csrc/dataops.hip: the scaled-factor operator, csrc/facops.hip: the fused
 quadratic form) against the extended-precision reference of oracle/cg_reference.py.
 

@@ -1,5 +1,5 @@
 """GPU: the CG path from the rank-k factors of the data (option cg_lowrank; csrc/hop.hip: H of the assembled-matrix operator
-in mode 1, csrc/dataops.hip: the matrix-free operator in factor form, csrc/cgops.hip, csrc/facops.hip: ts of H_alpha by fac_ts_kernel)
+in mode 1, csrc/dataops.hip: the matrix-free operator in factor form, csrc/prec.hip, csrc/facops.hip: ts of H_alpha by fac_ts_kernel)
 against the extended-precision reference of oracle/cg_reference.py.
 
 The inputs are those of tests/cg_lowrank_cases.py (constraints built from their factors; L1 one block in position space,
@@ -139,7 +139,7 @@ def _check_apply(dev, name, erank, tag, want_factored):
     errs = [cr.relerr(y, ref) for y, _ in res]
     print("CGLR apply %s %s erank=%d | oracle %.2e bound %.2e | device potrs %.2e inverse %.2e dense %.2e"
           % (name, tag, erank, err_o, bound, errs[0], errs[1], errs[2]))
-    # the dense form exists without linear rows from nvar 256 on (cgops.hip::prec_dense_worthwhile)
+    # the dense form exists without linear rows from nvar 256 on (prec.hip::prec_dense_worthwhile)
     assert [b for _, b in res] == [0, 0, 1 if (not lin and case.model.n >= 256) else 0]
     for e in errs:
         assert e <= bound, (errs, bound)

@@ -1,5 +1,5 @@
-"""GPU: the device PCG (csrc/cgops.hip: the two-launch recurrence, the host look-ahead, the H_alpha / H_beta setup and the
-SMW apply in its three forms) against the extended-precision reference of oracle/cg_reference.py.
+"""GPU: the device PCG (csrc/cgops.hip: the two-launch recurrence, the host look-ahead; csrc/prec.hip: the H_alpha / H_beta setup
+and the SMW apply in its three forms) against the extended-precision reference of oracle/cg_reference.py.
 
 The inputs come from seeds (cr.build_case); tests/test_cg_reference_cpu.py asserts on the CPU that they are fair: the
 tolerance lies in a gap of the reference's residual history (so the iteration count is determined: the device has to
@@ -286,3 +286,38 @@ def test_halpha_setup_from_W_alone(dev):
     err = cr.relerr(y, ref)
     print("PCGREF apply B erank=3 from W alone | oracle %.2e bound %.2e | device %.2e" % (err_o, bound, err))
     assert err <= bound, (err, bound)
+
+
+def test_z_factorisation_exit_leaves_counters_and_context_clean(dev):
+    """H_alpha on the indefinite W of the -13 case (from W alone, Jacobi route): 2W - Um Um' <= 2W has a negative
+    eigenvalue and the largest shift of the retry ladder is 1e-9 of the mean |lambda|, so all four attempts at
+    Z = chol(2W - Um Um') fail -- info != 0, three shifted retries counted, no part of ts reported.  An ordinary
+    numerical exit out of the middle of the setup: the same context then sets up case A and applies H_alpha with the
+    bits of a fresh context."""
+    import loraine_jl_amd
+    bad, good = cr.case_inputs("A-indefinite"), cr.case_inputs("A")
+    ts_keys = ("prec_ts_factored", "prec_ts_stored_rows", "prec_ts_diag_rows", "prec_ts_ragged")
+    _upload(dev, bad, with_G=False)
+    with options(dev, prec_eig=1):
+        z0 = dev.count("prec_z_shift")
+        info = dev.prec_setup(1, 1, 1)
+        shifts = dev.count("prec_z_shift") - z0
+        ts_counts = [dev.count(k) for k in ts_keys]
+        _upload(dev, good)
+        info_good = dev.prec_setup(1, 1, 1)
+        y = dev.prec_apply(good.x)
+    fresh = loraine_jl_amd.Device(0)
+    try:
+        _upload(fresh, good)
+        fresh.set_option("prec_eig", 1)
+        assert fresh.prec_setup(1, 1, 1) == 0
+        y_fresh = fresh.prec_apply(good.x)
+    finally:
+        fresh.close()
+    print("PCGREF A-indefinite prec=1 info=%d z_shifts=%d ts counters %s | then A: info=%d, max |y - y_fresh| %.2e"
+          % (info, shifts, ts_counts, info_good, float(np.abs(y - y_fresh).max())))
+    assert info != 0
+    assert shifts == 3
+    assert ts_counts == [0, 0, 0, 0]
+    assert info_good == 0
+    assert np.array_equal(y, y_fresh)

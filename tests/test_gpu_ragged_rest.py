@@ -1,7 +1,7 @@
 """GPU: what else runs on the compacted columns of a mixed-rank factored block -- Y = W V with the cross terms of the stored
 constraints and of the diagonal parts in the mode-1 assembly (library option ragged_cross; csrc/schur_factored.hip::factored_y,
 fac_cross_kernel and fac_cross_coldot_kernel on the compacted layout of csrc/fac_cols.h, csrc/diagops.hip: the store map of
-diag_sq) and ts of H_alpha (library option ragged_ts; csrc/cgops.hip::prec_setup, csrc/facops.hip: fac_ts_kernel on that layout).
+diag_sq) and ts of H_alpha (library option ragged_ts; csrc/prec.hip::prec_setup, csrc/facops.hip: fac_ts_kernel on that layout).
 
 Cases: tests/ragged_rest_cases.py (X1, X2, T1) and the mixed-rank CG cases of tests/cg_factored_cases.py (F1, F1h, F2) and
 tests/cg_diag_cases.py (D1, D1h, D2) as they are.  The fallback: D3 and L3 as a pure block (khat 1, a factor column for every
