@@ -443,7 +443,7 @@ int lrn_hbm_copy_peak(lrn_ctx* ctx, int64_t bytes, double* gbps);
 int lrn_dbg_gemm(lrn_ctx* ctx, int transA, int transB, int M, int N, int K, double alpha,
                  const double* A, int lda, const double* B, int ldb, double beta, double* C,
                  int ldc, int flags, int ksplit);
-/* One function of csrc/products.hip (or symadd of ipstep.hip) on host operands, on the context's stream.
+/* One function of csrc/products.hip (or symadd of matops.hip) on host operands, on the context's stream.
  * A, Bm: n x n column-major.  kind 0: pgemm_nt(A, Bm, out0, tri, alpha, Ct = out1 or NULL)
  *        1: pgemm_nt_sym(A, Bm, out0, alpha, tri)
  *        2: gemm_nt_sym_ns(A, Bm, scratch, a, T = out0, part) ; *scalar = part[0] + ... + part[npart-1], added on the host in index order

@@ -12,27 +12,17 @@
 #include "ctx.h"
 #include "ops.h"
 #include "prec.h"
+#include "reduce.h"
 
 namespace lrn {
 
 // ------------------------------------------------------------------ vector kernels (single workgroup)
-__device__ __forceinline__ double wg_sum1024(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < 16; ++i) s += sh[i];
-  return s;
-}
-
 // scal: [0]=gamma [1]=pAp [2]=alpha [3]=rr [4]=flag(alpha invalid) [5]=beta [6]=||b|| [7]=zr
 __global__ __launch_bounds__(1024) void cg_norm_kernel(const double* __restrict__ b, int n, double* __restrict__ scal, int slot) {
   __shared__ double sh[16];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) s += b[i] * b[i];
-  s = wg_sum1024(s, sh);
+  s = wg_sum<16>(s, sh);
   if (threadIdx.x == 0) scal[slot] = s;
 }
 
@@ -49,6 +39,7 @@ __global__ __launch_bounds__(1024) void cg_norm_kernel(const double* __restrict_
 // the test it has read (option pcg_lookahead); kernels queued beyond the last iteration find the flag set and leave
 // x, r, p alone -- count and result are those of the loop that tests after every step.  g = r'z alternates between
 // scal[10] and scal[11] (a workgroup of cg_d_kernel must not overwrite the value its neighbours are still reading).
+// (not wg_sum<4> of reduce.h: the CG scalars, and so the iteration counts, are pinned to this pairwise order of the waves)
 __device__ __forceinline__ double wg_sum256(double v, double* sh) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);

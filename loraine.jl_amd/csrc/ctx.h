@@ -60,7 +60,7 @@ struct LmiBlock {
   // --- NT scaling state (device, msz x msz col-major)
   lrn::DBuf X, S, W, G, Gi, Si, D, DDsi;
   lrn::DBuf Vprev;          // right singular vectors of the previous prepare_W (Jacobi warm start)
-  // --- device-resident iterate (ipstep.hip): C, residual, directions, predictor point
+  // --- device-resident iterate (ipstep.hip; its Lyapunov solve: lyap.hip): C, residual, directions, predictor point
   lrn::DBuf Cd, Rd, delX, delS, Xn, Sn, RNT, t0, t1, t2;
   bool resident = false;
   bool have_Vprev = false;

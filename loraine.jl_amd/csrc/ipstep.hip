@@ -6,48 +6,17 @@
 // Reference: src/predictor_corrector.jl:8-16,186,248-326 ; src/Solvers.jl:480-511 ;
 // src/kron_etc.jl.  nvar-/nlin-vectors and scalars stay with the host driver.
 //
-// eigmin (predictor_corrector.jl:272,285; Solvers.jl:503,505) is a Lanczos iteration on the
-// device (lz.hip); this file holds its callers.
+// The lrn_ip_* entry points at the end drive one static function per step and per route of the NT scaling (eigen-free:
+// b.nt_free, prepw.hip::prepare_w_ns; SVD: prepare_w_block).  The n x n helpers are in matops.hip, the Lyapunov solve in
+// lyap.hip, eigmin (predictor_corrector.jl:272,285; Solvers.jl:503,505) is a Lanczos iteration on the device (lz.hip).
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
 #include "../../include/loraine_hip.h"
 #include "ops.h"
 
 namespace lrn {
-
-// out = a*A + b*B + c*C (null pointers skipped), n elements
-__global__ void lin3_kernel(double* __restrict__ out, double a, const double* __restrict__ A, double b,
-                            const double* __restrict__ B, double c, const double* __restrict__ C, long n) {
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-    double v = 0.0;
-    if (A) v += a * A[e];
-    if (B) v += b * B[e];
-    if (C) v += c * C[e];
-    out[e] = v;
-  }
-}
-
-// out = (M + M')/2 (out may alias M only through the symmetric access pattern -> use a separate out)
-__global__ void sym_kernel(const double* __restrict__ M, double* __restrict__ out, int n) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    int i = (int)(e % n), j = (int)(e / n);
-    out[e] = 0.5 * (M[e] + M[(long)j + (long)i * n]);
-  }
-}
-
-// Q = sym( dd_j * M[i,j] * dd_i )   (predictor_corrector.jl:268-269)
-__global__ void scale_sym_kernel(const double* __restrict__ M, const double* __restrict__ dd, double* __restrict__ out, int n) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    int i = (int)(e % n), j = (int)(e / n);
-    out[e] = 0.5 * dd[i] * dd[j] * (M[e] + M[(long)j + (long)i * n]);
-  }
-}
 
 // RNT = -(Mx + Mx') ./ (D_i + D_j)   (predictor_corrector.jl:308-309)
 __global__ void rnt_kernel(const double* __restrict__ Mx, const double* __restrict__ D, double* __restrict__ out, int n) {
@@ -82,276 +51,7 @@ __global__ void tx_kernel(const double* __restrict__ T, double a, const double* 
   }
 }
 
-__global__ void add_diag_mat_kernel(double* __restrict__ M, int n, double eps) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) M[(long)i * n + i] += eps;
-}
-void add_diag_mat(hipStream_t st, double* M, int n, double eps) {
-  hipLaunchKernelGGL(add_diag_mat_kernel, dim3((n + 255) / 256), dim3(256), 0, st, M, n, eps);
-}
-
-// two-stage reductions: partial[b] = sum A.*B (B may be null -> A.*A)
-__global__ __launch_bounds__(256) void dot_part_kernel(const double* __restrict__ A, const double* __restrict__ B, long n,
-                                                       double* __restrict__ part) {
-  __shared__ double sh[4];
-  double s = 0.0;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) s += A[e] * (B ? B[e] : A[e]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-__global__ __launch_bounds__(256) void dot_final_kernel(const double* __restrict__ part, int np, double* __restrict__ out) {
-  __shared__ double sh[4];
-  double s = 0.0;
-  for (int e = threadIdx.x; e < np; e += 256) s += part[e];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-static int dot_dev(lrn_ctx* c, const double* A, const double* B, long n, double* out_dev) {
-  const int np = (int)std::min<long>(1024, (n + 255) / 256);
-  LRN_TRY(ensure(c, c->redbuf, (size_t)(np + 64) * 8));
-  hipLaunchKernelGGL(dot_part_kernel, dim3(np), dim3(256), 0, c->stream, A, B, n, c->redbuf.as<double>());
-  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(256), 0, c->stream, c->redbuf.as<double>(), np, out_dev);
-  return LRN_OK;
-}
-
-// ------------------------------------------------------------------ Lyapunov solve (eigen-free NT scaling)
-// out = scale (T + T') by 32 x 32 tiles (both reads coalesced); with `dotp`: part[block] = sum dotp .* out over the block's
-// tiles.  out is exactly symmetric: (i,j) and (j,i) add the same two numbers.
-__global__ __launch_bounds__(256) void symadd_kernel(SlabSrc T, int n, double scale, double* __restrict__ out,
-                                                     const double* __restrict__ dotp, double* __restrict__ part) {
-  __shared__ double ta[32][33], tb[32][33];
-  __shared__ double sh[4];
-  const int nt = (n + 31) / 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
-  double acc = 0.0;
-  for (long t = blockIdx.x; t < (long)nt * nt; t += gridDim.x) {
-    const int bi = (int)(t % nt) * 32, bj = (int)(t / nt) * 32;
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int i = bi + tx, j = bj + r;       // tile (bi, bj): element (i, j)
-      ta[r][tx] = (i < n && j < n) ? slab_sum(T, (long)i + (long)j * n) : 0.0;
-      const int i2 = bj + tx, j2 = bi + r;     // tile (bj, bi): element (i2, j2)
-      tb[r][tx] = (i2 < n && j2 < n) ? slab_sum(T, (long)i2 + (long)j2 * n) : 0.0;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int i = bi + tx, j = bj + r;
-      if (i < n && j < n) {
-        const double v = scale * (ta[r][tx] + tb[tx][r]);      // T[i,j] + T[j,i]
-        out[(long)i + (long)j * n] = v;
-        if (dotp) acc += dotp[(long)i + (long)j * n] * v;
-      }
-    }
-  }
-  if (!part) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-void symadd(hipStream_t st, unsigned grid, const SlabSrc& T, int n, double scale, double* out, const double* dotp, double* part) {
-  hipLaunchKernelGGL(symadd_kernel, dim3(grid), dim3(256), 0, st, T, n, scale, out, dotp, part);
-}
-
-__device__ __forceinline__ double block_sum_parts(const double* __restrict__ part, int np, double* sh) {
-  double s = 0.0;
-  for (int e = threadIdx.x; e < np; e += 256) s += part[e];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// out = (M + M') / 2: the tiled kernel above from msz 512 on (the element-wise one reads M' with stride n)
-static void sym_half(hipStream_t st, const double* M, double* out, int n) {
-  if (n >= 512) {
-    const long nt = (n + 31) / 32;
-    hipLaunchKernelGGL(symadd_kernel, dim3((unsigned)std::min<long>(1024, nt * nt)), dim3(256), 0, st, SlabSrc{M, 0, 1}, n, 0.5, out,
-                       (const double*)nullptr, (double*)nullptr);
-  } else {
-    hipLaunchKernelGGL(sym_kernel, dim3(nb((long)n * n)), dim3(256), 0, st, M, out, n);
-  }
-}
-
-// alpha = rr_k / <p, Ap> (every workgroup sums the same partials in the same order); R += alpha p; r -= alpha Ap;
-// part2[block] = sum r^2
-__global__ __launch_bounds__(256) void lyap_xr_kernel(const double* __restrict__ part1, int np1, const double* __restrict__ hist,
-                                                      int k, const double* __restrict__ p, const double* __restrict__ Ap,
-                                                      double* __restrict__ R, double* __restrict__ r, long total,
-                                                      double* __restrict__ part2) {
-  __shared__ double sh[4];
-  const double pAp = block_sum_parts(part1, np1, sh);
-  const double rr = hist[k];
-  const double alpha = (pAp > 0.0 && rr > 0.0) ? rr / pAp : 0.0;
-  double s = 0.0;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    R[e] += alpha * p[e];
-    const double v = r[e] - alpha * Ap[e];
-    r[e] = v;
-    s += v * v;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part2[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// beta = rr_{k+1} / rr_k; p = r + beta p; hist[k+1] = rr_{k+1}
-__global__ __launch_bounds__(256) void lyap_p_kernel(const double* __restrict__ part2, int np2, double* __restrict__ hist, int k,
-                                                     const double* __restrict__ r, double* __restrict__ p, long total) {
-  __shared__ double sh[4];
-  const double rn = block_sum_parts(part2, np2, sh);
-  const double rr = hist[k];
-  const double beta = rr > 0.0 ? rn / rr : 0.0;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) p[e] = r[e] + beta * p[e];
-  if (blockIdx.x == 0 && threadIdx.x == 0) hist[k + 1] = rn;
-}
-
-// R with Yh R + R Yh = Cm (Yh symmetric positive definite, Cm symmetric) by conjugate gradients in the Frobenius inner
-// product: one product Yh p per step (the other half of the operator is its transpose), all scalars stay on the device,
-// the host reads the residual history once per batch of steps.  Cm is used as the residual and destroyed.
-//
-// Round 4 -- the SAME solution from a better conditioned equation (option lyap_form = 1, default).  Zh = Yh^-1 is at hand
-// (the coupled Newton-Schulz iteration produces both), and multiplying  Yh R + R Yh = C  by Zh from both sides gives
-// Zh R + R Zh = Zh C Zh.  Any positive combination is again a Lyapunov equation for the same R:
-//     M R + R M = C / s + s Zh C Zh,      M = Yh / s + s Zh,
-// whose coefficient has the spectrum y / s + s / y: with s^2 = tr(Yh) / tr(Zh) (inside [y_min^2, y_max^2], free) its
-// condition number is ~ sqrt(cond(Yh)) / 2 and never above cond(Yh) / 2.  Still one product per CG step, two more for the
-// right-hand side; NumPy on spectra of cond(K) 1e2 / 1e3 / 1e4: 42 / 77 / 137 steps -> 14 / 21 / 29, same accuracy
-// (C5: 32-48 steps of a 10^4-cube product each, 1.1-1.6 s of a 2.8 s iteration).
-__global__ __launch_bounds__(256) void lyap_trace2_kernel(const double* __restrict__ Y, const double* __restrict__ Z, int n,
-                                                          double* __restrict__ sc) {
-  __shared__ double sh[8];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) { a += Y[(size_t)i * n + i]; b += Z[(size_t)i * n + i]; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = a; sh[4 + (threadIdx.x >> 6)] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double ty = sh[0] + sh[1] + sh[2] + sh[3], tz = sh[4] + sh[5] + sh[6] + sh[7];
-    double s = (ty > 0.0 && tz > 0.0) ? sqrt(ty / tz) : 1.0;
-    if (!(s > 0.0) || isinf(s)) s = 1.0;
-    sc[0] = s;
-    sc[1] = 1.0 / s;
-  }
-}
-
-// M = Y / s + s Z
-__global__ void lyap_mop_kernel(const double* __restrict__ Y, const double* __restrict__ Z, const double* __restrict__ sc,
-                                long total, double* __restrict__ Mop) {
-  const double s = sc[0], si = sc[1];
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x)
-    Mop[e] = Y[e] * si + s * Z[e];
-}
-
-// C <- C / s + s (T + T') / 2   (T = Zh C Zh up to rounding asymmetry), by 32 x 32 tiles as symadd_kernel
-__global__ __launch_bounds__(256) void lyap_rhs_kernel(double* __restrict__ Cm, const double* __restrict__ T, int n,
-                                                       const double* __restrict__ sc) {
-  __shared__ double ta[32][33], tb[32][33];
-  const double s = sc[0], si = sc[1];
-  const int nt = (n + 31) / 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (long t = blockIdx.x; t < (long)nt * nt; t += gridDim.x) {
-    const int bi = (int)(t % nt) * 32, bj = (int)(t / nt) * 32;
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int i = bi + tx, j = bj + r;
-      ta[r][tx] = (i < n && j < n) ? T[(long)i + (long)j * n] : 0.0;
-      const int i2 = bj + tx, j2 = bi + r;
-      tb[r][tx] = (i2 < n && j2 < n) ? T[(long)i2 + (long)j2 * n] : 0.0;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int i = bi + tx, j = bj + r;
-      if (i < n && j < n) {
-        const long e = (long)i + (long)j * n;
-        Cm[e] = Cm[e] * si + s * 0.5 * (ta[r][tx] + tb[tx][r]);
-      }
-    }
-  }
-}
-
-static int lyap_solve(lrn_ctx* c, LmiBlock& b, double* Cm, double* R, double* work, bool* ok, int* steps) {
-  const int n = b.msz;
-  const long nn = (long)n * n;
-  hipStream_t st = c->stream;
-  const int maxit = std::max(2, c->opt.lyap_maxit);
-  const int np = (int)std::min<long>(1024, (nn + 255) / 256);
-  const bool combined = c->opt.lyap_form != 0;
-  LRN_TRY(ensure(c, b.lyap, ((size_t)(combined ? 3 : 2) * nn + 2 * 1024 + maxit + 16) * 8));
-  double* p = b.lyap.as<double>();
-  double* Ap = p + nn;
-  double* part1 = Ap + nn;
-  double* part2 = part1 + 1024;
-  double* hist = part2 + 1024;
-  double* Mop = hist + maxit + 16;
-  double* r = Cm;
-  const double* Cop = b.Yh.as<double>();             // coefficient matrix of the equation that is iterated on
-  const int ntile0 = (n + 31) / 32;
-  if (combined) {
-    double* sc = part2;                               // (two doubles, free until the first lyap_xr_kernel)
-    hipLaunchKernelGGL(lyap_trace2_kernel, dim3(1), dim3(256), 0, st, b.Yh.as<double>(), b.Zh.as<double>(), n, sc);
-    hipLaunchKernelGGL(lyap_mop_kernel, dim3(np), dim3(256), 0, st, b.Yh.as<double>(), b.Zh.as<double>(), sc, nn, Mop);
-    LRN_TRY(pgemm_nt(c, st, n, b.Zh.as<double>(), Cm, work));                 // Zh C   (C symmetric)
-    LRN_TRY(pgemm_nt(c, st, n, work, b.Zh.as<double>(), Ap));                 // Zh C Zh
-    hipLaunchKernelGGL(lyap_rhs_kernel, dim3((unsigned)std::min<long>(1024, (long)ntile0 * ntile0)), dim3(256), 0, st, Cm, Ap, n, sc);
-    Cop = Mop;
-  }
-  LRN_HIP(c, hipMemsetAsync(R, 0, (size_t)nn * 8, st));
-  LRN_HIP(c, hipMemcpyAsync(p, r, (size_t)nn * 8, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(dot_part_kernel, dim3(np), dim3(256), 0, st, r, (const double*)nullptr, nn, part1);
-  hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(256), 0, st, part1, np, hist);
-  std::vector<double> h(maxit + 1, 0.0);
-  const double tol2 = c->opt.lyap_tol * c->opt.lyap_tol;
-  int k = 0;
-  *ok = false;
-  const int ntile = (n + 31) / 32;
-  const int np1 = (int)std::min<long>(1024, (long)ntile * ntile);
-  int batch = std::min(maxit, n >= 2000 ? 6 : 8);      // first look at the residual history
-  while (k < maxit) {
-    const int k1 = std::min(maxit, k + batch);
-    for (; k < k1; ++k) {
-      SlabSrc prod;                                  // (mid sizes: the slabs of the product are added by symadd_kernel)
-      LRN_TRY(prod_slabs(c, st, n, Cop, p, work, 1.0, 0, &prod));
-      hipLaunchKernelGGL(symadd_kernel, dim3(np1), dim3(256), 0, st, prod, n, 1.0, Ap, p, part1);
-      hipLaunchKernelGGL(lyap_xr_kernel, dim3(np), dim3(256), 0, st, part1, np1, hist, k, p, Ap, R, r, nn, part2);
-      hipLaunchKernelGGL(lyap_p_kernel, dim3(np), dim3(256), 0, st, part2, np, hist, k, r, p, nn);
-    }
-    LRN_HIP(c, hipMemcpyAsync(h.data(), hist, (size_t)(k + 1) * 8, hipMemcpyDeviceToHost, st));
-    LRN_HIP(c, hipStreamSynchronize(st));
-    if (!(h[k] == h[k])) break;                                   // NaN
-    if (h[0] == 0.0 || h[k] <= tol2 * h[0]) { *ok = true; break; }
-    // how many more steps at the rate of the last two (CG only gets faster): queue that many before the next look --
-    // a step is one n^3 product (31 ms at msz 10^4: none to waste), a look is a host round trip (20 us: too many at 800)
-    batch = n >= 2000 ? 2 : 4;
-    if (k >= 2 && h[k] > 0.0 && h[k] < h[k - 2]) {
-      const double f = 0.5 * std::log(h[k - 2] / h[k]);           // decrement of log ||r||^2 per step
-      const double m = std::log(h[k] / (tol2 * h[0])) / f;
-      const int lo_b = n >= 2000 ? 1 : 2;
-      batch = std::max(lo_b, std::min(8, (int)std::floor(0.9 * m + 0.5)));
-    }
-  }
-  if (steps) *steps = k;
-  return LRN_OK;
-}
-
-// ------------------------------------------------------------------ resident step
-static int ensure_resident(lrn_ctx* c, LmiBlock& b) {
+int ensure_resident(lrn_ctx* c, LmiBlock& b) {
   size_t mm_ = (size_t)b.msz * b.msz * 8;
   for (DBuf* d : {&b.Cd, &b.Rd, &b.delX, &b.delS, &b.Xn, &b.Sn, &b.RNT, &b.t0, &b.t1, &b.t2})
     if (d->bytes < mm_) LRN_TRY(ensure(c, *d, mm_, true));
@@ -359,53 +59,231 @@ static int ensure_resident(lrn_ctx* c, LmiBlock& b) {
   return LRN_OK;
 }
 
+// A block as the steps below see it: sizes, the grid of the element-wise kernels and the arrays by name.  Taken after
+// ensure_resident; the arrays of the scaling (W .. Qm) are those of the route that ran last and may be null.
+struct Blk {
+  LmiBlock* b;
+  int m;                  // msz
+  long mm;                // msz^2
+  size_t bytes;           // of one msz x msz array
+  unsigned g;             // workgroups of an element-wise pass
+  double *X, *S, *Cd, *Rd, *delX, *delS, *Xn, *Sn, *RNT, *t0, *t1, *t2;
+  double *G, *Gi, *D, *DDsi, *Si;                           // SVD route (Si: both)
+  double *LXf, *LXt, *Zh, *Ki, *Bs, *TX, *Qm;               // eigen-free route
+};
+
+static int block_view(lrn_ctx* c, LmiBlock& b, Blk* v) {
+  LRN_TRY(ensure_resident(c, b));
+  auto p = [](DBuf& d) { return d.as<double>(); };
+  const long mm = (long)b.msz * b.msz;
+  *v = Blk{&b, b.msz, mm, (size_t)mm * 8, nb(mm),
+           p(b.X), p(b.S), p(b.Cd), p(b.Rd), p(b.delX), p(b.delS), p(b.Xn), p(b.Sn), p(b.RNT), p(b.t0), p(b.t1), p(b.t2),
+           p(b.G), p(b.Gi), p(b.D), p(b.DDsi), p(b.Si),
+           p(b.LXf), p(b.LXt), p(b.Zh), p(b.Ki), p(b.Bs), p(b.TX), p(b.Qm)};
+  return LRN_OK;
+}
+
+// the view of block il for an entry point that addresses one block
+static int block_at(lrn_ctx* c, int il, Blk* v) {
+  if (!c || il < 0 || il >= c->nlmi) return LRN_ERR_ARG;
+  LRN_HIP(c, hipSetDevice(c->device));
+  return block_view(c, c->lmi[il], v);
+}
+
+// ------------------------------------------------------------------ right-hand sides
+// v1 += AA vec(W (Rd + S) W); with aax: aax += AA vec(X) beside it, and W M W only where AA reads it when every constraint
+// is sparse (one product instead of two).  Without aax always both products.
+static int rhs_pred_block(lrn_ctx* c, const Blk& v, double* aax) {
+  LmiBlock& b = *v.b;
+  double* v1 = c->v1.as<double>();
+  lin3(c->stream, v.t0, v.mm, 1.0, v.Rd, 1.0, v.S);
+  if (aax && wmw_pattern_ok(c, b)) {
+    LRN_TRY(aa_times(c, b, v.X, aax));
+    return aa_times_wmw_pattern(c, b, v.t0, v.t1, v1);
+  }
+  LRN_TRY(wmw(c, b, v.t0, v.t1, v.t2));
+  if (aax) return aa_times2(c, b, v.X, aax, v.t2, v1);
+  return aa_times(c, b, v.t2, v1);
+}
+
+// The corrector's term v1 += AA vec(G (G'RdG + D - sigma_mu/D - RNT) G')   (predictor_corrector.jl:186), per route.
+// Eigen-free: = AA vec(W Rd W + X - sigma_mu Si - G RNT G') with Qm = G RNT G'.  On the pattern: AA vec(W Rd W) where AA
+// reads it, AA vec(X - sigma_mu Si - Qm) by itself
+static int rhs_corr_eigenfree_pattern(lrn_ctx* c, const Blk& v, double sigma_mu) {
+  LRN_TRY(aa_times_wmw_pattern(c, *v.b, v.Rd, v.t1, c->v1.as<double>()));
+  lin3(c->stream, v.t0, v.mm, 1.0, v.X, -sigma_mu, v.Si, -1.0, v.Qm);
+  return aa_times(c, *v.b, v.t0, c->v1.as<double>());
+}
+
+static int rhs_corr_eigenfree_full(lrn_ctx* c, const Blk& v, double sigma_mu) {
+  LRN_TRY(wmw(c, *v.b, v.Rd, v.t1, v.t2));
+  lin3(c->stream, v.t0, v.mm, 1.0, v.t2, 1.0, v.X, -sigma_mu, v.Si);
+  lin3(c->stream, v.t2, v.mm, 1.0, v.t0, -1.0, v.Qm);
+  return aa_times(c, *v.b, v.t2, c->v1.as<double>());
+}
+
+static int rhs_corr_svd(lrn_ctx* c, const Blk& v, double sigma_mu) {
+  hipStream_t st = c->stream;
+  // t1 = G' Rd G
+  LRN_TRY(gemm_nn(st, v.m, v.G, true, v.Rd, false, v.t0));
+  LRN_TRY(gemm_nn(st, v.m, v.t0, false, v.G, false, v.t1));
+  hipLaunchKernelGGL(corr_inner_kernel, dim3(v.g), dim3(256), 0, st, v.t1, v.D, v.RNT, sigma_mu, v.t0, v.m);
+  // my_kron(G,G,inner) = vec(G inner G')
+  LRN_TRY(gemm_nn(st, v.m, v.G, false, v.t0, false, v.t1));
+  LRN_TRY(gemm_nn(st, v.m, v.t1, false, v.G, true, v.t2));
+  return aa_times(c, *v.b, v.t2, c->v1.as<double>());
+}
+
+// ------------------------------------------------------------------ find_step
+// delX from delS and the smallest eigenvalues of the two scaled directions (predictor_corrector.jl:253-285), per route.
+// t3 = Xn is free here: Xn / Sn are rebuilt by lrn_ip_update after the step lengths.
+//
+// Eigen-free: everything in the L_X basis (prepw.hip::prepare_w_ns): Bs = L_X' dS L_X, T = Z Bs Z / c,
+// TX = L_X^-1 dX L_X^-T = -I - T (+ sigma_mu K^-1 + R), dX = L_X TX L_X'                  (:253-257)
+static int find_step_eigenfree(lrn_ctx* c, const Blk& v, int predict, double sigma_mu, double* lamX, double* lamS) {
+  hipStream_t st = c->stream;
+  const int m = v.m;
+  const double ns_c = v.b->ns_c;
+  double* t3 = v.Xn;
+  LRN_TRY(pgemm_nt(c, st, m, v.LXt, v.delS, v.t0, GEMM_KFROM_M));                      // L_X' upper triangular
+  // (both second products are symmetric in exact arithmetic: from msz 1500 on the lower tiles + mirror, half the work;
+  // below, the full product and the average of the two triangles)
+  LRN_TRY(sym_product(c, st, m, v.t0, v.LXt, v.t1, v.Bs, 1.0, GEMM_KFROM_N));
+  LRN_TRY(pgemm_nt(c, st, m, v.Zh, v.Bs, v.t0));
+  LRN_TRY(sym_product(c, st, m, v.t0, v.Zh, v.t1, t3, 1.0 / ns_c, 0));
+  hipLaunchKernelGGL(tx_kernel, dim3(v.g), dim3(256), 0, st, t3, sigma_mu / ns_c, v.Ki,
+                     predict ? (const double*)nullptr : v.RNT, v.TX, m);
+  LRN_TRY(pgemm_nt(c, st, m, v.LXf, v.TX, v.t0, GEMM_KTO_M));                          // L_X lower triangular
+  LRN_TRY(pgemm_nt_sym(c, st, m, v.t0, v.LXf, v.delX, 1.0, GEMM_KTO_N));
+  // the scaled directions of the step-length rule are orthogonally similar to TX and T               (:263-285)
+  return eigmin_certified_pair(c, v.TX, t3, m, lamX, lamS);
+}
+
+static int find_step_svd(lrn_ctx* c, const Blk& v, int predict, double sigma_mu, double* lamX, double* lamS) {
+  hipStream_t st = c->stream;
+  const int m = v.m;
+  double *t0 = v.t0, *t1 = v.t1, *t2 = v.t2, *t3 = v.Xn;
+  // t2 = W delS W                                                (:253)
+  LRN_TRY(wmw(c, *v.b, v.delS, t1, t2));
+  if (predict) {
+    // delX = mat(-X - W delS W)                                  (:255)
+    lin3(st, t0, v.mm, -1.0, v.X, -1.0, t2);
+  } else {
+    // delX = mat(sigma_mu Si - X - W delS W + G RNT G')          (:257)
+    lin3(st, t0, v.mm, sigma_mu, v.Si, -1.0, v.X, -1.0, t2);
+    LRN_TRY(gemm_nn(st, m, v.G, false, v.RNT, false, t1));
+    LRN_TRY(gemm_nn(st, m, t1, false, v.G, true, t2));
+    lin3(st, t0, v.mm, 1.0, t0, 1.0, t2);
+  }
+  sym_half(st, t0, v.delX, m);
+  // step lengths: eigmin of DDsi-scaled G' delS G and Gi delX Gi'   (:263-291)
+  LRN_TRY(gemm_nn(st, m, v.Gi, false, v.delX, false, t0));
+  LRN_TRY(gemm_nn(st, m, t0, false, v.Gi, true, t1));
+  scale_sym(st, t1, v.DDsi, t2, m);
+  LRN_TRY(gemm_nn(st, m, v.G, true, v.delS, false, t0));
+  LRN_TRY(gemm_nn(st, m, t0, false, v.G, false, t1));
+  scale_sym(st, t1, v.DDsi, t3, m);
+  return eigmin_certified_pair(c, t2, t3, m, lamX, lamS);
+}
+
+// the step-length rule from the smallest eigenvalue of a scaled direction   (predictor_corrector.jl:274-291)
+static double step_length(double lam, double tau) { return lam > -1e-6 ? 0.99 : std::min(1.0, -tau / lam); }
+
+// ------------------------------------------------------------------ update
+// Xn = X + alpha delX, Sn = S + beta delS, *tr_dev = <Xn, Sn>
+static int predict_point(lrn_ctx* c, const Blk& v, double alpha, double beta, double* tr_dev) {
+  lin3(c->stream, v.Xn, v.mm, 1.0, v.X, alpha, v.delX);
+  lin3(c->stream, v.Sn, v.mm, 1.0, v.S, beta, v.delS);
+  return dot_dev(c, v.Xn, v.Sn, v.mm, tr_dev);
+}
+
+// Qm = G RNT G' without the eigenvectors: N = L_X^-1 dX dS L_X = TX Bs, Yh R + R Yh = -(N Zh + Zh N') / c, Qm = L_X R L_X'.
+// *ok = false: the Lyapunov iteration did not converge (K far from well conditioned), Qm is not formed
+static int second_order_eigenfree(lrn_ctx* c, const Blk& v, bool* ok) {
+  LmiBlock& b = *v.b;
+  hipStream_t st = c->stream;
+  const int m = v.m;
+  tic(c);
+  LRN_TRY(pgemm_nt(c, st, m, v.TX, v.Bs, v.t0));                                       // N
+  SlabSrc prod;
+  LRN_TRY(prod_slabs(c, st, m, v.t0, v.Zh, v.t1, 1.0, 0, &prod));                      // N Zh
+  symadd(st, sym_grid(m), prod, m, -1.0 / b.ns_c, v.t2, nullptr, nullptr);
+  int steps = 0;
+  LRN_TRY(lyap_solve(c, b, v.t2, v.RNT, v.t0, ok, &steps));
+  c->counts["lyap_steps"] += steps;
+  c->counts["lyap_solves"] += 1;
+  if (*ok) {
+    LRN_TRY(pgemm_nt(c, st, m, v.LXf, v.RNT, v.t0, GEMM_KTO_M));
+    LRN_TRY(pgemm_nt_sym(c, st, m, v.t0, v.LXf, v.Qm, 1.0, GEMM_KTO_N));
+  }
+  toc(c, "lyap");
+  return LRN_OK;
+}
+
+// RNT = -(Gi delX delS G + its transpose) ./ (D_i + D_j)     (predictor_corrector.jl:308-309)
+static int second_order_svd(lrn_ctx* c, const Blk& v) {
+  hipStream_t st = c->stream;
+  LRN_TRY(gemm_nn(st, v.m, v.Gi, false, v.delX, false, v.t0));
+  LRN_TRY(gemm_nn(st, v.m, v.t0, false, v.delS, false, v.t1));
+  LRN_TRY(gemm_nn(st, v.m, v.t1, false, v.G, false, v.t2));
+  hipLaunchKernelGGL(rnt_kernel, dim3(v.g), dim3(256), 0, st, v.t2, v.D, v.RNT, v.m);
+  return LRN_OK;
+}
+
+// the corrector's step: X <- sym(X + alpha delX), S <- sym(S + beta delS)
+static void take_step(lrn_ctx* c, const Blk& v, double alpha, double beta) {
+  v.b->chol_valid = false;
+  lin3(c->stream, v.t0, v.mm, 1.0, v.X, alpha, v.delX);
+  sym_half(c->stream, v.t0, v.X, v.m);
+  lin3(c->stream, v.t0, v.mm, 1.0, v.S, beta, v.delS);
+  sym_half(c->stream, v.t0, v.S, v.m);
+}
+
 }  // namespace lrn
 
 using namespace lrn;
 
-#define BLK(il)                                                        \
-  if (!c || (il) < 0 || (il) >= c->nlmi) return LRN_ERR_ARG;          \
-  LRN_HIP(c, hipSetDevice(c->device));                                 \
-  LmiBlock& b = c->lmi[(il)];                                          \
-  LRN_TRY(ensure_resident(c, b));                                      \
-  const size_t mm_ = (size_t)b.msz * b.msz * 8;                        \
-  (void)mm_;
-
 extern "C" int lrn_ip_set_c(lrn_ctx* c, int il, const double* C) {
-  BLK(il);
+  Blk v;
+  LRN_TRY(block_at(c, il, &v));
   if (!C) return LRN_ERR_ARG;
-  return copy_in(c, b.Cd.p, C, mm_);
+  return copy_in(c, v.Cd, C, v.bytes);
 }
 
 extern "C" int lrn_ip_set_iterate(lrn_ctx* c, int il, const double* X, const double* S) {
-  BLK(il);
+  Blk v;
+  LRN_TRY(block_at(c, il, &v));
   if (!X || !S) return LRN_ERR_ARG;
-  LRN_TRY(copy_in(c, b.X.p, X, mm_));
-  LRN_TRY(copy_in(c, b.S.p, S, mm_));
-  LRN_HIP(c, hipMemsetAsync(b.RNT.p, 0, mm_, c->stream));
-  b.have_Vprev = false;
-  b.chol_valid = false;
+  LRN_TRY(copy_in(c, v.X, X, v.bytes));
+  LRN_TRY(copy_in(c, v.S, S, v.bytes));
+  LRN_HIP(c, hipMemsetAsync(v.RNT, 0, v.bytes, c->stream));
+  v.b->have_Vprev = false;
+  v.b->chol_valid = false;
   return LRN_OK;
 }
 
 extern "C" int lrn_ip_get_iterate(lrn_ctx* c, int il, double* X, double* S) {
-  BLK(il);
-  if (X) LRN_TRY(copy_out(c, X, b.X.p, mm_));
-  if (S) LRN_TRY(copy_out(c, S, b.S.p, mm_));
+  Blk v;
+  LRN_TRY(block_at(c, il, &v));
+  if (X) LRN_TRY(copy_out(c, X, v.X, v.bytes));
+  if (S) LRN_TRY(copy_out(c, S, v.S, v.bytes));
   return LRN_OK;
 }
 
 extern "C" int lrn_ip_add_diag(lrn_ctx* c, int il, int which, double eps) {
-  BLK(il);
+  Blk v;
+  LRN_TRY(block_at(c, il, &v));
   if (which != 1 && which != 2) return LRN_ERR_ARG;
-  b.chol_valid = false;
-  add_diag_mat(c->stream, (which == 1 ? b.X : b.S).as<double>(), b.msz, eps);
+  v.b->chol_valid = false;
+  add_diag_mat(c->stream, which == 1 ? v.X : v.S, v.m, eps);
   return LRN_OK;
 }
 
 extern "C" int lrn_ip_prepare_w(lrn_ctx* c, int il, int* info) {
-  BLK(il);
+  Blk v;
+  LRN_TRY(block_at(c, il, &v));
   if (!info) return LRN_ERR_ARG;
+  LmiBlock& b = *v.b;
   PhaseTimer timer(c, c->profile);
   bool conv = false;
   if (c->opt.nt_mode == 1 && b.msz > 1) LRN_TRY(prepare_w_ns(c, b, info, &conv));
@@ -432,11 +310,10 @@ extern "C" int lrn_ip_residual_d(lrn_ctx* c, const double* y) {
   LRN_TRY(copy_in(c, c->v0.p, y, (size_t)c->nvar * 8));
   tic(c);
   for (auto& b : c->lmi) {
-    LRN_TRY(ensure_resident(c, b));
-    const long mm_ = (long)b.msz * b.msz;
-    LRN_TRY(aat_to_mat(c, b, c->v0.as<double>(), b.t0.as<double>()));
-    hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.Rd.as<double>(), 1.0, b.Cd.as<double>(),
-                       -1.0, b.S.as<double>(), -1.0, b.t0.as<double>(), mm_);
+    Blk v;
+    LRN_TRY(block_view(c, b, &v));
+    LRN_TRY(aat_to_mat(c, b, c->v0.as<double>(), v.t0));
+    lin3(c->stream, v.Rd, v.mm, 1.0, v.Cd, -1.0, v.S, -1.0, v.t0);
   }
   toc(c, "residual_d");
   return LRN_OK;
@@ -448,12 +325,9 @@ extern "C" int lrn_ip_rhs_pred(lrn_ctx* c, double* out) {
   const int n = c->nvar;
   LRN_HIP(c, hipMemsetAsync(c->v1.p, 0, (size_t)n * 8, c->stream));
   for (auto& b : c->lmi) {
-    LRN_TRY(ensure_resident(c, b));
-    const long mm_ = (long)b.msz * b.msz;
-    hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.Rd.as<double>(),
-                       1.0, b.S.as<double>(), 0.0, (const double*)nullptr, mm_);
-    LRN_TRY(wmw(c, b, b.t0.as<double>(), b.t1.as<double>(), b.t2.as<double>()));
-    LRN_TRY(aa_times(c, b, b.t2.as<double>(), c->v1.as<double>()));
+    Blk v;
+    LRN_TRY(block_view(c, b, &v));
+    LRN_TRY(rhs_pred_block(c, v, nullptr));
   }
   return copy_out(c, out, c->v1.p, (size_t)n * 8);
 }
@@ -467,17 +341,9 @@ extern "C" int lrn_ip_rhs_pred2(lrn_ctx* c, double* aax_out, double* out) {
   LRN_HIP(c, hipMemsetAsync(c->v1.p, 0, (size_t)n * 8, c->stream));
   LRN_HIP(c, hipMemsetAsync(c->v2.p, 0, (size_t)n * 8, c->stream));
   for (auto& b : c->lmi) {
-    LRN_TRY(ensure_resident(c, b));
-    const long mm_ = (long)b.msz * b.msz;
-    hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.Rd.as<double>(),
-                       1.0, b.S.as<double>(), 0.0, (const double*)nullptr, mm_);
-    if (wmw_pattern_ok(c, b)) {          // every constraint sparse: W M W only where AA reads it (one product instead of two)
-      LRN_TRY(aa_times(c, b, b.X.as<double>(), c->v2.as<double>()));
-      LRN_TRY(aa_times_wmw_pattern(c, b, b.t0.as<double>(), b.t1.as<double>(), c->v1.as<double>()));
-      continue;
-    }
-    LRN_TRY(wmw(c, b, b.t0.as<double>(), b.t1.as<double>(), b.t2.as<double>()));
-    LRN_TRY(aa_times2(c, b, b.X.as<double>(), c->v2.as<double>(), b.t2.as<double>(), c->v1.as<double>()));
+    Blk v;
+    LRN_TRY(block_view(c, b, &v));
+    LRN_TRY(rhs_pred_block(c, v, c->v2.as<double>()));
   }
   toc(c, "rhs");
   LRN_TRY(copy_out(c, aax_out, c->v2.p, (size_t)n * 8));
@@ -491,36 +357,11 @@ extern "C" int lrn_ip_rhs_corr(lrn_ctx* c, double sigma_mu, double* out) {
   tic(c);
   LRN_HIP(c, hipMemsetAsync(c->v1.p, 0, (size_t)n * 8, c->stream));
   for (auto& b : c->lmi) {
-    LRN_TRY(ensure_resident(c, b));
-    const int m = b.msz;
-    const long mm_ = (long)m * m;
-    if (b.nt_free) {
-      // G (G'RdG + D - sigma_mu/D - RNT) G' = W Rd W + X - sigma_mu Si - G RNT G'
-      if (wmw_pattern_ok(c, b)) {        // AA vec(W Rd W) on the pattern, AA vec(X - sigma_mu Si - G RNT G') by itself
-        LRN_TRY(aa_times_wmw_pattern(c, b, b.Rd.as<double>(), b.t1.as<double>(), c->v1.as<double>()));
-        hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.X.as<double>(), -sigma_mu,
-                           b.Si.as<double>(), -1.0, b.Qm.as<double>(), mm_);
-        LRN_TRY(aa_times(c, b, b.t0.as<double>(), c->v1.as<double>()));
-        continue;
-      }
-      LRN_TRY(wmw(c, b, b.Rd.as<double>(), b.t1.as<double>(), b.t2.as<double>()));
-      hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), 1.0, b.t2.as<double>(), 1.0,
-                         b.X.as<double>(), -sigma_mu, b.Si.as<double>(), mm_);
-      hipLaunchKernelGGL(lin3_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t2.as<double>(), 1.0, b.t0.as<double>(), -1.0,
-                         b.Qm.as<double>(), 0.0, (const double*)nullptr, mm_);
-      LRN_TRY(aa_times(c, b, b.t2.as<double>(), c->v1.as<double>()));
-      continue;
-    }
-    double* G = b.G.as<double>();
-    // t1 = G' Rd G
-    LRN_TRY(gemm_nn(c->stream, m, G, true, b.Rd.as<double>(), false, b.t0.as<double>()));
-    LRN_TRY(gemm_nn(c->stream, m, b.t0.as<double>(), false, G, false, b.t1.as<double>()));
-    hipLaunchKernelGGL(corr_inner_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t1.as<double>(), b.D.as<double>(),
-                       b.RNT.as<double>(), sigma_mu, b.t0.as<double>(), m);
-    // my_kron(G,G,inner) = vec(G inner G')
-    LRN_TRY(gemm_nn(c->stream, m, G, false, b.t0.as<double>(), false, b.t1.as<double>()));
-    LRN_TRY(gemm_nn(c->stream, m, b.t1.as<double>(), false, G, true, b.t2.as<double>()));
-    LRN_TRY(aa_times(c, b, b.t2.as<double>(), c->v1.as<double>()));
+    Blk v;
+    LRN_TRY(block_view(c, b, &v));
+    if (!b.nt_free) LRN_TRY(rhs_corr_svd(c, v, sigma_mu));
+    else if (wmw_pattern_ok(c, b)) LRN_TRY(rhs_corr_eigenfree_pattern(c, v, sigma_mu));
+    else LRN_TRY(rhs_corr_eigenfree_full(c, v, sigma_mu));
   }
   toc(c, "rhs");
   return copy_out(c, out, c->v1.p, (size_t)n * 8);
@@ -534,76 +375,16 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
   PhaseTimer timer(c, c->profile);
   for (int il = 0; il < c->nlmi; ++il) {
     LmiBlock& b = c->lmi[il];
-    LRN_TRY(ensure_resident(c, b));
-    const int m = b.msz;
-    const long mm_ = (long)m * m;
-    const unsigned g = nb(mm_);
-    double *t0 = b.t0.as<double>(), *t1 = b.t1.as<double>(), *t2 = b.t2.as<double>();
-    double *G = b.G.as<double>(), *Gi = b.Gi.as<double>();
+    Blk v;
+    LRN_TRY(block_view(c, b, &v));
     // delS = Rd - mat(AA' dely)                                   (:252)
-    LRN_TRY(aat_to_mat(c, b, c->v0.as<double>(), t0));
-    hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, b.delS.as<double>(), 1.0, b.Rd.as<double>(), -1.0, t0,
-                       0.0, (const double*)nullptr, mm_);
+    LRN_TRY(aat_to_mat(c, b, c->v0.as<double>(), v.t0));
+    lin3(c->stream, v.delS, v.mm, 1.0, v.Rd, -1.0, v.t0);
     double lamX = 0.0, lamS = 0.0;
-    double* t3 = b.Xn.as<double>();          // free here: Xn / Sn are rebuilt by lrn_ip_update after the step lengths
-    if (b.nt_free) {
-      // everything in the L_X basis (prepw.hip::prepare_w_ns): Bs = L_X' dS L_X, T = Z Bs Z / c,
-      // TX = L_X^-1 dX L_X^-T = -I - T (+ sigma_mu K^-1 + R), dX = L_X TX L_X'                  (:253-257)
-      const unsigned gs = (unsigned)std::min<long>(1024, ((long)(m + 31) / 32) * ((m + 31) / 32));
-      LRN_TRY(pgemm_nt(c, c->stream, m, b.LXt.as<double>(), b.delS.as<double>(), t0, GEMM_KFROM_M));    // L_X' upper triangular
-      // (both second products are symmetric in exact arithmetic: from msz 1500 on the lower tiles + mirror, half the work;
-      // below, the full product and the average of the two triangles)
-      if (m >= BIG_TILE_MIN_N) {
-        LRN_TRY(pgemm_nt_sym(c, c->stream, m, t0, b.LXt.as<double>(), b.Bs.as<double>(), 1.0, GEMM_KFROM_N));
-      } else {
-        SlabSrc prod;
-        LRN_TRY(prod_slabs(c, c->stream, m, t0, b.LXt.as<double>(), t1, 1.0, GEMM_KFROM_N, &prod));
-        hipLaunchKernelGGL(symadd_kernel, dim3(gs), dim3(256), 0, c->stream, prod, m, 0.5, b.Bs.as<double>(), (const double*)nullptr,
-                           (double*)nullptr);
-      }
-      LRN_TRY(pgemm_nt(c, c->stream, m, b.Zh.as<double>(), b.Bs.as<double>(), t0));
-      if (m >= BIG_TILE_MIN_N) {
-        LRN_TRY(pgemm_nt_sym(c, c->stream, m, t0, b.Zh.as<double>(), t3, 1.0 / b.ns_c));
-      } else {
-        SlabSrc prod;
-        LRN_TRY(prod_slabs(c, c->stream, m, t0, b.Zh.as<double>(), t1, 1.0 / b.ns_c, 0, &prod));
-        hipLaunchKernelGGL(symadd_kernel, dim3(gs), dim3(256), 0, c->stream, prod, m, 0.5, t3, (const double*)nullptr, (double*)nullptr);
-      }
-      hipLaunchKernelGGL(tx_kernel, dim3(g), dim3(256), 0, c->stream, t3, sigma_mu / b.ns_c, b.Ki.as<double>(),
-                         predict ? (const double*)nullptr : b.RNT.as<double>(), b.TX.as<double>(), m);
-      LRN_TRY(pgemm_nt(c, c->stream, m, b.LXf.as<double>(), b.TX.as<double>(), t0, GEMM_KTO_M));        // L_X lower triangular
-      LRN_TRY(pgemm_nt_sym(c, c->stream, m, t0, b.LXf.as<double>(), b.delX.as<double>(), 1.0, GEMM_KTO_N));
-      // the scaled directions of the step-length rule are orthogonally similar to TX and T               (:263-285)
-      LRN_TRY(eigmin_certified_pair(c, b.TX.as<double>(), t3, m, &lamX, &lamS));
-      alpha[il] = lamX > -1e-6 ? 0.99 : std::min(1.0, -tau / lamX);
-      beta[il] = lamS > -1e-6 ? 0.99 : std::min(1.0, -tau / lamS);
-      continue;
-    }
-    // t2 = W delS W                                                (:253)
-    LRN_TRY(wmw(c, b, b.delS.as<double>(), t1, t2));
-    if (predict) {
-      // delX = mat(-X - W delS W)                                  (:255)
-      hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, t0, -1.0, b.X.as<double>(), -1.0, t2, 0.0,
-                         (const double*)nullptr, mm_);
-    } else {
-      // delX = mat(sigma_mu Si - X - W delS W + G RNT G')          (:257)
-      hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, t0, sigma_mu, b.Si.as<double>(), -1.0,
-                         b.X.as<double>(), -1.0, t2, mm_);
-      LRN_TRY(gemm_nn(c->stream, m, G, false, b.RNT.as<double>(), false, t1));
-      LRN_TRY(gemm_nn(c->stream, m, t1, false, G, true, t2));
-      hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, t0, 1.0, t0, 1.0, t2, 0.0, (const double*)nullptr, mm_);
-    }
-    sym_half(c->stream, t0, b.delX.as<double>(), m);
-    // step lengths: eigmin of DDsi-scaled G' delS G and Gi delX Gi'   (:263-291)
-    LRN_TRY(gemm_nn(c->stream, m, Gi, false, b.delX.as<double>(), false, t0));
-    LRN_TRY(gemm_nn(c->stream, m, t0, false, Gi, true, t1));
-    hipLaunchKernelGGL(scale_sym_kernel, dim3(g), dim3(256), 0, c->stream, t1, b.DDsi.as<double>(), t2, m);
-    LRN_TRY(gemm_nn(c->stream, m, G, true, b.delS.as<double>(), false, t0));
-    LRN_TRY(gemm_nn(c->stream, m, t0, false, G, false, t1));
-    hipLaunchKernelGGL(scale_sym_kernel, dim3(g), dim3(256), 0, c->stream, t1, b.DDsi.as<double>(), t3, m);
-    LRN_TRY(eigmin_certified_pair(c, t2, t3, m, &lamX, &lamS));
-    alpha[il] = lamX > -1e-6 ? 0.99 : std::min(1.0, -tau / lamX);
-    beta[il] = lamS > -1e-6 ? 0.99 : std::min(1.0, -tau / lamS);
+    if (b.nt_free) LRN_TRY(find_step_eigenfree(c, v, predict, sigma_mu, &lamX, &lamS));
+    else LRN_TRY(find_step_svd(c, v, predict, sigma_mu, &lamX, &lamS));
+    alpha[il] = step_length(lamX, tau);
+    beta[il] = step_length(lamS, tau);
   }
   timer.stop("find_step");
   return LRN_OK;
@@ -612,63 +393,29 @@ extern "C" int lrn_ip_find_step(lrn_ctx* c, int predict, double sigma_mu, double
 extern "C" int lrn_ip_update(lrn_ctx* c, int predict, const double* alpha, const double* beta, double* trXnSn) {
   if (!c || !alpha || !beta) return LRN_ERR_ARG;
   LRN_HIP(c, hipSetDevice(c->device));
-  std::vector<double> tr(c->nlmi, 0.0);
   LRN_TRY(ensure(c, c->redout, 64 * 8));
   for (int il = 0; il < c->nlmi; ++il) {
     LmiBlock& b = c->lmi[il];
-    LRN_TRY(ensure_resident(c, b));
-    const int m = b.msz;
-    const long mm_ = (long)m * m;
-    const unsigned g = nb(mm_);
-    double *t0 = b.t0.as<double>(), *t1 = b.t1.as<double>(), *t2 = b.t2.as<double>();
-    if (predict) {
-      hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, b.Xn.as<double>(), 1.0, b.X.as<double>(), alpha[il],
-                         b.delX.as<double>(), 0.0, (const double*)nullptr, mm_);
-      hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, b.Sn.as<double>(), 1.0, b.S.as<double>(), beta[il],
-                         b.delS.as<double>(), 0.0, (const double*)nullptr, mm_);
-      LRN_TRY(dot_dev(c, b.Xn.as<double>(), b.Sn.as<double>(), mm_, c->redout.as<double>() + il));
-      if (b.nt_free) {
-        // Qm = G RNT G' without the eigenvectors: N = L_X^-1 dX dS L_X = TX Bs, Yh R + R Yh = -(N Zh + Zh N') / c,
-        // Qm = L_X R L_X'
-        tic(c);
-        LRN_TRY(pgemm_nt(c, c->stream, m, b.TX.as<double>(), b.Bs.as<double>(), t0));              // N
-        SlabSrc prod;
-        LRN_TRY(prod_slabs(c, c->stream, m, t0, b.Zh.as<double>(), t1, 1.0, 0, &prod));            // N Zh
-        hipLaunchKernelGGL(symadd_kernel, dim3((unsigned)std::min<long>(1024, ((long)(m + 31) / 32) * ((m + 31) / 32))), dim3(256), 0,
-                           c->stream, prod, m, -1.0 / b.ns_c, t2, (const double*)nullptr, (double*)nullptr);
-        bool ok = false;
-        int steps = 0;
-        LRN_TRY(lyap_solve(c, b, t2, b.RNT.as<double>(), t0, &ok, &steps));
-        c->counts["lyap_steps"] += steps;
-        c->counts["lyap_solves"] += 1;
-        if (ok) {
-          LRN_TRY(pgemm_nt(c, c->stream, m, b.LXf.as<double>(), b.RNT.as<double>(), t0, GEMM_KTO_M));
-          LRN_TRY(pgemm_nt_sym(c, c->stream, m, t0, b.LXf.as<double>(), b.Qm.as<double>(), 1.0, GEMM_KTO_N));
-          toc(c, "lyap");
-          continue;
-        }
-        // the Lyapunov iteration did not converge (K far from well conditioned): take the SVD for this iteration
-        toc(c, "lyap");
-        c->counts["lyap_fallback"] += 1;
-        int info = 0;
-        LRN_TRY(prepare_w_block(c, b, &info));
-        if (info != 0) return set_error(c, LRN_ERR_STATE, "SVD fallback of the NT scaling failed (info %d)", info);
-        b.nt_free = false;
-      }
-      // RNT = -(Gi delX delS G + its transpose) ./ (D_i + D_j)     (:308-309)
-      LRN_TRY(gemm_nn(c->stream, m, b.Gi.as<double>(), false, b.delX.as<double>(), false, t0));
-      LRN_TRY(gemm_nn(c->stream, m, t0, false, b.delS.as<double>(), false, t1));
-      LRN_TRY(gemm_nn(c->stream, m, t1, false, b.G.as<double>(), false, t2));
-      hipLaunchKernelGGL(rnt_kernel, dim3(g), dim3(256), 0, c->stream, t2, b.D.as<double>(), b.RNT.as<double>(), m);
-    } else {
-      b.chol_valid = false;
-      hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, t0, 1.0, b.X.as<double>(), alpha[0],
-                         b.delX.as<double>(), 0.0, (const double*)nullptr, mm_);
-      sym_half(c->stream, t0, b.X.as<double>(), m);
-      hipLaunchKernelGGL(lin3_kernel, dim3(g), dim3(256), 0, c->stream, t0, 1.0, b.S.as<double>(), beta[0],
-                         b.delS.as<double>(), 0.0, (const double*)nullptr, mm_);
-      sym_half(c->stream, t0, b.S.as<double>(), m);
+    Blk v;
+    LRN_TRY(block_view(c, b, &v));
+    if (!predict) {
+      take_step(c, v, alpha[0], beta[0]);
+      continue;
     }
+    LRN_TRY(predict_point(c, v, alpha[il], beta[il], c->redout.as<double>() + il));
+    if (b.nt_free) {
+      bool ok = false;
+      LRN_TRY(second_order_eigenfree(c, v, &ok));
+      if (ok) continue;
+      // take the SVD for this iteration
+      c->counts["lyap_fallback"] += 1;
+      int info = 0;
+      LRN_TRY(prepare_w_block(c, b, &info));
+      if (info != 0) return set_error(c, LRN_ERR_STATE, "SVD fallback of the NT scaling failed (info %d)", info);
+      b.nt_free = false;
+      LRN_TRY(block_view(c, b, &v));          // (the arrays of the SVD route are final only now)
+    }
+    LRN_TRY(second_order_svd(c, v));
   }
   if (predict && trXnSn && c->nlmi > 0) LRN_TRY(copy_out(c, trXnSn, c->redout.p, (size_t)c->nlmi * 8));
   LRN_HIP(c, hipGetLastError());
@@ -680,13 +427,12 @@ extern "C" int lrn_ip_stats(lrn_ctx* c, double* out5) {
   LRN_HIP(c, hipSetDevice(c->device));
   LRN_TRY(ensure(c, c->redout, (size_t)std::max(64, 5 * c->nlmi) * 8));
   for (int il = 0; il < c->nlmi; ++il) {
-    LmiBlock& b = c->lmi[il];
-    LRN_TRY(ensure_resident(c, b));
-    const long mm_ = (long)b.msz * b.msz;
+    Blk v;
+    LRN_TRY(block_view(c, c->lmi[il], &v));
     double* o = c->redout.as<double>() + 5 * il;
-    LRN_TRY(dot_dev(c, b.X.as<double>(), b.S.as<double>(), mm_, o + 0));
-    LRN_TRY(dot_dev(c, b.Rd.as<double>(), nullptr, mm_, o + 3));
-    LRN_TRY(dot_dev(c, b.Cd.as<double>(), b.X.as<double>(), mm_, o + 4));
+    LRN_TRY(dot_dev(c, v.X, v.S, v.mm, o + 0));
+    LRN_TRY(dot_dev(c, v.Rd, nullptr, v.mm, o + 3));
+    LRN_TRY(dot_dev(c, v.Cd, v.X, v.mm, o + 4));
   }
   LRN_TRY(copy_out(c, out5, c->redout.p, (size_t)5 * c->nlmi * 8));
   for (int il = 0; il < c->nlmi; ++il) {
@@ -707,96 +453,5 @@ extern "C" int lrn_ip_stats(lrn_ctx* c, double* out5) {
     out5[5 * il + 2] = ls;
     out5[5 * il + 3] = std::sqrt(out5[5 * il + 3]);
   }
-  return LRN_OK;
-}
-
-extern "C" int lrn_dbg_get_block(lrn_ctx* c, int il, const char* name, double* out, int* flag) {
-  if (!c || il < 0 || il >= c->nlmi || !name || !out) return LRN_ERR_ARG;
-  LRN_HIP(c, hipSetDevice(c->device));
-  LmiBlock& b = c->lmi[il];
-  const size_t mm_ = (size_t)b.msz * b.msz * 8, mv = (size_t)b.msz * 8;
-  struct { const char* n; DBuf* d; size_t bytes; } tab[] = {
-      {"W", &b.W, mm_}, {"Si", &b.Si, mm_}, {"G", &b.G, mm_}, {"Gi", &b.Gi, mm_}, {"D", &b.D, mv}, {"DDsi", &b.DDsi, mv},
-      {"X", &b.X, mm_}, {"S", &b.S, mm_}, {"delX", &b.delX, mm_}, {"delS", &b.delS, mm_}, {"RNT", &b.RNT, mm_},
-      {"LX", &b.LXf, mm_}, {"LS", &b.LSf, mm_}, {"Bs", &b.Bs, mm_}, {"TX", &b.TX, mm_}, {"Ki", &b.Ki, mm_}, {"Yh", &b.Yh, mm_},
-      {"Zh", &b.Zh, mm_}, {"Qm", &b.Qm, mm_}, {"Rd", &b.Rd, mm_}};
-  if (flag) *flag = b.nt_free ? 1 : 0;
-  c->timing["ns_c"] = b.ns_c;
-  for (auto& t : tab)
-    if (!strcmp(name, t.n)) {
-      if (!t.d->p || t.d->bytes < t.bytes) return set_error(c, LRN_ERR_STATE, "block array %s not allocated", name);
-      return copy_out(c, out, t.d->p, t.bytes);
-    }
-  return set_error(c, LRN_ERR_ARG, "unknown block array %s", name);
-}
-
-extern "C" int lrn_dbg_eigmin(lrn_ctx* c, int n, const double* M, double* lam, int* steps) {
-  if (!c || n <= 0 || !M || !lam) return LRN_ERR_ARG;
-  LRN_HIP(c, hipSetDevice(c->device));
-  DBuf d;
-  LRN_TRY(ensure(c, d, (size_t)n * n * 8));
-  LRN_TRY(copy_in(c, d.p, M, (size_t)n * n * 8));
-  int rc = steps ? eigmin_dev(c, d.as<double>(), n, lam, steps) : eigmin_certified(c, d.as<double>(), n, lam);
-  release(d);
-  return rc;
-}
-
-// ---- builder-defined synthetic problem on top of lrn_synthetic_dense_model
-namespace lrn {
-__global__ void synth_x0_kernel(double* __restrict__ X, const double* __restrict__ Q, int n, int r) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    int i = (int)(e % n), j = (int)(e / n);
-    double s = 0.0;
-    for (int k = 0; k < r; ++k) s += Q[i + (long)k * n] * Q[j + (long)k * n];
-    X[e] = s / n + (i == j ? 1.0 : 0.0);
-  }
-}
-__global__ void eye_add_kernel(double* __restrict__ out, const double* __restrict__ M, double sgn, int n) {
-  long total = (long)n * n;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x)
-    out[e] = sgn * M[e] + ((int)(e % n) == (int)(e / n) ? 1.0 : 0.0);
-}
-}  // namespace lrn
-
-extern "C" int lrn_synthetic_dense_problem(lrn_ctx* c, uint64_t seed, double* b_out, double* y0_out, double* normC) {
-  if (!c || c->nlmi != 1 || !b_out || !y0_out) return LRN_ERR_ARG;
-  LRN_HIP(c, hipSetDevice(c->device));
-  LmiBlock& b = c->lmi[0];
-  LRN_TRY(ensure_resident(c, b));
-  const int m = b.msz, n = c->nvar;
-  const long mm_ = (long)m * m;
-  // host-side small random factors (deterministic LCG-free: splitmix64 + Box-Muller)
-  auto next = [&seed]() {
-    seed += 0x9E3779B97F4A7C15ull;
-    uint64_t z = seed;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  };
-  auto unif = [&]() { return ((double)(next() >> 11) + 0.5) / 9007199254740992.0; };
-  auto gauss = [&]() { return std::sqrt(-2.0 * std::log(unif())) * std::cos(6.283185307179586 * unif()); };
-  const int r = 8;
-  std::vector<double> Q((size_t)m * r), y0(n);
-  for (auto& v : Q) v = gauss();
-  for (auto& v : y0) v = gauss() / std::sqrt((double)n);
-  LRN_TRY(copy_in(c, b.t1.p, Q.data(), Q.size() * 8));
-  hipLaunchKernelGGL(synth_x0_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.t0.as<double>(), b.t1.as<double>(), m, r);
-  // b = AA vec(X0)
-  LRN_HIP(c, hipMemsetAsync(c->v1.p, 0, (size_t)n * 8, c->stream));
-  LRN_TRY(aa_times(c, b, b.t0.as<double>(), c->v1.as<double>()));
-  LRN_TRY(copy_out(c, b_out, c->v1.p, (size_t)n * 8));
-  // C = I + mat(AA' y0)
-  LRN_TRY(copy_in(c, c->v0.p, y0.data(), (size_t)n * 8));
-  LRN_TRY(aat_to_mat(c, b, c->v0.as<double>(), b.t0.as<double>()));
-  hipLaunchKernelGGL(eye_add_kernel, dim3(nb(mm_)), dim3(256), 0, c->stream, b.Cd.as<double>(), b.t0.as<double>(), 1.0, m);
-  if (normC) {
-    LRN_TRY(ensure(c, c->redout, 64 * 8));
-    LRN_TRY(dot_dev(c, b.Cd.as<double>(), nullptr, mm_, c->redout.as<double>()));
-    double s = 0;
-    LRN_TRY(copy_out(c, &s, c->redout.p, 8));
-    *normC = std::sqrt(s);
-  }
-  memcpy(y0_out, y0.data(), (size_t)n * 8);
   return LRN_OK;
 }

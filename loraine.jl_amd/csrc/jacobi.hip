@@ -15,6 +15,7 @@
 
 #include "ctx.h"
 #include "jacobi.h"
+#include "reduce.h"
 
 namespace lrn {
 
@@ -26,16 +27,6 @@ __device__ __forceinline__ void rr_pair(int np, int round, int k, int* p, int* q
   else { a = (round + k) % m; b = (round - k + m) % m; }
   *p = a < b ? a : b;
   *q = a < b ? b : a;
-}
-
-__device__ __forceinline__ double block_sum256(double v, double* sh) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
 // whole SVD in one workgroup, n <= JAC_SMALL
@@ -590,7 +581,7 @@ __global__ __launch_bounds__(256) void colnorm_kernel(const double* __restrict__
   const double* a = A + (long)blockIdx.x * n;
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += a[i] * a[i];
-  s = block_sum256(s, sh);
+  s = wg_sum<4>(s, sh);
   if (threadIdx.x == 0) sig[blockIdx.x] = sqrt(s);
 }
 

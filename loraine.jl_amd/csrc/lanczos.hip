@@ -13,6 +13,7 @@
 
 #include "lz.h"
 #include "ops.h"
+#include "reduce.h"
 #include "tridiag.h"
 
 namespace lrn {
@@ -35,17 +36,6 @@ __global__ __launch_bounds__(256) void lx_symv_part_kernel(const double* __restr
   ypart[(long)blockIdx.y * n + i] = s;
 }
 
-__device__ __forceinline__ double lx_wg_sum(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < 16; ++i) s += sh[i];
-  return s;
-}
-
 // w = sum ypart ; alpha = q_j . w ; w -= alpha q_j + beta_prev q_{j-1}
 __global__ __launch_bounds__(1024) void lx_alpha_kernel(const double* __restrict__ ypart, int nchunk, int n, int j,
                                                         const double* __restrict__ Q, double* __restrict__ w,
@@ -62,7 +52,7 @@ __global__ __launch_bounds__(1024) void lx_alpha_kernel(const double* __restrict
     w[i] = s;
     a += q[i] * s;
   }
-  a = lx_wg_sum(a, sh);
+  a = wg_sum<16>(a, sh);
   for (int i = t; i < n; i += 1024) w[i] -= a * q[i] + (qp ? bprev * qp[i] : 0.0);
   if (t == 0) ab[2 * j] = a;
 }
@@ -74,11 +64,8 @@ __global__ __launch_bounds__(256) void lx_qtw_kernel(const double* __restrict__ 
   const double* col = Q + (long)blockIdx.x * n;
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += col[i] * w[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) cvec[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  s = wg_sum<4>(s, sh);
+  if (threadIdx.x == 0) cvec[blockIdx.x] = s;
 }
 
 // w -= Q[:, 0..nc) c
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(1024) void lx_norm_kernel(double* __restrict__ Q, i
   double* dst = Q + (long)(j + 1) * n;
   double s = 0.0;
   for (int i = t; i < n; i += 1024) s += src[i] * src[i];
-  s = lx_wg_sum(s, sh);
+  s = wg_sum<16>(s, sh);
   double b = sqrt(s);
   double r = b > 0.0 ? 1.0 / b : 0.0;
   for (int i = t; i < n; i += 1024) dst[i] = src[i] * r;
@@ -111,11 +98,8 @@ __global__ __launch_bounds__(256) void lx_trace_kernel(const double* __restrict_
   __shared__ double sh[4];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) s += M[(long)i * n + i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = sh[0] + sh[1] + sh[2] + sh[3];
+  s = wg_sum<4>(s, sh);
+  if (threadIdx.x == 0) *out = s;
 }
 
 // ---- host-side tridiagonal helpers

@@ -13,6 +13,7 @@
 
 #include "lz.h"
 #include "ops.h"
+#include "reduce.h"
 #include "tridiag.h"
 
 namespace lrn {
@@ -36,17 +37,6 @@ __global__ __launch_bounds__(256) void symv_part_kernel(const double* __restrict
   ypart[(long)blockIdx.y * n + i] = s;
 }
 
-__device__ __forceinline__ double wg_sum1024b(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < 16; ++i) s += sh[i];
-  return s;
-}
-
 // one Lanczos step (no re-orthogonalisation): w = sum ypart; a = q.w; w -= a q + b_prev q_prev;
 // b = ||w||; q_next = w / b.   j == -1: just normalise q in place (start vector).
 __global__ __launch_bounds__(1024) void lz_step_kernel(const double* __restrict__ ypart, int nchunk, int n, int j,
@@ -57,7 +47,7 @@ __global__ __launch_bounds__(1024) void lz_step_kernel(const double* __restrict_
   if (j < 0) {
     double s = 0.0;
     for (int i = t; i < n; i += 1024) s += q[i] * q[i];
-    s = wg_sum1024b(s, sh);
+    s = wg_sum<16>(s, sh);
     double r = 1.0 / sqrt(s);
     for (int i = t; i < n; i += 1024) { q[i] *= r; qprev[i] = 0.0; }
     return;
@@ -70,14 +60,14 @@ __global__ __launch_bounds__(1024) void lz_step_kernel(const double* __restrict_
     w[i] = s;
     a += q[i] * s;
   }
-  a = wg_sum1024b(a, sh);
+  a = wg_sum<16>(a, sh);
   double b2 = 0.0;
   for (int i = t; i < n; i += 1024) {
     double v = w[i] - a * q[i] - bprev * qprev[i];
     w[i] = v;
     b2 += v * v;
   }
-  b2 = wg_sum1024b(b2, sh);
+  b2 = wg_sum<16>(b2, sh);
   double b = sqrt(b2);
   double r = b > 0.0 ? 1.0 / b : 0.0;
   for (int i = t; i < n; i += 1024) {

@@ -1,5 +1,6 @@
 // Device-side operations shared between translation units: the data operators (dataops.hip), the NT scaling (prepw.hip),
-// the n x n products (products.hip), the Lanczos searches (lz.hip), the parts of the Schur assembly and a few helper launches.
+// the n x n products (products.hip) and helpers (matops.hip), the Lyapunov solve (lyap.hip), the Lanczos searches (lz.hip)
+// and the parts of the Schur assembly.
 #pragma once
 #include "ctx.h"
 namespace lrn {
@@ -19,6 +20,7 @@ int matvec_dev(lrn_ctx* c, const double* x, double* y);                     // y
 int matvec_partial_dev(lrn_ctx* c, const double* x, double* y, int rank, int world);   // the rows of Z of one rank; the caller all-reduces
 int lin_matvec(lrn_ctx* c, const double* x, double* y);                     // y += C_lin diag(xs) C_lin' x
 void lin_diag(lrn_ctx* c, double* d);                                       // d_i += sum_l C_lin[i,l]^2 xs_l
+// ---- prepw.hip
 int prepare_w_block(lrn_ctx* c, LmiBlock& b, int* info);                    // NT scaling from b.X, b.S (SVD route)
 // eigen-free NT scaling from b.X, b.S: W, Si, the Cholesky factors and K^(+-1/2); *converged = false: nothing usable, take
 // the SVD route
@@ -108,11 +110,33 @@ int aa_times_diag(lrn_ctx* c, LmiBlock& b, const double* Z, double* y);      // 
 int aat_to_mat_diag(lrn_ctx* c, LmiBlock& b, const double* x, double* M);    // M_ii -= sum_s x[nat(s)] a_si
 // ts of H_alpha (option "cg_diag"): ts[nat(s), a m + r] -= sum_i a_si Um[i, a] L[i, r] / sqrt(d[nat(s)]), added to the factor part
 int ts_diag(lrn_ctx* c, LmiBlock& b, const double* Lf, const double* Um, int erank, const double* d, double* ts);
-void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I (ipstep.hip)
-// out = scale (T + T') from T or its slabs by `grid` workgroups; dotp: part[0 .. grid) = partial sums of <dotp, out> (ipstep.hip)
-void symadd(hipStream_t st, unsigned grid, const SlabSrc& T, int n, double scale, double* out, const double* dotp, double* part);
-// n x n helpers (prepw.hip)
+// ---- matops.hip: passes over n x n matrices (column-major) on stream st, and the two-stage dot product
+void tril(hipStream_t st, double* A, int n);                               // strict upper triangle <- 0
 void eye_mat(hipStream_t st, double* V, int n);                            // V = I
 void mirror_lower(hipStream_t st, double* A, int n);                       // upper triangle <- lower triangle, in place
 void transpose_mat(hipStream_t st, const double* A, int n, double* B);     // B = A'
+void scale_cols(hipStream_t st, const double* A, const double* d, int n, int mode, double* B);   // B[:,j] = A[:,j] d_j^p, p = -1/2, 1/2, -1 for mode 0, 1, 2
+void coldot_rsqrt(hipStream_t st, const double* A, const double* B, int n, double* out);         // out_j = 1 / sqrt(A[:,j] . B[:,j])
+void add_diag_mat(hipStream_t st, double* M, int n, double eps);           // M += eps I
+// out = a A + b B + c C over n elements (null pointers skipped)
+void lin3(hipStream_t st, double* out, long n, double a, const double* A, double b, const double* B, double c = 0.0,
+          const double* C = nullptr);
+void sym_half(hipStream_t st, const double* M, double* out, int n);        // out = (M + M') / 2, out != M
+void scale_sym(hipStream_t st, const double* M, const double* dd, double* out, int n);           // out = sym(dd_i M_ij dd_j)
+unsigned sym_grid(int n);                                                  // workgroups of a pass by 32 x 32 tile pairs (symadd)
+// out = scale (T + T') from T or its slabs by `grid` workgroups; dotp: part[0 .. grid) = partial sums of <dotp, out>
+void symadd(hipStream_t st, unsigned grid, const SlabSrc& T, int n, double scale, double* out, const double* dotp, double* part);
+// out = alpha A Bm' for a product that is symmetric in exact arithmetic, exactly symmetric on either side of BIG_TILE_MIN_N:
+// lower tiles + mirror from there on, below it the average of the two triangles of the full product (work: its slabs)
+int sym_product(lrn_ctx* c, hipStream_t st, int n, const double* A, const double* Bm, double* work, double* out, double alpha,
+                int tri);
+// *out = sum A .* B (B null: A .* A) over n elements, in two launches through dot_parts_count(n) partial sums
+int dot_parts_count(long n);
+void dot_via(hipStream_t st, const double* A, const double* B, long n, double* part, double* out);
+int dot_dev(lrn_ctx* c, const double* A, const double* B, long n, double* out_dev);      // ... on c->stream through c->redbuf
+// ---- lyap.hip: R with Yh R + R Yh = Cm for the block's Yh (Zh beside it, option lyap_form) by CG; Cm is destroyed, work:
+// msz^2 doubles; *ok = false: not converged within lyap_maxit steps
+int lyap_solve(lrn_ctx* c, LmiBlock& b, double* Cm, double* R, double* work, bool* ok, int* steps);
+// ---- ipstep.hip
+int ensure_resident(lrn_ctx* c, LmiBlock& b);                              // the arrays of the resident IP step of a block exist
 }  // namespace lrn

@@ -3,6 +3,7 @@
 // split-K slabs of a mid-size product while they transpose or symmetrise it.
 #include "ctx.h"
 #include "ops.h"
+#include "reduce.h"
 
 namespace lrn {
 
@@ -113,11 +114,8 @@ __global__ __launch_bounds__(256) void slabs_sym_kernel(SlabSrc src, int n, doub
     }
   }
   if (!T || !part) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  acc = wg_sum<4>(acc, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 // The same from slabs that hold only the LOWER 64-tiles of the product (rows i, columns j with i / 64 >= j / 64; gemm_slabs
@@ -170,11 +168,8 @@ __global__ __launch_bounds__(256) void slabs_symlow_kernel(SlabSrc src, int n, d
     }
   }
   if (!T || !part) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  acc = wg_sum<4>(acc, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 // C = (S + S') / 2 of S = alpha A Bm' from its split-K slabs -- the lower 64-tiles alone where gemm_slabs provides them, else the

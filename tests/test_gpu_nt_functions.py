@@ -191,7 +191,7 @@ def test_one_iteration_function_by_function_on_ill_conditioned_iterates(dev, con
 @pytest.mark.parametrize("nt_mode", [1, 0])
 def test_one_iteration_function_by_function_at_the_size_of_the_128_tile_kernels(dev, nt_mode):
     """msz 1536: from 1500 on the products with the Cholesky factors (L_X' dS L_X, L_X TX L_X', L_X Z L_X', L_S^-T L_S^-1)
-    run on the 128-tile kernel over the triangular K ranges only (csrc/prepw.hip::pgemm_nt, round 4), and P = Z Y of the
+    run on the 128-tile kernel over the triangular K ranges only (csrc/products.hip::pgemm_nt, round 4), and P = Z Y of the
     Newton-Schulz iteration as lower tiles + mirror."""
     m, nvar = 1536, 6
     rng = np.random.default_rng(2)
@@ -226,9 +226,9 @@ def _run(path, device, **opts):
 @pytest.mark.parametrize("name,opts", [("theta1", dict(kit=0, eDIMACS=1e-6, initpoint=1)), ("control1", dict(kit=0, eDIMACS=1e-6))])
 @pytest.mark.parametrize("knob,value,counter", [("ns_maxit", 4, "ns_fallback"), ("lyap_maxit", 3, "lyap_fallback")])
 def test_forced_fallbacks_keep_the_oracle_trajectory(dev, name, opts, knob, value, counter):
-    """`ns_maxit = 4`: Newton-Schulz cannot converge -> the SVD route runs for the iteration (prepw.hip `ns_fallback`).
+    """`ns_maxit = 4`: Newton-Schulz cannot converge -> the SVD route runs for the iteration (prepw.hip::prepare_w_ns, counter `ns_fallback`).
     `lyap_maxit = 3`: the Lyapunov CG of the second-order term gives up -> the SVD quantities are formed in the middle of
-    the iteration, after the predictor's directions came from the other route (ipstep.hip `lyap_fallback`).  Both must
+    the iteration, after the predictor's directions came from the other route (lyap.hip::lyap_solve gives up, ipstep.hip::lrn_ip_update counts `lyap_fallback`).  Both must
     leave the per-iteration trace within 1e-8 of the oracle's."""
     path = os.path.join(GOLD, f"{name}.dat-s")
     ref = lo.MySolver(lo.model_from_sdpa(path), dict(opts, verb=0))
@@ -306,3 +306,40 @@ def test_both_forms_of_the_lyapunov_equation_give_the_same_solve(dev, name, opts
         assert a == pytest.approx(b, rel=1e-9, abs=1e-10)
     print(name, "Lyapunov CG steps per solve:", runs[0][2], "->", runs[1][2])
     assert runs[1][2] < runs[0][2]
+
+
+def _well_conditioned_spd(m, seed):
+    A = np.random.default_rng(seed).standard_normal((m, m))
+    return A @ A.T / m + np.eye(m)
+
+
+@pytest.mark.parametrize("streams", [1, 0])
+@pytest.mark.parametrize("nt_mode", [1, 0])
+@pytest.mark.parametrize("m", [20, 150])
+def test_not_pd_verdicts_on_both_routes(dev, m, nt_mode, streams):
+    """The verdict of the two Cholesky factorisations that open the NT scaling (csrc/prepw.hip::factor_pair, shared by the
+    eigen-free and the SVD route), through `ip_set_iterate` + `ip_prepare_w`: X not positive definite -> info 1, S -> 2,
+    both -> 1 (the reference's order, prepare_W.jl:33-34).  msz 20: one Cholesky panel, Jacobi in one workgroup; msz 150:
+    above CHOL_NB = 64 and JAC_SMALL = 96 (blocked factorisation, multi-workgroup SVD).  The good pair on the SAME context
+    afterwards gives info 0 and W S W = X on the route that was asked for: a refused factorisation leaves no stale
+    `chol_valid` and no stream still writing the scratch."""
+    A = [[sp.csc_matrix((m, m)), sp.identity(m, format="csc")]]
+    model = lo.make_model(A, np.ones(1), 0.0, None, None)
+    X, S = _well_conditioned_spd(m, 1), _well_conditioned_spd(m, 2)
+    Xb = X.copy(); Xb[3, 3] = -1.0
+    Sb = S.copy(); Sb[7, 7] = -1.0
+    dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes)
+    dev.set_option("nt_mode", nt_mode)
+    dev.set_option("prepw_streams", streams)
+    try:
+        for Xi, Si, want in ((Xb, S, 1), (X, Sb, 2), (Xb, Sb, 1), (X, S, 0)):
+            dev.ip_set_iterate(0, Xi, Si)
+            assert dev.ip_prepare_w(0) == want
+        W, flag = dev.dbg_get_block(0, "W")
+    finally:
+        dev.set_option("nt_mode", 1)
+        dev.set_option("prepw_streams", 1)
+    err = relerr(W @ S @ W, X)
+    print(f"msz {m} nt_mode={nt_mode} prepw_streams={streams}: verdicts 1 2 1 0, relerr(W S W, X) = {err:.1e}, route flag {flag}")
+    assert flag == nt_mode
+    assert err < 1e-10

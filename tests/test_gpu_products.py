@@ -1,4 +1,4 @@
-"""The n x n product layer (csrc/products.hip, symadd of csrc/ipstep.hip) and the triangular-K ranges of the GEMM
+"""The n x n product layer (csrc/products.hip, symadd of csrc/matops.hip) and the triangular-K ranges of the GEMM
 (GEMM_KFROM_M/_N, GEMM_KTO_M/_N, GEMM_C_MIRROR) by themselves, through lrn_dbg_gemm and lrn_dbg_product.
 
 Why the inputs are integers.  Operands hold integers from {-3 .. 3} and alpha is 1 or 0.5, so with K <= 1502 every partial

@@ -1,5 +1,5 @@
 """CPU: the mathematics of the eigen-free NT scaling (csrc/prepw.hip::prepare_w_ns,
-csrc/ipstep.hip) restated in NumPy (tools/nt_eigenfree_proto.py) against the oracle's SVD route
+csrc/ipstep.hip, csrc/lyap.hip) restated in NumPy (tools/nt_eigenfree_proto.py) against the oracle's SVD route
 (src/prepare_W.jl:28-94, src/predictor_corrector.jl:186,248-326): whole solves must walk the same iterates.  Also the
 stability property the device code depends on: the coupled Newton-Schulz iteration is stable only with its products
 taken literally."""

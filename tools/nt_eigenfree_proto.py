@@ -101,7 +101,7 @@ def makeBBBB_rank1(n, nlmi, B, G_unused, solver=None):
 
 
 def find_step(solver):
-    """Everything in the L_X basis, as ipstep.hip does it (no inverse of L_X anywhere)."""
+    """Everything in the L_X basis, as ipstep.hip::find_step_eigenfree does it (no inverse of L_X anywhere)."""
     m = solver.model
     for i in range(m.nlmi):
         LX, Z = solver._LX[i], solver._Z[i]
