@@ -103,6 +103,29 @@ int lrn_set_factored(lrn_ctx* ctx, int ilmi, int on);
  * "schur_diag" (assemblies of a block with diagonal rows), "diag_sq_rows" / "diag_sq_mfma" (squared-operand products by form),
  * "diag_stored_cross" (cross terms with stored rows); timing keys under "profile": "diag_dd", "diag_cross", "diag_stored". */
 int lrn_upload_diag(lrn_ctx* ctx, int ilmi, int64_t nrows, const int64_t* rows, const double* a);
+/* Low-rank detection: which of `cnt` dense symmetric m x m matrices (A: one after the other, column-major, host or device)
+ * are V diag(d) V' with at most kmax (16 or 64) columns, and their factors -- what a caller that holds matrices needs to reach
+ * lrn_upload_lowrank / lrn_set_factored.  Symmetric Nystrom identity with the caller's sketch matrix omega (m x l, l = kmax + 8,
+ * column-major, e.g. standard normals): Y = A omega, C = omega' Y = U Lambda U' (batched two-sided Jacobi in LDS, one workgroup
+ * per matrix), V = Y U_r |Lambda_r|^-1/2, d = sign Lambda_r over the r eigenvalues with |lambda| > rank_rtol max|lambda|.
+ * Per matrix k: rank_out[k] = r >= 0, or -1 for "not of rank <= kmax within tol"; resid_out[k] = the computed
+ * ||A_k - V_k D_k V_k'||_F (FP64 MFMA over 64 x 64 tiles, fixed summation order) -- of the factor returned, so ||A_k||_F for a
+ * matrix rejected on its eigenvalue count, for which no factor is formed; V_out: cnt x (m x kmax, column-major), columns >= r
+ * zero; d_out: cnt x kmax, +-1, zero in the padding.  The residual is the arbiter: rank_out[k] = r only if resid_out[k] <= tol
+ * (absolute), -1 otherwise (V_out, d_out then hold the factor that missed).  m >= 1 (m < l is legal), 1 <= cnt <= 65535.
+ * The result for a matrix depends on A_k and omega alone -- not on cnt, its place in the chunk or its neighbours -- and
+ * repeated calls agree bit for bit (no atomics).  Stateless with respect to the model: needs the context only, may be called
+ * before lrn_upload_model; the workspace (cnt m^2 + cnt m (kmax + l + 8) doubles and change, counted in "device_bytes") stays
+ * with the context until lrn_set_option("detect_release", 1) (any non-zero value; 0 does nothing) or lrn_destroy -- the
+ * caller chooses the chunk.  Symmetry of A is ASSUMED, not verified: the sketch reads all of A_k, the residual only its 64 x 64
+ * tiles on and below the diagonal (and counts the off-diagonal ones twice), so for an unsymmetric A_k -- one triangle alone,
+ * say -- resid_out is not ||A_k - V D V'||_F and the verdict is meaningless; the caller checks (the Python host does, in
+ * detect.detect_factors).
+ * lrn_get_count: "detect_calls", "detect_accepted", "detect_rejected" (matrices by verdict), "detect_sweeps_max" (most Jacobi
+ * sweeps any matrix took); timing keys under "profile": "detect" and its steps "detect_upload", "detect_sketch",
+ * "detect_core", "detect_eig", "detect_factor", "detect_resid". */
+int lrn_lowrank_detect(lrn_ctx* ctx, int m, int cnt, const double* A, int kmax, double tol, double rank_rtol,
+                       const double* omega, int32_t* rank_out, double* resid_out, double* V_out, double* d_out);
 /* Builder-defined synthetic dense SDP data generated on the device:
  * A_k = (R_k + R_k')/2, R_k iid N(0,1) from a counter-based Philox stream; nlmi = 1. */
 int lrn_synthetic_dense_model(lrn_ctx* ctx, int msz, int nvar, uint64_t seed);

@@ -90,6 +90,23 @@ function upload_diag!(ctx::Ctx, i::Integer, rows::Vector{Int64}, a::Matrix{Float
         ctx.h, i - 1, length(rows0), rows0, a), "lrn_upload_diag")
 end
 
+# ---- low-rank detection (what prep_B does for datarank = -1, for ranks up to kmax = 16 or 64): A is m x m x cnt, dense and
+# symmetric; omega an m x (kmax + 8) sketch matrix (randn).  -> rank (r >= 0, or -1: keep the matrix), resid = ||A - V D V'||_F,
+# V (m x kmax x cnt, columns beyond r zero), d (kmax x cnt, +-1).  Needs the context only: may run before upload_model!
+function lowrank_detect(ctx::Ctx, A::Array{Float64, 3}, kmax::Integer, omega::Matrix{Float64};
+                        tol::Float64 = 5.0e-6, rank_rtol::Float64 = 1.0e-12)
+    m, cnt = size(A, 1), size(A, 3)
+    rank = zeros(Cint, cnt)
+    resid = zeros(Float64, cnt)
+    V = zeros(Float64, m, kmax, cnt)
+    d = zeros(Float64, kmax, cnt)
+    check(ctx, ccall((:lrn_lowrank_detect, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Cint, Cdouble, Cdouble, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}),
+        ctx.h, m, cnt, A, kmax, tol, rank_rtol, omega, rank, resid, V, d), "lrn_lowrank_detect")
+    return rank, resid, V, d
+end
+
 # ---- prepare_W (src/prepare_W.jl:28-94) -------------------------------------------------------
 function prepare_W(ctx::Ctx, solver)
     for i in 1:solver.model.nlmi

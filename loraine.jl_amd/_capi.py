@@ -31,6 +31,8 @@ SIGNATURES = {
     "lrn_upload_lowrank": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrn_set_factored": (C.c_int, [c_ctx, C.c_int, C.c_int]),
     "lrn_upload_diag": (C.c_int, [c_ctx, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrn_lowrank_detect": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrn_synthetic_dense_model": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_uint64]),
     "lrn_synthetic_dense_problem": (C.c_int, [c_ctx, C.c_uint64, C.c_void_p, C.c_void_p, PD]),
     "lrn_get_constraint": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_void_p]),

@@ -10,6 +10,7 @@
 using namespace lrn;
 
 void lrn_free_model(lrn_ctx* c);
+void lrn_detect_free(lrn_ctx* c);
 
 extern "C" {
 
@@ -49,6 +50,7 @@ int lrn_destroy(lrn_ctx* c) {
   prec_free(c);
   comm_free(c);
   lrn_free_model(c);
+  lrn_detect_free(c);
   release(c->info_dev);
   release(c->scratch);
   release(c->jscratch);
@@ -165,6 +167,7 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "lyap_maxit")) c->opt.lyap_maxit = (int)value;
   else if (!strcmp(key, "lyap_form")) c->opt.lyap_form = (int)value;
   else if (!strcmp(key, "shard_bs")) { if (value < 0) return LRN_ERR_ARG; c->shard_bs_opt = (int)value; lrn::update_shard_bs(c); }
+  else if (!strcmp(key, "detect_release")) { if (value != 0.0) lrn_detect_free(c); }      // the workspace of lrn_lowrank_detect, before the model goes up (0: nothing)
   else if (!strcmp(key, "reset_timing")) { c->timing.clear(); c->counts.clear(); }
   else return set_error(c, LRN_ERR_ARG, "unknown option %s", key);
   return LRN_OK;

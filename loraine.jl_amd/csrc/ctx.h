@@ -291,6 +291,9 @@ struct lrn_ctx {
   lrn::DBuf scratch, jscratch, redbuf, redout, lzbuf, lzbuf2, lxbuf, ezbuf;
   lrn::DBuf triw;               // tri-weights of the matrices the dense passes multiply with (2 msz^2)
   lrn::DBuf commvec, commmat;   // multi-GPU: partial results of the sharded passes over dense constraint data
+  // lrn_lowrank_detect (detect.hip): the chunk of matrices (host input only), Omega, Y = A Omega, the factors V, and
+  // OmT | C | T | d | resid | tile sums | rank | sweeps in one buffer -- independent of the uploaded model
+  lrn::DBuf det_A, det_Om, det_Y, det_V, det_small;
   // preconditioner / CG state
   lrn::Prec* prec = nullptr;
   // multi-GPU communicator (comm.hip; lrn_comm_init / lrn_comm_init_host)

@@ -207,6 +207,31 @@ class Device:
             raise ValueError(f"diagonal parts of {a.shape[0]} entries, block {ilmi} has side {self.msizes[ilmi]}")
         self._chk(self.lib.lrn_upload_diag(self.h, int(ilmi), int(rows.size), ptr(rows), ptr(a)), "lrn_upload_diag")
 
+    def lowrank_detect(self, mats, kmax, tol=None, rank_rtol=1e-12, omega=None):
+        """Which of the dense symmetric matrices `mats` (cnt x m x m) are V diag(d) V' with at most kmax (16 or 64)
+        columns (csrc/detect.hip) -> (rank (cnt; -1 = keep the matrix), resid (cnt), V (cnt x m x kmax, unused columns zero),
+        d (cnt x kmax)).  omega: the m x (kmax + 8) sketch matrix, standard normals from Philox(0) when None; tol:
+        model.LOWRANK_TOL when None.  Needs no uploaded model."""
+        mats = np.ascontiguousarray(mats, dtype=np.float64)
+        if mats.ndim != 3 or mats.shape[1] != mats.shape[2]:
+            raise ValueError(f"lowrank_detect: mats is {mats.shape}, not cnt x m x m")
+        cnt, m = int(mats.shape[0]), int(mats.shape[1])
+        if tol is None:
+            from . import model
+            tol = model.LOWRANK_TOL
+        if omega is None:
+            omega = np.random.Generator(np.random.Philox(0)).standard_normal((m, int(kmax) + 8))
+        omega = f64(omega)
+        if omega.shape != (m, int(kmax) + 8):
+            raise ValueError(f"lowrank_detect: omega is {omega.shape}, not {(m, int(kmax) + 8)}")
+        rank = np.zeros(cnt, dtype=np.int32)
+        resid = np.zeros(cnt)
+        V = np.zeros((cnt, int(kmax), m))            # (each m x kmax, column-major)
+        d = np.zeros((cnt, int(kmax)))
+        self._chk(self.lib.lrn_lowrank_detect(self.h, m, cnt, ptr(mats), int(kmax), float(tol), float(rank_rtol), ptr(omega),
+                                              ptr(rank), ptr(resid), ptr(V), ptr(d)), "lrn_lowrank_detect")
+        return rank, resid, V.transpose(0, 2, 1), d
+
     def synthetic_dense_model(self, msz, nvar, seed):
         self._chk(self.lib.lrn_synthetic_dense_model(self.h, int(msz), int(nvar), C.c_uint64(seed)),
                   "lrn_synthetic_dense_model")

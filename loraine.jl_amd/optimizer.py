@@ -66,8 +66,17 @@ class Optimizer:
         return "Loraine"
 
     # ---- model input (copy_to, :142-232): options are frozen here, like in the reference (:224)
-    def read_from_file(self, path):
-        self._pending = ("sdpa", path)
+    def read_from_file(self, path, detect_kmax=None):
+        """detect_kmax = 16 or 64: the constraint matrices of the file go through load_detected_model(kmax=detect_kmax) with
+        its defaults; None (default): the file is loaded as it always was."""
+        if detect_kmax is None:
+            self._pending = ("sdpa", path)
+            return self
+        if not self.resident:
+            raise ValueError(self._NEEDS_RESIDENT)
+        if isinstance(detect_kmax, bool) or detect_kmax not in (16, 64):
+            raise ValueError(f"read_from_file: detect_kmax is None, 16 or 64, not {detect_kmax!r}")
+        self._pending = ("sdpa_detected", (path, dict(self._DETECT_DEFAULTS, kmax=int(detect_kmax))))
         return self
 
     def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factors=None):
@@ -113,8 +122,7 @@ class Optimizer:
         if not isinstance(wide, bool) and not (isinstance(wide, str) and wide == "diag"):
             raise ValueError(f"load_factored_model: wide is False or True (or \"diag\"), not {wide!r}")
         if not self.resident:
-            raise ValueError("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
-                             "multiplies by AA")
+            raise ValueError(self._NEEDS_RESIDENT)
         cg_diag = isinstance(cg, str) and cg == "diag"
         if isinstance(cg, str) and not cg_diag:
             raise ValueError(f"load_factored_model: cg is False, True or \"diag\", not {cg!r}")
@@ -125,6 +133,81 @@ class Optimizer:
                                       bool(cg)))
         return self
 
+    _NEEDS_RESIDENT = ("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
+                       "multiplies by AA")
+    _DETECT_DEFAULTS = dict(kmax=16, max_stored=16, cg=False, cg_diag=False, ragged=False, factored_form=-1, budget_mb=None,
+                            seed=0, host_side=None)
+
+    def load_detected_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, kmax=16, max_stored=16,
+                            cg=False, ragged=False, factored_form=-1, budget_mb=None, seed=0, host_side=None):
+        """The problem of load_model, given as matrices, solved as load_factored_model would solve it: every constraint matrix
+        that is V diag(d) V' with at most kmax columns becomes a factor, the others stay stored matrices beside them (hybrid
+        blocks).  The factors are found when the model goes to the device (detect.detect_factors: the device for dense
+        constraints, batched in chunks of budget_mb MiB; the host's eigh for supports of side <= host_side, default 96;
+        constraints of at most `datasparsity` non-zeros stay stored without a look), never by an eigh per dense constraint.
+        kmax: 16, or 64 (implies wide=True of load_factored_model: ranks 17 .. 64 become factors too).
+        cg, ragged, factored_form: as in load_factored_model, with the same checks (kit = 1 needs cg=True).
+        Fallback: the whole model takes the general path -- build_model, bit for bit what load_model does -- when no constraint
+        was accepted, or when some block would keep more than max_stored stored constraints with more than `datasparsity`
+        non-zeros; `detect_report` of the optimizer and `lowrank_note` of the model say which route was taken and why."""
+        if not self.resident:
+            raise ValueError(self._NEEDS_RESIDENT)
+        if isinstance(kmax, bool) or kmax not in (16, 64):
+            raise ValueError(f"load_detected_model: kmax is 16 or 64, not {kmax!r}")
+        if isinstance(max_stored, bool) or not isinstance(max_stored, (int, np.integer)) or max_stored < 0:
+            raise ValueError(f"load_detected_model: max_stored is a count >= 0, not {max_stored!r}")
+        cg_diag = isinstance(cg, str) and cg == "diag"
+        if isinstance(cg, str) and not cg_diag:
+            raise ValueError(f"load_detected_model: cg is False, True or \"diag\", not {cg!r}")
+        if isinstance(ragged, str) and ragged not in ("ops", "all"):
+            raise ValueError(f"load_detected_model: ragged is False, True, \"ops\" or \"all\", not {ragged!r}")
+        if factored_form not in (-1, 1):
+            raise ValueError(f"factored_form = {factored_form} (-1 auto, 1 always factored)")
+        if budget_mb is not None and not budget_mb > 0:
+            raise ValueError(f"load_detected_model: budget_mb is a size in MiB > 0 (or None), not {budget_mb!r}")
+        for name, v in (("host_side", host_side), ("seed", seed)):
+            if (v is not None or name == "seed") and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError(f"load_detected_model: {name} is a whole number{' (or None)' if name == 'host_side' else ''}, "
+                                 f"not {v!r}")
+        opts = dict(kmax=int(kmax), max_stored=int(max_stored), cg=bool(cg), cg_diag=cg_diag,
+                    ragged=ragged if isinstance(ragged, str) else bool(ragged), factored_form=int(factored_form),
+                    budget_mb=budget_mb, seed=int(seed), host_side=host_side)
+        self._pending = ("detected", ((A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense)), opts))
+        return self
+
+    def _detected_model(self, arrays, o, drank, kappa):
+        """Detection on the device, then build_factored_model exactly as load_factored_model would call it -- or build_model,
+        when the fallback rule says so."""
+        from . import detect
+        from .device import Device
+        A, b, b_const, d_lin, C_lin, max_sense = arrays
+        self.max_sense = max_sense
+        if self._device is None:
+            self._device = Device(self._device_index)
+        hs = detect.HOST_SIDE if o["host_side"] is None else int(o["host_side"])
+        items, report = detect.detect_factors(A, len(b), o["kmax"], self._device, budget_mb=o["budget_mb"], seed=o["seed"],
+                                              datasparsity=kappa, host_side=hs)
+        reason = detect.fallback_reason(report["accepted"], report["kept_nnz"], o["max_stored"], kappa)
+        report["route"] = "general" if reason else "factored"
+        report["reason"] = reason
+        self.detect_report = report
+        if reason:
+            model = build_model(A, b, b_const, d_lin, C_lin, datarank=drank, kappa=kappa)
+            note = f"load_detected_model: general path, {reason}"
+            model.lowrank_note = f"{model.lowrank_note}; {note}" if model.lowrank_note else note
+            return model
+        wide = o["kmax"] == 64
+        model = build_factored_model([blk[0] for blk in A], items, b, b_const, d_lin, C_lin, kappa=kappa,
+                                     factored_form=o["factored_form"], max_rank=64 if wide else 16, wide_diag=False)
+        model.factored_cg = o["cg"] and model.factored
+        model.factored_cg_diag = o["cg_diag"] and model.factored
+        model.ragged = o["ragged"] if model.factored else False
+        model.lowrank_note = (f"load_detected_model: {report['accepted']} constraints as factors of rank <= {o['kmax']}, "
+                              f"{sum(len(k) for k in report['kept_nnz'])} stored")
+        check_factored_kit(model, self.options.get("kit", 0))
+        check_diag_kit(model, self.options.get("kit", 0))
+        return model
+
     def _copy_to(self):
         kind, payload = self._pending
         drank = int(self.options.get("datarank", 0))
@@ -132,6 +215,12 @@ class Optimizer:
         if kind == "sdpa":
             model = model_from_sdpa(payload, datarank=drank, kappa=kappa)
             self.max_sense = False
+        elif kind == "sdpa_detected":
+            general = model_from_sdpa(payload[0], datarank=0, kappa=kappa)      # (the file's A, b, linear rows)
+            model = self._detected_model((general.A, general.b, general.b_const, general.d_lin, general.C_lin, False),
+                                         payload[1], drank, kappa)
+        elif kind == "detected":
+            model = self._detected_model(payload[0], payload[1], drank, kappa)
         elif kind == "factored":
             F0, factors, b, b_const, d_lin, C_lin, max_sense, form, ragged, wide, cg_diag, cg = payload
             self.max_sense = max_sense
