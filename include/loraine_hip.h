@@ -491,6 +491,27 @@ int lrn_dbg_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int 
  * split; shares3 = this rank's share of the useful work of GEMM1', GEMM2', GEMM3'. */
 int lrn_dbg_schur_chol_plan(int msz, int nd, int rank, int world, int64_t pcap_hint, const int* opts6, int64_t* out10, int* kb,
                             int* ke, int* weights, double* shares3);
+/* What lrn_upload_model lays out for one LMI block, its rank-one factors and the linear part (csrc/model_layout.h), on the host
+ * alone (no context, no device).  The arrays are the arguments of lrn_upload_model for one block: AA (nvar x msz^2 CSC, 1-based),
+ * sigma = the block's column of sigmaA (1-based), qA = its first entry of qA; pos_space = 1 for a model of one block; B and
+ * C_lin may be NULL (nlin = 0).  dense_threshold: the option of that name; free_bytes: what hipMemGetInfo would report.
+ * name: "sigma" "ipos" "nnz" "qA" "npos_nz" "nd" "q_wave" "ent_ptr" "ent_r" "ent_c" "ent_v" "hidx" "cq_q" "cq_ptr" "cq_j" "cq_v"
+ * "sp_ok" "pc_ptr" "pc_r" "pc_t" "ent_t" "sp_long_cols" | "b_ptr" "b_col" "b_val" | "cl_ptr" "cl_row" "cl_rown" "lp_r" "lp_c"
+ * "lp_ptr" "lp_l" "lp_w" "cr_ptr" "cr_col" "cr_val" (ctx.h describes them).  *count = the length of that array; its elements go to
+ * iout (integers, widened to int64) or dout (ent_v, cq_v, b_val, lp_w, cr_val) where the pointer is not NULL: call once with
+ * both NULL for the length.  A failed check of the upload returns its code and writes its message to msg (msg_len bytes). */
+int lrn_dbg_model_layout(const char* name, int msz, int nvar, const int64_t* AA_colptr, const int64_t* AA_rowval,
+                         const double* AA_nzval, const int64_t* sigma, int64_t qA, int pos_space, double dense_threshold,
+                         int64_t free_bytes, const int64_t* B_colptr, const int64_t* B_rowval, const double* B_nzval, int nlin,
+                         const int64_t* Clin_colptr, const int64_t* Clin_rowval, const double* Clin_nzval, int64_t* count,
+                         int64_t* iout, double* dout, char* msg, int msg_len);
+/* The same for lrn_upload_lowrank (V, d, khat: its arguments; NULL / 0: none) and lrn_upload_diag (rows, nrows) on a block whose
+ * constraint -> position map is ipos (0-based) and whose positions [0, npos_nz) are stored.  name: "v_ptr" "v_col" "v_val" "v_w"
+ * (doubles: v_val, v_w), "v_partial", "stored_and_factored" (the first stored position with a weighted factor column, or -1) |
+ * "dg_h" "dg_nat" "dg_of_pos".  Messages name block 0. */
+int lrn_dbg_factor_layout(const char* name, int msz, int nvar, const int64_t* ipos, int npos_nz, int pos_space, int khat,
+                          const int64_t* V_colptr, const int64_t* V_rowval, const double* V_nzval, const double* d, int64_t nrows,
+                          const int64_t* rows, int64_t* count, int64_t* iout, double* dout, char* msg, int msg_len);
 int lrn_dbg_mfma_probe(lrn_ctx* ctx, const double* A16x4, const double* B4x16, double* D16x16);
 int lrn_dbg_potrf(lrn_ctx* ctx, int n, double* A, int* info);
 int lrn_dbg_potrs(lrn_ctx* ctx, int n, const double* A, const double* b, double* x, int* info);

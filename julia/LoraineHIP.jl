@@ -330,4 +330,55 @@ function matvec_partial!(ctx::Ctx, Ax::Vector{Float64}, x::Vector{Float64})   # 
     check(ctx, ccall((:lrn_matvec_partial, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.h, x, Ax), "lrn_matvec_partial")
 end
 
+# ---- debug: the device layout of a model, computed on the host alone (csrc/model_layout.h; no context, no GPU) ----
+# One named array of what lrn_upload_model lays out for a block (AA nvar x msz^2, sigma and qA 1-based as in the model), its
+# rank-one factors B and the linear part Clin (`nothing`: none).  Returns a Vector{Int64}, or a Vector{Float64} for the
+# value arrays (ent_v, cq_v, b_val, lp_w, cr_val); the names: include/loraine_hip.h.
+function dbg_model_layout(name::String, msz::Int, AA::SparseMatrixCSC{Float64,Int64}, sigma::Vector{Int64}, qA::Int;
+                          pos_space::Bool = true, dense_threshold::Float64 = -1.0, free_bytes::Int = 0,
+                          B::Union{Nothing,SparseMatrixCSC{Float64,Int64}} = nothing,
+                          Clin::Union{Nothing,SparseMatrixCSC{Float64,Int64}} = nothing)
+    nvar = size(AA, 1)
+    pI(x) = x === nothing ? Ptr{Int64}(C_NULL) : pointer(x)
+    pD(x) = x === nothing ? Ptr{Float64}(C_NULL) : pointer(x)
+    bc, br, bv = B === nothing ? (nothing, nothing, nothing) : (B.colptr, B.rowval, B.nzval)
+    lc, lr, lv = Clin === nothing ? (nothing, nothing, nothing) : (Clin.colptr, Clin.rowval, Clin.nzval)
+    nlin = Clin === nothing ? 0 : size(Clin, 2)
+    count = Int64[0]; msg = zeros(UInt8, 1024)
+    call(iout, dout) = GC.@preserve AA sigma B Clin iout dout msg ccall((:lrn_dbg_model_layout, LIB), Cint,
+        (Cstring, Cint, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Int64, Cint, Cdouble, Int64, Ptr{Int64}, Ptr{Int64},
+         Ptr{Float64}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cstring, Cint),
+        name, msz, nvar, pointer(AA.colptr), pointer(AA.rowval), pointer(AA.nzval), pointer(sigma), qA, pos_space ? 1 : 0, dense_threshold, free_bytes, pI(bc), pI(br),
+        pD(bv), nlin, pI(lc), pI(lr), pD(lv), pointer(count), pI(iout), pD(dout), Cstring(pointer(msg)), length(msg))
+    rc = call(nothing, nothing)
+    rc == 0 || error("lrn_dbg_model_layout($name) failed ($rc): " * unsafe_string(pointer(msg)))
+    isreal = name in ("ent_v", "cq_v", "b_val", "lp_w", "cr_val")
+    iout = isreal ? nothing : Vector{Int64}(undef, count[1]); dout = isreal ? Vector{Float64}(undef, count[1]) : nothing
+    call(iout, dout)
+    return isreal ? dout : iout
+end
+
+# The same for the factors of lrn_upload_lowrank (V, d, khat) or the rows of lrn_upload_diag on a block with the constraint ->
+# position map ipos (0-based) whose positions [0, npos_nz) are stored; v_val and v_w come back as Float64.
+function dbg_factor_layout(name::String, msz::Int, ipos::Vector{Int64}, npos_nz::Int; pos_space::Bool = true, khat::Int = 0,
+                           V::Union{Nothing,SparseMatrixCSC{Float64,Int64}} = nothing, d::Union{Nothing,Vector{Float64}} = nothing,
+                           rows::Union{Nothing,Vector{Int64}} = nothing)
+    pI(x) = x === nothing ? Ptr{Int64}(C_NULL) : pointer(x)
+    pD(x) = x === nothing ? Ptr{Float64}(C_NULL) : pointer(x)
+    vc, vr, vv = V === nothing ? (nothing, nothing, nothing) : (V.colptr, V.rowval, V.nzval)
+    nrows = rows === nothing ? 0 : length(rows)
+    count = Int64[0]; msg = zeros(UInt8, 1024)
+    call(iout, dout) = GC.@preserve ipos V d rows iout dout msg ccall((:lrn_dbg_factor_layout, LIB), Cint,
+        (Cstring, Cint, Cint, Ptr{Int64}, Cint, Cint, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64},
+         Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cstring, Cint),
+        name, msz, length(ipos), pointer(ipos), npos_nz, pos_space ? 1 : 0, khat, pI(vc), pI(vr), pD(vv), pD(d), nrows, pI(rows),
+        pointer(count), pI(iout), pD(dout), Cstring(pointer(msg)), length(msg))
+    rc = call(nothing, nothing)
+    rc == 0 || error("lrn_dbg_factor_layout($name) failed ($rc): " * unsafe_string(pointer(msg)))
+    isreal = name in ("v_val", "v_w")
+    iout = isreal ? nothing : Vector{Int64}(undef, count[1]); dout = isreal ? Vector{Float64}(undef, count[1]) : nothing
+    call(iout, dout)
+    return isreal ? dout : iout
+end
+
 end # module

@@ -93,6 +93,12 @@ SIGNATURES = {
     "lrn_dbg_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                     C.c_int, C.c_int, PI]),
     "lrn_dbg_schur_chol_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, PI, PI64, PI, PI, PI, PD]),
+    "lrn_dbg_model_layout": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_int, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, PI64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]),
+    "lrn_dbg_factor_layout": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, PI64, C.c_void_p, C.c_void_p,
+                                        C.c_char_p, C.c_int]),
     "lrn_dbg_mfma_probe": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrn_dbg_potrf": (C.c_int, [c_ctx, C.c_int, C.c_void_p, PI]),
     "lrn_dbg_potrs": (C.c_int, [c_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, PI]),

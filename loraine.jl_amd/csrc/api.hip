@@ -9,7 +9,6 @@
 
 using namespace lrn;
 
-void lrn_free_model(lrn_ctx* c);
 void lrn_detect_free(lrn_ctx* c);
 
 extern "C" {
@@ -71,6 +70,8 @@ int lrn_destroy(lrn_ctx* c) {
   (void)hipEventDestroy(c->ev1);
   if (c->evA) (void)hipEventDestroy(c->evA);
   if (c->evB) (void)hipEventDestroy(c->evB);
+  if (c->evC) (void)hipEventDestroy(c->evC);
+  if (c->evD) (void)hipEventDestroy(c->evD);
   (void)hipStreamDestroy(c->stream);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
   if (c->stream3) (void)hipStreamDestroy(c->stream3);

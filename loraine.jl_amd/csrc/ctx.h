@@ -109,10 +109,21 @@ struct LmiBlock {
   int dg_n = 0;
   lrn::DBuf dg_h, dg_nat, dg_of_pos;   // int32 [dg_n], [dg_n], [nvar]
   lrn::DBuf dg_a;                      // double [msz * dg_n]
+  // --- every device buffer above, named once, in three lists: the rank-class plan (dropped with its scalars by
+  // lrn::drop_rank_classes), the diagonal parts (lrn::drop_diag), and all the others.  A DBuf added to the block goes into one
+  std::vector<lrn::DBuf*> rank_class_bufs() { return {&rg_src, &rg_wc, &rg_gh, &rg_hg, &rg_tiles, &rg_cg, &Vc, &Yc}; }
+  std::vector<lrn::DBuf*> diag_bufs() { return {&dg_h, &dg_nat, &dg_of_pos, &dg_a}; }
+  std::vector<lrn::DBuf*> other_bufs() {
+    return {&ent_ptr, &ent_r, &ent_c, &ent_v, &Adense, &tri_tab, &hidx, &sigma_d, &ipos_d, &cq_q, &cq_ptr, &cq_j, &cq_v,
+            &pc_ptr, &pc_r, &pc_t, &ent_t, &Mv, &Zs, &b_ptr, &b_col, &b_val, &v_ptr, &v_col, &v_val, &v_w,
+            &X, &S, &W, &G, &Gi, &Si, &D, &DDsi, &Vprev, &Cd, &Rd, &delX, &delS, &Xn, &Sn, &RNT, &t0, &t1, &t2,
+            &LXf, &LXt, &LSf, &Yh, &Zh, &Ki, &Bs, &TX, &Qm, &lyap, &Bd, &Vd, &Ys};
+  }
 };
 
 struct lrn_ctx;
-namespace lrn { void update_shard_bs(lrn_ctx* c); }
+namespace lrn { void update_shard_bs(lrn_ctx* c); }      // ctx.hip
+void lrn_free_model(lrn_ctx* c);                         // model.hip
 
 // lrn_set_option knobs: per context (two contexts of one process -- Julia threads, tests -- do not see each
 // other's settings)
@@ -298,6 +309,13 @@ struct lrn_ctx {
   lrn::Prec* prec = nullptr;
   // multi-GPU communicator (comm.hip; lrn_comm_init / lrn_comm_init_host)
   lrn::Comm* comm = nullptr;
+  // the buffers that belong to the uploaded model, named once (lrn_free_model releases them with the blocks); every other
+  // DBuf above lives as long as the context (lrn_destroy)
+  std::vector<lrn::DBuf*> model_bufs() {
+    return {&cl_ptr, &cl_row, &cl_val, &cl_rown, &lin_xs, &lp_r, &lp_c, &lp_ptr, &lp_l, &lp_w, &cr_ptr, &cr_col, &cr_val,
+            &H, &L, &cholwork, &v0, &v1, &v2, &v3, &hdiag, &P, &P2, &T, &slabs, &Hd, &BG, &m0, &m1, &m2, &cgbuf,
+            &facY, &facM, &dgP, &dgC, &dgH, &dgT, &dgTA, &wchol};
+  }
 };
 
 namespace lrn {
@@ -309,6 +327,16 @@ int copy_in(lrn_ctx* c, void* dst_dev, const void* src, size_t bytes);    // src
 int copy_out(lrn_ctx* c, void* dst, const void* src_dev, size_t bytes);   // dst host or device
 void tic(lrn_ctx* c);
 void toc(lrn_ctx* c, const char* key);
+// ensure + copy_in: `bytes` from src (host or device) into b, allocated to at least alloc_bytes (>= bytes: some kernels read a
+// few bytes past the last element)
+int upload(lrn_ctx* c, DBuf& b, const void* src, size_t bytes, size_t alloc_bytes);
+template <class T>
+int upload(lrn_ctx* c, DBuf& b, const std::vector<T>& v, size_t pad_bytes = 0) {
+  return upload(c, b, v.data(), v.size() * sizeof(T), v.size() * sizeof(T) + pad_bytes);
+}
+// the rank-class plan of a block and everything built with it; the diagonal parts of a block (buffers and scalars)
+void drop_rank_classes(LmiBlock& b);
+void drop_diag(LmiBlock& b);
 
 // comm.hip
 int comm_allreduce(lrn_ctx* c, double* buf_dev, long count, int op);     // in place on c->stream; op 0 sum, 1 min, 2 max
@@ -414,4 +442,9 @@ struct PhaseTimer {
   do {                            \
     int rc__ = (expr);            \
     if (rc__ != LRN_OK) return rc__; \
+  } while (0)
+// a check of model_layout.h (LayoutError: code and message text) that failed becomes the context's error
+#define LRN_LAYOUT(c, expr)                                                                 \
+  do {                                                                                      \
+    if (auto e__ = (expr)) return lrn::set_error((c), e__.code, "%s", e__.msg.c_str());     \
   } while (0)

@@ -3,6 +3,7 @@
 
 #include "../../include/loraine_hip.h"
 #include "jacobi.h"
+#include "model_layout.h"
 #include "ops.h"
 
 using namespace lrn;
@@ -56,4 +57,103 @@ extern "C" int lrn_dbg_svd_jacobi(lrn_ctx* c, int n, const double* A, double* U_
   int rc = copy_out(c, sigma, dS.p, (size_t)n * 8);
   release(dA); release(dV); release(dS);
   return rc;
+}
+
+// ---- the layouts of model_layout.h on caller arrays: no context, no device (tests/test_model_layout_cpu.py)
+namespace {
+// hands the array called `name` back: its length in *count, its elements in iout (integers, widened) or dout (doubles) where given
+struct NamedOut {
+  const char* name;
+  int64_t* count;
+  int64_t* iout;
+  double* dout;
+  bool found = false;
+  bool hit(const char* n) { return !strcmp(n, name) && (found = true); }
+  template <class T> void ints(const char* n, const std::vector<T>& v) {
+    if (!hit(n)) return;
+    *count = (int64_t)v.size();
+    for (size_t i = 0; iout && i < v.size(); ++i) iout[i] = (int64_t)v[i];
+  }
+  void scalar(const char* n, long v) { ints(n, std::vector<long>(1, v)); }
+  void reals(const char* n, const std::vector<double>& v) {
+    if (!hit(n)) return;
+    *count = (int64_t)v.size();
+    for (size_t i = 0; dout && i < v.size(); ++i) dout[i] = v[i];
+  }
+};
+
+int layout_result(const LayoutError& e, const NamedOut& o, char* msg, int msg_len) {
+  std::string text = e ? e.msg : o.found ? std::string() : std::string("unknown layout array ") + o.name;
+  if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", text.c_str());
+  return e ? e.code : o.found ? LRN_OK : LRN_ERR_ARG;
+}
+}  // namespace
+
+extern "C" int lrn_dbg_model_layout(const char* name, int msz, int nvar, const int64_t* AA_colptr, const int64_t* AA_rowval,
+                                    const double* AA_nzval, const int64_t* sigma, int64_t qA, int pos_space, double dense_threshold,
+                                    int64_t free_bytes, const int64_t* B_colptr, const int64_t* B_rowval, const double* B_nzval, int nlin,
+                                    const int64_t* Clin_colptr, const int64_t* Clin_rowval, const double* Clin_nzval, int64_t* count,
+                                    int64_t* iout, double* dout, char* msg, int msg_len) {
+  if (!name || !count || msz <= 0 || nvar <= 0 || nlin < 0 || free_bytes < 0 || !AA_colptr || !sigma) return LRN_ERR_ARG;
+  NamedOut o{name, count, iout, dout};
+  *count = 0;
+  BlockLayout L;
+  LayoutError e = block_layout(msz, nvar, AA_colptr, AA_rowval, AA_nzval, sigma, qA, pos_space != 0, dense_threshold,
+                               (size_t)free_bytes, L);
+  if (e) return layout_result(e, o, msg, msg_len);
+  o.ints("sigma", L.sigma); o.ints("ipos", L.ipos); o.ints("nnz", L.nnz);
+  o.scalar("qA", L.qA); o.scalar("npos_nz", L.npos_nz); o.scalar("nd", L.nd); o.scalar("q_wave", L.q_wave);
+  o.ints("ent_ptr", L.ent_ptr); o.ints("ent_r", L.ent_r); o.ints("ent_c", L.ent_c); o.reals("ent_v", L.ent_v);
+  o.ints("hidx", L.hidx);
+  o.ints("cq_q", L.cq_q); o.ints("cq_ptr", L.cq_ptr); o.ints("cq_j", L.cq_j); o.reals("cq_v", L.cq_v);
+  o.scalar("sp_ok", L.sp_ok); o.ints("pc_ptr", L.pc_ptr); o.ints("pc_r", L.pc_r); o.ints("pc_t", L.pc_t);
+  o.ints("ent_t", L.ent_t); o.ints("sp_long_cols", L.sp_long_cols);
+  if (!o.found && B_colptr && !strncmp(name, "b_", 2)) {
+    RankOneLayout R;
+    rank_one_layout(msz, nvar, B_colptr, B_rowval, B_nzval, L.ipos, pos_space != 0, R);
+    o.ints("b_ptr", R.b_ptr); o.ints("b_col", R.b_col); o.reals("b_val", R.b_val);
+  }
+  if (!o.found && nlin > 0 && Clin_colptr) {
+    LinearLayout C;
+    e = linear_layout(nvar, nlin, Clin_colptr, Clin_rowval, Clin_nzval, &L.ipos, pos_space != 0, C);
+    if (e) return layout_result(e, o, msg, msg_len);
+    o.ints("cl_ptr", C.cl_ptr); o.ints("cl_row", C.cl_row); o.ints("cl_rown", C.cl_rown);
+    o.ints("lp_r", C.lp_r); o.ints("lp_c", C.lp_c); o.ints("lp_ptr", C.lp_ptr); o.ints("lp_l", C.lp_l); o.reals("lp_w", C.lp_w);
+    o.ints("cr_ptr", C.cr_ptr); o.ints("cr_col", C.cr_col); o.reals("cr_val", C.cr_val);
+  }
+  return layout_result(e, o, msg, msg_len);
+}
+
+extern "C" int lrn_dbg_factor_layout(const char* name, int msz, int nvar, const int64_t* ipos, int npos_nz, int pos_space, int khat,
+                                     const int64_t* V_colptr, const int64_t* V_rowval, const double* V_nzval, const double* d,
+                                     int64_t nrows, const int64_t* rows, int64_t* count, int64_t* iout, double* dout, char* msg,
+                                     int msg_len) {
+  if (!name || !count || msz <= 0 || nvar <= 0 || !ipos || npos_nz < 0 || npos_nz > nvar || nrows < 0 || nrows > nvar)
+    return LRN_ERR_ARG;
+  NamedOut o{name, count, iout, dout};
+  *count = 0;
+  std::vector<int> ip(nvar), sg(nvar, 0);
+  for (int k = 0; k < nvar; ++k) {
+    if (ipos[k] < 0 || ipos[k] >= nvar) return LRN_ERR_ARG;
+    ip[k] = (int)ipos[k];
+    sg[ip[k]] = k;
+  }
+  LayoutError e;
+  if (V_colptr && d && khat > 0) {
+    LowrankLayout L;
+    e = lowrank_check_size(msz, nvar, khat);
+    if (!e) e = lowrank_check_colptr(msz, V_colptr);
+    if (!e) e = lowrank_layout(msz, nvar, khat, V_colptr, V_rowval, V_nzval, d, ip, pos_space != 0, L);
+    if (e) return layout_result(e, o, msg, msg_len);
+    o.ints("v_ptr", L.v_ptr); o.ints("v_col", L.v_col); o.reals("v_val", L.v_val); o.reals("v_w", L.v_w);
+    o.scalar("v_partial", factors_partial(pos_space != 0, sg, npos_nz, khat, L.v_w.data()));
+    o.scalar("stored_and_factored", stored_and_factored(pos_space != 0, sg, npos_nz, khat, L.v_w.data()));
+  }
+  if (!o.found && rows) {
+    DiagRowsLayout D;
+    e = diag_rows_layout(nvar, 0, (int)nrows, rows, ip, npos_nz, pos_space != 0, D);
+    if (e) return layout_result(e, o, msg, msg_len);
+    o.ints("dg_h", D.dg_h); o.ints("dg_nat", D.dg_nat); o.ints("dg_of_pos", D.dg_of_pos);
+  }
+  return layout_result(e, o, msg, msg_len);
 }

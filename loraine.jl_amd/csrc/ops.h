@@ -13,7 +13,7 @@ bool wmw_pattern_ok(const lrn_ctx* c, const LmiBlock& b);
 int aa_times_wmw_pattern(lrn_ctx* c, LmiBlock& b, const double* M, double* N, double* y);
 int aa_times2(lrn_ctx* c, LmiBlock& b, const double* Z1, double* y1, const double* Z2, double* y2);   // both, one pass over dense data
 int aat_to_mat(lrn_ctx* c, LmiBlock& b, const double* x, double* M, bool factor_form = false);        // M = mat(AA' x)
-// route of the passes over the dense constraint data of b, decided once b.Adense is filled (model.hip): the symmetry check
+// route of the passes over the dense constraint data of b, decided once b.Adense is filled (model.hip, synth.hip): the symmetry check
 // on the device and the chunk table of the column tails; sym_known: the data are symmetric by construction, no check
 int dense_route_setup(lrn_ctx* c, LmiBlock& b, bool sym_known);
 int matvec_dev(lrn_ctx* c, const double* x, double* y);                     // y = AA vec(W mat(AA' x) W) (+ the C_lin term): MyA
@@ -137,6 +137,8 @@ int dot_dev(lrn_ctx* c, const double* A, const double* B, long n, double* out_de
 // ---- lyap.hip: R with Yh R + R Yh = Cm for the block's Yh (Zh beside it, option lyap_form) by CG; Cm is destroyed, work:
 // msz^2 doubles; *ok = false: not converged within lyap_maxit steps
 int lyap_solve(lrn_ctx* c, LmiBlock& b, double* Cm, double* R, double* work, bool* ok, int* steps);
+// ---- model.hip: H, the solve vectors and the scaling matrices of every block, once the blocks are laid out
+int alloc_common(lrn_ctx* c);
 // ---- ipstep.hip
 int ensure_resident(lrn_ctx* c, LmiBlock& b);                              // the arrays of the resident IP step of a block exist
 }  // namespace lrn

@@ -15,7 +15,7 @@ SHARD_BS = 128
 
 
 def auto_bs(nvar, world):
-    """Block width the C library picks when the option "shard_bs" is 0 (update_shard_bs in csrc/model.hip):
+    """Block width the C library picks when the option "shard_bs" is 0 (update_shard_bs in csrc/ctx.hip):
     two blocks per rank, rounded up to the 128-column tile."""
     if world <= 1 or nvar <= 0:
         return SHARD_BS

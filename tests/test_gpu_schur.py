@@ -796,3 +796,66 @@ def test_dense_route_is_decided_at_upload(dev):
         assert dev.count("op_dense_tri") == 2 and dev.count("op_dense_stream") == 0 and dev.count("op_dense_scalar") == 0
     finally:
         dev.set_option("dense_threshold", -1)
+
+
+# ---- the upload itself (csrc/model.hip over csrc/model_layout.h; the layout is pinned without a device in
+# tests/test_model_layout_cpu.py, which also checks that this model has 0 < nd = 3 < npos_nz = 5 in block 0)
+def _two_block_device(AA, sigma, qA, ms):
+    import loraine_jl_amd
+    d = loraine_jl_amd.Device(0)
+    d.set_option("dense_threshold", 5)
+    d.upload_model(AA, sigma, qA, ms)
+    return d
+
+
+def _two_block_H(d, ms):
+    for il, m in enumerate(ms):
+        d.set_scaling(il, *_spd(m, 40 + il))
+    return d.schur_assemble(0, want_H=True)
+
+
+def test_upload_returns_every_constraint_bit_for_bit():
+    """dense slots (positions 0 .. 2 of block 0), entry lists, and the constraint without an entry"""
+    import model_layout_cases as mc
+    AA, sigma, qA, ms = mc.two_block()
+    d = _two_block_device(AA, sigma, qA, ms)
+    try:
+        for il, m in enumerate(ms):
+            R = sp.csr_matrix(AA[il])
+            for k in range(R.shape[0]):
+                want = 0.0 - R[k].toarray().reshape(m, m, order="F")
+                assert np.array_equal(d.get_constraint(il, k), want), (il, k)
+                assert (k == 4 and il == 0) == (not want.any())
+    finally:
+        d.close()
+
+
+@pytest.mark.parametrize("failing_block", [0, 1])
+def test_failed_upload_leaves_no_model(failing_block):
+    """sigmaA of one block made unsorted -- block 0, or block 1 of the model with its blocks exchanged, so that a whole block is
+    on the device when the upload fails: the error keeps its text, no model is left (lrn_schur_plan says so, the device
+    memory is back where it was), and the valid model then uploads and assembles the H of a fresh context."""
+    import loraine_jl_amd
+    from loraine_jl_amd._capi import LoraineHipError
+    import model_layout_cases as mc
+    AA, sigma, qA, ms = mc.two_block()
+    if failing_block == 1:
+        AA, sigma = AA[::-1], np.ascontiguousarray(sigma[:, ::-1])
+    bad = sigma.copy()
+    bad[[0, 3], failing_block] = bad[[3, 0], failing_block]          # 3 entries before 9
+    fresh = _two_block_device(AA, sigma, qA, ms)
+    d = loraine_jl_amd.Device(0)
+    try:
+        H_fresh = _two_block_H(fresh, ms)
+        d.set_option("dense_threshold", 5)
+        before = d.count("device_bytes")
+        with pytest.raises(LoraineHipError, match=r"sigmaA is not sorted by decreasing nnz \(model\.jl:159\)"):
+            d.upload_model(AA, bad, qA, ms)
+        with pytest.raises(LoraineHipError, match="no model uploaded"):
+            d.schur_plan(0)
+        assert d.count("device_bytes") == before
+        d.upload_model(AA, sigma, qA, ms)
+        assert np.array_equal(_two_block_H(d, ms), H_fresh)
+    finally:
+        d.close()
+        fresh.close()

@@ -1,5 +1,5 @@
 """GPU: diagonal parts on wide factored blocks, A_k = diag(a_k) + V_k D_k V_k' with up to 64 factor columns (library option
-wide_diag beside lowrank_wide; csrc/diagops.hip::diag_sq_wide_mfma_kernel, the gates of csrc/model.hip) through Device / the C ABI
+wide_diag beside lowrank_wide; csrc/diagops.hip::diag_sq_wide_mfma_kernel, the gates of csrc/model_factored.hip) through Device / the C ABI
 and through Optimizer.load_factored_model(..., wide="diag"), on the cases of tests/wide_diag_cases.py.
 
 Bounds are the project's own: H and the data operators -- 1e-12 relative Frobenius against np.longdouble from the materialised

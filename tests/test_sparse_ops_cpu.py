@@ -1,5 +1,5 @@
 """The designed inputs of tests/sparse_ops_cases.py hold what they are built for, and a float64 NumPy restatement of the
-pattern route (the tables of csrc/model.hip, the walks of csrc/dataops.hip, both size regimes, whole and column-sharded)
+pattern route (the tables of csrc/model_layout.h, the walks of csrc/dataops.hip, both size regimes, whole and column-sharded)
 agrees with the longdouble reference within its bound -- and stops doing so, by a factor of 1e3 at least, under each of
 the single faults the inputs are meant to expose.  No device."""
 import numpy as np
@@ -14,7 +14,7 @@ PATTERN_CASES = [n for n in sc.NAMES if n != "P"]
 
 # ---------------------------------------------------------------------------------------------- the restatement
 class Tables:
-    """What lrn_upload_model builds for one block with nd = 0 (csrc/model.hip): stored columns of AA (cq_*), the pattern
+    """What lrn_upload_model builds for one block with nd = 0 (csrc/model_layout.h): stored columns of AA (cq_*), the pattern
     by columns (pc_ptr, pc_r), the twin of every stored position (pc_t), the entry lists in position order (ent_*)."""
 
     def __init__(self, A, m, sigma):
