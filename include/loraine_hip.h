@@ -155,6 +155,11 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * GEMM1'/2' without epilogue / K loop / first load, one workgroup per CU, whole K range, one matrix for every batch
  * element -- tools/gemm12_overhead.py), "gemm3_stagger" (experiment: K-walk stagger of the workgroups of
  * GEMM3' in chunks of 16, 0 = off), "pair_lanes" (lanes per entry of the sparse pair kernel: 0 auto / 4 / 8 / 16 / 64),
+ * "pair_local" (0, default / 1; anything else: LRN_ERR_ARG -- 1: the sparse owners of a block whose partners all have a support
+ * of at most 32 rows and columns, and which have at least "pair_local_min" entries, are assembled from A[S, S] on their
+ * supports, two small MFMA products per pair; one GPU -- an empty range or a sharded context counts "pair_local_skipped" and
+ * takes the pair kernels, bit for bit; counts "pair_local_owners", "pair_local_pairs", timing "local"), "pair_local_min"
+ * (>= 1, default 36 entries: read by the next lrn_upload_model),
  * "jacobi_cross" (1: cross-pair rotations only after round 0), "jacobi_early" (relative level below which a sweep's
  * rotations make it the last one; 0 = always run the confirming sweep), "eigmin_pair" (the two
  * smallest-eigenvalue searches of a step-length computation: 2, default = their Lanczos runs in lock-step, one launch per

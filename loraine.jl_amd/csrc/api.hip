@@ -110,6 +110,15 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   else if (!strcmp(key, "jacobi_block")) c->opt.jacobi_block = (int)value;
   else if (!strcmp(key, "jacobi_inner")) c->opt.jacobi_inner = (int)value;
   else if (!strcmp(key, "pair_lanes")) c->opt.pair_lanes = (int)value;
+  else if (!strcmp(key, "pair_local")) {      // (an H assembled under the other setting is not reused by the CG operator)
+    if (value != 0.0 && value != 1.0) return set_error(c, LRN_ERR_ARG, "pair_local is 0 or 1");
+    c->opt.pair_local = (int)value;
+    c->hop_version = -1;
+  }
+  else if (!strcmp(key, "pair_local_min")) {      // read by the next lrn_upload_model
+    if (!(value >= 1.0 && value <= 1.0e9)) return set_error(c, LRN_ERR_ARG, "pair_local_min is a count of entries >= 1");
+    c->opt.pair_local_min = (int)value;
+  }
   else if (!strcmp(key, "matvec_sparse")) c->opt.matvec_sparse = (int)value;
   else if (!strcmp(key, "prec_dense")) c->opt.prec_dense = (int)value;
   else if (!strcmp(key, "wmw_pattern_min")) c->opt.wmw_pattern_min = std::max(2, (int)value);

@@ -31,6 +31,15 @@ struct LmiBlock {
   int tri_nch = 0;
   lrn::DBuf hidx;           // int32 [nvar] position -> row/col index of the Schur matrix
   lrn::DBuf sigma_d, ipos_d; // int32 [nvar] device copies of sigma / ipos
+  // local route of the sparse owners (option "pair_local", localops.hip; the lists: model_layout.h::block_local): owners
+  // [loc_lo, loc_hi).  The host lists wait here from the upload on; the first assembly by that route moves them to the device
+  // (loc_ready) and empties them -- a model that never takes the route holds no device copy
+  int loc_lo = 0, loc_hi = 0;
+  bool loc_ready = false;
+  std::vector<long> loc_sptr, loc_aptr;
+  std::vector<int> loc_sup;
+  std::vector<double> loc_a;
+  lrn::DBuf loc_sptr_d, loc_aptr_d, loc_sup_d, loc_a_d;   // int64 [nvar+1], int64 [nvar+1], int32, double
   // stored columns of AA (sparse constraints only) for the deterministic AA'x gather
   long ncq = 0;
   lrn::DBuf cq_q, cq_ptr;   // int64 [ncq], [ncq+1]
@@ -117,7 +126,7 @@ struct LmiBlock {
     return {&ent_ptr, &ent_r, &ent_c, &ent_v, &Adense, &tri_tab, &hidx, &sigma_d, &ipos_d, &cq_q, &cq_ptr, &cq_j, &cq_v,
             &pc_ptr, &pc_r, &pc_t, &ent_t, &Mv, &Zs, &b_ptr, &b_col, &b_val, &v_ptr, &v_col, &v_val, &v_w,
             &X, &S, &W, &G, &Gi, &Si, &D, &DDsi, &Vprev, &Cd, &Rd, &delX, &delS, &Xn, &Sn, &RNT, &t0, &t1, &t2,
-            &LXf, &LXt, &LSf, &Yh, &Zh, &Ki, &Bs, &TX, &Qm, &lyap, &Bd, &Vd, &Ys};
+            &LXf, &LXt, &LSf, &Yh, &Zh, &Ki, &Bs, &TX, &Qm, &lyap, &Bd, &Vd, &Ys, &loc_sptr_d, &loc_aptr_d, &loc_sup_d, &loc_a_d};
   }
 };
 
@@ -170,6 +179,9 @@ struct LrnOptions {
   int lyap_maxit = 300;
   int lyap_form = 1;              // 1: the better conditioned equivalent equation (Yh/s + s Zh) R + R (.) = C/s + s Zh C Zh, 0: Yh R + R Yh = C
   int pair_lanes = 0;             // pair_wave_kernel: lanes per Schur entry, 0 auto (16 for short products), 16, 64
+  int pair_local = 0;             // sparse owners with a small support, [loc_lo, loc_hi) of a block, through the dense A[S, S] on the
+                                  // MFMA (localops.hip): 1, the pair kernels as always: 0.  One GPU ("pair_local_skipped" otherwise)
+  int pair_local_min = 36;        // read by lrn_upload_model: entries from which on a sparse owner may take that route (model_layout.h)
   int matvec_sparse = 0;          // 0 auto, 1 dense GEMM path, 2 sparse path whenever the pattern allows
   int shard_products = 1;         // multi-GPU: the n^3 products of the resident path (Newton-Schulz, Lyapunov CG, step) by
   int shard_products_min = 4096;  // column blocks + all-gather from this matrix side on (one product of 10^4: 31 ms; below, the

@@ -108,6 +108,8 @@ extern "C" int lrn_dbg_model_layout(const char* name, int msz, int nvar, const i
   o.ints("cq_q", L.cq_q); o.ints("cq_ptr", L.cq_ptr); o.ints("cq_j", L.cq_j); o.reals("cq_v", L.cq_v);
   o.scalar("sp_ok", L.sp_ok); o.ints("pc_ptr", L.pc_ptr); o.ints("pc_r", L.pc_r); o.ints("pc_t", L.pc_t);
   o.ints("ent_t", L.ent_t); o.ints("sp_long_cols", L.sp_long_cols);
+  o.scalar("loc_lo", L.loc_lo); o.scalar("loc_hi", L.loc_hi); o.ints("loc_sptr", L.loc_sptr); o.ints("loc_sup", L.loc_sup);
+  o.ints("loc_aptr", L.loc_aptr); o.reals("loc_a", L.loc_a);
   if (!o.found && B_colptr && !strncmp(name, "b_", 2)) {
     RankOneLayout R;
     rank_one_layout(msz, nvar, B_colptr, B_rowval, B_nzval, L.ipos, pos_space != 0, R);

@@ -77,6 +77,13 @@ static int upload_block(lrn_ctx* c, LmiBlock& b, BlockLayout& L) {
   b.q_wave = L.q_wave;
   b.nent = L.nent();
   b.ncq = L.ncq();
+  b.loc_lo = L.loc_lo;      // (the lists of the local route stay on the host until an assembly takes it: localops.hip)
+  b.loc_hi = L.loc_hi;
+  b.loc_ready = false;
+  b.loc_sptr.swap(L.loc_sptr);
+  b.loc_aptr.swap(L.loc_aptr);
+  b.loc_sup.swap(L.loc_sup);
+  b.loc_a.swap(L.loc_a);
   LRN_TRY(upload(c, b.cq_q, L.cq_q));
   LRN_TRY(upload(c, b.cq_ptr, L.cq_ptr));
   LRN_TRY(upload(c, b.cq_j, L.cq_j));
@@ -166,7 +173,7 @@ static int upload_model(lrn_ctx* c, int nlmi, int nvar, const int64_t* msizes, c
     (void)hipMemGetInfo(&free_b, &total_b);
     BlockLayout L;
     LRN_LAYOUT(c, block_layout(m, nvar, AA_colptr[il], AA_rowval[il], AA_nzval[il], sigmaA + (long)il * nvar, qA[2 * il],
-                               c->pos_space, c->opt.dense_threshold, free_b, L));
+                               c->pos_space, c->opt.dense_threshold, free_b, L, c->opt.pair_local_min));
     LRN_TRY(upload_block(c, b, L));
     LRN_TRY(scatter_dense_prefix(c, b));
     b.has_B = false;

@@ -47,9 +47,19 @@ struct BlockLayout {
   bool sp_ok = false;                // pattern of mat(AA'x): kept when no constraint is dense and the pattern is symmetric
   std::vector<long> pc_ptr;
   std::vector<int> pc_r, pc_t, ent_t, sp_long_cols;
+  // local route of the sparse owners (block_local, localops.hip): owners [loc_lo, loc_hi); for the positions p >= loc_lo of a
+  // non-empty range the support S_p (ascending) at loc_sup[loc_sptr[p] ..) and A_p[S_p, S_p] (column-major, unpadded, value =
+  // ent_v) at loc_a[loc_aptr[p] ..); positions below loc_lo, and every position of an empty range, have empty lists
+  int loc_lo = 0, loc_hi = 0;
+  std::vector<long> loc_sptr, loc_aptr;
+  std::vector<int> loc_sup;
+  std::vector<double> loc_a;
   long nent() const { return (long)ent_r.size(); }
   long ncq() const { return (long)cq_q.size(); }
 };
+
+constexpr int LOCAL_SUPPORT_MAX = 32;      // side of the largest support the local route takes: two MFMA tiles of 16
+constexpr int PAIR_LOCAL_MIN = 36;         // default of option pair_local_min: the measured cross-over, a dense support of 6
 
 // dense (MFMA) prefix by cost model: pair path cost nnz_p * suffix_nnz vs 3 m^3 GEMM work; dense_threshold >= 0 decides
 // instead of the model; at most 0.55 of free_bytes go to the dense copies
@@ -172,14 +182,72 @@ inline void block_pattern(int m, BlockLayout& L) {
     if (L.pc_ptr[q + 1] - L.pc_ptr[q] > 64) L.sp_long_cols.push_back((int)q);
 }
 
+// the local range of the sparse owners and its lists (option pair_local, localops.hip): tr(A_i W A_j W) from the dense
+// A_p[S_p, S_p] on the supports S_p.  An owner meets every partner j >= i up to npos_nz, so all of them need a support of
+// at most LOCAL_SUPPORT_MAX indices.
+//   loc_hi: the first position of [nd, q_wave) with fewer than pair_local_min entries -- positions are sorted by decreasing
+//           nnz, one scan; below that many entries the pair kernel's nnz_i nnz_j terms are the cheaper route
+//   loc_lo: the smallest position >= nd from which every support up to loc_hi fits -- one scan down from loc_hi
+// The tail [loc_hi, npos_nz): a symmetric constraint has an entry in every row of its support, so s <= nnz < pair_local_min,
+// which is within the bound up to pair_local_min = 33 -- not for the default 36 (35 entries can touch 35 indices), not for an
+// unsymmetric entry list (an off-diagonal entry without its twin: s <= 2 nnz), not for a larger setting.  So the tail is
+// scanned whatever the option says -- it is linear in its entries -- and one support above the bound behind loc_hi leaves no
+// owner whose partners all fit: the range is empty (loc_lo = loc_hi).  Nothing is scanned when no sparse owner reaches pair_local_min entries.
+inline void block_local(int m, int pair_local_min, BlockLayout& L) {
+  const int nvar = (int)L.nnz.size();
+  L.loc_sptr.assign(nvar + 1, 0);
+  L.loc_aptr.assign(nvar + 1, 0);
+  L.loc_sup.clear();
+  L.loc_a.clear();
+  int hi = L.nd;
+  while (hi < L.q_wave && L.nnz[hi] >= pair_local_min) ++hi;
+  L.loc_lo = L.loc_hi = hi;
+  if (hi == L.nd) return;
+  std::vector<int> mark(m, -1);
+  auto fits = [&](int p) {      // at most LOCAL_SUPPORT_MAX distinct indices among the rows and columns of position p
+    int s = 0;
+    for (long e = L.ent_ptr[p]; e < L.ent_ptr[p + 1] && s <= LOCAL_SUPPORT_MAX; ++e)
+      for (int idx : {L.ent_r[e], L.ent_c[e]})
+        if (mark[idx] != p) { mark[idx] = p; ++s; }
+    return s <= LOCAL_SUPPORT_MAX;
+  };
+  for (int p = hi; p < L.npos_nz; ++p)
+    if (!fits(p)) return;
+  int lo = hi;
+  while (lo > L.nd && fits(lo - 1)) --lo;
+  L.loc_lo = lo;
+  if (lo == hi) return;
+  std::vector<int> slot(m, 0);
+  for (int p = lo; p < L.npos_nz; ++p) {
+    const size_t s0 = L.loc_sup.size();
+    for (long e = L.ent_ptr[p]; e < L.ent_ptr[p + 1]; ++e)
+      for (int idx : {L.ent_r[e], L.ent_c[e]})
+        if (mark[idx] != -2 - p) { mark[idx] = -2 - p; L.loc_sup.push_back(idx); }
+    std::sort(L.loc_sup.begin() + (long)s0, L.loc_sup.end());
+    const int s = (int)(L.loc_sup.size() - s0);
+    for (int a = 0; a < s; ++a) slot[L.loc_sup[s0 + a]] = a;
+    const size_t a0 = L.loc_a.size();
+    L.loc_a.resize(a0 + (size_t)s * s, 0.0);
+    for (long e = L.ent_ptr[p]; e < L.ent_ptr[p + 1]; ++e) L.loc_a[a0 + slot[L.ent_r[e]] + (size_t)slot[L.ent_c[e]] * s] = L.ent_v[e];
+    L.loc_sptr[p + 1] = (long)L.loc_sup.size();
+    L.loc_aptr[p + 1] = (long)L.loc_a.size();
+  }
+  for (int p = L.npos_nz; p < nvar; ++p) {
+    L.loc_sptr[p + 1] = L.loc_sptr[p];
+    L.loc_aptr[p + 1] = L.loc_aptr[p];
+  }
+}
+
 // the whole block.  pos_space: the Schur matrix is kept in position space (nlmi == 1); free_bytes: the free device memory
 inline LayoutError block_layout(int m, int nvar, const int64_t* cp, const int64_t* rv, const double* nz, const int64_t* sigma1,
-                                int64_t qA, bool pos_space, double dense_threshold, size_t free_bytes, BlockLayout& L) {
+                                int64_t qA, bool pos_space, double dense_threshold, size_t free_bytes, BlockLayout& L,
+                                int pair_local_min = PAIR_LOCAL_MIN) {
   L = BlockLayout();
   if (LayoutError e = block_entries(m, nvar, cp, rv, nz, sigma1, qA, L)) return e;
   L.nd = dense_prefix(L.nnz, L.qA, L.npos_nz, m, nvar, dense_threshold, free_bytes);
   L.q_wave = L.nd;
   while (L.q_wave < L.npos_nz && L.nnz[L.q_wave] > 4) L.q_wave++;
+  block_local(m, pair_local_min, L);
   block_stored_columns(m, cp, rv, nz, L);
   block_pattern(m, L);
   L.hidx.resize(nvar);

@@ -83,6 +83,9 @@ __device__ __forceinline__ long h_lower(int hi, int hj, int ldh) {
 // sparse partners; whether the next assembly of the block would take the Cholesky path, and its batch hint
 int assemble_dense(lrn_ctx* c, LmiBlock& b);
 bool chol_path_applicable(lrn_ctx* c, LmiBlock& b, long* pcap_out);
+// localops.hip: the sparse owners [loc_lo, loc_hi) of a block against all their partners, from A[S, S] on the supports
+// (option "pair_local"); the caller has checked that the range is not empty and that one GPU runs
+int assemble_local(lrn_ctx* c, LmiBlock& b);
 // schur_factored.hip: rank-one data (mode -1), rank-k data (mode 1), cross terms of a hybrid factored block
 int assemble_rank1(lrn_ctx* c, LmiBlock& b);
 int assemble_lowrank(lrn_ctx* c, LmiBlock& b);

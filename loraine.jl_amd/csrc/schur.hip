@@ -17,15 +17,17 @@
 //   owner sparse (positions >= nd):  one WAVEFRONT per entry (i,j), lanes over the
 //        nnz_i x nnz_j product terms a_e a_f W[c_e,r_f] W[c_f,r_e]   (the _dot kernel);
 //        owners with <= 4 nonzeros use one THREAD per entry (the nnz==1 fast path,
-//        makeBBBB.jl:188-209, is its 1x1 case).
+//        makeBBBB.jl:188-209, is its 1x1 case).  Option "pair_local": owners whose partners all have a support of at most
+//        32 rows and columns take the dense A[S, S] on the MFMA instead (localops.hip).
 //   rank-one data (mode -1): BG = B G (sparse x dense), H += (BG BG').^2 with the square
 //        fused in the MFMA GEMM epilogue (makeBBBB.jl:7-14).
 //   rank-k data (mode 1): U = G' V, H += blocksum(d d' .* (U'U).^2) over khat x khat blocks, again in the
 //        epilogue of one MFMA product (assemble_lowrank).  Option "lowrank_ragged": a block of mixed ranks by rank class, on
 //        the compacted columns (raggedops.hip).
 // This file: the sparse owners, the linear part, the driver schur_assemble, factorisation and solve.  schur_dense.hip: the dense
-// owners; schur_factored.hip: rank-one / rank-k data and hybrid blocks; raggedops.hip: rank-k data by rank class; diagops.hip:
-// diagonal parts of factored blocks; schur_plan.h, ragged_plan.h: the launch decisions, host only.
+// owners; localops.hip: sparse owners with a small support; schur_factored.hip: rank-one / rank-k data and hybrid blocks;
+// raggedops.hip: rank-k data by rank class; diagops.hip: diagonal parts of factored blocks; schur_plan.h, ragged_plan.h: the
+// launch decisions, host only.
 #include <algorithm>
 
 #include "ops.h"
@@ -164,6 +166,12 @@ int schur_plan(lrn_ctx* c, int mode) {
 static int assemble_sparse(lrn_ctx* c, LmiBlock& b) {
   const int n = c->nvar;
   double* H = c->H.as<double>();
+  // option "pair_local": the owners [loc_lo, loc_hi) go to assemble_local (localops.hip) with all their partners, the wave
+  // kernel keeps [nd, loc_lo) and [loc_hi, q_wave).  One GPU; with the option off, an empty range or world > 1 the launches
+  // below are the ones there always were
+  const bool local_on = c->opt.pair_local != 0 && c->world == 1 && b.loc_hi > b.loc_lo;
+  if (c->opt.pair_local != 0 && !local_on) c->counts["pair_local_skipped"] += 1;
+  const int wave_parts[2][2] = {{b.nd, local_on ? b.loc_lo : b.q_wave}, {local_on ? b.loc_hi : b.q_wave, b.q_wave}};
   tic(c);
   if (b.q_wave > b.nd) {
     // entries per wavefront by the typical product length: mean nnz of the sparse owners squared
@@ -173,7 +181,10 @@ static int assemble_sparse(lrn_ctx* c, LmiBlock& b) {
     int lanes = c->opt.pair_lanes;
     if (lanes != 4 && lanes != 8 && lanes != 16 && lanes != 64) lanes = mean_nnz * mean_nnz <= 512.0 ? 16 : 64;
     const int per_wg = 256 / lanes;
-    for (const auto& rg : owned_ranges(c->rank, c->world, c->shard_bs, b.nd, b.q_wave, 2048)) {
+    std::vector<std::pair<int, int>> ranges;
+    for (const auto& part : wave_parts)
+      for (const auto& rg : owned_ranges(c->rank, c->world, c->shard_bs, part[0], part[1], 2048)) ranges.push_back(rg);
+    for (const auto& rg : ranges) {
       const int a = rg.first, ny = rg.second - rg.first;
       dim3 grid((b.npos_nz - a + per_wg - 1) / per_wg, ny);
 #define LRN_PAIR_LAUNCH(L)                                                                                           \
@@ -197,6 +208,7 @@ static int assemble_sparse(lrn_ctx* c, LmiBlock& b) {
     }
   }
   toc(c, "sparse");
+  if (local_on) LRN_TRY(assemble_local(c, b));
   return LRN_OK;
 }
 

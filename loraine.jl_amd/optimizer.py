@@ -44,6 +44,7 @@ class Optimizer:
         self._device = device
         self._device_index = device_index
         self._pending = None
+        self._local_support = False
 
     # ---- MOI.RawOptimizerAttribute (MOI_wrapper.jl:86-103)
     def supports(self, name):
@@ -66,12 +67,16 @@ class Optimizer:
         return "Loraine"
 
     # ---- model input (copy_to, :142-232): options are frozen here, like in the reference (:224)
-    def read_from_file(self, path, detect_kmax=None):
+    def read_from_file(self, path, detect_kmax=None, local_support=False):
         """detect_kmax = 16 or 64: the constraint matrices of the file go through load_detected_model(kmax=detect_kmax) with
-        its defaults; None (default): the file is loaded as it always was."""
+        its defaults; None (default): the file is loaded as it always was.
+        local_support: as in load_model (the file loaded as it always was: detect_kmax=None)."""
+        self._local_support = self._check_local_support("read_from_file", local_support)
         if detect_kmax is None:
             self._pending = ("sdpa", path)
             return self
+        if self._local_support:
+            raise ValueError("read_from_file: local_support=True goes with detect_kmax=None (stored constraints)")
         if not self.resident:
             raise ValueError(self._NEEDS_RESIDENT)
         if isinstance(detect_kmax, bool) or detect_kmax not in (16, 64):
@@ -79,11 +84,22 @@ class Optimizer:
         self._pending = ("sdpa_detected", (path, dict(self._DETECT_DEFAULTS, kmax=int(detect_kmax))))
         return self
 
-    def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factors=None):
+    @staticmethod
+    def _check_local_support(who, value):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: local_support is False or True, not {value!r}")
+        return bool(value)
+
+    def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factors=None, local_support=False):
         """Problem in the reference's own form: max/min over y with LMIs sum_j y_j A_ij - A_i0 >= 0
         given as A[i] = [F_0, F_1, ..., F_n] and rows  C_lin' y <= d_lin.
         factors (optional): factors[i][k] = (V, d) with A[i][k + 1] = V diag(d) V' (V msz x r, r <= 16, d = +-1), used
-        instead of the factors datarank >= 1 would compute; checked against A (||A - V D V'||_F <= 5e-6, else ValueError)."""
+        instead of the factors datarank >= 1 would compute; checked against A (||A - V D V'||_F <= 5e-6, else ValueError).
+        local_support=True (opt-in): stored constraints that touch at most 32 rows and columns and are dense there -- element
+        matrices of a finite-element model -- are assembled from A[S, S] on their supports S instead of entry pair by entry
+        pair (library option pair_local); one GPU, kit = 0 and kit = 1 (where the CG operator goes through the assembled
+        Schur matrix).  Every other constraint keeps its route."""
+        self._local_support = self._check_local_support("load_model", local_support)
         self._pending = ("arrays", (A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense), factors))
         return self
 
@@ -235,6 +251,7 @@ class Optimizer:
             A, b, b_const, d_lin, C_lin, max_sense, factors = payload
             self.max_sense = max_sense
             model = build_model(A, b, b_const, d_lin, C_lin, datarank=drank, kappa=kappa, factors=factors)
+        model.local_support = self._local_support and kind in ("sdpa", "arrays")
         opts = dict(self.options)
         if self.silent:
             opts["verb"] = 0

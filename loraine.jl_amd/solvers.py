@@ -13,6 +13,7 @@ default of `optimizer.Optimizer` -- overrides them with the device-resident `lrn
 """
 import math
 import time
+import weakref
 
 import numpy as np
 import scipy.linalg as sla
@@ -27,6 +28,9 @@ DEFAULT_OPTIONS = {
     "preconditioner": 1, "erank": 1, "aamat": 1, "fig_ev": 0, "verb": 1, "datarank": 0,
     "initpoint": 0, "timing": 1, "maxit": 100, "datasparsity": 8,
 }
+
+# devices a solve with load_model(..., local_support=True) left at pair_local = 1: the next solve on one of them sets it back
+_PAIR_LOCAL_ON = weakref.WeakSet()
 
 
 def _vec(M):
@@ -119,6 +123,14 @@ class MySolver:
             self.dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes,
                                   B=model.B if len(model.B) else None,
                                   C_lin=model.C_lin if model.nlin else None)    # [GPU] one-time
+        # load_model(..., local_support=True): stored constraints with a small support through A[S, S].  False sets the option
+        # back to 0 on a device an earlier solve left at 1; a device that never had it on is at the library's default, 0
+        local = bool(getattr(model, "local_support", False))
+        if local or self.dev in _PAIR_LOCAL_ON:
+            self.dev.set_option("pair_local", 1 if local else 0)
+            (_PAIR_LOCAL_ON.add if local else _PAIR_LOCAL_ON.discard)(self.dev)
+        if local:
+            self._say(" ---Stored constraints with a support of at most 32 are assembled from A[S, S] (pair_local = 1)")
         # datarank = k >= 1: the rank-k factors of the data go to the device; a model whose data has no such form (or
         # k > 16) takes the general path, as the reference's docs promise (docs/src/Loraine_options.md).  kit = 0: the Schur
         # matrix from the factors (mode 1).  kit = 1: the CG path from them wherever the library's cost model finds that
