@@ -160,6 +160,13 @@ int lrn_get_constraint(lrn_ctx* ctx, int ilmi, int k, double* A_out);
  * supports, two small MFMA products per pair; one GPU -- an empty range or a sharded context counts "pair_local_skipped" and
  * takes the pair kernels, bit for bit; counts "pair_local_owners", "pair_local_pairs", timing "local"), "pair_local_min"
  * (>= 1, default 36 entries: read by the next lrn_upload_model),
+ * "pair_long" (0, default / 1; anything else: LRN_ERR_ARG -- 1: the sparse owners of a block with at least "pair_long_min" entries
+ * (>= 1: read by the next lrn_upload_model), a trace row or a band, are assembled from Z_i = (A_i W) on their rows, nnz_j |R_i|
+ * products per pair cut into slices of "pair_long_split" products (>= 1) over workgroups; partners with a support of at most 32
+ * through the FP64 MFMA unless "pair_long_mfma" is 0 (0 / 1); Z_i lives in a scratch of at most "pair_long_scratch_mb" MiB
+ * (>= 0, default 1024).  One GPU -- an empty range, an owner that does not fit the scratch or a sharded context counts
+ * "pair_long_skipped" and takes the pair kernels, bit for bit; counts "pair_long_owners", "pair_long_pairs",
+ * "pair_long_mfma_pairs", "pair_long_slices", timing "long"),
  * "jacobi_cross" (1: cross-pair rotations only after round 0), "jacobi_early" (relative level below which a sweep's
  * rotations make it the last one; 0 = always run the confirming sweep), "eigmin_pair" (the two
  * smallest-eigenvalue searches of a step-length computation: 2, default = their Lanczos runs in lock-step, one launch per

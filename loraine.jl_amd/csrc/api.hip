@@ -119,6 +119,30 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
     if (!(value >= 1.0 && value <= 1.0e9)) return set_error(c, LRN_ERR_ARG, "pair_local_min is a count of entries >= 1");
     c->opt.pair_local_min = (int)value;
   }
+  else if (!strcmp(key, "pair_long")) {       // (as pair_local: an H assembled under the other setting is not reused)
+    if (value != 0.0 && value != 1.0) return set_error(c, LRN_ERR_ARG, "pair_long is 0 or 1");
+    c->opt.pair_long = (int)value;
+    c->hop_version = -1;
+  }
+  else if (!strcmp(key, "pair_long_min")) {      // read by the next lrn_upload_model
+    if (!(value >= 1.0 && value <= 1.0e9)) return set_error(c, LRN_ERR_ARG, "pair_long_min is a count of entries >= 1");
+    c->opt.pair_long_min = (int)value;
+  }
+  else if (!strcmp(key, "pair_long_split")) {
+    if (!(value >= 1.0 && value <= 1.0e15)) return set_error(c, LRN_ERR_ARG, "pair_long_split is a count of products >= 1");
+    c->opt.pair_long_split = (long)value;
+    c->hop_version = -1;
+  }
+  else if (!strcmp(key, "pair_long_mfma")) {
+    if (value != 0.0 && value != 1.0) return set_error(c, LRN_ERR_ARG, "pair_long_mfma is 0 or 1");
+    c->opt.pair_long_mfma = (int)value;
+    c->hop_version = -1;
+  }
+  else if (!strcmp(key, "pair_long_scratch_mb")) {
+    if (!(value >= 0.0)) return set_error(c, LRN_ERR_ARG, "pair_long_scratch_mb is a size >= 0");
+    c->opt.pair_long_scratch_mb = value;
+    c->hop_version = -1;
+  }
   else if (!strcmp(key, "matvec_sparse")) c->opt.matvec_sparse = (int)value;
   else if (!strcmp(key, "prec_dense")) c->opt.prec_dense = (int)value;
   else if (!strcmp(key, "wmw_pattern_min")) c->opt.wmw_pattern_min = std::max(2, (int)value);

@@ -40,6 +40,20 @@ struct LmiBlock {
   std::vector<int> loc_sup;
   std::vector<double> loc_a;
   lrn::DBuf loc_sptr_d, loc_aptr_d, loc_sup_d, loc_a_d;   // int64 [nvar+1], int64 [nvar+1], int32, double
+  // long route of the sparse owners (option "pair_long", longops.hip; the lists: model_layout.h::block_long): eligible owners
+  // [nd, lg_hi).  As above the host lists wait for the first assembly by that route (lg_ready) and are emptied then; lg_rho, the
+  // number of distinct rows of every eligible owner, stays.  The launch plan (work items of the entry kernel, pairs of the reduce
+  // and of the MFMA kernel, owner batches and offsets of Zc) is rebuilt when lg_plan_key -- the options and ranges it depends
+  // on -- changes.  lg_z: Zc of one batch of owners, lg_part: one partial sum per work item
+  int lg_hi = 0;
+  bool lg_ready = false;
+  std::vector<long> lg_rptr, lg_eptr;
+  std::vector<int> lg_rows, lg_ec, lg_rho;
+  std::vector<double> lg_ev;
+  std::vector<long> lg_plan_key, lg_item_ptr, lg_pair_ptr, lg_mf_ptr;   // the three: [owners + 1] ranges of the tables by owner
+  std::vector<int> lg_batch;                                             // owner index at which each batch of Zc starts, and the end
+  lrn::DBuf lg_rptr_d, lg_rows_d, lg_eptr_d, lg_ec_d, lg_ev_d;          // int64, int32, int64, int32, double
+  lrn::DBuf lg_items_d, lg_pairs_d, lg_mf_d, lg_zoff_d, lg_z, lg_part;  // int4, int4, int2, int64 [owners], double, double
   // stored columns of AA (sparse constraints only) for the deterministic AA'x gather
   long ncq = 0;
   lrn::DBuf cq_q, cq_ptr;   // int64 [ncq], [ncq+1]
@@ -126,7 +140,8 @@ struct LmiBlock {
     return {&ent_ptr, &ent_r, &ent_c, &ent_v, &Adense, &tri_tab, &hidx, &sigma_d, &ipos_d, &cq_q, &cq_ptr, &cq_j, &cq_v,
             &pc_ptr, &pc_r, &pc_t, &ent_t, &Mv, &Zs, &b_ptr, &b_col, &b_val, &v_ptr, &v_col, &v_val, &v_w,
             &X, &S, &W, &G, &Gi, &Si, &D, &DDsi, &Vprev, &Cd, &Rd, &delX, &delS, &Xn, &Sn, &RNT, &t0, &t1, &t2,
-            &LXf, &LXt, &LSf, &Yh, &Zh, &Ki, &Bs, &TX, &Qm, &lyap, &Bd, &Vd, &Ys, &loc_sptr_d, &loc_aptr_d, &loc_sup_d, &loc_a_d};
+            &LXf, &LXt, &LSf, &Yh, &Zh, &Ki, &Bs, &TX, &Qm, &lyap, &Bd, &Vd, &Ys, &loc_sptr_d, &loc_aptr_d, &loc_sup_d, &loc_a_d,
+            &lg_rptr_d, &lg_rows_d, &lg_eptr_d, &lg_ec_d, &lg_ev_d, &lg_items_d, &lg_pairs_d, &lg_mf_d, &lg_zoff_d, &lg_z, &lg_part};
   }
 };
 
@@ -182,6 +197,13 @@ struct LrnOptions {
   int pair_local = 0;             // sparse owners with a small support, [loc_lo, loc_hi) of a block, through the dense A[S, S] on the
                                   // MFMA (localops.hip): 1, the pair kernels as always: 0.  One GPU ("pair_local_skipped" otherwise)
   int pair_local_min = 36;        // read by lrn_upload_model: entries from which on a sparse owner may take that route (model_layout.h)
+  int pair_long = 0;              // long sparse owners (a trace row, a band), [nd, lg_hi) of a block, from Z_i = (A_i W) on their rows
+                                  // (longops.hip): 1, the pair kernels as always: 0.  One GPU ("pair_long_skipped" otherwise)
+  int pair_long_min = 64;         // read by lrn_upload_model: entries from which on a sparse owner may take that route (measured:
+                                  // model_layout.h, PAIR_LONG_MIN)
+  long pair_long_split = 1L << 15; // products nnz_j rho_i of a pair per slice of the entry kernel (measured: PAIR_LONG_SPLIT)
+  int pair_long_mfma = 1;         // partners with local lists (support <= 32) through the FP64 MFMA: 1, through the entry kernel: 0
+  double pair_long_scratch_mb = 1024.0;   // cap of Zc, the scratch of that route; an owner that does not fit: the route is skipped
   int matvec_sparse = 0;          // 0 auto, 1 dense GEMM path, 2 sparse path whenever the pattern allows
   int shard_products = 1;         // multi-GPU: the n^3 products of the resident path (Newton-Schulz, Lyapunov CG, step) by
   int shard_products_min = 4096;  // column blocks + all-gather from this matrix side on (one product of 10^4: 31 ms; below, the

@@ -110,6 +110,8 @@ extern "C" int lrn_dbg_model_layout(const char* name, int msz, int nvar, const i
   o.ints("ent_t", L.ent_t); o.ints("sp_long_cols", L.sp_long_cols);
   o.scalar("loc_lo", L.loc_lo); o.scalar("loc_hi", L.loc_hi); o.ints("loc_sptr", L.loc_sptr); o.ints("loc_sup", L.loc_sup);
   o.ints("loc_aptr", L.loc_aptr); o.reals("loc_a", L.loc_a);
+  o.scalar("lg_hi", L.lg_hi); o.ints("lg_rptr", L.lg_rptr); o.ints("lg_rows", L.lg_rows); o.ints("lg_eptr", L.lg_eptr);
+  o.ints("lg_ec", L.lg_ec); o.reals("lg_ev", L.lg_ev);
   if (!o.found && B_colptr && !strncmp(name, "b_", 2)) {
     RankOneLayout R;
     rank_one_layout(msz, nvar, B_colptr, B_rowval, B_nzval, L.ipos, pos_space != 0, R);

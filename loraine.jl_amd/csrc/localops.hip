@@ -122,8 +122,8 @@ __global__ __launch_bounds__(64 * LC_WAVES) void local_pair_kernel(
   }
 }
 
-// the device copies of the lists, on the first assembly that takes the route
-static int local_upload(lrn_ctx* c, LmiBlock& b) {
+// the device copies of the lists, on the first assembly that takes the route (or the long route's MFMA kernel, longops.hip)
+int local_upload(lrn_ctx* c, LmiBlock& b) {
   if (b.loc_ready) return LRN_OK;
   LRN_TRY(upload(c, b.loc_sptr_d, b.loc_sptr));
   LRN_TRY(upload(c, b.loc_aptr_d, b.loc_aptr));

@@ -84,6 +84,16 @@ static int upload_block(lrn_ctx* c, LmiBlock& b, BlockLayout& L) {
   b.loc_aptr.swap(L.loc_aptr);
   b.loc_sup.swap(L.loc_sup);
   b.loc_a.swap(L.loc_a);
+  b.lg_hi = L.lg_hi;        // (the same for the long route: longops.hip)
+  b.lg_ready = false;
+  b.lg_plan_key.clear();
+  b.lg_rho.clear();
+  for (size_t k = 0; k + 1 < L.lg_rptr.size(); ++k) b.lg_rho.push_back((int)(L.lg_rptr[k + 1] - L.lg_rptr[k]));
+  b.lg_rptr.swap(L.lg_rptr);
+  b.lg_eptr.swap(L.lg_eptr);
+  b.lg_rows.swap(L.lg_rows);
+  b.lg_ec.swap(L.lg_ec);
+  b.lg_ev.swap(L.lg_ev);
   LRN_TRY(upload(c, b.cq_q, L.cq_q));
   LRN_TRY(upload(c, b.cq_ptr, L.cq_ptr));
   LRN_TRY(upload(c, b.cq_j, L.cq_j));
@@ -173,7 +183,7 @@ static int upload_model(lrn_ctx* c, int nlmi, int nvar, const int64_t* msizes, c
     (void)hipMemGetInfo(&free_b, &total_b);
     BlockLayout L;
     LRN_LAYOUT(c, block_layout(m, nvar, AA_colptr[il], AA_rowval[il], AA_nzval[il], sigmaA + (long)il * nvar, qA[2 * il],
-                               c->pos_space, c->opt.dense_threshold, free_b, L, c->opt.pair_local_min));
+                               c->pos_space, c->opt.dense_threshold, free_b, L, c->opt.pair_local_min, c->opt.pair_long_min));
     LRN_TRY(upload_block(c, b, L));
     LRN_TRY(scatter_dense_prefix(c, b));
     b.has_B = false;

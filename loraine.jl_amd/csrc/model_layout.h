@@ -54,12 +54,36 @@ struct BlockLayout {
   std::vector<long> loc_sptr, loc_aptr;
   std::vector<int> loc_sup;
   std::vector<double> loc_a;
+  // long route of the sparse owners (block_long, longops.hip): the eligible owners are [nd, lg_hi).  For position nd + k the
+  // ascending distinct row indices R at lg_rows[lg_rptr[k] ..), and for the g-th row of lg_rows its entries in ascending column
+  // order at lg_ec / lg_ev[lg_eptr[g] ..) (value = ent_v); all five lists are empty when lg_hi == nd
+  int lg_hi = 0;
+  std::vector<long> lg_rptr, lg_eptr;
+  std::vector<int> lg_rows, lg_ec;
+  std::vector<double> lg_ev;
   long nent() const { return (long)ent_r.size(); }
   long ncq() const { return (long)cq_q.size(); }
 };
 
 constexpr int LOCAL_SUPPORT_MAX = 32;      // side of the largest support the local route takes: two MFMA tiles of 16
 constexpr int PAIR_LOCAL_MIN = 36;         // default of option pair_local_min: the measured cross-over, a dense support of 6
+
+// Defaults of the options pair_long_min and pair_long_split, both measured: the smallest diag(a) row from which
+// the route beats the pair kernels by more than both spreads beside 400 tiny partners, and the fastest slice size on the identity
+// self pair at msz 2000 (2^14 .. 2^16 give 61 .. 64 slices there and lie within each other's spread)
+constexpr int PAIR_LONG_MIN = 64;
+constexpr long PAIR_LONG_SPLIT = 1L << 15;
+constexpr int LONG_SLICES_MAX = 64;
+
+// slices of one pair of the long route's entry kernel: nnz_j * rho_i products above `split` are cut into
+// ceil(work / split) slices of `*per` consecutive entries of the partner, at most LONG_SLICES_MAX; a function of (nnz_j, rho_i) alone
+inline int long_slices(long nnz_j, long rho_i, long split, long* per) {
+  const long work = nnz_j * rho_i;
+  long ns = split > 0 ? (work + split - 1) / split : 1;
+  ns = std::max(1L, std::min({ns, (long)LONG_SLICES_MAX, nnz_j}));
+  *per = (nnz_j + ns - 1) / ns;
+  return (int)((nnz_j + *per - 1) / *per);
+}
 
 // dense (MFMA) prefix by cost model: pair path cost nnz_p * suffix_nnz vs 3 m^3 GEMM work; dense_threshold >= 0 decides
 // instead of the model; at most 0.55 of free_bytes go to the dense copies
@@ -238,16 +262,47 @@ inline void block_local(int m, int pair_local_min, BlockLayout& L) {
   }
 }
 
+// the eligible owners of the long route and their lists (option pair_long, longops.hip): H_ij from Z_i = (A_i W) on the
+// distinct rows R_i of A_i, nnz_i msz flop once per owner and nnz_j |R_i| per pair.  lg_hi: the first position of [nd, q_wave)
+// with fewer than pair_long_min entries -- positions are sorted by decreasing nnz, so the owners are a prefix.  The entries of
+// a position come ordered by (column, row); a stable sort by row gives every row its entries in ascending column order.
+// Nothing is scanned or built when no sparse owner reaches pair_long_min entries.
+inline void block_long(int m, int pair_long_min, BlockLayout& L) {
+  (void)m;
+  int hi = L.nd;
+  while (hi < L.q_wave && L.nnz[hi] >= pair_long_min) ++hi;
+  L.lg_hi = hi;
+  if (hi == L.nd) return;
+  L.lg_rptr.assign(1, 0);
+  L.lg_eptr.assign(1, 0);
+  std::vector<long> order;
+  for (int p = L.nd; p < hi; ++p) {
+    order.resize((size_t)(L.ent_ptr[p + 1] - L.ent_ptr[p]));
+    for (size_t k = 0; k < order.size(); ++k) order[k] = L.ent_ptr[p] + (long)k;
+    std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return L.ent_r[a] < L.ent_r[b]; });
+    for (size_t k = 0; k < order.size(); ++k) {
+      const long e = order[k];
+      if (k > 0 && L.ent_r[e] != L.ent_r[order[k - 1]]) L.lg_eptr.push_back((long)L.lg_ec.size());
+      if (k == 0 || L.ent_r[e] != L.ent_r[order[k - 1]]) L.lg_rows.push_back(L.ent_r[e]);
+      L.lg_ec.push_back(L.ent_c[e]);
+      L.lg_ev.push_back(L.ent_v[e]);
+    }
+    L.lg_eptr.push_back((long)L.lg_ec.size());
+    L.lg_rptr.push_back((long)L.lg_rows.size());
+  }
+}
+
 // the whole block.  pos_space: the Schur matrix is kept in position space (nlmi == 1); free_bytes: the free device memory
 inline LayoutError block_layout(int m, int nvar, const int64_t* cp, const int64_t* rv, const double* nz, const int64_t* sigma1,
                                 int64_t qA, bool pos_space, double dense_threshold, size_t free_bytes, BlockLayout& L,
-                                int pair_local_min = PAIR_LOCAL_MIN) {
+                                int pair_local_min = PAIR_LOCAL_MIN, int pair_long_min = PAIR_LONG_MIN) {
   L = BlockLayout();
   if (LayoutError e = block_entries(m, nvar, cp, rv, nz, sigma1, qA, L)) return e;
   L.nd = dense_prefix(L.nnz, L.qA, L.npos_nz, m, nvar, dense_threshold, free_bytes);
   L.q_wave = L.nd;
   while (L.q_wave < L.npos_nz && L.nnz[L.q_wave] > 4) L.q_wave++;
   block_local(m, pair_local_min, L);
+  block_long(m, pair_long_min, L);
   block_stored_columns(m, cp, rv, nz, L);
   block_pattern(m, L);
   L.hidx.resize(nvar);

@@ -86,6 +86,12 @@ bool chol_path_applicable(lrn_ctx* c, LmiBlock& b, long* pcap_out);
 // localops.hip: the sparse owners [loc_lo, loc_hi) of a block against all their partners, from A[S, S] on the supports
 // (option "pair_local"); the caller has checked that the range is not empty and that one GPU runs
 int assemble_local(lrn_ctx* c, LmiBlock& b);
+int local_upload(lrn_ctx* c, LmiBlock& b);      // the device copies of that route's lists, once per upload
+// longops.hip: the long sparse owners [nd, lg_end) of a block against all their partners, from Z_i = (A_i W) on their rows
+// (option "pair_long").  long_fits: the scratch cap admits every owner of the range one at a time; the caller has checked it,
+// that the range is not empty and that one GPU runs
+bool long_fits(const lrn_ctx* c, const LmiBlock& b, int lg_end);
+int assemble_long(lrn_ctx* c, LmiBlock& b, int lg_end);
 // schur_factored.hip: rank-one data (mode -1), rank-k data (mode 1), cross terms of a hybrid factored block
 int assemble_rank1(lrn_ctx* c, LmiBlock& b);
 int assemble_lowrank(lrn_ctx* c, LmiBlock& b);

@@ -18,7 +18,8 @@
 //        nnz_i x nnz_j product terms a_e a_f W[c_e,r_f] W[c_f,r_e]   (the _dot kernel);
 //        owners with <= 4 nonzeros use one THREAD per entry (the nnz==1 fast path,
 //        makeBBBB.jl:188-209, is its 1x1 case).  Option "pair_local": owners whose partners all have a support of at most
-//        32 rows and columns take the dense A[S, S] on the MFMA instead (localops.hip).
+//        32 rows and columns take the dense A[S, S] on the MFMA instead (localops.hip).  Option "pair_long": long sparse
+//        owners (a trace row, a band) from Z_i = (A_i W) on their rows, nnz_j |R_i| per pair, sliced (longops.hip).
 //   rank-one data (mode -1): BG = B G (sparse x dense), H += (BG BG').^2 with the square
 //        fused in the MFMA GEMM epilogue (makeBBBB.jl:7-14).
 //   rank-k data (mode 1): U = G' V, H += blocksum(d d' .* (U'U).^2) over khat x khat blocks, again in the
@@ -171,7 +172,14 @@ static int assemble_sparse(lrn_ctx* c, LmiBlock& b) {
   // below are the ones there always were
   const bool local_on = c->opt.pair_local != 0 && c->world == 1 && b.loc_hi > b.loc_lo;
   if (c->opt.pair_local != 0 && !local_on) c->counts["pair_local_skipped"] += 1;
-  const int wave_parts[2][2] = {{b.nd, local_on ? b.loc_lo : b.q_wave}, {local_on ? b.loc_hi : b.q_wave, b.q_wave}};
+  // option "pair_long": the long owners [nd, lg_end) go to assemble_long (longops.hip) with all their partners; where both
+  // routes could take an owner the local route keeps it.  One GPU, and Zc of every owner within the scratch cap; otherwise
+  // "pair_long_skipped" and, again, the launches there always were
+  const int lg_end = local_on ? std::min(b.lg_hi, b.loc_lo) : b.lg_hi;
+  const bool long_on = c->opt.pair_long != 0 && c->world == 1 && lg_end > b.nd && long_fits(c, b, lg_end);
+  if (c->opt.pair_long != 0 && !long_on) c->counts["pair_long_skipped"] += 1;
+  const int wave_lo = long_on ? lg_end : b.nd;
+  const int wave_parts[2][2] = {{wave_lo, local_on ? b.loc_lo : b.q_wave}, {local_on ? b.loc_hi : b.q_wave, b.q_wave}};
   tic(c);
   if (b.q_wave > b.nd) {
     // entries per wavefront by the typical product length: mean nnz of the sparse owners squared
@@ -209,6 +217,7 @@ static int assemble_sparse(lrn_ctx* c, LmiBlock& b) {
   }
   toc(c, "sparse");
   if (local_on) LRN_TRY(assemble_local(c, b));
+  if (long_on) LRN_TRY(assemble_long(c, b, lg_end));
   return LRN_OK;
 }
 

@@ -45,6 +45,7 @@ class Optimizer:
         self._device_index = device_index
         self._pending = None
         self._local_support = False
+        self._long_rows = False
 
     # ---- MOI.RawOptimizerAttribute (MOI_wrapper.jl:86-103)
     def supports(self, name):
@@ -67,11 +68,13 @@ class Optimizer:
         return "Loraine"
 
     # ---- model input (copy_to, :142-232): options are frozen here, like in the reference (:224)
-    def read_from_file(self, path, detect_kmax=None, local_support=False):
+    def read_from_file(self, path, detect_kmax=None, local_support=False, long_rows=False):
         """detect_kmax = 16 or 64: the constraint matrices of the file go through load_detected_model(kmax=detect_kmax) with
         its defaults; None (default): the file is loaded as it always was.
-        local_support: as in load_model (the file loaded as it always was: detect_kmax=None)."""
+        local_support: as in load_model (the file loaded as it always was: detect_kmax=None).
+        long_rows: as in load_model, with either way of loading the file."""
         self._local_support = self._check_local_support("read_from_file", local_support)
+        self._long_rows = self._check_flag("read_from_file", "long_rows", long_rows)
         if detect_kmax is None:
             self._pending = ("sdpa", path)
             return self
@@ -90,7 +93,14 @@ class Optimizer:
             raise ValueError(f"{who}: local_support is False or True, not {value!r}")
         return bool(value)
 
-    def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factors=None, local_support=False):
+    @staticmethod
+    def _check_flag(who, name, value):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: {name} is False or True, not {value!r}")
+        return bool(value)
+
+    def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factors=None, local_support=False,
+                   long_rows=False):
         """Problem in the reference's own form: max/min over y with LMIs sum_j y_j A_ij - A_i0 >= 0
         given as A[i] = [F_0, F_1, ..., F_n] and rows  C_lin' y <= d_lin.
         factors (optional): factors[i][k] = (V, d) with A[i][k + 1] = V diag(d) V' (V msz x r, r <= 16, d = +-1), used
@@ -98,13 +108,18 @@ class Optimizer:
         local_support=True (opt-in): stored constraints that touch at most 32 rows and columns and are dense there -- element
         matrices of a finite-element model -- are assembled from A[S, S] on their supports S instead of entry pair by entry
         pair (library option pair_local); one GPU, kit = 0 and kit = 1 (where the CG operator goes through the assembled
-        Schur matrix).  Every other constraint keeps its route."""
+        Schur matrix).  Every other constraint keeps its route.
+        long_rows=True (opt-in): long sparse stored constraints -- a trace row, a weighted-trace row diag(a), a band: hundreds of
+        entries on up to msz rows, kept sparse -- are assembled from Z = (A W) on their rows, sliced over workgroups, instead of
+        on one wavefront per pair (library option pair_long); one GPU, kit = 0 and kit = 1.  Independent of local_support: both
+        may be on, and where both could take a constraint local_support keeps it."""
         self._local_support = self._check_local_support("load_model", local_support)
+        self._long_rows = self._check_flag("load_model", "long_rows", long_rows)
         self._pending = ("arrays", (A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense), factors))
         return self
 
     def load_factored_model(self, F0, factors, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factored_form=-1,
-                            cg=False, ragged=False, wide=False):
+                            cg=False, ragged=False, wide=False, long_rows=False):
         """The same problem given by its factors alone: F0[i] the constant matrix of block i (the A[i][0] of load_model),
         factors[i][k] = (V, d) with A_i,k+1 = V diag(d) V' (V msz x r, r <= 16 -- r <= 64 with wide=True --, d = +-1, dense or
         sparse).  No A_ik, no row of AA and no dense constraint slab is ever formed, on the host or on the device; implies datarank = the
@@ -134,7 +149,9 @@ class Optimizer:
         with 17 .. 64 factors and a trace row (None, [], ones) beside it go in as factors and diagonal rows (library option
         wide_diag beside lowrank_wide).  Combines with ragged= and cg= as wide=True does; kit = 1 on such a model needs cg="diag".
         factored_form: -1 (auto) materialises a block whose factors are tiny -- sum_k nnz(V_k V_k') at most datasparsity
-        times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored."""
+        times the number of constraints -- as sparse AA, the existing path; 1 keeps every block factored.
+        long_rows=True (opt-in): as in load_model, for the stored matrices of a hybrid block (H_SS of a stored trace row)."""
+        self._long_rows = self._check_flag("load_factored_model", "long_rows", long_rows)
         if not isinstance(wide, bool) and not (isinstance(wide, str) and wide == "diag"):
             raise ValueError(f"load_factored_model: wide is False or True (or \"diag\"), not {wide!r}")
         if not self.resident:
@@ -155,7 +172,7 @@ class Optimizer:
                             seed=0, host_side=None)
 
     def load_detected_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, kmax=16, max_stored=16,
-                            cg=False, ragged=False, factored_form=-1, budget_mb=None, seed=0, host_side=None):
+                            cg=False, ragged=False, factored_form=-1, budget_mb=None, seed=0, host_side=None, long_rows=False):
         """The problem of load_model, given as matrices, solved as load_factored_model would solve it: every constraint matrix
         that is V diag(d) V' with at most kmax columns becomes a factor, the others stay stored matrices beside them (hybrid
         blocks).  The factors are found when the model goes to the device (detect.detect_factors: the device for dense
@@ -165,7 +182,9 @@ class Optimizer:
         cg, ragged, factored_form: as in load_factored_model, with the same checks (kit = 1 needs cg=True).
         Fallback: the whole model takes the general path -- build_model, bit for bit what load_model does -- when no constraint
         was accepted, or when some block would keep more than max_stored stored constraints with more than `datasparsity`
-        non-zeros; `detect_report` of the optimizer and `lowrank_note` of the model say which route was taken and why."""
+        non-zeros; `detect_report` of the optimizer and `lowrank_note` of the model say which route was taken and why.
+        long_rows=True (opt-in): as in load_model, for the constraints that stay stored matrices."""
+        self._long_rows = self._check_flag("load_detected_model", "long_rows", long_rows)
         if not self.resident:
             raise ValueError(self._NEEDS_RESIDENT)
         if isinstance(kmax, bool) or kmax not in (16, 64):
@@ -252,6 +271,7 @@ class Optimizer:
             self.max_sense = max_sense
             model = build_model(A, b, b_const, d_lin, C_lin, datarank=drank, kappa=kappa, factors=factors)
         model.local_support = self._local_support and kind in ("sdpa", "arrays")
+        model.long_rows = self._long_rows
         opts = dict(self.options)
         if self.silent:
             opts["verb"] = 0

@@ -31,6 +31,8 @@ DEFAULT_OPTIONS = {
 
 # devices a solve with load_model(..., local_support=True) left at pair_local = 1: the next solve on one of them sets it back
 _PAIR_LOCAL_ON = weakref.WeakSet()
+# ... and the same for long_rows=True and pair_long
+_PAIR_LONG_ON = weakref.WeakSet()
 
 
 def _vec(M):
@@ -131,6 +133,13 @@ class MySolver:
             (_PAIR_LOCAL_ON.add if local else _PAIR_LOCAL_ON.discard)(self.dev)
         if local:
             self._say(" ---Stored constraints with a support of at most 32 are assembled from A[S, S] (pair_local = 1)")
+        # long_rows=True of the loaders: long sparse stored constraints from Z = (A W) on their rows; set and set back the same way
+        long_rows = bool(getattr(model, "long_rows", False))
+        if long_rows or self.dev in _PAIR_LONG_ON:
+            self.dev.set_option("pair_long", 1 if long_rows else 0)
+            (_PAIR_LONG_ON.add if long_rows else _PAIR_LONG_ON.discard)(self.dev)
+        if long_rows:
+            self._say(" ---Long sparse stored constraints are assembled from Z = (A W) on their rows (pair_long = 1)")
         # datarank = k >= 1: the rank-k factors of the data go to the device; a model whose data has no such form (or
         # k > 16) takes the general path, as the reference's docs promise (docs/src/Loraine_options.md).  kit = 0: the Schur
         # matrix from the factors (mode 1).  kit = 1: the CG path from them wherever the library's cost model finds that
