@@ -524,6 +524,18 @@ int lrn_dbg_model_layout(const char* name, int msz, int nvar, const int64_t* AA_
 int lrn_dbg_factor_layout(const char* name, int msz, int nvar, const int64_t* ipos, int npos_nz, int pos_space, int khat,
                           const int64_t* V_colptr, const int64_t* V_rowval, const double* V_nzval, const double* d, int64_t nrows,
                           const int64_t* rows, int64_t* count, int64_t* iout, double* dout, char* msg, int msg_len);
+/* The keys of lrn_set_option (csrc/options.h), on the host alone.  lrn_dbg_option_name: the index-th key it accepts -- the value
+ * options of the table, then the keys the context serves itself -- or NULL past the end. */
+const char* lrn_dbg_option_name(int index);
+/* lrn_set_option(key, value) on a context that exists on the host only (no stream, no device call, one block), started from
+ * hop_version = 7, t_cap = 5 and p_cap = 6 of its block and one entry in the timing and the count map.  *rc = what
+ * lrn_set_option returned, msg = the error text it left (msg_len bytes), opt_bytes = the first opt_cap bytes of the options
+ * struct afterwards, *opt_size = its size, watched14 = { hop_version, profile, lz_res_limit, lz_wh_left, lz_wh_fired, lz_wh_run,
+ * lz_wh_step, lz_wh_wg, shard_bs_opt, shard_bs, t_cap, p_cap, timing entries, count entries }.  key = NULL: nothing is set (the
+ * defaults).  Returns LRN_ERR_ARG for the keys whose action needs a device or a communicator: "comm_fail_ensure",
+ * "detect_release". */
+int lrn_dbg_option_probe(const char* key, double value, int* rc, char* msg, int msg_len, unsigned char* opt_bytes, int opt_cap,
+                         int* opt_size, int64_t* watched14);
 int lrn_dbg_mfma_probe(lrn_ctx* ctx, const double* A16x4, const double* B4x16, double* D16x16);
 int lrn_dbg_potrf(lrn_ctx* ctx, int n, double* A, int* info);
 int lrn_dbg_potrs(lrn_ctx* ctx, int n, const double* A, const double* b, double* x, int* info);

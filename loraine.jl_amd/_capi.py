@@ -99,6 +99,8 @@ SIGNATURES = {
     "lrn_dbg_factor_layout": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, PI64, C.c_void_p, C.c_void_p,
                                         C.c_char_p, C.c_int]),
+    "lrn_dbg_option_name": (C.c_char_p, [C.c_int]),
+    "lrn_dbg_option_probe": (C.c_int, [C.c_char_p, C.c_double, PI, C.c_char_p, C.c_int, C.c_void_p, C.c_int, PI, PI64]),
     "lrn_dbg_mfma_probe": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrn_dbg_potrf": (C.c_int, [c_ctx, C.c_int, C.c_void_p, PI]),
     "lrn_dbg_potrs": (C.c_int, [c_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, PI]),

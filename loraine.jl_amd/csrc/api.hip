@@ -4,12 +4,15 @@
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
 #include "ops.h"
+#include "options.h"
 #include "prec.h"
 #include "schur_plan.h"
 
 using namespace lrn;
 
 void lrn_detect_free(lrn_ctx* c);
+
+static_assert(OPT_OK == LRN_OK && OPT_ERR_ARG == LRN_ERR_ARG, "options.h returns the library's codes");
 
 extern "C" {
 
@@ -89,91 +92,18 @@ const char* lrn_last_error(lrn_ctx* c) {
 
 int lrn_set_option(lrn_ctx* c, const char* key, double value) {
   if (!c || !key) return LRN_ERR_ARG;
-  if (!strcmp(key, "dense_threshold")) c->opt.dense_threshold = value;
-  else if (!strcmp(key, "profile")) c->profile = value != 0.0;
-  else if (!strcmp(key, "t_batch")) { c->opt.t_batch = (long)value; for (auto& b : c->lmi) b.t_cap = b.p_cap = 0; }
-  else if (!strcmp(key, "p_batch")) { c->opt.p_batch = (long)value; for (auto& b : c->lmi) b.t_cap = b.p_cap = 0; }
-  else if (!strcmp(key, "prec_eig")) c->opt.prec_eig = (int)value;
-  else if (!strcmp(key, "pivot_boost")) c->opt.pivot_boost = value;
-  else if (!strcmp(key, "schur_chol")) c->opt.schur_chol = (int)value;
-  else if (!strcmp(key, "schur_plan")) c->opt.schur_plan = (int)value;
-  else if (!strcmp(key, "gemm3_ksplit")) c->opt.gemm3_ksplit = (int)value;
-  else if (!strcmp(key, "gemm_no_skip")) c->opt.gemm_no_skip = (int)value;
-  else if (!strcmp(key, "gemm_dyn_masks")) c->opt.gemm_dyn_masks = (int)value;
-  else if (!strcmp(key, "gemm1_diag")) c->opt.gemm1_diag = (int)value;
-  else if (!strcmp(key, "gemm_lab")) c->opt.gemm_lab = (int)value & 127;
-  else if (!strcmp(key, "gemm3_sched")) c->opt.gemm3_sched = (int)value;
-  else if (!strcmp(key, "gemm3_tile")) c->opt.gemm3_tile = (int)value;
-  else if (!strcmp(key, "gemm3_strip")) c->opt.gemm3_strip = (int)value;
-  else if (!strcmp(key, "gemm3_stagger")) c->opt.gemm3_stagger = (int)value;
-  else if (!strcmp(key, "jacobi_wgs")) c->opt.jacobi_wgs = (int)value;
-  else if (!strcmp(key, "jacobi_block")) c->opt.jacobi_block = (int)value;
-  else if (!strcmp(key, "jacobi_inner")) c->opt.jacobi_inner = (int)value;
-  else if (!strcmp(key, "pair_lanes")) c->opt.pair_lanes = (int)value;
-  else if (!strcmp(key, "pair_local")) {      // (an H assembled under the other setting is not reused by the CG operator)
-    if (value != 0.0 && value != 1.0) return set_error(c, LRN_ERR_ARG, "pair_local is 0 or 1");
-    c->opt.pair_local = (int)value;
-    c->hop_version = -1;
+  // a value option: the table of options.h stores it, the context pays what the table says it owes
+  unsigned effects = 0;
+  const char* msg = nullptr;
+  const int rc = option_apply(c->opt, key, value, &effects, &msg);
+  if (rc == LRN_ERR_ARG) return set_error(c, LRN_ERR_ARG, "%s", msg);
+  if (rc == LRN_OK) {
+    if (effects & OPT_INVALIDATES_HOP) c->hop_version = -1;
+    if (effects & OPT_RESETS_BATCH_CAPS) for (auto& b : c->lmi) b.t_cap = b.p_cap = 0;
+    return LRN_OK;
   }
-  else if (!strcmp(key, "pair_local_min")) {      // read by the next lrn_upload_model
-    if (!(value >= 1.0 && value <= 1.0e9)) return set_error(c, LRN_ERR_ARG, "pair_local_min is a count of entries >= 1");
-    c->opt.pair_local_min = (int)value;
-  }
-  else if (!strcmp(key, "pair_long")) {       // (as pair_local: an H assembled under the other setting is not reused)
-    if (value != 0.0 && value != 1.0) return set_error(c, LRN_ERR_ARG, "pair_long is 0 or 1");
-    c->opt.pair_long = (int)value;
-    c->hop_version = -1;
-  }
-  else if (!strcmp(key, "pair_long_min")) {      // read by the next lrn_upload_model
-    if (!(value >= 1.0 && value <= 1.0e9)) return set_error(c, LRN_ERR_ARG, "pair_long_min is a count of entries >= 1");
-    c->opt.pair_long_min = (int)value;
-  }
-  else if (!strcmp(key, "pair_long_split")) {
-    if (!(value >= 1.0 && value <= 1.0e15)) return set_error(c, LRN_ERR_ARG, "pair_long_split is a count of products >= 1");
-    c->opt.pair_long_split = (long)value;
-    c->hop_version = -1;
-  }
-  else if (!strcmp(key, "pair_long_mfma")) {
-    if (value != 0.0 && value != 1.0) return set_error(c, LRN_ERR_ARG, "pair_long_mfma is 0 or 1");
-    c->opt.pair_long_mfma = (int)value;
-    c->hop_version = -1;
-  }
-  else if (!strcmp(key, "pair_long_scratch_mb")) {
-    if (!(value >= 0.0)) return set_error(c, LRN_ERR_ARG, "pair_long_scratch_mb is a size >= 0");
-    c->opt.pair_long_scratch_mb = value;
-    c->hop_version = -1;
-  }
-  else if (!strcmp(key, "matvec_sparse")) c->opt.matvec_sparse = (int)value;
-  else if (!strcmp(key, "prec_dense")) c->opt.prec_dense = (int)value;
-  else if (!strcmp(key, "wmw_pattern_min")) c->opt.wmw_pattern_min = std::max(2, (int)value);
-  else if (!strcmp(key, "profile_symv")) c->opt.profile_symv = (int)value;
-  else if (!strcmp(key, "profile_ops")) c->opt.profile_ops = (int)value;
-  else if (!strcmp(key, "matvec_h")) { c->opt.matvec_h = (int)value; c->hop_version = -1; }
-  else if (!strcmp(key, "comm_fail_ensure")) lrn::comm_inject_ensure_failure(c);      // test hook (tests/test_gpu_comm.py)
-  else if (!strcmp(key, "pcg_lookahead")) c->opt.pcg_lookahead = std::max(0, std::min(8, (int)value));
-  else if (!strcmp(key, "lowrank_form")) c->opt.lowrank_form = std::max(-1, std::min(1, (int)value));
-  else if (!strcmp(key, "lowrank_ragged")) { c->opt.lowrank_ragged = value != 0.0 ? 1 : 0; c->hop_version = -1; }
-  else if (!strcmp(key, "lowrank_wide")) { c->opt.lowrank_wide = value != 0.0 ? 1 : 0; c->hop_version = -1; }
-  else if (!strcmp(key, "wide_diag")) { c->opt.wide_diag = value != 0.0 ? 1 : 0; c->hop_version = -1; }
-  else if (!strcmp(key, "ragged_ops")) { c->opt.ragged_ops = value != 0.0 ? 1 : 0; c->hop_version = -1; }
-  else if (!strcmp(key, "ragged_cross")) { c->opt.ragged_cross = value != 0.0 ? 1 : 0; c->hop_version = -1; }
-  else if (!strcmp(key, "ragged_ts")) c->opt.ragged_ts = value != 0.0 ? 1 : 0;
-  else if (!strcmp(key, "ragged_ops_split")) c->opt.ragged_ops_split = std::max(0, std::min(16, (int)value));
-  else if (!strcmp(key, "cg_lowrank")) {      // (the operator choice is taken again; an H of the other mode is not reused)
-    c->opt.cg_lowrank = std::max(-1, std::min(1, (int)value));
-    c->hop_version = -1;
-  }
-  else if (!strcmp(key, "cg_factored")) { c->opt.cg_factored = value != 0.0 ? 1 : 0; c->hop_version = -1; }
-  else if (!strcmp(key, "cg_diag")) { c->opt.cg_diag = value != 0.0 ? 1 : 0; c->hop_version = -1; }
-  else if (!strcmp(key, "hop_max_mb")) { c->opt.hop_max_mb = value < 0.0 ? -1.0 : value; c->hop_version = -1; }
-  else if (!strcmp(key, "fac_op_scaled")) { c->opt.fac_op_scaled = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }
-  else if (!strcmp(key, "fac_quadform")) { c->opt.fac_quadform = std::max(-1, std::min(1, (int)value)); c->hop_version = -1; }
-  else if (!strcmp(key, "diag_sq_mfma")) c->opt.diag_sq_mfma = std::max(-1, std::min(1, (int)value));
-  else if (!strcmp(key, "fac_cross_lds")) c->opt.fac_cross_lds = std::max(-1, std::min(1, (int)value));
-  else if (!strcmp(key, "jacobi_cross")) c->opt.jacobi_cross = (int)value;
-  else if (!strcmp(key, "jacobi_early")) c->opt.jacobi_early = value;
-  else if (!strcmp(key, "eigmin_pair")) c->opt.eigmin_pair = (int)value;
-  else if (!strcmp(key, "lz_resident")) c->opt.lz_resident = (int)value;
+  // state of the context, actions and test hooks (options.h::kContextOptions)
+  if (!strcmp(key, "profile")) c->profile = value != 0.0;
   else if (!strcmp(key, "lz_res_limit")) {      // an option can shorten the wait of a resident launch, never lengthen it
     if (!(value == value)) return LRN_ERR_ARG;
     c->lz_res_limit = (long long)std::max(1000.0, std::min(2000000.0, value));
@@ -185,22 +115,8 @@ int lrn_set_option(lrn_ctx* c, const char* key, double value) {
     c->lz_wh_left = code % 100000;
     c->lz_wh_run = (int)(sel % 2); c->lz_wh_step = (int)(sel / 2 % 3); c->lz_wh_wg = (int)(sel / 6);
   }
-  else if (!strcmp(key, "prepw_streams")) c->opt.prepw_streams = (int)value;
-  else if (!strcmp(key, "jacobi_warm")) c->opt.jacobi_warm = value != 0.0;
-  else if (!strcmp(key, "nt_mode")) c->opt.nt_mode = (int)value;
-  else if (!strcmp(key, "prec_inv")) c->opt.prec_inv = (int)value;
-  else if (!strcmp(key, "shard_passes")) c->opt.shard_passes = (int)value;
-  else if (!strcmp(key, "shard_products")) c->opt.shard_products = (int)value;
-  else if (!strcmp(key, "shard_products_min")) c->opt.shard_products_min = std::max(16, (int)value);
-  else if (!strcmp(key, "ns_l0")) c->opt.ns_l0 = value;
-  else if (!strcmp(key, "ns_maxit")) c->opt.ns_maxit = (int)value;
-  else if (!strcmp(key, "ns_lanczos")) c->opt.ns_lanczos = (int)value;
-  else if (!strcmp(key, "ns_lanczos_min")) c->opt.ns_lanczos_min = std::max(8, (int)value);
-  else if (!strcmp(key, "ns_dual")) c->opt.ns_dual = (int)value;
-  else if (!strcmp(key, "lyap_tol")) c->opt.lyap_tol = value;
-  else if (!strcmp(key, "lyap_maxit")) c->opt.lyap_maxit = (int)value;
-  else if (!strcmp(key, "lyap_form")) c->opt.lyap_form = (int)value;
   else if (!strcmp(key, "shard_bs")) { if (value < 0) return LRN_ERR_ARG; c->shard_bs_opt = (int)value; lrn::update_shard_bs(c); }
+  else if (!strcmp(key, "comm_fail_ensure")) lrn::comm_inject_ensure_failure(c);      // test hook (tests/test_gpu_comm.py)
   else if (!strcmp(key, "detect_release")) { if (value != 0.0) lrn_detect_free(c); }      // the workspace of lrn_lowrank_detect, before the model goes up (0: nothing)
   else if (!strcmp(key, "reset_timing")) { c->timing.clear(); c->counts.clear(); }
   else return set_error(c, LRN_ERR_ARG, "unknown option %s", key);

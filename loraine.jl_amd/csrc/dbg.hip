@@ -1,10 +1,12 @@
 // Debug entry points of the C ABI (the tests' window on the resident state and on single device routines).
 #include <cstring>
+#include <new>
 
 #include "../../include/loraine_hip.h"
 #include "jacobi.h"
 #include "model_layout.h"
 #include "ops.h"
+#include "options.h"
 
 using namespace lrn;
 
@@ -160,4 +162,36 @@ extern "C" int lrn_dbg_factor_layout(const char* name, int msz, int nvar, const 
     o.ints("dg_h", D.dg_h); o.ints("dg_nat", D.dg_nat); o.ints("dg_of_pos", D.dg_of_pos);
   }
   return layout_result(e, o, msg, msg_len);
+}
+
+// ---- lrn_set_option without a device (options.h; tests/test_options_cpu.py)
+extern "C" const char* lrn_dbg_option_name(int index) { return option_name(index); }
+
+// Not probed: the keys whose action needs a device or a communicator -- "comm_fail_ensure", "detect_release"
+extern "C" int lrn_dbg_option_probe(const char* key, double value, int* rc, char* msg, int msg_len, unsigned char* opt_bytes,
+                                    int opt_cap, int* opt_size, int64_t* watched14) {
+  if (!rc || !opt_size || !watched14 || opt_cap < 0 || (opt_cap > 0 && !opt_bytes)) return LRN_ERR_ARG;
+  if (key && (!strcmp(key, "comm_fail_ensure") || !strcmp(key, "detect_release"))) return LRN_ERR_ARG;
+  // a context that exists on the host only: zeroed storage (the padding of LrnOptions compares equal from call to call), no
+  // stream, one block; what an option may touch beside LrnOptions starts from values it can be told from
+  void* mem = calloc(1, sizeof(lrn_ctx));
+  if (!mem) return LRN_ERR_NOMEM;
+  lrn_ctx* c = new (mem) lrn_ctx;
+  c->hop_version = 7;
+  c->lmi.resize(1);
+  c->lmi[0].t_cap = 5;
+  c->lmi[0].p_cap = 6;
+  c->timing["probe"] = 1.0;
+  c->counts["probe"] = 1;
+  *rc = key ? lrn_set_option(c, key, value) : LRN_OK;      // (no key: the defaults)
+  if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", c->err.c_str());
+  *opt_size = (int)sizeof(LrnOptions);
+  if (opt_cap > 0) memcpy(opt_bytes, &c->opt, std::min((size_t)opt_cap, sizeof(LrnOptions)));
+  const int64_t w[14] = {c->hop_version, c->profile ? 1 : 0, c->lz_res_limit, c->lz_wh_left, c->lz_wh_fired, c->lz_wh_run,
+                         c->lz_wh_step,  c->lz_wh_wg,        c->shard_bs_opt, c->shard_bs,   c->lmi[0].t_cap, c->lmi[0].p_cap,
+                         (int64_t)c->timing.size(), (int64_t)c->counts.size()};
+  for (int i = 0; i < 14; ++i) watched14[i] = w[i];
+  c->~lrn_ctx();
+  free(mem);
+  return LRN_OK;
 }

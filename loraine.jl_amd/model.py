@@ -6,7 +6,7 @@ its construction: SDPA sparse files -> MOI-equivalent sign mapping (src/MOI_wrap
     max  b'y - b_const   s.t.  sum_j y_j A_ij <= C_i  (i = 1..nlmi),   C_lin' y <= d_lin
 """
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Union
 
 import numpy as np
 import scipy.sparse as sp
@@ -54,11 +54,16 @@ class MyModel:
     # diag(a) + V diag(d) V' with its factors in `lowrank` (none for a purely diagonal constraint, e.g. a trace row).  {} for a
     # block without them and for a materialised block, whose entries hold the diagonal
     diag: list = field(default_factory=list)
+    # Optimizer.load_model(..., local_support=True) / long_rows=True of the loaders: stored constraints with a small support are
+    # assembled from A[S, S], long sparse ones from Z = (A W) on their rows -- the solver sets the library options pair_local /
+    # pair_long = 1 after the upload (routes.py)
+    local_support: bool = False
+    long_rows: bool = False
     # Optimizer.load_factored_model(..., ragged=True): mode 1 assembles a block of mixed ranks by rank class (ragged_plan below) --
     # the solver sets the library option lowrank_ragged = 1.  ragged="ops": the data operators of such a block run on the
     # compacted columns as well (ragged_columns below) -- library option ragged_ops = 1 beside it.  ragged="all": so do the cross
     # terms of the assembly (stored rows, diagonal parts) and ts of H_alpha -- ragged_cross = 1 and ragged_ts = 1 beside the two
-    ragged: bool = False
+    ragged: Union[bool, str] = False      # False, True, "ops" or "all"
 
     @property
     def wide(self):

@@ -73,7 +73,7 @@ class Optimizer:
         its defaults; None (default): the file is loaded as it always was.
         local_support: as in load_model (the file loaded as it always was: detect_kmax=None).
         long_rows: as in load_model, with either way of loading the file."""
-        self._local_support = self._check_local_support("read_from_file", local_support)
+        self._local_support = self._check_flag("read_from_file", "local_support", local_support)
         self._long_rows = self._check_flag("read_from_file", "long_rows", long_rows)
         if detect_kmax is None:
             self._pending = ("sdpa", path)
@@ -88,16 +88,20 @@ class Optimizer:
         return self
 
     @staticmethod
-    def _check_local_support(who, value):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: local_support is False or True, not {value!r}")
-        return bool(value)
-
-    @staticmethod
     def _check_flag(who, name, value):
         if not isinstance(value, (bool, np.bool_)):
             raise ValueError(f"{who}: {name} is False or True, not {value!r}")
         return bool(value)
+
+    @staticmethod
+    def _check_cg_ragged(who, cg, ragged):
+        """cg: False, True or "diag"; ragged: False, True, "ops" or "all" -> (cg_diag, ragged as the model holds it)"""
+        cg_diag = isinstance(cg, str) and cg == "diag"
+        if isinstance(cg, str) and not cg_diag:
+            raise ValueError(f"{who}: cg is False, True or \"diag\", not {cg!r}")
+        if isinstance(ragged, str) and ragged not in ("ops", "all"):
+            raise ValueError(f"{who}: ragged is False, True, \"ops\" or \"all\", not {ragged!r}")
+        return cg_diag, ragged if isinstance(ragged, str) else bool(ragged)
 
     def load_model(self, A, b, b_const=0.0, d_lin=None, C_lin=None, max_sense=False, factors=None, local_support=False,
                    long_rows=False):
@@ -113,7 +117,7 @@ class Optimizer:
         entries on up to msz rows, kept sparse -- are assembled from Z = (A W) on their rows, sliced over workgroups, instead of
         on one wavefront per pair (library option pair_long); one GPU, kit = 0 and kit = 1.  Independent of local_support: both
         may be on, and where both could take a constraint local_support keeps it."""
-        self._local_support = self._check_local_support("load_model", local_support)
+        self._local_support = self._check_flag("load_model", "local_support", local_support)
         self._long_rows = self._check_flag("load_model", "long_rows", long_rows)
         self._pending = ("arrays", (A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense), factors))
         return self
@@ -156,14 +160,9 @@ class Optimizer:
             raise ValueError(f"load_factored_model: wide is False or True (or \"diag\"), not {wide!r}")
         if not self.resident:
             raise ValueError(self._NEEDS_RESIDENT)
-        cg_diag = isinstance(cg, str) and cg == "diag"
-        if isinstance(cg, str) and not cg_diag:
-            raise ValueError(f"load_factored_model: cg is False, True or \"diag\", not {cg!r}")
-        if isinstance(ragged, str) and ragged not in ("ops", "all"):
-            raise ValueError(f"load_factored_model: ragged is False, True, \"ops\" or \"all\", not {ragged!r}")
+        cg_diag, ragged = self._check_cg_ragged("load_factored_model", cg, ragged)
         self._pending = ("factored", (F0, factors, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense),
-                                      int(factored_form), ragged if isinstance(ragged, str) else bool(ragged), wide, cg_diag,
-                                      bool(cg)))
+                                      int(factored_form), ragged, wide, cg_diag, bool(cg)))
         return self
 
     _NEEDS_RESIDENT = ("a factored model needs the resident solver (Optimizer(resident=True)): the NumPy host loop "
@@ -191,11 +190,7 @@ class Optimizer:
             raise ValueError(f"load_detected_model: kmax is 16 or 64, not {kmax!r}")
         if isinstance(max_stored, bool) or not isinstance(max_stored, (int, np.integer)) or max_stored < 0:
             raise ValueError(f"load_detected_model: max_stored is a count >= 0, not {max_stored!r}")
-        cg_diag = isinstance(cg, str) and cg == "diag"
-        if isinstance(cg, str) and not cg_diag:
-            raise ValueError(f"load_detected_model: cg is False, True or \"diag\", not {cg!r}")
-        if isinstance(ragged, str) and ragged not in ("ops", "all"):
-            raise ValueError(f"load_detected_model: ragged is False, True, \"ops\" or \"all\", not {ragged!r}")
+        cg_diag, ragged = self._check_cg_ragged("load_detected_model", cg, ragged)
         if factored_form not in (-1, 1):
             raise ValueError(f"factored_form = {factored_form} (-1 auto, 1 always factored)")
         if budget_mb is not None and not budget_mb > 0:
@@ -204,9 +199,8 @@ class Optimizer:
             if (v is not None or name == "seed") and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
                 raise ValueError(f"load_detected_model: {name} is a whole number{' (or None)' if name == 'host_side' else ''}, "
                                  f"not {v!r}")
-        opts = dict(kmax=int(kmax), max_stored=int(max_stored), cg=bool(cg), cg_diag=cg_diag,
-                    ragged=ragged if isinstance(ragged, str) else bool(ragged), factored_form=int(factored_form),
-                    budget_mb=budget_mb, seed=int(seed), host_side=host_side)
+        opts = dict(kmax=int(kmax), max_stored=int(max_stored), cg=bool(cg), cg_diag=cg_diag, ragged=ragged,
+                    factored_form=int(factored_form), budget_mb=budget_mb, seed=int(seed), host_side=host_side)
         self._pending = ("detected", ((A, np.asarray(b, float), float(b_const), d_lin, C_lin, bool(max_sense)), opts))
         return self
 

@@ -13,12 +13,12 @@ default of `optimizer.Optimizer` -- overrides them with the device-resident `lrn
 """
 import math
 import time
-import weakref
 
 import numpy as np
 import scipy.linalg as sla
 import scipy.sparse as sp
 
+from . import routes
 from .device import Device
 from .model import MyModel, check_diag_kit, check_factored_kit
 
@@ -28,11 +28,6 @@ DEFAULT_OPTIONS = {
     "preconditioner": 1, "erank": 1, "aamat": 1, "fig_ev": 0, "verb": 1, "datarank": 0,
     "initpoint": 0, "timing": 1, "maxit": 100, "datasparsity": 8,
 }
-
-# devices a solve with load_model(..., local_support=True) left at pair_local = 1: the next solve on one of them sets it back
-_PAIR_LOCAL_ON = weakref.WeakSet()
-# ... and the same for long_rows=True and pair_long
-_PAIR_LONG_ON = weakref.WeakSet()
 
 
 def _vec(M):
@@ -125,21 +120,10 @@ class MySolver:
             self.dev.upload_model(model.AA, model.sigmaA, model.qA, model.msizes,
                                   B=model.B if len(model.B) else None,
                                   C_lin=model.C_lin if model.nlin else None)    # [GPU] one-time
-        # load_model(..., local_support=True): stored constraints with a small support through A[S, S].  False sets the option
-        # back to 0 on a device an earlier solve left at 1; a device that never had it on is at the library's default, 0
-        local = bool(getattr(model, "local_support", False))
-        if local or self.dev in _PAIR_LOCAL_ON:
-            self.dev.set_option("pair_local", 1 if local else 0)
-            (_PAIR_LOCAL_ON.add if local else _PAIR_LOCAL_ON.discard)(self.dev)
-        if local:
-            self._say(" ---Stored constraints with a support of at most 32 are assembled from A[S, S] (pair_local = 1)")
-        # long_rows=True of the loaders: long sparse stored constraints from Z = (A W) on their rows; set and set back the same way
-        long_rows = bool(getattr(model, "long_rows", False))
-        if long_rows or self.dev in _PAIR_LONG_ON:
-            self.dev.set_option("pair_long", 1 if long_rows else 0)
-            (_PAIR_LONG_ON.add if long_rows else _PAIR_LONG_ON.discard)(self.dev)
-        if long_rows:
-            self._say(" ---Long sparse stored constraints are assembled from Z = (A W) on their rows (pair_long = 1)")
+        # the opt-in routes of the loaders (local_support, long_rows, wide, ragged, cg): routes.resolve says which library options
+        # they need and at which point of the uploads below
+        plan = routes.resolve(model, self.kit, self.datarank)
+        routes.apply(self.dev, plan.after_upload, self._say)
         # datarank = k >= 1: the rank-k factors of the data go to the device; a model whose data has no such form (or
         # k > 16) takes the general path, as the reference's docs promise (docs/src/Loraine_options.md).  kit = 0: the Schur
         # matrix from the factors (mode 1).  kit = 1: the CG path from them wherever the library's cost model finds that
@@ -147,61 +131,22 @@ class MySolver:
         self.lowrank = False
         if self.datarank >= 1 and model.nlmi > 0:
             if model.lowrank:
-                # load_factored_model(..., wide=True): constraints of rank 17 .. 64, khat 32 or 64 (0 on a device another solve used)
-                wide = bool(getattr(model, "wide", False))
-                self.dev.set_option("lowrank_wide", 1 if wide else 0)
-                if wide:
-                    self._say(" ---Factored constraints carry up to 64 factor columns; their blocks are assembled by rank class "
-                              "(lowrank_wide = 1)")
-                wide_diag = None
+                routes.apply(self.dev, plan.before_lowrank, self._say)
+                first_factored = True
                 for i, (V, d, khat) in enumerate(model.lowrank):
                     self.dev.upload_lowrank(i, khat, V, d)                      # [GPU] one-time
-                    if getattr(model, "factored", False) and model.factored_blocks[i]:
+                    if model.factored and model.factored_blocks[i]:
                         self.dev.set_factored(i)                                # [GPU] the factors are the data
-                        if wide_diag is None:
-                            # load_factored_model(..., wide="diag"): diagonal parts on a wide block.  Set where it is first needed,
-                            # before any upload_diag, in both states (0 on a device another solve used); upload_model has
-                            # cleared the diagonal rows of a used block, so no wide upload_lowrank above met any
-                            wide_diag = bool(getattr(model, "wide_diag", False))
-                            self.dev.set_option("wide_diag", 1 if wide_diag else 0)
-                            if wide_diag:
-                                self._say(" ---Wide factored blocks carry diagonal parts (wide_diag = 1)")
-                        dg = model.diag[i] if getattr(model, "diag", None) else {}
+                        if first_factored:
+                            routes.apply(self.dev, plan.first_factored, self._say)
+                            first_factored = False
+                        dg = model.diag[i] if model.diag else {}
                         if dg:                                                  # [GPU] ... and the diagonal parts beside them
                             rows = sorted(dg)
                             self.dev.upload_diag(i, rows, np.column_stack([dg[k] for k in rows]))
                 self.lowrank = True
-                if getattr(model, "factored", False):
-                    # kit = 1 was checked above: the model allows it.  kit = 0 on a device another solve used: the default
-                    self.dev.set_option("cg_factored", 1 if self.kit == 1 else 0)
-                    if self.kit == 1:
-                        self._say(" ---The CG path runs from the factors of the factored blocks (cg_factored = 1)")
-                    # ... with diagonal parts only when the model was loaded with cg="diag" (check_diag_kit above)
-                    cg_diag = self.kit == 1 and bool(getattr(model, "factored_cg_diag", False))
-                    self.dev.set_option("cg_diag", 1 if cg_diag else 0)
-                    if cg_diag:
-                        self._say(" ---The CG path holds the diagonal parts of the factored blocks (cg_diag = 1)")
-                    # load_factored_model(..., ragged=True): blocks of mixed ranks are assembled by rank class
-                    # ... ragged="ops": and their two data operators run on the same compacted columns
-                    # ... ragged="all": and the cross terms of the assembly and ts of H_alpha
-                    rg = getattr(model, "ragged", False)
-                    rest = isinstance(rg, str) and rg == "all"
-                    ragged, ops = bool(rg), rest or (isinstance(rg, str) and rg == "ops")
-                    self.dev.set_option("lowrank_ragged", 1 if ragged else 0)
-                    self.dev.set_option("ragged_ops", 1 if ops else 0)
-                    self.dev.set_option("ragged_cross", 1 if rest else 0)
-                    self.dev.set_option("ragged_ts", 1 if rest else 0)
-                    if rest:
-                        self._say(" ---The Schur assembly with its cross terms, the data operators and H_alpha group the factored "
-                                  "constraints by rank class (lowrank_ragged = 1, ragged_ops = 1, ragged_cross = 1, ragged_ts = 1)")
-                    elif ops:
-                        self._say(" ---The Schur assembly and the data operators group the factored constraints by rank class "
-                                  "(lowrank_ragged = 1, ragged_ops = 1)")
-                    elif ragged:
-                        self._say(" ---The Schur assembly groups the factored constraints by rank class (lowrank_ragged = 1)")
-                if self.kit == 1:
-                    self.dev.set_option("cg_lowrank", -1)
-                    self._say(f" ---The CG path uses the rank-{self.datarank} factors of the data (cg_lowrank = -1)")
+                routes.apply(self.dev, plan.after_factored, self._say)          # (nothing unless the model is factored)
+                routes.apply(self.dev, plan.kit1, self._say)
             else:
                 self._say(f" ---No rank-{self.datarank} factors ({model.lowrank_note}), setting datarank = 0")
                 self.datarank = 0

@@ -188,8 +188,8 @@ def test_host_opt_in(ragged):
 def test_default_model_is_the_parents():
     fm = rc.model("R2")
     names = [f.name for f in dataclasses.fields(fm)]
-    assert names == PARENT_FIELDS + ["ragged"]
-    assert fm.ragged is False
+    assert names == PARENT_FIELDS + ["local_support", "long_rows", "ragged"]      # (the two opt-ins of the stored routes: declared, off)
+    assert fm.ragged is False and fm.local_support is False and fm.long_rows is False
     fm2 = dataclasses.replace(fm, ragged=True)
     for f in PARENT_FIELDS:
         assert getattr(fm2, f) is getattr(fm, f)

@@ -181,7 +181,7 @@ def test_algebra_of_both_operators_matches_the_materialised_constraints(name, ks
 # ---------------------------------------------------------------------------------------------- host opt-in
 PARENT_FIELDS = ["A", "AA", "B", "C", "nzA", "sigmaA", "qA", "b", "b_const", "d_lin", "C_lin", "n", "msizes", "nlin", "nlmi",
                  "lowrank", "lowrank_note", "factored", "from_factors", "factored_blocks", "aa_fro", "stored", "factored_cg",
-                 "factored_cg_diag", "diag", "ragged"]
+                 "factored_cg_diag", "diag", "local_support", "long_rows", "ragged"]
 
 
 class _Stop(RuntimeError):
@@ -225,5 +225,5 @@ def test_host_opt_in(ragged, want):
 def test_model_fields_are_unchanged():
     fm = rc.model("R2")
     assert [f.name for f in dataclasses.fields(fm)] == PARENT_FIELDS
-    assert fm.ragged is False
+    assert fm.ragged is False and fm.local_support is False and fm.long_rows is False
     assert RAGGED_CLASSES == (16, 8, 4, 2, 1)
