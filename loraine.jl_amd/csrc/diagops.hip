@@ -14,22 +14,16 @@
 // khat block sum sits in the epilogue, nothing of size dg_n x R reaches HBM.
 //   rows form (few rows): one wave per column group g, lanes stride i, eight rows' sums in registers (blockIdx.y picks the
 //     eight), weight-0 columns skipped, one shuffle tree per row.  B is read once per eight rows.
-//   MFMA form: 256 threads, workgroup tile = 64 rows s x 64 columns c, K = msz in steps of 16.  Both operands are K-contiguous
-//     in memory (column s of Ad, column c of B), so both are staged as facops.hip stages Vd:
-//       As[s][k] = Ad[k0 + k, s0 + s],  Bs[c][k] = B[k0 + k, c0 + c]^2   64 x 16 doubles each, row stride 18
+//   MFMA form: the 64 x 64 tile of mfma_tile.h (256 threads, K = msz in steps of 16).  Both operands are K-contiguous in
+//     memory (column s of Ad, column c of B), so both panels are [row][k]:
+//       As[s][k] = Ad[k0 + k, s0 + s],  Bs[c][k] = B[k0 + k, c0 + c]^2
 //     (B is squared as it is staged) -- 2 x 9 216 = 18 432 bytes of LDS, eight workgroups per CU by LDS; the compiler reports
 //     92 VGPRs + 32 accumulator registers per lane, 124 of the 128 that four waves per SIMD allow (the rows form: 64, eight
-//     waves).  The global loads of the next step are issued before the MFMAs of this one.  Wave w owns the 32 x 32 block (w >> 1, w & 1) as 2 x 2 accumulators
-//     of v_mfma_f64_16x16x4_f64 (A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15], C/D: col = l & 15, row = (l >> 4) +
-//     4 reg).  Fragment reads are ds_read_b64 (bank = dword address mod 64, conflicts within a 32-lane half): a half reads rows
-//     r .. r + 15 at k and k + 1 -- 36 r mod 64 runs through the sixteen multiples of 4, the two k fill the dword pairs between
-//     them: conflict-free for both operands (the fragment reads only).  Staging writes are ds_write_b64 of 16 consecutive k
-//     per row, row stride 36 dwords, bank = dword mod 32: free of conflicts if stores are served in groups of 16 contiguous
-//     lanes (one row each), two-way conflicted under a wider grouping (rows start at 0, 4, 8, 12 mod 32) -- not measured.
+//     waves).  Lane maps, LDS banks and the K loop: mfma_tile.h.
 //     Epilogue: the accumulator element of column c is multiplied by w[c]; kh (a power of two <= 16) divides 16, so a column
 //     group lies on kh neighbouring lanes of one accumulator block and is summed by an xor butterfly of log2 kh steps; the
 //     lane with c % kh == 0 writes D[s, c / kh].  kh = 32 and 64 (a wide block, option "wide_diag"): diag_sq_wide_mfma_kernel,
-//     the same tile and K loop with an epilogue that goes on across the wave's two accumulators and, for 64, across two waves.
+//     the same product with an epilogue that goes on across the wave's two accumulators and, for 64, across two waves.
 //   Option "ragged_cross" (DESIGN section 20): C from Yc = W Vc, one launch of either form per rank class, the store going
 //     through a group -> H index map (hmap) -- the one change to both kernels, a null map being the code as it was.
 // No atomics, fixed order in both forms: two calls give the same bits.  The forms differ from each other in rounding.
@@ -40,16 +34,12 @@
 
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
+#include "mfma_tile.h"
 #include "ops.h"
 #include "ragged_plan.h"
 
 namespace lrn {
 
-typedef double dg_v4 __attribute__((ext_vector_type(4)));
-
-static constexpr int DG_T = 64;        // tile side (diagonal rows, columns of B)
-static constexpr int DG_K = 16;        // K step
-static constexpr int DG_LD = 18;       // row stride of As, Bs (doubles)
 static constexpr int DG_ROWS = 8;      // rows per wave of the rows form
 static constexpr int DG_MFMA_MIN = 16; // auto: the MFMA form from this many diagonal rows on (measured at msz 2000 / nvar 4000 / khat 2: the rows
                                        // form is 1.8 x faster at 1 row, the MFMA form 1.3 x at 16, 3 x at 64, 13 x at 4000; 2 .. 15 rows not measured).
@@ -93,62 +83,40 @@ __global__ __launch_bounds__(256) void diag_sq_rows_kernel(const double* __restr
   }
 }
 
-__global__ __launch_bounds__(256) void diag_sq_mfma_kernel(const double* __restrict__ Ad, int ns, const double* __restrict__ B,
-                                                           long ldb, int m, long nc, int kh, const double* __restrict__ w,
-                                                           double* __restrict__ D, long ldd, const int* __restrict__ hmap) {
-  __shared__ double As[DG_T * DG_LD];
-  __shared__ double Bs[DG_T * DG_LD];
-  const int t = threadIdx.x, lane = t & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = wv >> 1, wc = wv & 1;
-  const int ci = lane & 15, kq = lane >> 4;
-  const long c0 = (long)blockIdx.x * DG_T;
-  const int s0 = blockIdx.y * DG_T;
-  dg_v4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = dg_v4{0.0, 0.0, 0.0, 0.0};
-  // staging map of both operands: thread (k = t & 15, row = (t >> 4) + 16 pass)
-  const int vk = t & 15, vr = t >> 4;
+// acc = the tile (rows s0 .., columns c0 ..) of Ad' (B o B): the product of both MFMA kernels below, which differ in the epilogue
+__device__ __forceinline__ void diag_sq_tile(const MtLane& ln, const double* __restrict__ Ad, int ns, const double* __restrict__ B,
+                                             long ldb, int m, long nc, int s0, long c0, double* __restrict__ As,
+                                             double* __restrict__ Bs, v4f64 (&acc)[2][2]) {
   double areg[4], breg[4];
   auto fetch = [&](int k0) {
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-      const int s = s0 + vr + 16 * ps;
-      const long cc = c0 + vr + 16 * ps;
-      const bool kin = k0 + vk < m;
-      areg[ps] = (kin && s < ns) ? Ad[(long)(k0 + vk) + (long)s * m] : 0.0;
-      breg[ps] = (kin && cc < nc) ? B[(long)(k0 + vk) + cc * ldb] : 0.0;
+      const int k = k0 + MtRowK::sk(ln.t, ps);
+      const int s = s0 + MtRowK::srow(ln.t, ps);
+      const long cc = c0 + MtRowK::srow(ln.t, ps);
+      const bool kin = k < m;
+      areg[ps] = (kin && s < ns) ? Ad[(long)k + (long)s * m] : 0.0;
+      breg[ps] = (kin && cc < nc) ? B[(long)k + cc * ldb] : 0.0;
     }
   };
-  fetch(0);
-  for (int k0 = 0; k0 < m; k0 += DG_K) {
-    __syncthreads();                       // the waves are done with the previous step's tiles
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      As[(vr + 16 * ps) * DG_LD + vk] = areg[ps];
-      Bs[(vr + 16 * ps) * DG_LD + vk] = breg[ps] * breg[ps];
-    }
-    __syncthreads();
-    if (k0 + DG_K < m) fetch(k0 + DG_K);
-#pragma unroll
-    for (int ks = 0; ks < DG_K / 4; ++ks) {
-      const int k = 4 * ks + kq;
-      const double a0 = As[(32 * wr + ci) * DG_LD + k];
-      const double a1 = As[(32 * wr + 16 + ci) * DG_LD + k];
-      const double b0 = Bs[(32 * wc + ci) * DG_LD + k];
-      const double b1 = Bs[(32 * wc + 16 + ci) * DG_LD + k];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-  }
-  // element (row s0 + 32 wr + 16 ib + kq + 4 r, column c0 + 32 wc + 16 jb + ci): weight, sum over the kh lanes of the group
+  auto stage = [&](int ps, double* a, double* b) { *a = areg[ps]; *b = breg[ps] * breg[ps]; };
+  mt_kloop<MtRowK, MtRowK>(ln, As, Bs, 0, m, fetch, stage, acc);
+}
+
+__global__ __launch_bounds__(256) void diag_sq_mfma_kernel(const double* __restrict__ Ad, int ns, const double* __restrict__ B,
+                                                           long ldb, int m, long nc, int kh, const double* __restrict__ w,
+                                                           double* __restrict__ D, long ldd, const int* __restrict__ hmap) {
+  __shared__ double As[MtRowK::SIZE];
+  __shared__ double Bs[MtRowK::SIZE];
+  const MtLane ln = mt_lane();
+  const long c0 = (long)blockIdx.x * MT_T;
+  const int s0 = blockIdx.y * MT_T;
+  v4f64 acc[2][2];
+  diag_sq_tile(ln, Ad, ns, B, ldb, m, nc, s0, c0, As, Bs, acc);
+  // weight, sum over the kh lanes of the group
 #pragma unroll
   for (int jb = 0; jb < 2; ++jb) {
-    const long cc = c0 + 32 * wc + 16 * jb + ci;
+    const long cc = c0 + mt_col(ln, jb);
     const double wcol = cc < nc ? (w ? w[cc] : 1.0) : 0.0;
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib)
@@ -156,16 +124,16 @@ __global__ __launch_bounds__(256) void diag_sq_mfma_kernel(const double* __restr
       for (int r = 0; r < 4; ++r) {
         double v = acc[ib][jb][r] * wcol;
         for (int off = 1; off < kh; off <<= 1) v += __shfl_xor(v, off, 64);      // (kh is uniform: every lane takes part)
-        const int s = s0 + 32 * wr + 16 * ib + kq + 4 * r;
-        if ((ci & (kh - 1)) == 0 && s < ns && cc < nc) D[(long)s * ldd + (hmap ? (long)hmap[cc / kh] : cc / kh)] = v;
+        const int s = s0 + mt_row(ln, ib, r);
+        if ((ln.ci & (kh - 1)) == 0 && s < ns && cc < nc) D[(long)s * ldd + (hmap ? (long)hmap[cc / kh] : cc / kh)] = v;
       }
   }
 }
 
 // ---- the MFMA form for column groups of 32 and 64 (a wide block with diagonal parts, option "wide_diag").
-// A second kernel, not a template parameter of the one above: that kernel's code is to stay what it is (see the comment above
-// ts_diag_mfma_kernel), and a second body keeps its source untouched.  Tile, staging and K loop are the ones above, written out
-// again.  Geometry: the tile covers the columns c0 .. c0 + 63 with c0 % 64 == 0 and wave (wr, wc) holds the columns
+// A second kernel over the same product (diag_sq_tile), not a branch on kh in the one above: the two epilogues share no code,
+// and as two kernels each keeps the registers it had (124 of the 128 that four waves per SIMD allow; mfma_tile.h).
+// Geometry: the tile covers the columns c0 .. c0 + 63 with c0 % 64 == 0 and wave (wr, wc) holds the columns
 // 32 wc + 16 jb + ci, so a group of 32 is exactly one wave's columns and a group of 64 the columns of the waves wc = 0 and
 // wc = 1 of one wr.  Order of the sum, fixed -- the rule of raggedops.hip::ragged_wide_epilogue:
 //   1. the accumulator element of column cc is multiplied by w[cc]; a column beyond nc has weight 0 (its operand is zero too);
@@ -183,55 +151,14 @@ __global__ __launch_bounds__(256) void diag_sq_mfma_kernel(const double* __restr
 __global__ __launch_bounds__(256) void diag_sq_wide_mfma_kernel(const double* __restrict__ Ad, int ns, const double* __restrict__ B,
                                                                 long ldb, int m, long nc, int kh, const double* __restrict__ w,
                                                                 double* __restrict__ D, long ldd, const int* __restrict__ hmap) {
-  __shared__ double As[DG_T * DG_LD];
-  __shared__ double Bs[DG_T * DG_LD];
-  const int t = threadIdx.x, lane = t & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = wv >> 1, wc = wv & 1;
-  const int ci = lane & 15, kq = lane >> 4;
-  const long c0 = (long)blockIdx.x * DG_T;
-  const int s0 = blockIdx.y * DG_T;
-  dg_v4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = dg_v4{0.0, 0.0, 0.0, 0.0};
-  // staging map of both operands: thread (k = t & 15, row = (t >> 4) + 16 pass)
-  const int vk = t & 15, vr = t >> 4;
-  double areg[4], breg[4];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      const int s = s0 + vr + 16 * ps;
-      const long cc = c0 + vr + 16 * ps;
-      const bool kin = k0 + vk < m;
-      areg[ps] = (kin && s < ns) ? Ad[(long)(k0 + vk) + (long)s * m] : 0.0;
-      breg[ps] = (kin && cc < nc) ? B[(long)(k0 + vk) + cc * ldb] : 0.0;
-    }
-  };
-  fetch(0);
-  for (int k0 = 0; k0 < m; k0 += DG_K) {
-    __syncthreads();                       // the waves are done with the previous step's tiles
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      As[(vr + 16 * ps) * DG_LD + vk] = areg[ps];
-      Bs[(vr + 16 * ps) * DG_LD + vk] = breg[ps] * breg[ps];
-    }
-    __syncthreads();
-    if (k0 + DG_K < m) fetch(k0 + DG_K);
-#pragma unroll
-    for (int ks = 0; ks < DG_K / 4; ++ks) {
-      const int k = 4 * ks + kq;
-      const double a0 = As[(32 * wr + ci) * DG_LD + k];
-      const double a1 = As[(32 * wr + 16 + ci) * DG_LD + k];
-      const double b0 = Bs[(32 * wc + ci) * DG_LD + k];
-      const double b1 = Bs[(32 * wc + 16 + ci) * DG_LD + k];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-  }
+  __shared__ double As[MtRowK::SIZE];
+  __shared__ double Bs[MtRowK::SIZE];
+  const MtLane ln = mt_lane();
+  const int wr = ln.wr, wc = ln.wc, ci = ln.ci, kq = ln.kq;
+  const long c0 = (long)blockIdx.x * MT_T;
+  const int s0 = blockIdx.y * MT_T;
+  v4f64 acc[2][2];
+  diag_sq_tile(ln, Ad, ns, B, ldb, m, nc, s0, c0, As, Bs, acc);
   // element (row s0 + 32 wr + 16 ib + kq + 4 r, column c0 + 32 wc + 16 jb + ci): steps 1 to 3, v[ib][r] = the wave's 32 columns
   double v[2][4];
   {
@@ -298,7 +225,7 @@ static int diag_sq(lrn_ctx* c, const double* Ad, int ns, const double* B, long l
       if (!c->opt.wide_diag) return set_error(c, LRN_ERR_ARG, "diag_sq: the MFMA form needs khat in 1, 2, 4, 8, 16, not %d", kh);
       return set_error(c, LRN_ERR_ARG, "diag_sq: the MFMA form needs khat in 1, 2, 4, 8, 16, or 32 or 64 under option wide_diag, not %d", kh);
     }
-    const long tx = (nc + DG_T - 1) / DG_T, ty = (ns + DG_T - 1) / DG_T;
+    const long tx = (nc + MT_T - 1) / MT_T, ty = (ns + MT_T - 1) / MT_T;
     if (tx > 2147483647L || ty > 65535) return set_error(c, LRN_ERR_ARG, "diag_sq: %ld x %ld tiles", tx, ty);
     if (wide)
       hipLaunchKernelGGL(diag_sq_wide_mfma_kernel, dim3((unsigned)tx, (unsigned)ty), dim3(256), 0, c->stream, Ad, ns, B, ldb, m,
@@ -534,9 +461,12 @@ int aat_to_mat_diag(lrn_ctx* c, LmiBlock& b, const double* x, double* M) {
 // factor part, a zero for a purely diagonal constraint).  With L the Cholesky factor of 2 W - Um Um' (lower, upper triangle
 // zeroed, element (i, r) at L[i + r m]) and u_a column a of Um,
 //     ts[nat(s), a m + r] += -(1 / sqrt(d[nat(s)])) sum_{i >= r} Ad[i, s] Um[i, a] L[i, r]
-// is a dense product with both operands K-contiguous (column r of L, column s of Ad) -- the tile of diag_sq_mfma_kernel,
-// written out a second time: with the K step in a shared inline function the compiler orders the address arithmetic of
-// diag_sq_mfma_kernel differently (one instruction more), and that kernel's code is to stay what it is.  The differences:
+// is a dense product with both operands K-contiguous (column r of L, column s of Ad) -- the tile of mfma_tile.h with two
+// [row][k] panels, as in diag_sq_mfma_kernel, but WRITTEN OUT here, the one kernel of the family that is: over mt_kloop it
+// compiled to 120 instead of 116 registers with another order of the staging stores and measured 2 to 3 % slower at one
+// diagonal row (0.124 against 0.121 ms at msz 2000, both runs of both sides; profiles/mfma_tile_refactor_ab.txt).  As written
+// here its code object is the one it had.  A change to the loop in mfma_tile.h is to be made here too.
+// What is particular to this kernel:
 //   operands: As[r][k] = L[k0 + k, r0 + r],  Bs[s][k] = Ad[k0 + k, s0 + s] Um[k0 + k, a]  (scaled as it is staged, where diag_sq
 //     squares; one value of Um per thread and K step, its staging column k is fixed); blockIdx.x picks 64 columns r of L,
 //     blockIdx.y 64 diagonal rows s, blockIdx.z the eigenvector a
@@ -552,20 +482,21 @@ __global__ __launch_bounds__(256) void ts_diag_mfma_kernel(const double* __restr
                                                            const double* __restrict__ Um, const int* __restrict__ nat,
                                                            const double* __restrict__ d, int m, int nvar,
                                                            double* __restrict__ ts) {
-  __shared__ double As[DG_T * DG_LD];
-  __shared__ double Bs[DG_T * DG_LD];
+  constexpr int LD = MtRowK::LD;
+  __shared__ double As[MtRowK::SIZE];
+  __shared__ double Bs[MtRowK::SIZE];
   const int t = threadIdx.x, lane = t & 63;
   const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wr = wv >> 1, wc = wv & 1;
   const int ci = lane & 15, kq = lane >> 4;
-  const int r0 = blockIdx.x * DG_T;
-  const int s0 = blockIdx.y * DG_T;
+  const int r0 = blockIdx.x * MT_T;
+  const int s0 = blockIdx.y * MT_T;
   const double* __restrict__ ua = Um + (long)blockIdx.z * m;
-  dg_v4 acc[2][2];
+  v4f64 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = dg_v4{0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < 2; ++b) acc[a][b] = v4f64{0.0, 0.0, 0.0, 0.0};
   // staging map of both operands: thread (k = t & 15, row = (t >> 4) + 16 pass)
   const int vk = t & 15, vr = t >> 4;
   double areg[4], breg[4], ureg;
@@ -580,24 +511,24 @@ __global__ __launch_bounds__(256) void ts_diag_mfma_kernel(const double* __restr
       breg[ps] = (kin && s < ns) ? Ad[(long)(k0 + vk) + (long)s * m] : 0.0;
     }
   };
-  const int kbeg = r0 & ~(DG_K - 1);         // rows of L above r0 are zero in every column of the tile
+  const int kbeg = r0 & ~(MT_K - 1);         // rows of L above r0 are zero in every column of the tile
   fetch(kbeg);
-  for (int k0 = kbeg; k0 < m; k0 += DG_K) {
+  for (int k0 = kbeg; k0 < m; k0 += MT_K) {
     __syncthreads();                       // the waves are done with the previous step's tiles
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-      As[(vr + 16 * ps) * DG_LD + vk] = areg[ps];
-      Bs[(vr + 16 * ps) * DG_LD + vk] = breg[ps] * ureg;
+      As[(vr + 16 * ps) * LD + vk] = areg[ps];
+      Bs[(vr + 16 * ps) * LD + vk] = breg[ps] * ureg;
     }
     __syncthreads();
-    if (k0 + DG_K < m) fetch(k0 + DG_K);
+    if (k0 + MT_K < m) fetch(k0 + MT_K);
 #pragma unroll
-    for (int ks = 0; ks < DG_K / 4; ++ks) {
+    for (int ks = 0; ks < MT_K / 4; ++ks) {
       const int k = 4 * ks + kq;
-      const double a0 = As[(32 * wr + ci) * DG_LD + k];
-      const double a1 = As[(32 * wr + 16 + ci) * DG_LD + k];
-      const double b0 = Bs[(32 * wc + ci) * DG_LD + k];
-      const double b1 = Bs[(32 * wc + 16 + ci) * DG_LD + k];
+      const double a0 = As[(32 * wr + ci) * LD + k];
+      const double a1 = As[(32 * wr + 16 + ci) * LD + k];
+      const double b0 = Bs[(32 * wc + ci) * LD + k];
+      const double b1 = Bs[(32 * wc + 16 + ci) * LD + k];
       acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
       acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
       acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
@@ -627,7 +558,7 @@ __global__ __launch_bounds__(256) void ts_diag_mfma_kernel(const double* __restr
 int ts_diag(lrn_ctx* c, LmiBlock& b, const double* Lf, const double* Um, int erank, const double* d, double* ts) {
   const int m = b.msz, ns = b.dg_n;
   if (ns <= 0 || erank <= 0) return LRN_OK;
-  const long tx = (m + DG_T - 1) / DG_T, ty = (ns + DG_T - 1) / DG_T;
+  const long tx = (m + MT_T - 1) / MT_T, ty = (ns + MT_T - 1) / MT_T;
   if (ty > 65535 || erank > 65535) return set_error(c, LRN_ERR_ARG, "ts_diag: %ld row tiles, erank %d", ty, erank);
   hipLaunchKernelGGL(ts_diag_mfma_kernel, dim3((unsigned)tx, (unsigned)ty, (unsigned)erank), dim3(256), 0, c->stream, Lf,
                      b.dg_a.as<double>(), ns, Um, b.dg_nat.as<int>(), d, m, c->nvar, ts);

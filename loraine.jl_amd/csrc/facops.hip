@@ -6,18 +6,13 @@
 // the regime of kit = 1 (msz in the low hundreds, nvar in the tens of thousands).  Here Q never leaves the registers.
 //
 // fac_quadform_kernel: 256 threads, workgroup tile = 64 rows of Z (strip blockIdx.y) x 64 factor columns (blockIdx.x).  khat
-// is a power of two <= 64 (32 and 64: a wide block), so a column tile holds whole constraints.  K = m is walked in steps of 16: the workgroup stages
-//   Zs[k][i] = Z[i0 + i, k0 + k]   16 x 64 doubles, row stride 80   (Z is symmetric: read down its columns, coalesced)
-//   Vs[c][k] = Vd[k0 + k, c0 + c]  64 x 16 doubles, row stride 18
+// is a power of two <= 64 (32 and 64: a wide block), so a column tile holds whole constraints.  The product is the tile of
+// mfma_tile.h over K = m (lane maps, LDS banks and the K loop are derived there), one panel of each layout:
+//   Zs[k][i] = Z[i0 + i, k0 + k]   the [k][row] panel (Z is symmetric: read down its columns, coalesced)
+//   Vs[c][k] = Vd[k0 + k, c0 + c]  the [row][k] panel
 // 10 240 + 9 216 bytes, and 1 024 bytes for the sums of the two wave rows: 20 480 bytes of LDS, eight workgroups per CU of
 // 160 KiB by LDS; the registers (80 VGPRs + 32 accumulator registers per lane) allow four waves per SIMD, i.e. four
-// workgroups per CU.  The global loads of the next step are issued before the MFMAs of the current one.
-// Wave w owns the 32 x 32 block (w >> 1, w & 1) of the tile as 2 x 2 accumulators of v_mfma_f64_16x16x4_f64 (A: lane l holds
-// A[l & 15][l >> 4], B: B[l >> 4][l & 15], C/D: col = l & 15, row = (l >> 4) + 4 reg).  Fragment reads are ds_read_b64 (bank = dword address mod 64, conflicts within a
-// 32-lane half): the A read of a half touches Zs rows k, k + 1 and 16 consecutive i -- 160 dwords apart, i.e. 32 mod 64, the
-// two rows fill the two halves of the bank row; the B read touches Vs[c .. c + 15][k, k + 1] -- 36 c mod 64 runs through the
-// sixteen multiples of 4: both conflict-free.  Staging writes are ds_write_b64 of 32 lanes (bank = dword mod 32): 2 cycles,
-// the minimum for 256 bytes.
+// workgroups per CU.
 // Epilogue: every accumulator element is multiplied by the element of Vd it belongs to (row i of column c) and the rows are
 // summed per column: registers, then the xor-16 / xor-32 butterfly over the four row groups of a wave, then the two wave
 // rows through LDS in the order 0, 1.  One partial per (strip, column) goes to a slab of ceil(m / 64) x R doubles, 1 / 64
@@ -28,85 +23,51 @@
 #include "ctx.h"
 #include "ops.h"
 #include "fac_cols.h"
+#include "mfma_tile.h"
 
 namespace lrn {
 
-typedef double fq_v4 __attribute__((ext_vector_type(4)));
-
-static constexpr int FQ_T = 64;        // tile side (rows of Z, factor columns)
-static constexpr int FQ_K = 16;        // K step
-static constexpr int FQ_LDZ = 80;      // row stride of Zs (doubles)
-static constexpr int FQ_LDV = 18;      // row stride of Vs
+static constexpr int FQ_T = MT_T;      // tile side (rows of Z, factor columns)
 
 __global__ __launch_bounds__(256) void fac_quadform_kernel(const double* __restrict__ Z, const double* __restrict__ Vd, int m,
                                                            long R, double* __restrict__ part) {
-  __shared__ double Zs[FQ_K * FQ_LDZ];
-  __shared__ double Vs[FQ_T * FQ_LDV];
+  __shared__ double Zs[MtKRow::SIZE];
+  __shared__ double Vs[MtRowK::SIZE];
   __shared__ double red[2][FQ_T];
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = w >> 1, wc = w & 1;
-  const int ci = lane & 15, kq = lane >> 4;
+  const MtLane ln = mt_lane();
+  const int t = ln.t;
   const long c0 = (long)blockIdx.x * FQ_T;
   const int i0 = blockIdx.y * FQ_T;
-  fq_v4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = fq_v4{0.0, 0.0, 0.0, 0.0};
-  // staging maps: Z -- thread (i = t & 63, k = t >> 6 + 4 pass); Vd -- thread (k = t & 15, c = t >> 4 + 16 pass)
-  const int zi = t & 63, zk = t >> 6;
-  const int vk = t & 15, vc = t >> 4;
-  // the global loads of step k0 + 16 are issued before the MFMAs of step k0 and waited for after them
+  v4f64 acc[2][2];
   double zreg[4], vreg[4];
   auto fetch = [&](int k0) {
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-      const int k = k0 + zk + 4 * ps, i = i0 + zi;
+      const int k = k0 + MtKRow::sk(t, ps), i = i0 + MtKRow::srow(t, ps);
       zreg[ps] = (k < m && i < m) ? Z[(long)i + (long)k * m] : 0.0;
-      const long c = c0 + vc + 16 * ps;
-      vreg[ps] = (k0 + vk < m && c < R) ? Vd[(long)(k0 + vk) + c * m] : 0.0;
+      const int kv = k0 + MtRowK::sk(t, ps);
+      const long c = c0 + MtRowK::srow(t, ps);
+      vreg[ps] = (kv < m && c < R) ? Vd[(long)kv + c * m] : 0.0;
     }
   };
-  fetch(0);
-  for (int k0 = 0; k0 < m; k0 += FQ_K) {
-    __syncthreads();                       // the waves are done with the previous step's tiles
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      Zs[(zk + 4 * ps) * FQ_LDZ + zi] = zreg[ps];
-      Vs[(vc + 16 * ps) * FQ_LDV + vk] = vreg[ps];
-    }
-    __syncthreads();
-    if (k0 + FQ_K < m) fetch(k0 + FQ_K);
-#pragma unroll
-    for (int ks = 0; ks < FQ_K / 4; ++ks) {
-      const int k = 4 * ks + kq;
-      const double a0 = Zs[k * FQ_LDZ + 32 * wr + ci];
-      const double a1 = Zs[k * FQ_LDZ + 32 * wr + 16 + ci];
-      const double b0 = Vs[(32 * wc + ci) * FQ_LDV + k];
-      const double b1 = Vs[(32 * wc + 16 + ci) * FQ_LDV + k];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-  }
-  // <Q(:, c), Vd(:, c)> over the 32 rows of this wave: rows (l >> 4) + 4 reg of each 16-row block, column l & 15
+  auto stage = [&](int ps, double* a, double* b) { *a = zreg[ps]; *b = vreg[ps]; };
+  mt_kloop<MtKRow, MtRowK>(ln, Zs, Vs, 0, m, fetch, stage, acc);
+  // <Q(:, c), Vd(:, c)> over the 32 rows of this wave
 #pragma unroll
   for (int jb = 0; jb < 2; ++jb) {
-    const long c = c0 + 32 * wc + 16 * jb + ci;
+    const long c = c0 + mt_col(ln, jb);
     double s = 0.0;
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int i = i0 + 32 * wr + 16 * ib + kq + 4 * r;
+        const int i = i0 + mt_row(ln, ib, r);
         const double v = (i < m && c < R) ? Vd[(long)i + c * m] : 0.0;
         s += acc[ib][jb][r] * v;
       }
     s += __shfl_xor(s, 16, 64);
     s += __shfl_xor(s, 32, 64);
-    if (kq == 0) red[wr][32 * wc + 16 * jb + ci] = s;
+    if (ln.kq == 0) red[ln.wr][mt_col(ln, jb)] = s;
   }
   __syncthreads();
   if (t < FQ_T && c0 + t < R) part[(long)blockIdx.y * R + c0 + t] = red[0][t] + red[1][t];

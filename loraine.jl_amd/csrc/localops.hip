@@ -11,8 +11,6 @@
 
 namespace lrn {
 
-typedef double lc_v4 __attribute__((ext_vector_type(4)));
-
 constexpr int LC_LD = 33;          // leading dimension of a wave's W tile in LDS (32 rows + 1: column reads shift by one bank pair)
 constexpr int LC_WAVES = 4;        // waves of a workgroup
 constexpr int LC_SLICE = 32;       // partners of one workgroup: eight a wave
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void local_pair_kernel(
 #pragma unroll
         for (int ti = 0; ti < 2; ++ti) {
           if (ti < nti) {
-            lc_v4 P = {0.0, 0.0, 0.0, 0.0}, Q = {0.0, 0.0, 0.0, 0.0};
+            v4f64 P = {0.0, 0.0, 0.0, 0.0}, Q = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk)
               if (4 * kk < s_i) P = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[ti][kk], Wt[4 * kk + kq + LC_LD * (16 * tj + ci)], P, 0, 0, 0);

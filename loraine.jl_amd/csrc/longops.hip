@@ -17,8 +17,6 @@
 
 namespace lrn {
 
-typedef double lg_v4 __attribute__((ext_vector_type(4)));
-
 constexpr int LG_TILE = 64;        // long_z_kernel: a 64 x 64 tile of Z through LDS
 constexpr int LG_TILE_LD = 65;     //   its leading dimension (rows of x): the transposed reads of 64 lanes fall on 64 distinct bank pairs
 constexpr int LG_STRIPES = 8;      // long_entry_kernel: row indices of the first 8 thread stripes (rho <= 2048) live in registers
@@ -165,11 +163,11 @@ __global__ __launch_bounds__(256) void long_local_kernel(const int2* __restrict_
   const int al = lane & 31, uh = lane >> 5;
   double* ZS = lds + wv * 2 * LG_LDA * 32;
   double* WS = ZS + LG_LDA * 32;
-  lg_v4 acc[2][2];
+  v4f64 acc[2][2];
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-    for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = lg_v4{0.0, 0.0, 0.0, 0.0};
+    for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = v4f64{0.0, 0.0, 0.0, 0.0};
   const int nch = (int)(ld / LG_CH);
   for (int ch = wv; ch < nch; ch += 4) {
     const int a = ch * LG_CH + al;

@@ -13,15 +13,9 @@
 // ragged_blocksum_kernel: 256 threads, one workgroup per tile record, tile = at most 64 rows x 64 columns of T inside ONE
 // class pair (rows: class A, columns: class B, A at or before B in the layout; all tiles of seg_A x seg_B for A != B, tile row
 // >= tile column for A == B).  Tiles are anchored at the segment starts and every class size divides 64, so the ka x kb blocks
-// of a tile are uniform and none straddles a tile or a 16 x 16 accumulator block.  K = msz is walked in steps of 16 (tail
-// zero-filled).  Both operands are K-contiguous columns:
-//   As[i][k] = A[k0 + k, r0 + i]   Bs[j][k] = B[k0 + k, c0 + j]    64 x 16 doubles each, row stride 18
-// 2 x 9 216 = 18 432 bytes of LDS.  The global loads of the next step are issued before the MFMAs of the current one.  Wave w
-// owns the 32 x 32 block (w >> 1, w & 1) as 2 x 2 accumulators of v_mfma_f64_16x16x4_f64 (A: lane l holds A[l & 15][l >> 4],
-// B: B[l >> 4][l & 15], C/D: col = l & 15, row = (l >> 4) + 4 reg).  Fragment reads are ds_read_b64 (bank = dword address mod
-// 64, conflicts within a 32-lane half): a half reads rows i .. i + 15 at k and k + 1 -- 36 i mod 64 runs through the sixteen
-// multiples of 4, the two dwords of an element and the two k fill the four banks of each: conflict-free (derived from the bank
-// rule, as for Vs of facops.hip; not measured).  Staging writes are ds_write_b64 of 16 consecutive k per row.
+// of a tile are uniform and none straddles a tile or a 16 x 16 accumulator block.  The product is the tile of mfma_tile.h over
+// K = msz (lane maps, LDS banks and the K loop are derived there); both operands are K-contiguous columns, two [row][k] panels:
+//   As[i][k] = A[k0 + k, r0 + i]   Bs[j][k] = B[k0 + k, c0 + j]    2 x 9 216 = 18 432 bytes of LDS
 // Epilogue: each accumulator element is squared and weighted by wc[row] wc[col]; the kb columns of a block are summed over
 // neighbouring lanes (xor 1 .. kb / 2), the ka rows over the lane quarters (xor 16, 32) and, from ka = 8 on, over the
 // registers first -- the scheme of the blocked epilogue of gemm_f64.hip with independent row and column sizes.  A butterfly
@@ -35,15 +29,13 @@
 // above, unchanged.
 #include "../../include/loraine_hip.h"
 #include "ctx.h"
+#include "mfma_tile.h"
 #include "ops.h"
 #include "ragged_plan.h"
 
 namespace lrn {
 
-typedef double rg_v4 __attribute__((ext_vector_type(4)));
-
-static constexpr int RG_K = 16;        // K step
-static constexpr int RG_LD = 18;       // row stride of As / Bs (doubles)
+static_assert(RG_TILE == MT_T && RG_KSTEP == MT_K, "the plan's tiles and K chunks are those of mfma_tile.h");
 
 // Vc[:, h] = factor column src[h] of the CSR by factor column (zero-filled by the caller; padding columns stay zero)
 __global__ void ragged_dense_kernel(const long* __restrict__ ptr, const int* __restrict__ col, const double* __restrict__ val,
@@ -66,7 +58,7 @@ __global__ void ragged_dense_kernel(const long* __restrict__ ptr, const int* __r
 // consecutive slots, i.e. consecutive doubles -- at most 16 of them, distinct bank pairs -- and the reads are the same
 // addresses offset by a multiple of 32 doubles, one pass each: conflict-free (derived from the bank rule, not measured).
 // One writer per entry of H, no atomics.
-__device__ __forceinline__ void ragged_wide_epilogue(const RaggedTile& tl, const rg_v4 (&acc)[2][2], const double* __restrict__ wc,
+__device__ __forceinline__ void ragged_wide_epilogue(const RaggedTile& tl, const v4f64 (&acc)[2][2], const double* __restrict__ wc,
                                                      const int* __restrict__ gh, double* __restrict__ H, int ldh,
                                                      double* __restrict__ red, int w, int lane) {
   const int ka = tl.ka, kb = tl.kb;
@@ -158,56 +150,27 @@ __global__ __launch_bounds__(256) void ragged_blocksum_kernel(const double* __re
                                                               const RaggedTile* __restrict__ tiles,
                                                               const double* __restrict__ wc, const int* __restrict__ gh,
                                                               double* __restrict__ H, int ldh) {
-  __shared__ double As[RG_TILE * RG_LD];
-  __shared__ double Bs[RG_TILE * RG_LD];
+  __shared__ double As[MtRowK::SIZE];
+  __shared__ double Bs[MtRowK::SIZE];
   const RaggedTile tl = tiles[blockIdx.x];
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = w >> 1, wn = w & 1;
-  const int ci = lane & 15, kq = lane >> 4;
-  rg_v4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = rg_v4{0.0, 0.0, 0.0, 0.0};
-  // staging map of both operands: thread (k = t & 15, column = t >> 4 + 16 pass)
-  const int sk = t & 15, sc = t >> 4;
+  const MtLane ln = mt_lane();
+  const int wr = ln.wr, wn = ln.wc, ci = ln.ci, kq = ln.kq;
+  v4f64 acc[2][2];
   double areg[4], breg[4];
   auto fetch = [&](int k0) {
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-      const int k = k0 + sk;
-      const int i = tl.r0 + sc + 16 * ps, j = tl.c0 + sc + 16 * ps;
+      const int k = k0 + MtRowK::sk(ln.t, ps);
+      const int i = tl.r0 + MtRowK::srow(ln.t, ps), j = tl.c0 + MtRowK::srow(ln.t, ps);
       areg[ps] = (k < m && i < tl.r1) ? A[(long)k + (long)i * m] : 0.0;
       breg[ps] = (k < m && j < tl.c1) ? B[(long)k + (long)j * m] : 0.0;
     }
   };
-  fetch(0);
-  for (int k0 = 0; k0 < m; k0 += RG_K) {
-    __syncthreads();                       // the waves are done with the previous step's tiles
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      As[(sc + 16 * ps) * RG_LD + sk] = areg[ps];
-      Bs[(sc + 16 * ps) * RG_LD + sk] = breg[ps];
-    }
-    __syncthreads();
-    if (k0 + RG_K < m) fetch(k0 + RG_K);
-#pragma unroll
-    for (int ks = 0; ks < RG_K / 4; ++ks) {
-      const int k = 4 * ks + kq;
-      const double a0 = As[(32 * wr + ci) * RG_LD + k];
-      const double a1 = As[(32 * wr + 16 + ci) * RG_LD + k];
-      const double b0 = Bs[(32 * wn + ci) * RG_LD + k];
-      const double b1 = Bs[(32 * wn + 16 + ci) * RG_LD + k];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-  }
+  auto stage = [&](int ps, double* a, double* b) { *a = areg[ps]; *b = breg[ps]; };
+  mt_kloop<MtRowK, MtRowK>(ln, As, Bs, 0, m, fetch, stage, acc);
   const int ka = tl.ka, kb = tl.kb;
   if (ka > 16 || kb > 16) {                          // a tile of a wide block (uniform over the workgroup): see below
-    ragged_wide_epilogue(tl, acc, wc, gh, H, ldh, As, w, lane);
+    ragged_wide_epilogue(tl, acc, wc, gh, H, ldh, As, 2 * wr + wn, ln.lane);
     return;
   }
   // ---- epilogue: ka x kb blocks inside the 16 x 16 accumulator blocks (ka, kb | 16; uniform over the workgroup)
@@ -316,28 +279,28 @@ int assemble_ragged(lrn_ctx* c, LmiBlock& b) {
 // no group and contributes nothing.  Every sum has a fixed order and one writer: no atomics.
 //
 // ragged_syrk_kernel: 256 threads, grid = lower tiles x K-chunks.  Workgroup (t, s): the 64 x 64 tile (ti, tj), ti >= tj, of M
-// over the columns of chunk s (ragged_plan.h::ragged_chunk_cols), in steps of 16 columns, the tail zero-filled.  Both panels
-// are staged as [k][i], coalesced along the rows of F:
-//   Ps[k][i] = s_c F[i0 + i, c]   Qs[k][j] = F[j0 + j, c]   c = chunk start + k0 + k      16 x 64 doubles each, row stride 80
-// 2 x 10 240 = 20 480 bytes of LDS.  s_c is computed while staging (thread (i = t & 63, k = t >> 6 + 4 pass): k, hence c and
-// s_c, are wave-uniform) -- no scaled copy of the factors is written or read back.  The global loads of the next step are
-// issued before the MFMAs of the current one.  Wave w owns the 32 x 32 block (w >> 1, w & 1) as 2 x 2 accumulators of
-// v_mfma_f64_16x16x4_f64 with the j side as the A operand and the i side as the B operand: D[row = j][col = i], so the 16
-// lanes of a quarter hold 16 consecutive i of one column j of M -- 128-byte stores.  Both fragment reads are the A read of
-// fac_quadform_kernel's Zs (rows k, k + 1, sixteen consecutive i, row stride 80): conflict-free by the derivation there --
-// derived, not measured.  The tile goes to slab s of c->slabs (ks > 1) or straight to M (ks = 1; the part of a diagonal tile
+// over the columns of chunk s (ragged_plan.h::ragged_chunk_cols), in steps of 16 columns, the tail zero-filled: the tile of
+// mfma_tile.h (lane maps, LDS banks and the order of a K step are derived there) with both panels [k][row], coalesced along the
+// rows of F -- WRITTEN OUT here: over mt_kloop its aat_to_mat times came out 0.4 to 1.0 % above the parent's in most figures
+// of tools/ragged_ops_times.py, both runs of both sides (profiles/mfma_tile_refactor_ab.txt); as written its code object is
+// the one it had.  A change to the loop in mfma_tile.h is to be made here too.
+//   Ps[k][i] = s_c F[i0 + i, c]   Qs[k][j] = F[j0 + j, c]   c = chunk start + k0 + k      2 x 10 240 = 20 480 bytes of LDS
+// s_c is computed while staging (thread (i = t & 63, k = t >> 6 + 4 pass): k, hence c and s_c, are wave-uniform) -- no scaled
+// copy of the factors is written or read back.  Wave w owns the 32 x 32 block (w >> 1, w & 1) with the j side as the A operand
+// and the i side as the B operand: D[row = j][col = i], so the 16 lanes of a quarter hold 16 consecutive i of one column j of
+// M -- 128-byte stores.  Both fragment reads are conflict-free by the derivation of mfma_tile.h -- derived, not measured.
+// The tile goes to slab s of c->slabs (ks > 1) or straight to M (ks = 1; the part of a diagonal tile
 // above the diagonal is written too and overwritten by the mirror).
 // ragged_syrk_reduce_kernel: adds the slabs in the order 0 .. ks - 1 for i >= j and writes M[i, j] and M[j, i] from the one
 // sum, by 32 x 32 tile pairs through LDS as mirror_lower_tiled_kernel does: M is exactly symmetric, two calls give equal bits.
-static constexpr int RS_LD = 80;       // row stride of Ps / Qs (doubles)
-
 __global__ __launch_bounds__(256) void ragged_syrk_kernel(const double* __restrict__ F, int m, long Rc,
                                                           const double* __restrict__ wc, const int* __restrict__ cg,
                                                           const int* __restrict__ gh, const int* __restrict__ sigma,
                                                           const double* __restrict__ x, int ks, double* __restrict__ out,
                                                           long slab_stride) {
-  __shared__ double Ps[RG_KSTEP * RS_LD];
-  __shared__ double Qs[RG_KSTEP * RS_LD];
+  constexpr int LD = MtKRow::LD;
+  __shared__ double Ps[MtKRow::SIZE];
+  __shared__ double Qs[MtKRow::SIZE];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wr = w >> 1, wn = w & 1;
@@ -351,11 +314,11 @@ __global__ __launch_bounds__(256) void ragged_syrk_kernel(const double* __restri
   const int i0 = (int)ti * RG_TILE, j0 = tj * RG_TILE;
   long cb, ce;
   ragged_chunk_cols(Rc, ks, blockIdx.y, &cb, &ce);
-  rg_v4 acc[2][2];
+  v4f64 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = rg_v4{0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < 2; ++b) acc[a][b] = v4f64{0.0, 0.0, 0.0, 0.0};
   // staging map of both panels: thread (row = t & 63, k = t >> 6 + 4 pass)
   const int zi = t & 63, zk = t >> 6;
   const bool iok = i0 + zi < m, jok = j0 + zi < m;
@@ -380,18 +343,18 @@ __global__ __launch_bounds__(256) void ragged_syrk_kernel(const double* __restri
     __syncthreads();                       // the waves are done with the previous step's panels
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-      Ps[(zk + 4 * ps) * RS_LD + zi] = preg[ps];
-      Qs[(zk + 4 * ps) * RS_LD + zi] = qreg[ps];
+      Ps[(zk + 4 * ps) * LD + zi] = preg[ps];
+      Qs[(zk + 4 * ps) * LD + zi] = qreg[ps];
     }
     __syncthreads();
     if (cb + k0 + RG_KSTEP < ce) fetch(k0 + RG_KSTEP);
 #pragma unroll
     for (int kk = 0; kk < RG_KSTEP / 4; ++kk) {
       const int k = 4 * kk + kq;
-      const double a0 = Qs[k * RS_LD + 32 * wn + ci];
-      const double a1 = Qs[k * RS_LD + 32 * wn + 16 + ci];
-      const double b0 = Ps[k * RS_LD + 32 * wr + ci];
-      const double b1 = Ps[k * RS_LD + 32 * wr + 16 + ci];
+      const double a0 = Qs[k * LD + 32 * wn + ci];
+      const double a1 = Qs[k * LD + 32 * wn + 16 + ci];
+      const double b0 = Ps[k * LD + 32 * wr + ci];
+      const double b1 = Ps[k * LD + 32 * wr + 16 + ci];
       acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
       acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
       acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);

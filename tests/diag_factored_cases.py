@@ -7,8 +7,10 @@ import numpy as np
 import scipy.sparse as sp
 
 # (msz, nvar, khat, diagonal rows): msz not a multiple of 16 or 64, R = nvar khat not a multiple of 64; one pure trace row,
-# three rows (two of them adjacent in H order), the tile edge 63 / 64 / 65, every constraint a sum
-CASES = [(16, 5, 1, 1), (33, 37, 2, 3), (65, 70, 4, 63), (65, 70, 4, 64), (65, 70, 4, 65), (130, 130, 16, 130), (333, 300, 2, 3)]
+# three rows (two of them adjacent in H order), the tile edge 63 / 64 / 65, every constraint a sum; msz 13: one partial K step
+# of the MFMA kernels (no prefetch of a next step), 66 columns; msz 72: a second tile of 64 whose K range is one partial step
+CASES = [(16, 5, 1, 1), (33, 37, 2, 3), (65, 70, 4, 63), (65, 70, 4, 64), (65, 70, 4, 65), (130, 130, 16, 130), (333, 300, 2, 3),
+         (13, 33, 2, 1), (72, 70, 1, 65)]
 
 
 def _factors(m, n, khat, seed):

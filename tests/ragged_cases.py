@@ -10,6 +10,8 @@ left unchanged.
     R5  96 + 130 / 37  two blocks, R2's and one of R3's kind (msz 130, one rank 9 among 36 x rank 1), plus C_lin: H in natural
         order, the blocks accumulate into shared entries
     R6  R2 with constraints 0 and 7 stored as sparse matrices and constraint 3 = (None, [], ones): hybrid block + diagonal row
+    R7  13 / 33    ranks cycling 2, 1, 4: classes 4, 2, 1 of 11 groups each (Rc = 77, no multiple of 16) in single partial tiles,
+        and K = msz = 13: one partial K step, the prefetch of a next step never taken
 """
 import functools
 
@@ -17,7 +19,7 @@ import numpy as np
 import scipy.sparse as sp
 
 LD = np.longdouble
-NAMES = ["R1", "R2", "R3", "R4", "R5", "R6"]
+NAMES = ["R1", "R2", "R3", "R4", "R5", "R6", "R7"]
 
 
 def spd(m, seed):
@@ -53,11 +55,13 @@ def ranks_of(name):
         return [1] * 18 + [9] + [1] * 18
     if name == "R4":
         return [2] * 33 + [5 + k % 4 for k in range(37)]
+    if name == "R7":
+        return [(2, 1, 4)[k % 3] for k in range(33)]
     raise KeyError(name)
 
 
-SIZES = {"R1": (16, 5), "R2": (96, 37), "R3": (130, 130), "R4": (257, 70), "R5b": (130, 37), "R6": (96, 37)}
-SEEDS = {"R1": 101, "R2": 102, "R3": 103, "R4": 104, "R5b": 105, "R6": 102}
+SIZES = {"R1": (16, 5), "R2": (96, 37), "R3": (130, 130), "R4": (257, 70), "R5b": (130, 37), "R6": (96, 37), "R7": (13, 33)}
+SEEDS = {"R1": 101, "R2": 102, "R3": 103, "R4": 104, "R5b": 105, "R6": 102, "R7": 107}
 
 
 @functools.lru_cache(maxsize=None)

@@ -262,8 +262,9 @@ def _eig_ld_once():
 @pytest.mark.parametrize("erank", [1, 2])
 @pytest.mark.parametrize("m,n,khat,count", dfc.CASES)
 def test_ts_kernel_at_its_edges(dev, m, n, khat, count, erank):
-    """msz 16 (one K step), 33, 65 (the second tile of columns of L starts at K = 64 and has one column), 130, 333 (six tiles,
-    K starts 0 .. 320); 1, 3, 63 / 64 / 65, 130 diagonal rows; with the stored rows of the generator (an identity, a 9-entry
+    """msz 13 (one partial K step), 16 (one K step), 33, 65 (the second tile of columns of L starts at K = 64 and has one
+    column), 72 (it has eight, and a second tile of 65 diagonal rows beside it), 130, 333 (six tiles, K starts 0 .. 320); 1, 3,
+    63 / 64 / 65, 130 diagonal rows; with the stored rows of the generator (an identity, a 9-entry
     matrix, a dense slot).  The apply against the longdouble H_alpha of the materialised model."""
     fm, case = _edge_case(m, n, khat, count)
     with _eig_ld_once():

@@ -163,7 +163,9 @@ def test_operator_on_factored_and_hybrid_blocks(dev, name):
 SHAPES = [  # msz, nvar, khat, sparse factors: tests/test_gpu_factored.py::CASES
     (16, 5, 1, False), (16, 37, 16, False), (96, 37, 2, True), (96, 130, 4, False), (130, 37, 8, True),
     (130, 130, 16, False), (257, 5, 4, True), (257, 130, 1, True), (333, 37, 8, False), (333, 300, 2, False),
-    (257, 300, 1, False), (130, 300, 16, True), (333, 130, 4, True), (96, 5, 8, False)]
+    (257, 300, 1, False), (130, 300, 16, True), (333, 130, 4, True), (96, 5, 8, False),
+    # the K range of the tile: one partial step, two steps and a tail of 8, a second row strip of 8 rows
+    (13, 33, 2, False), (40, 37, 4, True), (72, 33, 16, False)]
 
 
 def _factors(m, n, khat, seed, sparse):
@@ -195,7 +197,8 @@ def _matvec_numpy(facs, W, x):
 @pytest.mark.parametrize("m,n,khat,sparse", SHAPES)
 def test_fused_quadratic_form_against_numpy(dev, m, n, khat, sparse):
     """fac_quadform_kernel + fac_quadform_reduce_kernel inside matvec: ranks 0 .. khat mixed (weight-0 columns), khat up to 16,
-    msz and R off and on the tile of 64, one strip and six, under both operator forms; twice for the bits."""
+    msz and R off and on the tile of 64, one strip and six, msz 13 / 40 / 72 for the K range of the tile (one partial step; two
+    steps and a tail; a second strip of eight rows), under both operator forms; twice for the bits."""
     from loraine_jl_amd.model import build_factored_model
     facs = _factors(m, n, khat, 1000 * m + n + khat, sparse)
     fm = build_factored_model([-np.eye(m)], [facs], np.zeros(n), factored_form=1)
